@@ -47,7 +47,7 @@ EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_
            "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_hot_ptr", "cc_db_feat_ptr", "cc_pack_scans", "cc_db_add_packed",
            "cc_packed_sizes", "cc_db_bucket_state", "cc_est_sens_tf",
            "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
-           "cc_db_add_scan_host", "cc_db_query_host", "cc_db_set_lanes",
+           "cc_db_add_scan_host", "cc_db_query_host", "cc_db_set_lanes", "cc_db_set_dynamic_thres",
            "cc_db_add_scans_host", "cc_db_query_batch_host", "cc_db_check_hints", "cc_db_check_hints_host", "cc_db_debug_passes",
            "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
            "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
@@ -92,6 +92,7 @@ def lib():
         _lib.cc_db_check_hints_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_void_p]
         _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
+        _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
     return _lib
 
 
@@ -344,6 +345,11 @@ class Database:
     def set_lanes(self, n):
         """1 = query chunks one after the other, 2 (default) = two 256-query chunks in flight on internal streams."""
         _chk(lib().cc_db_set_lanes(self.h, int(n)), "cc_db_set_lanes")
+
+    def set_dynamic_thres(self, on):
+        """The reference's DYNAMIC_THRES=1 build: True raises the bars from check to check (up to the ub thresholds) for every
+        query submitted after the call; False (the default) keeps them constant."""
+        _chk(lib().cc_db_set_dynamic_thres(self.h, 1 if on else 0), "cc_db_set_dynamic_thres")
 
     def bucket_state(self):
         sizes = np.zeros((3, 6), np.int32)

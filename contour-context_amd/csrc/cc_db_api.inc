@@ -105,6 +105,8 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   int *d_cnt = nullptr;               // [4] list heads (CC_CNT_*)
   cc_pass_rec *d_pass = nullptr;      // [QB][CC_CHK_STRIDE] dense, index = candidate iteration order
   unsigned char *d_pass_ok = nullptr; // [QB][CC_CHK_STRIDE]
+  cc_cand_post *d_cpost = nullptr;    // [QB][CC_MAXCAND] dynamic thresholds only (cc_db_set_dynamic_thres): post-bar inputs per problem
+  unsigned char *d_tidy = nullptr;    // [QB][CC_MAXCAND] ... and the candidates that survive the post bars
   int *d_pass_cnt = nullptr;
   cc_cand_out *d_cands = nullptr;     // [QB][CC_MAXCAND]
   cc_qstate *d_qstate = nullptr;
@@ -181,6 +183,7 @@ struct cc_db {
                                // with the caller's streams, more than 2 lanes only pay off with GPU_MAX_HW_QUEUES raised)
   cc_qlane lane[NLANE];
   int n_lanes = 2;      // lanes in use (cc_db_set_lanes)
+  int dyn_thres = 0;    // cc_db_set_dynamic_thres: the chains submitted from now on replay the reference's DYNAMIC_THRES=1 bars
   int next_lane = 0;    // lane of the next query chunk
   struct {  // launch geometry of the list-driven kernels (workgroups); env CC_B1_GRID / CC_B2_GRID / CC_GMM_GRID, read once
     int b1 = 256 * 16, b2 = 256 * 16, gmm = 256 * 16;
@@ -276,6 +279,8 @@ static void db_free(cc_db *db) {
     hipFree(ln.d_pass);
     hipFree(ln.d_pass_cnt);
     hipFree(ln.d_pass_ok);
+    hipFree(ln.d_cpost);
+    hipFree(ln.d_tidy);
     hipFree(ln.d_cands);
     hipFree(ln.d_qstate);
     hipFree(ln.d_results);
@@ -321,8 +326,25 @@ static int lane_env_int(const char *name, int lo, int hi, int dflt) {
   const int v = atoi(e);
   return v >= lo && v <= hi ? v : dflt;
 }
+// the dynamic-threshold buffers of a lane (19 MB at QB = 1 024): allocated once the mode is first switched on
+// (both or neither: a failed call leaves the lane without them, and the next call tries again)
+static int lane_alloc_dyn(cc_qlane &ln) {
+  if (ln.d_tidy) return CC_OK;
+  const size_t n = (size_t)cc_db::QB * CC_MAXCAND;
+  hipError_t e = hipMalloc(&ln.d_cpost, sizeof(cc_cand_post) * n);
+  if (e == hipSuccess) {
+    e = hipMalloc(&ln.d_tidy, n);
+    if (e != hipSuccess) {
+      hipFree(ln.d_cpost);
+      ln.d_cpost = nullptr;
+    }
+  } else {
+    ln.d_cpost = nullptr;
+  }
+  return e == hipSuccess ? CC_OK : set_err(CC_EHIP, "lane_alloc_dyn: hipMalloc", e);
+}
 static int lane_alloc(cc_db *db, cc_qlane &ln) {
-  if (ln.d_qmeta) return CC_OK;
+  if (ln.d_qmeta) return db->dyn_thres ? lane_alloc_dyn(ln) : CC_OK;  // (an earlier call may have failed on the dynamic buffers)
   const int QB = cc_db::QB, NS = CC_NQLEV * CC_NPIV;
 #define LN_CHK(x)                                                           \
   do {                                                                      \
@@ -386,7 +408,7 @@ static int lane_alloc(cc_db *db, cc_qlane &ln) {
     for (auto &e : ln.pev)
       if (!e) LN_CHK(hipEventCreate(&e));
 #undef LN_CHK
-  return CC_OK;
+  return db->dyn_thres ? lane_alloc_dyn(ln) : CC_OK;
 }
 
 int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db **out) {
@@ -656,6 +678,23 @@ int cc_db_bucket_state(const cc_db *db, int32_t *tree_sizes, float *ranges) {
   }
 #define DB_POISON_CHK(db, what) \
   if ((db)->poisoned) return set_err(CC_EHIP, what ": the database handle is in a failed state (an earlier HIP error); destroy it")
+
+// DYNAMIC_THRES=1 of the reference (contour_db.h:439-466, 566-574): recorded per chunk when it is submitted, so chunks in
+// flight keep the mode they were launched with
+int cc_db_set_dynamic_thres(cc_db *db, int on) {
+  if (!db || (on != 0 && on != 1)) return set_err(CC_EINVAL, "cc_db_set_dynamic_thres: db must be valid and on 0 or 1");
+  DB_POISON_CHK(db, "cc_db_set_dynamic_thres");
+  if (on) {
+    HIPCHK(hipSetDevice(db->device));
+    for (auto &ln : db->lane)
+      if (ln.d_qmeta) {
+        const int rc = lane_alloc_dyn(ln);
+        if (rc != CC_OK) return rc;
+      }
+  }
+  db->dyn_thres = on;
+  return CC_OK;
+}
 
 // the buckets' indexed intervals at the current epoch, filed with the epoch's other history
 static void push_idx_state(cc_db *db) {
@@ -1046,40 +1085,50 @@ static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q,
 
 // The launches of one chunk after the retrieval: checks (K4), proposal merge (K4b), correlation (K5), selection (K6).
 // ev: profiling events [2..5] or nullptr; d_scores: per-check gate scores (hint flow) or nullptr.
-static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_params &CP, const cc_score_t *lb, int max_fine_opt,
-                                hipEvent_t *ev, int *d_scores, bool zc /*results and counters straight into the lane's pinned host buffers*/) {
+static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_params &CP, const cc_score_t *lb, const cc_score_t *ub,
+                                int max_fine_opt, hipEvent_t *ev, int *d_scores, bool zc /*results and counters straight into the lane's pinned host buffers*/) {
   hipStream_t ls = ln.stream;
+  // dynamic thresholds (the mode at submission): the stages leave their scores in the pass records, cc_k_check_dyn replays the
+  // checks in order, cc_k_select<true> / cc_k_final<true> the post bars
+  const bool dyn = db->dyn_thres != 0;
+  if (dyn && !ln.d_tidy) return set_err(CC_EHIP, "launch_scoring_chain: the lane has no dynamic-threshold buffers");
+  cc_pass_rec *const dpass = dyn ? ln.d_pass : nullptr;
+  unsigned char *const dok = dyn ? ln.d_pass_ok : nullptr;
   const cc_hot_desc_t *qh = ln.d_qhot, *dh = db->d_hot;
   const size_t n_slots = (size_t)nb * CC_CHK_STRIDE;
   hipLaunchKernelGGL(cc_k_check_a, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), LDSPAD(chka), ls, CP, qh, dh, nb, (const cc_knn_hit_t *)ln.d_hits,
-                     (const int *)ln.d_hit_cnt, ln.d_items, ln.d_cnt, ln.d_pass_ok, ln.d_pass_cnt, d_scores);
+                     (const int *)ln.d_hit_cnt, ln.d_items, ln.d_cnt, ln.d_pass_ok, ln.d_pass_cnt, d_scores, dpass);
   if (db->tune.b1_wpe == 5) {
     hipLaunchKernelGGL((cc_k_check_b1<CC_PP_SMALL, false, 5>), dim3(db->tune.b1), dim3(64), LDSPAD(b1), ls, CP, qh, dh, (const cc_chk_item *)ln.d_items,
-                     ln.d_redo, ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores);
+                     ln.d_redo, ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
   } else {
     hipLaunchKernelGGL((cc_k_check_b1<CC_PP_SMALL, false>), dim3(db->tune.b1), dim3(64), LDSPAD(b1), ls, CP, qh, dh, (const cc_chk_item *)ln.d_items,
-                     ln.d_redo, ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores);
+                     ln.d_redo, ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
   }
   hipLaunchKernelGGL((cc_k_check_b1<CC_PP_MAX, true>), dim3((db->tune.b1 + 3) / 4), dim3(64), LDSPAD(b1big), ls, CP, qh, dh, (const cc_chk_item *)ln.d_items, ln.d_redo,
-                     ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores);
+                     ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
   hipLaunchKernelGGL(cc_k_compact_cstl, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), LDSPAD(cmp), ls, CP, (const cc_cstl_item *)ln.d_cstl, ln.d_cnt,
                      ln.d_cstl_idx);
   hipLaunchKernelGGL(cc_k_check_b2, dim3(db->tune.b2), dim3(64), LDSPAD(b2), ls, CP, qh, dh, (const cc_cstl_item *)ln.d_cstl,
-                     (const int *)ln.d_cstl_idx, (const int *)ln.d_cnt, ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt, d_scores);
+                     (const int *)ln.d_cstl_idx, (const int *)ln.d_cnt, ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt, d_scores, dyn ? 1 : 0);
   hipLaunchKernelGGL(cc_k_check_c, dim3((db->tune.b2 + 3) / 4), dim3(256), LDSPAD(chkc), ls, (const cc_cstl_item *)ln.d_cstl,
                      (const int *)ln.d_cstl_idx, (const int *)ln.d_cnt, ln.d_pass, (const unsigned char *)ln.d_pass_ok);
+  if (dyn)
+    hipLaunchKernelGGL(cc_k_check_dyn, dim3(nb), dim3(64), 0, ls, nb, *lb, *ub, (const cc_pass_rec *)ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt,
+                       d_scores);
   if (ev) HIPCHK(hipEventRecord(ev[2], ls));
   hipLaunchKernelGGL(cc_k_merge, dim3(nb), dim3(CC_MERGE_BLOCK), LDSPAD(merge), ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
                      (const unsigned char *)ln.d_pass_ok, (const int *)ln.d_pass_cnt, ln.d_cands, ln.d_qstate, ln.d_prob, ln.d_prob_list,
-                     ln.d_nprob, ln.d_merge_phase);
+                     ln.d_nprob, ln.d_merge_phase, dyn ? ln.d_cpost : (cc_cand_post *)nullptr);
   if (ev) HIPCHK(hipEventRecord(ev[3], ls));
   // initial correlation of every candidate; the candidates fineOptimize would refine; L-BFGS on those only
   hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), LDSPAD(init), ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
                      (const int *)ln.d_nprob, (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, ln.d_gres,
                      cc_gmm_code_pool{ln.d_codes, ln.code_cap, ln.d_heads + 9, ln.d_nprob + 3, ln.pool_cap});
-  hipLaunchKernelGGL(cc_k_select, dim3(nb), dim3(64), LDSPAD(select), ls, nb, lb->correlation, max_fine_opt, (const cc_cand_out *)ln.d_cands,
-                     (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, ln.d_sel, ln.prob_cap, ln.d_nprob + 1, ln.d_heads + 8,
-                     (const unsigned short *)db->d_perm_tab, ln.d_sel + 3 * (size_t)ln.prob_cap, ln.d_heads + 12, ln.d_nprob + 3, ln.d_pool_off);
+  hipLaunchKernelGGL(dyn ? cc_k_select<true> : cc_k_select<false>, dim3(nb), dim3(64), LDSPAD(select), ls, nb, lb->correlation, max_fine_opt,
+                     (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, ln.d_sel, ln.prob_cap,
+                     ln.d_nprob + 1, ln.d_heads + 8, (const unsigned short *)db->d_perm_tab, ln.d_sel + 3 * (size_t)ln.prob_cap, ln.d_heads + 12,
+                     ln.d_nprob + 3, ln.d_pool_off, (const cc_cand_post *)ln.d_cpost, ln.d_tidy, *lb, *ub);
   hipLaunchKernelGGL(cc_k_gmm_refine<16>, dim3(db->tune.gmm), dim3(64), LDSPAD(r16), ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1),
                      (const int *)ln.d_sel, (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap), (const int *)(ln.d_nprob + 2),
                      (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, lb->correlation, ln.d_pool,
@@ -1090,9 +1139,10 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
                      ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
                      (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
   if (ev) HIPCHK(hipEventRecord(ev[4], ls));
-  hipLaunchKernelGGL(cc_k_final, dim3(nb), dim3(64), LDSPAD(final), ls, nb, lb->correlation, max_fine_opt, (const cc_cand_out *)ln.d_cands,
-                     (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt, (const int *)ln.d_hit_cnt,
-                     qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob, zc ? ln.h_nprob : (int *)nullptr);
+  hipLaunchKernelGGL(dyn ? cc_k_final<true> : cc_k_final<false>, dim3(nb), dim3(64), LDSPAD(final), ls, nb, lb->correlation, max_fine_opt,
+                     (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
+                     (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
+                     zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy);
   if (ev) HIPCHK(hipEventRecord(ev[5], ls));
   HIPCHK(hipGetLastError());
   return CC_OK;
@@ -1238,6 +1288,10 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
     db->next_lane = (db->next_lane + 1) % db->n_lanes;
     rc = lane_finish(db, ln);
     if (rc != CC_OK) break;
+    if (db->dyn_thres) {  // before anything of the chunk is queued (a lane whose earlier allocation failed tries again)
+      rc = lane_alloc_dyn(ln);
+      if (rc != CC_OK) break;
+    }
     hipStream_t ls = ln.stream;
     bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
     for (int i = 0; i < nb; i++) {
@@ -1307,7 +1361,7 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
                          ln.d_hits, ln.d_hit_cnt);
     }
     if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, db->cfg.max_fine_opt, ev, nullptr, zc);
+    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc);
     if (rc != CC_OK) {
       lane_abort(db, ln);
       break;
@@ -1550,6 +1604,10 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
   HIPCHK(hipSetDevice(db->device));
   if (!db->d_hint_scores) HIPCHK(hipMalloc(&db->d_hint_scores, sizeof(int) * (size_t)CC_CHK_STRIDE * CC_NSCORE));
   cc_qlane &ln = db->lane[0];
+  if (db->dyn_thres) {
+    const int arc = lane_alloc_dyn(ln);
+    if (arc != CC_OK) return arc;
+  }
   HIPCHK(hipEventRecord(ln.done, stream));  // start after what the caller queued
   HIPCHK(hipStreamWaitEvent(ln.stream, ln.done, 0));
   if (db->add_done) HIPCHK(hipStreamWaitEvent(ln.stream, db->add_done, 0));  // ... and after the last append, whatever stream it used
@@ -1576,7 +1634,7 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
       if (h_hints[i].seq_tgt >= ql.n_cont[h_hints[i].level - 1])
         return set_err(CC_EINVAL, "cc_db_check_hints: hint names a contour of the query scan that does not exist");
   }
-  rc = launch_scoring_chain(db, ln, 1, CP, lb, max_fine_opt, nullptr, db->d_hint_scores, false);
+  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false);
   if (rc != CC_OK) return rc;
   std::vector<int> sc((size_t)CC_CHK_STRIDE * CC_NSCORE);
   std::vector<unsigned char> ok(CC_CHK_STRIDE);

@@ -39,13 +39,25 @@ struct cc_pass_rec {
   int order;       // slot * CC_KNN_MAX + j : position in the reference's candidate iteration order
   int gidx;        // candidate scan
   int n_pairs;     // tmp_pairs2.size() (vote weight)
-  int flags;       // bit0: a capacity (CC_PP_MAX / CC_CSTL_MAX) was hit
-  int pad;
+  int flags;       // bit0: a capacity (CC_PP_MAX / CC_CSTL_MAX) was hit; bits 8-23 reserved (dynamic thresholds: CC_DYN_PAIR)
+  int pad;         // (dynamic thresholds: CC_DYN_PAD | CC_DYN_RNG)
   double tf[3];    // T_pass = (x, y, theta)
   double cs[3];    // cos(theta), sin(theta), atan2(sin, cos): entries of the Isometry2d built by rotate(theta), hoisted out of
                    // the sequential merge
   unsigned long long bits[7];  // constellation pairs as a set: bit (level-1)*100 + seq_src*10 + seq_tgt
 };
+
+// Dynamic thresholds (DYNAMIC_THRES=1, cc_db_set_dynamic_thres): every check that passes stage 2 under the initial bars
+// leaves its five gate scores in its (dense, slot-indexed) pass record -- `pad` = ovlp_sum | max_one << 10 | in_ang_rng << 19
+// (<= 768, 256, 256), `flags` >> 8 = indiv_sim | orie_sim << 8 (<= 64 each) -- and pass_ok = 2 when it fails stage 3 there
+// (1 = passes); cc_k_check_dyn then replays the checks in order under the rising bars.
+#define CC_DYN_PAD(sum, mx) ((sum) | ((mx) << 10))
+#define CC_DYN_RNG(rng) ((rng) << 19)
+#define CC_DYN_PAIR(indiv, orie) (((indiv) << 8) | ((orie) << 16))
+#define CC_PASS_FLAGS_USED 0xFFu  // cc_pass_rec.flags bits of its own (bit0 today); the scores take bits 8-23
+static_assert((CC_PASS_FLAGS_USED & CC_DYN_PAIR(0xFF, 0xFF)) == 0, "pass-record flag bits collide with the dynamic scores");
+static_assert(3 * 256 < (1 << 10) && 256 < (1 << 9) && CC_PP_MAX < (1 << 9) && CC_CSTL_MAX < (1 << 8),
+              "the five scores fit their fields: ovlp_sum 10 bits, max_one and in_ang_rng 9, indiv_sim and orie_sim 8");
 
 struct cc_check_params {
   cc_sim_cfg_t sim;
@@ -116,7 +128,8 @@ __global__ void __launch_bounds__(CC_CHKA_BLOCK)
 cc_k_check_a(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
              int nq, const cc_knn_hit_t *__restrict__ hits, const int *__restrict__ hit_cnt, cc_chk_item *__restrict__ items,
              int *__restrict__ cnt, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt /*[nq][4]*/,
-             int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] or nullptr: per-check gate scores (hint flow)*/) {
+             int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] or nullptr: per-check gate scores (hint flow)*/,
+             cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/) {
   const int NS = CC_NQLEV * CC_NPIV;
   const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int q = (int)(gt / CC_CHK_STRIDE), t = (int)(gt - (size_t)q * CC_CHK_STRIDE);
@@ -162,6 +175,7 @@ cc_k_check_a(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc
     }
   }
   if (in_range) pass_ok[gt] = 0;
+  if (dyn && keep) dyn[gt].pad = CC_DYN_PAD(sc_sum, sc_max);
   if (scores && in_range) {
     int *sc = scores + gt * CC_NSCORE;
     sc[0] = sc_sum;
@@ -499,7 +513,8 @@ template <int PPM, bool REDO, int WPE = 4>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8)))
 cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
               const cc_chk_item *__restrict__ items, int *__restrict__ redo_idx, int *__restrict__ cnt, cc_cstl_item *__restrict__ cstl,
-              int *__restrict__ pass_cnt, int *__restrict__ scores /*see cc_k_check_a; or nullptr*/) {
+              int *__restrict__ pass_cnt, int *__restrict__ scores /*see cc_k_check_a; or nullptr*/,
+              cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/, unsigned char *__restrict__ dyn_ok) {
   __shared__ cc_b1_lds<PPM> LG[CC_CHKB_GPW];
   const int G = CC_G;
   const int sub = threadIdx.x / CC_G, sl = threadIdx.x % CC_G;
@@ -649,6 +664,8 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       if (sl == 0) atomicOr((unsigned *)&pass_cnt[q * 4 + 0], (unsigned)CC_QF_CHECK_CAP);
     }
     if (sl == 0) atomicAdd(&pass_cnt[q * 4 + 2], 1);
+    cc_pass_rec *drec = dyn ? dyn + (size_t)q * CC_CHK_STRIDE + t : nullptr;  // a stage-2 passer: its scores for the replay
+    if (drec && sl == 0) drec->pad |= CC_DYN_RNG(longest);
     // (3/4, first part) the individual similarity of the window pairs and the anchors (contour_mng.h:1138-1160) is
     // decided here, where the pairs are at hand: a check that keeps too few pairs ends without a record (a third of those
     // that reach this point), and stage B2 is handed the pairs that passed, in cstl_in order, instead of reading the
@@ -674,6 +691,10 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       ncs += __popc(ms);
     }
     if (sc && sl == 0) sc[3] = ncs;
+    if (drec && sl == 0) {
+      drec->flags = CC_DYN_PAIR(ncs, 0);  // checkConstellCorrespSim returns i_orie_sim = 0 when it stops here (contour_mng.h:1168)
+      if (ncs < P.lb.i_indiv_sim) dyn_ok[(size_t)q * CC_CHK_STRIDE + t] = 2;
+    }
     CC_ABLATE_AT(6);
     if (ncs < P.lb.i_indiv_sim) continue;
     if (sl == 0) {
@@ -752,7 +773,7 @@ __global__ void __launch_bounds__(64)
 cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
               const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl_idx, const int *__restrict__ cnt,
               cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt,
-              int *__restrict__ scores) {
+              int *__restrict__ scores, int dyn /*dynamic thresholds: the scores into the pass records*/) {
   __shared__ cc_b2_lds LG[CC_CHKB_GPW];
   const int G = CC_G;
   const int sub = threadIdx.x / CC_G, sl = threadIdx.x % CC_G;
@@ -918,7 +939,13 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
     }
     if (sc && sl == 0) sc[4] = ncs;
     CC_ABLATE_AT(13);
-    if (ncs < P.lb.i_orie_sim) continue;
+    if (ncs < P.lb.i_orie_sim) {
+      if (dyn && sl == 0) {
+        pass[(size_t)q * CC_CHK_STRIDE + t].flags = CC_DYN_PAIR(n_in, ncs);
+        pass_ok[(size_t)q * CC_CHK_STRIDE + t] = 2;
+      }
+      continue;
+    }
     // (4/4) getTFFromConstell: 2-D umeyama without scaling, closed form.  The sums run over the list in parallel
     // (partial sums per lane, then a fixed butterfly): the same terms as the reference's sequential sums in another
     // association, i.e. equal up to f64 rounding of the sum -- far inside the pose tolerance.
@@ -1005,8 +1032,8 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       rec->order = t;
       rec->gidx = gidx;
       rec->n_pairs = ncs;
-      rec->flags = flags;
-      rec->pad = 0;
+      rec->flags = dyn ? flags | CC_DYN_PAIR(n_in, ncs) : flags;
+      if (!dyn) rec->pad = 0;  // (dynamic thresholds: the stage-2 scores stage A and B1 left there)
       rec->tf[0] = dmx - (r00 * smx + (-r10) * smy);
       rec->tf[1] = dmy - (r10 * smx + r00 * smy);
       // the rotation's angle and the entries of Isometry2d::rotate(angle) are filled in by cc_k_check_c, one lane per
@@ -1031,7 +1058,7 @@ cc_k_check_c(const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const cc_cstl_item *it = cstl + cstl_idx[i];
     const size_t slot = (size_t)it->q * CC_CHK_STRIDE + it->t;
-    if (!pass_ok[slot]) continue;
+    if (pass_ok[slot] != 1) continue;  // (2: failed stage 3 under the initial bars, dynamic thresholds)
     cc_pass_rec *rec = &pass[slot];
     const double r00 = rec->cs[0], r10 = rec->cs[1];
     const double th = atan2(r10, r00);
@@ -1040,5 +1067,85 @@ cc_k_check_c(const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl
     rec->cs[0] = c_;
     rec->cs[1] = s_2;
     rec->cs[2] = atan2(s_2, c_);
+  }
+}
+
+// ---- dynamic thresholds: the ordered replay of the checks ----------------------------------------------------------
+// With DYNAMIC_THRES=1 (contour_db.h:439-457) every check that passes raises the five bars of stages 2 and 3 to
+// min(max(bar, i_orie_sim), ub), so each check depends on every check before it in the reference's iteration order.
+// The gates compare their scores with the bars only in `>=` tests that end the check early (contour_mng.h:307, 361-363,
+// 1168, 1203), so the scores computed once under the initial bars decide a check under any raised bars, and a check that
+// fails under the initial bars fails under all later ones.  Stages A-C ran under the initial bars; this kernel walks
+// the stage-2 passers in slot order and clears pass_ok of those the raised bars drop (cc_k_merge filters on it).
+// Wave-parallel: per 64-slot window, every lane tests its check against the current bars, a ballot finds the first passer
+// that RAISES a bar, everything up to it is decided, the bars move and the rest of the window goes again -- rounds are
+// bounded by the bar raises (<= ub - lb per field), not by the checks.  Counters cand_aft_check2/3 are rewritten; in the
+// hint flow (scores != nullptr) so are the partial scores a gate returns under a raised bar: i_in_ang_rng = 0 when the
+// popcount gate fails (contour_mng.h:307), sim_pair = 0 when stage 2 fails, i_orie_sim = 0 when indiv_sim fails.
+template <typename T>
+__device__ __forceinline__ T cc_dyn_bar(T bar, T v, T ub) {  // alignLB, then alignUB (tools/algos.h:125-148)
+  const T r = bar < v ? v : bar;
+  return r > ub ? ub : r;
+}
+
+// grid = nq, block = 64
+__global__ void __launch_bounds__(64)
+cc_k_check_dyn(int nq, cc_score_t lb, cc_score_t ub, const cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok,
+               int *__restrict__ pass_cnt, int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] (hint flow) or nullptr*/) {
+  const int q = blockIdx.x, lane = threadIdx.x;
+  if (q >= nq) return;
+  int b0 = lb.i_ovlp_sum, b1 = lb.i_ovlp_max_one, b2 = lb.i_in_ang_rng, b3 = lb.i_indiv_sim, b4 = lb.i_orie_sim;
+  int c2 = 0, c3 = 0;
+  for (int w0 = 0; w0 < CC_CHK_STRIDE; w0 += 64) {
+    const size_t slot = (size_t)q * CC_CHK_STRIDE + w0 + lane;
+    const bool cand = pass_ok[slot] != 0;  // passed stage 2 under the initial bars
+    if (!__ballot(cand) && !scores) continue;
+    int s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+    if (scores) {  // every check's full scores (the other checks' partial scores change too)
+      const int *sc = scores + slot * CC_NSCORE;
+      s0 = sc[0];
+      s1 = sc[1];
+      s2 = sc[2];
+      s3 = sc[3];
+      s4 = sc[4];
+    } else if (cand) {
+      const int pd = pass[slot].pad, fl = pass[slot].flags;
+      s0 = pd & 0x3FF;
+      s1 = (pd >> 10) & 0x1FF;
+      s2 = (pd >> 19) & 0x1FF;
+      s3 = (fl >> 8) & 0xFF;
+      s4 = (fl >> 16) & 0xFF;
+    }
+    for (int start = 0; start < 64;) {  // (uniform)
+      const bool pc = s0 >= b0 && s1 >= b1, st2 = pc && s2 >= b2;
+      const bool p2 = cand && st2, p3 = p2 && s3 >= b3 && s4 >= b4;
+      // alignLB then alignUB (tools/algos.h) with cnt_curr_valid = i_orie_sim
+      const int n0 = cc_dyn_bar(b0, s4, ub.i_ovlp_sum), n1 = cc_dyn_bar(b1, s4, ub.i_ovlp_max_one), n2 = cc_dyn_bar(b2, s4, ub.i_in_ang_rng);
+      const int n3 = cc_dyn_bar(b3, s4, ub.i_indiv_sim), n4 = cc_dyn_bar(b4, s4, ub.i_orie_sim);
+      const bool raise = p3 && (n0 != b0 || n1 != b1 || n2 != b2 || n3 != b3 || n4 != b4);
+      const unsigned long long mr = __ballot(lane >= start && raise);
+      const int end = mr ? __ffsll(mr) - 1 : 63;
+      const bool dec = lane >= start && lane <= end;
+      if (dec && cand) pass_ok[slot] = p3 ? 1 : 0;
+      if (dec && scores) {
+        int *sc = scores + slot * CC_NSCORE;
+        sc[2] = pc ? s2 : 0;
+        sc[3] = st2 ? s3 : 0;
+        sc[4] = st2 && s3 >= b3 ? s4 : 0;
+      }
+      c2 += __popcll(__ballot(dec && p2));
+      c3 += __popcll(__ballot(dec && p3));
+      if (!mr) break;
+      b0 = __shfl(n0, end);
+      b1 = __shfl(n1, end);
+      b2 = __shfl(n2, end);
+      b3 = __shfl(n3, end);
+      b4 = __shfl(n4, end);
+      start = end + 1;
+    }
+  }
+  if (lane == 0) {
+    pass_cnt[q * 4 + 2] = c2;
+    pass_cnt[q * 4 + 3] = c3;
   }
 }

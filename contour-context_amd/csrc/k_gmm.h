@@ -1631,16 +1631,57 @@ __device__ __forceinline__ int cc_tidy_order(int nc, const unsigned char *has, u
 }
 
 // ------------------------------------------------------------------------------------------------
+// Dynamic thresholds (DYNAMIC_THRES=1, contour_db.h:566-574): tidyUpCandidates raises its three post bars to each
+// survivor's (area_perc, neg_est_dist, corr_init), so whether a candidate survives depends on the candidates before it.
+// The area and distance bars of the initial lb already ran in cc_k_merge and the correlation bar here; the bars only rise,
+// so this walk only removes candidates from `has`.  Same wave-parallel form as cc_k_check_dyn: per window of 64
+// candidates (first-appearance order), the first survivor that raises a bar ends a round.  The float bar of the distance
+// is compared with the double value and raised to it rounded to float; corr_init is cast to float first (as the reference).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cc_post_walk(int nc, unsigned char *has, const int *gm, const cc_cand_post *__restrict__ post,
+                                             const cc_gmm_result *__restrict__ gres, const cc_score_t &lb, const cc_score_t &ub, int lane) {
+  float ba = lb.area_perc, bn = lb.neg_est_dist, bc = lb.correlation;
+  for (int w0 = 0; w0 < nc; w0 += 64) {  // (uniform)
+    const int k = w0 + lane;
+    const bool h = k < nc && has[k];
+    float a = 0.f, c = 0.f;
+    double ng = 0.0;
+    if (h) {
+      const int g = gm[k];
+      a = post[g].area_perc;
+      ng = post[g].neg_est_dist;
+      c = (float)gres[g].corr_init;
+    }
+    for (int start = 0; start < 64;) {
+      const bool ok = h && !(a < ba) && !(ng < (double)bn) && !(c < bc);
+      const float na = cc_dyn_bar(ba, a, ub.area_perc), nn = cc_dyn_bar(bn, (float)ng, ub.neg_est_dist), nco = cc_dyn_bar(bc, c, ub.correlation);
+      const bool raise = ok && (na != ba || nn != bn || nco != bc);
+      const unsigned long long mr = __ballot(lane >= start && raise);
+      const int end = mr ? __ffsll(mr) - 1 : 63;
+      if (h && lane >= start && lane <= end) has[k] = ok ? 1 : 0;
+      if (!mr) break;
+      ba = __shfl(na, end);
+      bn = __shfl(nn, end);
+      bc = __shfl(nco, end);
+      start = end + 1;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K5s: which candidates of a query get refined -- the first max_fine_opt_ of candidates_ after tidyUpCandidates'
 // compaction and fineOptimize's sort on the still-all-zero correlation_ (the same replay as in K6; contour_db.h:560-616).
 // Their GMM problems are appended to sel_list.  One wave per query.
+// DYN (dynamic thresholds): the survivors come from cc_post_walk and are handed to cc_k_final<true> in `tidy`.
 // ------------------------------------------------------------------------------------------------
+template <bool DYN>
 __global__ void __launch_bounds__(64)
 cc_k_select(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
             const cc_gmm_result *__restrict__ gres, int *__restrict__ sel_list /*[3][sel_stride]*/, int sel_stride,
             int *__restrict__ n_sel /*[2]*/, int *__restrict__ n_sel_wide, const unsigned short *__restrict__ perm_tab,
             int *__restrict__ cls_list /*[CC_GMM_NCLS][sel_stride]: the long problems by length class*/, int *__restrict__ cls_cnt /*[CC_GMM_NCLS]*/,
-            int *__restrict__ pool_head, int *__restrict__ pool_off /*[problem slot]: where a selected problem's records go in the pair pool*/) {
+            int *__restrict__ pool_head, int *__restrict__ pool_off /*[problem slot]: where a selected problem's records go in the pair pool*/,
+            const cc_cand_post *__restrict__ post, unsigned char *__restrict__ tidy /*[nq][CC_MAXCAND]*/, cc_score_t lb, cc_score_t ub /*DYN only*/) {
   __shared__ unsigned short idx[CC_MAXCAND];
   __shared__ unsigned short scr[CC_MAXCAND];
   __shared__ unsigned char has[CC_MAXCAND];
@@ -1657,6 +1698,11 @@ cc_k_select(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restri
     has[k] = (g >= 0 && !((float)gres[g].corr_init < corr_lb)) ? 1 : 0;
   }
   __syncthreads();
+  if constexpr (DYN) {
+    cc_post_walk(nc, has, gm, post, gres, lb, ub, lane);
+    __syncthreads();
+    for (int k = lane; k < nc; k += 64) tidy[(size_t)q * CC_MAXCAND + k] = has[k];
+  }
   const int n = cc_tidy_order(nc, has, idx, scr, perm_tab, lane);
   if (n <= 0) return;
   const int pre = max_fine_opt < n ? max_fine_opt : n;
@@ -1729,12 +1775,15 @@ cc_k_select(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restri
 // K6: per query, the rest of tidyUpCandidates (correlation bar + order-changing compaction, contour_db.h:560-592) and
 // fineOptimize (contour_db.h:604-648): std::sort on the still-all-zero correlation_ (replayed), take the first
 // max_fine_opt_, adopt their refined score/pose, re-sort those, return the best.  One lane per query.
+// DYN (dynamic thresholds): the survivors are those cc_k_select<true> left in `tidy`.
 // ------------------------------------------------------------------------------------------------
+template <bool DYN>
 __global__ void __launch_bounds__(64)
 cc_k_final(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
            const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
            const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
-           const int *__restrict__ nprob /*the chunk's problem counters and pool head*/, int *__restrict__ nprob_host /*or nullptr: copy them there*/) {
+           const int *__restrict__ nprob /*the chunk's problem counters and pool head*/, int *__restrict__ nprob_host /*or nullptr: copy them there*/,
+           const unsigned char *__restrict__ tidy /*DYN only*/) {
   // one wave per query: lanes fetch the per-candidate inputs and order the candidates in parallel (cc_tidy_order), lane 0
   // replays the short order-dependent rest on LDS
   __shared__ unsigned short idx[CC_MAXCAND];
@@ -1760,7 +1809,7 @@ cc_k_final(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restric
     bool h = false;
     float co = 0.f;
     if (g >= 0) {
-      h = !((float)gres[g].corr_init < corr_lb);
+      h = DYN ? tidy[(size_t)q * CC_MAXCAND + k] != 0 : !((float)gres[g].corr_init < corr_lb);
       co = (float)gres[g].corr_opt;
       gfl |= gres[g].flags;
     }

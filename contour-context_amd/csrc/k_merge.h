@@ -32,6 +32,11 @@ struct cc_dcand {  // CandidatePoseData (working state of one lane)
 struct cc_cand_out {  // what the final-selection kernel needs of a candidate
   int gidx, nprops, gmm_idx, pad;
 };
+struct cc_cand_post {  // dynamic thresholds: what tidyUpCandidates' post bars test of a candidate (contour_db.h:532-553)
+  double neg_est_dist;  // -|getEstSensTF(T_delta).translation()| (a double, compared with a float bar)
+  float area_perc;
+  int pad;
+};
 struct cc_qstate {
   int n_cand;  // candidates_.size() before tidyUpCandidates
   int flags;
@@ -59,7 +64,8 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
            const int *__restrict__ pass_cnt, cc_cand_out *__restrict__ cands_all, cc_qstate *__restrict__ qstate,
            cc_gmm_problem *__restrict__ probs /*[nq][CC_MAXCAND]: problem of candidate k of query q*/,
            int *__restrict__ prob_list /*dense list of the problems that exist*/, int *__restrict__ n_prob,
-           long long *__restrict__ phase /*tuning aid (CC_MERGE_PHASES=1): [nq][8] ticks per stage, else nullptr*/) {
+           long long *__restrict__ phase /*tuning aid (CC_MERGE_PHASES=1): [nq][8] ticks per stage, else nullptr*/,
+           cc_cand_post *__restrict__ post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
   __shared__ cc_merge_lds L;
 #define CC_MERGE_STAMP(i)                                                                                   \
   do {                                                                                                      \
@@ -305,6 +311,13 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
         pb.tf[1] = p0->ty;
         pb.tf[2] = p0->ang;
         probs[gi] = pb;
+        if (post) {
+          cc_cand_post cp;
+          cp.neg_est_dist = neg;
+          cp.area_perc = p0->area_perc;
+          cp.pad = 0;
+          post[gi] = cp;
+        }
       }
     }
     L.want[k] = gi >= 0 ? 1 : 0;

@@ -8,13 +8,14 @@
 #include "../tools/bm_util.h"
 #include "contour_mng.h"
 
-// The reference's DYNAMIC_THRES=1 build (CMakeLists.txt:13-21; contour_db.h:439-466, 566-574) raises the lower bars of a
-// query's checks from candidate to candidate inside CandidateManager -- a sequential dependence between the checks of one
-// query.  The device path evaluates a query's checks side by side with CONSTANT bars (the shipped DYNAMIC_THRES=0; the upper
-// ensemble is validated -- lb.strictSmaller(ub) -- and otherwise unused, as in that build).  A driver compiled for the
-// dynamic variant must not silently get the constant one:
+// The reference's DYNAMIC_THRES=1 build (CMakeLists.txt:19-20; contour_db.h:439-466, 566-574) raises the lower bars of a
+// query's checks from candidate to candidate inside CandidateManager.  Built with that macro, every database of this mirror
+// runs in the library's dynamic mode (cc_db_set_dynamic_thres): the device evaluates a query's checks side by side under the
+// initial bars and then replays them in order under the rising ones.
 #if defined(DYNAMIC_THRES) && DYNAMIC_THRES
-#error "cont2_amd: DYNAMIC_THRES=1 is not supported (checks of a query run in parallel with constant thresholds); build with -DDYNAMIC_THRES=0"
+#define CC_MIRROR_DYNAMIC_THRES 1
+#else
+#define CC_MIRROR_DYNAMIC_THRES 0
 #endif
 
 // As in the reference (contour_db.h:23): the library records its stage timers ("KNN search", "Constell", "L2 opt") into a
@@ -273,6 +274,10 @@ class ContourDB {
     // per-stage DEVICE times of every query under the reference's stage names (six events per query: they cost a few
     // per cent, so only on request); the wall time of the call is recorded either way
     if (getenv("CC_STP_DEVICE_TIMERS")) cc_db_profile_enable(db_, 1);
+    if (CC_MIRROR_DYNAMIC_THRES && cc_db_set_dynamic_thres(db_, 1) != CC_OK) {
+      fprintf(stderr, "cont2_amd: %s\n", cc_last_error());
+      abort();
+    }
     if (specDepth() > 0) cc_db_set_lanes(db_, 4);  // one chain per queued query
   }
 
@@ -442,6 +447,7 @@ class CandidateManager {
       pos.clear();
       keep.clear();
       if (cc_db_create(ctx, &cfg, cap, &db) != CC_OK) die();
+      if (CC_MIRROR_DYNAMIC_THRES && cc_db_set_dynamic_thres(db, 1) != CC_OK) die();
     }
     bool has(const ContourManager *p) const { return pos.count(p) != 0; }
     int add(const std::shared_ptr<const ContourManager> &cm) {
@@ -468,6 +474,7 @@ class CandidateManager {
       st.ctx = cc_host::context(cm.ccfg());
       if (const char *e = getenv("CC_CAND_STORE_CAP")) st.cap = atoi(e) > 0 ? atoi(e) : st.cap;
       if (cc_db_create(st.ctx, &st.cfg, st.cap, &st.db) != CC_OK) die();
+      if (CC_MIRROR_DYNAMIC_THRES && cc_db_set_dynamic_thres(st.db, 1) != CC_OK) die();
     }
     return st;
   }
@@ -502,8 +509,8 @@ class CandidateManager {
   }
 
   std::shared_ptr<const ContourManager> cm_tgt_;
-  const CandidateScoreEnsemble sim_ub_;
-  CandidateScoreEnsemble sim_var_;
+  const CandidateScoreEnsemble sim_lb_, sim_ub_;  // the device always gets the initial bars (raised ones may reach ub)
+  CandidateScoreEnsemble sim_var_;                 // the bars as they stand after the hints so far (DYNAMIC_THRES=1)
   Store *st_ = nullptr;
   std::vector<cc_hint_t> hints_;                                // cand_gidx = index into my_cands_ until the call is made
   std::vector<std::shared_ptr<const ContourManager>> my_cands_;  // this manager's candidate scans, first-appearance order
@@ -514,7 +521,7 @@ class CandidateManager {
   int cand_aft_check1 = 0, cand_aft_check2 = 0, cand_aft_check3 = 0;
 
   CandidateManager(std::shared_ptr<const ContourManager> cm_q, const CandidateScoreEnsemble sim_lb, const CandidateScoreEnsemble sim_ub)
-      : cm_tgt_(std::move(cm_q)), sim_ub_(sim_ub), sim_var_(sim_lb) {
+      : cm_tgt_(std::move(cm_q)), sim_lb_(sim_lb), sim_ub_(sim_ub), sim_var_(sim_lb) {
     CC_CHECK(sim_lb.sim_constell.strictSmaller(sim_ub.sim_constell));
     CC_CHECK(sim_lb.sim_pair.strictSmaller(sim_ub.sim_pair));
     CC_CHECK(sim_lb.sim_post.strictSmaller(sim_ub.sim_post));
@@ -539,15 +546,42 @@ class CandidateManager {
     h.seq_src = anchor_pair.seq_src;
     h.seq_tgt = anchor_pair.seq_tgt;
     h.pad = 0;
-    const cc_score_t lb = to_c(sim_var_), ub = to_c(sim_ub_);
+    const cc_score_t lb = to_c(sim_lb_), ub = to_c(sim_ub_);
     cc_query_result_t r;
     cc_hint_score_t sc;
     if (cc_db_check_hints_host(st.db, &cm_tgt_->desc(), &h, 1, &lb, &ub, 1, &r, &sc) != CC_OK) die();
     h.cand_gidx = it->second;  // recorded by the manager's own numbering
     hints_.push_back(h);
     cand_aft_check1 += r.cand_aft_check1;
+#if CC_MIRROR_DYNAMIC_THRES
+    {  // the full scores under the initial bars decide the hint under the current ones (the gates are monotone in the
+       // bars, contour_mng.h:307, 361-363, 1168, 1203); what the gates return under a raised bar is partial
+      const CandidateScoreEnsemble &B = sim_var_;
+      const bool pc = sc.i_ovlp_sum >= B.sim_constell.i_ovlp_sum && sc.i_ovlp_max_one >= B.sim_constell.i_ovlp_max_one;
+      const bool st2 = r.cand_aft_check2 > 0 && pc && sc.i_in_ang_rng >= B.sim_constell.i_in_ang_rng;
+      const bool st3 = st2 && r.cand_aft_check3 > 0 && sc.i_indiv_sim >= B.sim_pair.i_indiv_sim && sc.i_orie_sim >= B.sim_pair.i_orie_sim;
+      if (!pc) sc.i_in_ang_rng = 0;
+      if (!(pc && sc.i_in_ang_rng >= B.sim_constell.i_in_ang_rng)) sc.i_indiv_sim = sc.i_orie_sim = 0;
+      else if (sc.i_indiv_sim < B.sim_pair.i_indiv_sim) sc.i_orie_sim = 0;
+      cand_aft_check2 += st2 ? 1 : 0;
+      cand_aft_check3 += st3 ? 1 : 0;
+      if (st3) {  // contour_db.h:439-457
+        const int cnt = sc.i_orie_sim;
+        auto raise = [cnt](int &var, int ub) {
+          var = var < cnt ? cnt : var;
+          var = var > ub ? ub : var;
+        };
+        raise(sim_var_.sim_constell.i_ovlp_sum, sim_ub_.sim_constell.i_ovlp_sum);
+        raise(sim_var_.sim_constell.i_ovlp_max_one, sim_ub_.sim_constell.i_ovlp_max_one);
+        raise(sim_var_.sim_constell.i_in_ang_rng, sim_ub_.sim_constell.i_in_ang_rng);
+        raise(sim_var_.sim_pair.i_indiv_sim, sim_ub_.sim_pair.i_indiv_sim);
+        raise(sim_var_.sim_pair.i_orie_sim, sim_ub_.sim_pair.i_orie_sim);
+      }
+    }
+#else
     cand_aft_check2 += r.cand_aft_check2;
     cand_aft_check3 += r.cand_aft_check3;
+#endif
     CandidateScoreEnsemble ret;
     ret.sim_constell.i_ovlp_sum = sc.i_ovlp_sum;
     ret.sim_constell.i_ovlp_max_one = sc.i_ovlp_max_one;
@@ -572,7 +606,7 @@ class CandidateManager {
     res_corr.clear();
     res_T.clear();
     if (hints_.empty() || !st_) return 0;
-    const cc_score_t lb = to_c(sim_var_), ub = to_c(sim_ub_);
+    const cc_score_t lb = to_c(sim_lb_), ub = to_c(sim_ub_);  // (dynamic mode: the device replays the rising bars itself)
     cc_query_result_t r;
     ensureMine();
     std::vector<cc_hint_t> hs(hints_);

@@ -70,7 +70,7 @@ def read_bin(path):
     return a[:len(a) // 4 * 4].reshape(-1, 4)
 
 
-def run(config_path, lib_path=None, chunk=256, verbose=True):
+def run(config_path, lib_path=None, chunk=256, verbose=True, dynamic_thres=False):
     cfg = load_config(config_path)
     m, d, lb, ub = structs_from_config(cfg)
     ev = E.ContLCDEvaluator(cfg["fpath_sens_gt_pose"], cfg["fpath_lidar_bins"], float(cfg["correlation_thres"]))
@@ -93,6 +93,8 @@ def run(config_path, lib_path=None, chunk=256, verbose=True):
     ctx, db = C.c_void_p(), C.c_void_p()
     chk(lib.cc_create(0, C.byref(m), int(chunk), C.byref(ctx)), "cc_create")
     chk(lib.cc_db_create(ctx, C.byref(d), n + 8, C.byref(db)), "cc_db_create")
+    if dynamic_thres:  # the reference's DYNAMIC_THRES=1 build
+        chk(lib.cc_db_set_dynamic_thres(db, 1), "cc_db_set_dynamic_thres")
     desc = np.zeros(n, L.scan_desc_dt)
     for c0 in range(0, n, chunk):
         c1 = min(c0 + chunk, n)
@@ -137,5 +139,6 @@ if __name__ == "__main__":
     ap.add_argument("config")
     ap.add_argument("--lib", default=None, help="shared library exporting the cc_* C-ABI (default: the package's libcont2_amd.so)")
     ap.add_argument("--chunk", type=int, default=256, help="scans ingested per call")
+    ap.add_argument("--dynamic-thres", action="store_true", help="the reference's DYNAMIC_THRES=1 build: bars rise from check to check")
     a = ap.parse_args()
-    run(a.config, a.lib, a.chunk)
+    run(a.config, a.lib, a.chunk, dynamic_thres=a.dynamic_thres)

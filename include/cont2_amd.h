@@ -370,11 +370,12 @@ int cc_db_add_scans_prepare(cc_db *db, const cc_scan_desc_t *d_desc, int n, void
  *   d_knn   : optional [nq][CC_NQLEV][CC_NPIV][CC_KNN_MAX] hits + d_knn_cnt [nq][3][6] i32
  *             (parity/debug; NULL to skip)
  *   thres_lb: the bars of the four gates and of the post-checks (CandidateScoreEnsemble sim_lb, contour_db.h:374-596)
- *   thres_ub: validated like CandidateManager's ctor does (lb.strictSmaller(ub), contour_db.h:365-367: CC_EINVAL otherwise)
- *             and otherwise UNUSED: the bars stay constant during a query, which is the reference's shipped DYNAMIC_THRES=0
- *             build (CMakeLists.txt:13-21).  The DYNAMIC_THRES=1 variant (contour_db.h:439-466, 566-574 raise the bars from
- *             candidate to candidate, a sequential dependence between a query's checks) is NOT implemented; the class mirror
- *             refuses to compile with that macro set (hostcpp/cont2/contour_db.h). */
+ *   thres_ub: validated like CandidateManager's ctor does (lb.strictSmaller(ub), contour_db.h:365-367: CC_EINVAL otherwise).
+ *             By default the bars stay constant during a query, the reference's shipped DYNAMIC_THRES=0 build
+ *             (CMakeLists.txt:19-20), and thres_ub is not used further.  After cc_db_set_dynamic_thres(db, 1) the query
+ *             replays the DYNAMIC_THRES=1 build instead: every check that passes raises the five check bars to
+ *             min(max(bar, i_orie_sim), ub) (contour_db.h:439-457), every candidate that survives the post-checks raises
+ *             the three post bars to min(max(bar, value), ub) (contour_db.h:566-574), in the reference's iteration order. */
 int cc_db_query_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch,
                       const cc_score_t *thres_lb, const cc_score_t *thres_ub,
                       cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt,
@@ -497,6 +498,11 @@ int cc_db_profile_read(cc_db *db, double ms_out[5], int *n_launches);
  * (the f64-bound correlation of one chunk overlaps the latency-bound retrieval/checks of the next).  n = 1 runs the
  * chunks one after the other (per-kernel timing, debugging); default 2.  No reference counterpart. */
 int cc_db_set_lanes(cc_db *db, int n);
+/* The reference's DYNAMIC_THRES=1 build (see cc_db_query_batch, thres_ub): on = 1 raises the bars from check to check and from
+ * candidate to candidate, on = 0 (the default) keeps them constant.  The mode applies to every query entry point (batch,
+ * submit, host, scan, scan batch, hints) called after this; chunks already submitted keep the mode they were submitted
+ * with.  on other than 0 / 1 or a NULL db: CC_EINVAL.  The first switch to 1 allocates ~19 MB per query lane. */
+int cc_db_set_dynamic_thres(cc_db *db, int on);
 
 /* Host-side introspection of the K0 bookkeeping for parity tests:
  * tree sizes per (layer, bucket) and bucket ranges at the current epoch. */
