@@ -82,7 +82,6 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
   hipEvent_t pev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // boundaries of K3 | K4 | merge | K5 | final
-  hipGraphExec_t gexec = nullptr;     // the launch chain of a small chunk as an executable graph (cc_db_query_submit), updated in place per call
   hipEvent_t prep = nullptr;          // the chunk's query descriptors have been read (recorded after the prep kernels)
   hipEvent_t fin = nullptr;           // the chunk's chain has finished (device-side guard of the sorted-view buffers)
   int view[CC_NQLEV] = {0, 0, 0};     // which buffer of each layer's sorted view the chunk in flight reads
@@ -95,8 +94,6 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   cc_knn_hit_t *d_hits = nullptr;
   int *d_hit_cnt = nullptr;
   int *d_knn_order = nullptr;         // [CC_NQLEV][CC_KNN_ORDER_CAP] + [CC_NQLEV]: searches by key[0] (shared-walk / tiled K3)
-  long long *d_merge_phase = nullptr; // tuning aid (CC_MERGE_PHASES=1): per query stage ticks of cc_k_merge
-  long long *d_knn_phase = nullptr;   // tuning aid (CC_KNN_PHASES=1): per workgroup phase ticks of cc_k_knn_tile
   cc_chk_item *d_items = nullptr;     // [QB * CC_CHK_STRIDE] checks that passed stage A
   int *d_redo = nullptr;              // [QB * CC_CHK_STRIDE] indices of the checks left to the large B1 instance
   cc_cstl_item *d_cstl = nullptr;     // [QB * CC_CHK_STRIDE] constellation record of check i (n_in = 0: did not pass the window test)
@@ -126,10 +123,6 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   int *h_nprob = nullptr;             // [4]
 };
 
-// CC_LDS_PAD (tuning aid): extra dynamic LDS per query kernel, by launch site
-enum { CC_PAD_pack, CC_PAD_prep, CC_PAD_chka, CC_PAD_b1, CC_PAD_b1big, CC_PAD_cmp, CC_PAD_b2, CC_PAD_chkc, CC_PAD_merge, CC_PAD_init, CC_PAD_select, CC_PAD_r16, CC_PAD_r64,
-       CC_PAD_final, CC_NPAD };
-#define LDSPAD(name) ((size_t)db->tune.lds_pad[CC_PAD_##name])
 struct cc_db {
   cc_ctx *ctx = nullptr;
   int device = 0;         // the context's device (kept here: the context may be destroyed first)
@@ -187,7 +180,6 @@ struct cc_db {
   int next_lane = 0;    // lane of the next query chunk
   struct {  // launch geometry of the list-driven kernels (workgroups); env CC_B1_GRID / CC_B2_GRID / CC_GMM_GRID, read once
     int b1 = 256 * 16, b2 = 256 * 16, gmm = 256 * 16;
-    int lds_pad[CC_NPAD];  // CC_LDS_PAD (tuning aid)
     int gmm64 = 256 * 32;  // CC_GMM_GRID64: workgroups (= waves = problems at a time) of the 64-lane refinement instance: with one
                            // problem per workgroup and thousands of long problems per dense-world chunk a small grid makes every
                            // workgroup chain two or three of them and the launch end on its unluckiest chain (2 048 / 8 192 /
@@ -198,13 +190,6 @@ struct cc_db {
                         // scans, +53 % at 50 000 scans)
     int a_class[3] = {8, 14, 22};    // CC_A_CLASSES: overlap counts separating the size classes of the check list (stage A -> B1)
     int b2_class[3] = {6, 10, 16};   // CC_B2_CLASSES: constellation lengths separating the size classes of stage B2's list
-    int split_streamed = 0;          // CC_SPLIT_STREAMED=1 (tuning aid): streamed submits are cut per lane like synchronous calls
-    int graph_max = 0;               // CC_QUERY_GRAPH=n: chunks of up to n queries go out as ONE graph launch.  Off by default: measured on
-                                     // the per-scan loop (one query per call, 5 k-scan DB) 0.466 ms per queryRangedKNN with the graph against
-                                     // 0.447 ms without -- the call is not bound by its ~20 launches but by the dependent chain of ~20 kernels
-                                     // of a few microseconds each behind the scan's own ingest kernels (0.27 ms), which a graph does not shorten
-    int ablate = 0;                  // CC_ABLATE (a -DCC_TUNE build only): see cc_check_params
-    int b1_wpe = 4;   // CC_B1_WPE: waves per SIMD the common B1 instance is compiled for (4: 104 VGPRs; 5: 96 VGPRs + 32 B of scratch: 7 % slower since the pairwise checkSim moved into the kernel)
   } tune;
   ScanLite *d_lite = nullptr;
   ScanLite *h_lite_zc = nullptr;  // [CC_ZC_MAX] pinned, device-visible: cc_k_extract writes a small append's records straight to the host
@@ -269,8 +254,6 @@ static void db_free(cc_db *db) {
     hipFree(ln.d_hits);
     hipFree(ln.d_hit_cnt);
     hipFree(ln.d_knn_order);
-    hipFree(ln.d_knn_phase);
-    hipFree(ln.d_merge_phase);
     hipFree(ln.d_items);
     hipFree(ln.d_redo);
     hipFree(ln.d_cstl);
@@ -299,7 +282,6 @@ static void db_free(cc_db *db) {
     if (ln.fin) hipEventDestroy(ln.fin);
     for (auto &e : ln.pev)
       if (e) hipEventDestroy(e);
-    if (ln.gexec) hipGraphExecDestroy(ln.gexec);
     if (ln.stream) stream_give(db->device, ln.stream);
   }
   hipFree(db->d_lite);
@@ -354,7 +336,7 @@ static int lane_alloc(cc_db *db, cc_qlane &ln) {
   // A lane's stream is created when the lane comes into use (cc_db_set_lanes): a process has few hardware queues
   // (4 by default) and HIP hands them to streams in creation order, so streams of lanes nobody uses would push the
   // caller's own streams (e.g. the one it ingests on) onto a queue shared with a busy lane -- measured: 7 % on the bench.
-  if (!ln.stream) LN_CHK(lane_stream_take(db->device, &ln.stream));
+  if (!ln.stream) LN_CHK(stream_take(db->device, &ln.stream));
   LN_CHK(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
   LN_CHK(hipEventCreateWithFlags(&ln.prep, hipEventDisableTiming));
   LN_CHK(hipEventCreateWithFlags(&ln.fin, hipEventDisableTiming));
@@ -364,14 +346,6 @@ static int lane_alloc(cc_db *db, cc_qlane &ln) {
   LN_CHK(hipMalloc(&ln.d_hits, sizeof(cc_knn_hit_t) * (size_t)QB * NS * CC_KNN_MAX));
   LN_CHK(hipMalloc(&ln.d_hit_cnt, sizeof(int) * QB * NS));
   LN_CHK(hipMalloc(&ln.d_knn_order, sizeof(int) * CC_KNN_ORD_INTS));
-  if (getenv("CC_MERGE_PHASES")) {
-    LN_CHK(hipMalloc(&ln.d_merge_phase, sizeof(long long) * 8 * QB));
-    LN_CHK(hipMemsetAsync(ln.d_merge_phase, 0, sizeof(long long) * 8 * QB, nullptr));
-  }
-  if (getenv("CC_KNN_PHASES")) {
-    LN_CHK(hipMalloc(&ln.d_knn_phase, sizeof(long long) * 8 * CC_NQLEV * cc_db::KQB * CC_NPIV));
-    LN_CHK(hipMemsetAsync(ln.d_knn_phase, 0, sizeof(long long) * 8 * CC_NQLEV * cc_db::KQB * CC_NPIV, nullptr));
-  }
   LN_CHK(hipMalloc(&ln.d_items, sizeof(cc_chk_item) * (size_t)QB * CC_CHK_STRIDE));
   LN_CHK(hipMalloc(&ln.d_redo, sizeof(int) * (size_t)QB * CC_CHK_STRIDE));
   LN_CHK(hipMalloc(&ln.d_cstl, sizeof(cc_cstl_item) * (size_t)QB * CC_CHK_STRIDE));
@@ -482,28 +456,10 @@ int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db 
   db->tune.b1 = env_int("CC_B1_GRID", 1, 1 << 20, db->tune.b1);
   db->tune.b2 = env_int("CC_B2_GRID", 1, 1 << 20, db->tune.b2);
   db->tune.gmm = env_int("CC_GMM_GRID", 1, 1 << 20, db->tune.gmm);
-  {  // CC_LDS_PAD="name:bytes,name:bytes": dynamic LDS nobody uses on top of a query kernel's own (tuning aid: how many of its workgroups share a CU,
-     // and what fits beside them; DESIGN.md 3.2).  Names: pack prep chka b1 b1big cmp b2 chkc merge init select r16 r64 final
-    static const char *const names[CC_NPAD] = {"pack", "prep", "chka", "b1", "b1big", "cmp", "b2", "chkc", "merge", "init", "select", "r16", "r64", "final"};
-    for (int i = 0; i < CC_NPAD; i++) db->tune.lds_pad[i] = 0;
-    const char *e = getenv("CC_LDS_PAD");
-    while (e && *e) {
-      const char *c = strchr(e, ':');
-      if (!c) break;
-      for (int i = 0; i < CC_NPAD; i++)
-        if ((size_t)(c - e) == strlen(names[i]) && strncmp(e, names[i], (size_t)(c - e)) == 0) {
-          const int v = atoi(c + 1);
-          db->tune.lds_pad[i] = v > 0 && v <= 48 * 1024 ? v : 0;
-        }
-      e = strchr(c, ',');
-      if (e) e++;
-    }
-  }
   db->tune.gmm64 = env_int("CC_GMM_GRID64", 1, 1 << 20, getenv("CC_GMM_GRID") ? (db->tune.gmm + 1) / 2 : db->tune.gmm64);
   db->tune.knn_mode = env_int("CC_KNN_MODE", 0, 2, db->tune.knn_mode);
   db->add_timers = getenv("CC_ADD_TIMERS") != nullptr;
   db->tune.chunk = env_int("CC_CHUNK", 64, cc_db::QB, db->tune.chunk);
-  db->tune.b1_wpe = env_int("CC_B1_WPE", 4, 5, db->tune.b1_wpe);
   auto env_triple = [](const char *name, int (&v)[3]) {
     const char *e = getenv(name);
     int a, b, c;
@@ -513,9 +469,6 @@ int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db 
       v[2] = c;
     }
   };
-  db->tune.ablate = env_int("CC_ABLATE", 0, 99, 0);
-  db->tune.split_streamed = env_int("CC_SPLIT_STREAMED", 0, 1, 0);
-  db->tune.graph_max = env_int("CC_QUERY_GRAPH", 0, cc_db::QB, db->tune.graph_max);
   env_triple("CC_A_CLASSES", db->tune.a_class);
   env_triple("CC_B2_CLASSES", db->tune.b2_class);
   for (int i = 0; i < db->n_lanes; i++) {
@@ -574,59 +527,6 @@ int cc_db_profile_enable(cc_db *db, int on) {
 }
 int cc_db_profile_read(cc_db *db, double ms_out[5], int *n_launches) {
   if (!db || !ms_out) return set_err(CC_EINVAL, "cc_db_profile_read: bad argument");
-  if (db->lane[0].d_merge_phase) {  // tuning aid: stage times of the last cc_k_merge launch of lane 0, per query
-    std::vector<long long> h((size_t)cc_db::QB * 8);
-    if (hipMemcpy(h.data(), db->lane[0].d_merge_phase, sizeof(long long) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
-      double a[5] = {0}, nn = 0, ncand = 0;
-      std::vector<double> tot;
-      for (int w = 0; w < cc_db::QB; w++) {
-        const long long *p = &h[(size_t)w * 8];
-        if (p[5] == 0) continue;
-        for (int i = 0; i < 5; i++) a[i] += (double)(p[i + 1] - p[i]) * 0.01;
-        tot.push_back((double)(p[5] - p[0]) * 0.01);
-        nn += (double)p[6];
-        ncand += (double)p[7];
-      }
-      if (!tot.empty()) {
-        const double u = (double)tot.size();
-        std::sort(tot.begin(), tot.end());
-        fprintf(stderr, "[cc_k_merge stages, mean us over %d queries] list %.1f  gather %.1f  thread %.1f  replay %.1f  problems %.1f | passes %.1f  "
-                        "candidates %.1f | total p50 %.0f  p90 %.0f  max %.0f\n", (int)tot.size(), a[0] / u, a[1] / u, a[2] / u, a[3] / u, a[4] / u,
-                nn / u, ncand / u, tot[tot.size() / 2], tot[tot.size() * 9 / 10], tot.back());
-      }
-    }
-  }
-  if (db->lane[0].d_knn_phase) {  // tuning aid: mean phase times of the last cc_k_knn_tile launch of lane 0, per workgroup
-    const int nwg = CC_NQLEV * cc_db::KQB * CC_NPIV;
-    std::vector<long long> h((size_t)nwg * 8);
-    if (hipMemcpy(h.data(), db->lane[0].d_knn_phase, sizeof(long long) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
-      double a[8] = {0}, tmax = 0, rmax = 0;
-      int used = 0;
-      std::vector<double> tot;
-      for (int w = 0; w < nwg; w++) {
-        if (h[(size_t)w * 8 + 6] == 0) continue;
-        used++;
-        double t = 0;
-        for (int i = 0; i < 8; i++) {
-          a[i] += (double)h[(size_t)w * 8 + i];
-          if (i < 6) t += (double)h[(size_t)w * 8 + i];
-        }
-        tot.push_back(t * 0.01);
-        tmax = t > tmax ? t : tmax;
-        rmax = (double)h[(size_t)w * 8 + 6] > rmax ? (double)h[(size_t)w * 8 + 6] : rmax;
-      }
-      if (used) {
-        std::sort(tot.begin(), tot.end());
-        fprintf(stderr, "[cc_k_knn_tile workgroup time percentiles, us] p10 %.0f  p50 %.0f  p90 %.0f  p99 %.0f  max %.0f\n", tot[tot.size() / 10],
-                tot[tot.size() / 2], tot[tot.size() * 9 / 10], tot[tot.size() * 99 / 100], tot.back());
-      }
-      if (used)
-        fprintf(stderr, "[cc_k_knn_tile phases, mean over %d workgroups, us] setup %.1f  steps %.1f  barrier %.1f  passes %.1f  cut-back %.1f  "
-                        "results %.1f | rounds %.1f  passes %.1f | slowest workgroup %.1f us, most rounds %.0f\n", used, a[0] / used * 0.01,
-                a[1] / used * 0.01, a[2] / used * 0.01, a[3] / used * 0.01, a[4] / used * 0.01, a[5] / used * 0.01, a[6] / used, a[7] / used,
-                tmax * 0.01, rmax);
-    }
-  }
   for (int i = 0; i < 5; i++) {
     ms_out[i] = db->ms_acc[i];
     db->ms_acc[i] = 0;
@@ -1076,9 +976,9 @@ static bool thres_strict_smaller(const cc_score_t *lb, const cc_score_t *ub) {
 static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q, int nb, bool meta_from_host = false) {
   (void)db;
   hipStream_t ls = ln.stream;
-  hipLaunchKernelGGL(cc_k_pack_hot, dim3(nb), dim3(256), LDSPAD(pack), ls, d_q, nb, ln.d_qhot, ln.d_heads, ln.d_pass_cnt,  // d_heads = d_nprob[4] | d_cnt[4]
+  hipLaunchKernelGGL(cc_k_pack_hot, dim3(nb), dim3(256), 0, ls, d_q, nb, ln.d_qhot, ln.d_heads, ln.d_pass_cnt,  // d_heads = d_nprob[4] | d_cnt[4]
                      meta_from_host ? (const cc_query_meta *)ln.h_meta : (const cc_query_meta *)nullptr, ln.d_qmeta);
-  hipLaunchKernelGGL(cc_k_gmm_prep, dim3(nb), dim3(CC_GMM_PREP_BLOCK), LDSPAD(prep), ls, d_q, nb, ln.d_qfeat);
+  hipLaunchKernelGGL(cc_k_gmm_prep, dim3(nb), dim3(CC_GMM_PREP_BLOCK), 0, ls, d_q, nb, ln.d_qfeat);
   HIPCHK(hipGetLastError());
   return CC_OK;
 }
@@ -1096,50 +996,45 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
   unsigned char *const dok = dyn ? ln.d_pass_ok : nullptr;
   const cc_hot_desc_t *qh = ln.d_qhot, *dh = db->d_hot;
   const size_t n_slots = (size_t)nb * CC_CHK_STRIDE;
-  hipLaunchKernelGGL(cc_k_check_a, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), LDSPAD(chka), ls, CP, qh, dh, nb, (const cc_knn_hit_t *)ln.d_hits,
+  hipLaunchKernelGGL(cc_k_check_a, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), 0, ls, CP, qh, dh, nb, (const cc_knn_hit_t *)ln.d_hits,
                      (const int *)ln.d_hit_cnt, ln.d_items, ln.d_cnt, ln.d_pass_ok, ln.d_pass_cnt, d_scores, dpass);
-  if (db->tune.b1_wpe == 5) {
-    hipLaunchKernelGGL((cc_k_check_b1<CC_PP_SMALL, false, 5>), dim3(db->tune.b1), dim3(64), LDSPAD(b1), ls, CP, qh, dh, (const cc_chk_item *)ln.d_items,
+  hipLaunchKernelGGL((cc_k_check_b1<CC_PP_SMALL, false>), dim3(db->tune.b1), dim3(64), 0, ls, CP, qh, dh, (const cc_chk_item *)ln.d_items,
                      ln.d_redo, ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
-  } else {
-    hipLaunchKernelGGL((cc_k_check_b1<CC_PP_SMALL, false>), dim3(db->tune.b1), dim3(64), LDSPAD(b1), ls, CP, qh, dh, (const cc_chk_item *)ln.d_items,
-                     ln.d_redo, ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
-  }
-  hipLaunchKernelGGL((cc_k_check_b1<CC_PP_MAX, true>), dim3((db->tune.b1 + 3) / 4), dim3(64), LDSPAD(b1big), ls, CP, qh, dh, (const cc_chk_item *)ln.d_items, ln.d_redo,
+  hipLaunchKernelGGL((cc_k_check_b1<CC_PP_MAX, true>), dim3((db->tune.b1 + 3) / 4), dim3(64), 0, ls, CP, qh, dh, (const cc_chk_item *)ln.d_items, ln.d_redo,
                      ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
-  hipLaunchKernelGGL(cc_k_compact_cstl, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), LDSPAD(cmp), ls, CP, (const cc_cstl_item *)ln.d_cstl, ln.d_cnt,
+  hipLaunchKernelGGL(cc_k_compact_cstl, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), 0, ls, CP, (const cc_cstl_item *)ln.d_cstl, ln.d_cnt,
                      ln.d_cstl_idx);
-  hipLaunchKernelGGL(cc_k_check_b2, dim3(db->tune.b2), dim3(64), LDSPAD(b2), ls, CP, qh, dh, (const cc_cstl_item *)ln.d_cstl,
+  hipLaunchKernelGGL(cc_k_check_b2, dim3(db->tune.b2), dim3(64), 0, ls, CP, qh, dh, (const cc_cstl_item *)ln.d_cstl,
                      (const int *)ln.d_cstl_idx, (const int *)ln.d_cnt, ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt, d_scores, dyn ? 1 : 0);
-  hipLaunchKernelGGL(cc_k_check_c, dim3((db->tune.b2 + 3) / 4), dim3(256), LDSPAD(chkc), ls, (const cc_cstl_item *)ln.d_cstl,
+  hipLaunchKernelGGL(cc_k_check_c, dim3((db->tune.b2 + 3) / 4), dim3(256), 0, ls, (const cc_cstl_item *)ln.d_cstl,
                      (const int *)ln.d_cstl_idx, (const int *)ln.d_cnt, ln.d_pass, (const unsigned char *)ln.d_pass_ok);
   if (dyn)
     hipLaunchKernelGGL(cc_k_check_dyn, dim3(nb), dim3(64), 0, ls, nb, *lb, *ub, (const cc_pass_rec *)ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt,
                        d_scores);
   if (ev) HIPCHK(hipEventRecord(ev[2], ls));
-  hipLaunchKernelGGL(cc_k_merge, dim3(nb), dim3(CC_MERGE_BLOCK), LDSPAD(merge), ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
+  hipLaunchKernelGGL(cc_k_merge, dim3(nb), dim3(CC_MERGE_BLOCK), 0, ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
                      (const unsigned char *)ln.d_pass_ok, (const int *)ln.d_pass_cnt, ln.d_cands, ln.d_qstate, ln.d_prob, ln.d_prob_list,
-                     ln.d_nprob, ln.d_merge_phase, dyn ? ln.d_cpost : (cc_cand_post *)nullptr);
+                     ln.d_nprob, dyn ? ln.d_cpost : (cc_cand_post *)nullptr);
   if (ev) HIPCHK(hipEventRecord(ev[3], ls));
   // initial correlation of every candidate; the candidates fineOptimize would refine; L-BFGS on those only
-  hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), LDSPAD(init), ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
+  hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
                      (const int *)ln.d_nprob, (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, ln.d_gres,
                      cc_gmm_code_pool{ln.d_codes, ln.code_cap, ln.d_heads + 9, ln.d_nprob + 3, ln.pool_cap});
-  hipLaunchKernelGGL(dyn ? cc_k_select<true> : cc_k_select<false>, dim3(nb), dim3(64), LDSPAD(select), ls, nb, lb->correlation, max_fine_opt,
+  hipLaunchKernelGGL(dyn ? cc_k_select<true> : cc_k_select<false>, dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
                      (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, ln.d_sel, ln.prob_cap,
                      ln.d_nprob + 1, ln.d_heads + 8, (const unsigned short *)db->d_perm_tab, ln.d_sel + 3 * (size_t)ln.prob_cap, ln.d_heads + 12,
                      ln.d_nprob + 3, ln.d_pool_off, (const cc_cand_post *)ln.d_cpost, ln.d_tidy, *lb, *ub);
-  hipLaunchKernelGGL(cc_k_gmm_refine<16>, dim3(db->tune.gmm), dim3(64), LDSPAD(r16), ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1),
+  hipLaunchKernelGGL(cc_k_gmm_refine<16>, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1),
                      (const int *)ln.d_sel, (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap), (const int *)(ln.d_nprob + 2),
                      (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, lb->correlation, ln.d_pool,
                      ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes, (const int *)nullptr, (const int *)nullptr, 0);
-  hipLaunchKernelGGL(cc_k_gmm_refine<64>, dim3(db->tune.gmm64), dim3(64), LDSPAD(r64), ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 2),
+  hipLaunchKernelGGL(cc_k_gmm_refine<64>, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 2),
                      (const int *)(ln.d_sel + ln.prob_cap), (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap),
                      (const int *)(ln.d_nprob + 1), (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, lb->correlation,
                      ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
                      (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
   if (ev) HIPCHK(hipEventRecord(ev[4], ls));
-  hipLaunchKernelGGL(dyn ? cc_k_final<true> : cc_k_final<false>, dim3(nb), dim3(64), LDSPAD(final), ls, nb, lb->correlation, max_fine_opt,
+  hipLaunchKernelGGL(dyn ? cc_k_final<true> : cc_k_final<false>, dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
                      (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
                      (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
                      zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy);
@@ -1177,7 +1072,7 @@ static int lane_finish(cc_db *db, cc_qlane &ln) {
 static void lane_abort(cc_db *db, cc_qlane &ln) {
   if (ln.stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ln.stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {  // a failure inside a captured chain
+    if (hipStreamIsCapturing(ln.stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {  // a caller's capture that reached the lane through the event waits
       hipGraph_t g = nullptr;
       if (hipStreamEndCapture(ln.stream, &g) == hipSuccess && g) hipGraphDestroy(g);
       (void)hipGetLastError();
@@ -1245,9 +1140,6 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
     CP.size_class[i] = db->tune.a_class[i];
     CP.cstl_class[i] = db->tune.b2_class[i];
   }
-#ifdef CC_TUNE
-  CP.ablate = db->tune.ablate;
-#endif
 
   for (int i = 0; i < nq; i++)
     if (h_epoch[i] < 0 || h_epoch[i] > db->n_scans) return set_err(CC_EINVAL, "cc_db_query_batch: epoch out of range");
@@ -1270,7 +1162,7 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
   // batches deep, and an append in between has to wait for the chunks that still read the view buffer it rewrites
   // (measured on the online loop with 512-scan sub-batches and four lanes: 188 k against 265 k scans/s).
   int qb = (((nq + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
-  if (!db->sync_call && !db->tune.split_streamed && nq >= cc_db::QB) qb = cc_db::QB;
+  if (!db->sync_call && nq >= cc_db::QB) qb = cc_db::QB;
   qb = qb > db->tune.chunk ? db->tune.chunk : qb;
   // A HIP call that fails once part of a chunk's chain is queued: the lane is drained (its pinned staging buffers must not
   // be reused under copies still in flight) and the handle is marked failed, as the appends do.
@@ -1310,16 +1202,10 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
     }
     ln.profiled = db->prof && (db->prof_tick++ % db->prof_every) == 0;
     hipEvent_t *ev = ln.profiled ? ln.pev : nullptr;
-    // Optional (CC_QUERY_GRAPH, see tune.graph_max): the chain of a chunk of a few queries recorded by stream capture and
-    // sent as one graph launch; the lane's executable graph is kept and UPDATED from the freshly captured one
-    // (hipGraphExecUpdate: same topology, new kernel arguments -- key counts, view buffers and thresholds change from call
-    // to call), re-instantiated only if the update is refused.
-    const bool graphed = nb <= db->tune.graph_max && !ev && !ln.d_knn_phase && !ln.d_merge_phase;
-    if (graphed) LANE_CHK(hipStreamBeginCapture(ls, hipStreamCaptureModeThreadLocal));
     // a chunk of a few queries (the per-scan loop brings one): the searches read the epoch records from the lane's pinned
     // host buffer (cc_k_pack_hot brings them over) and cc_k_final writes the results there -- three copy commands less in a
     // chain of ~15 short kernels
-    const bool zc = nb <= CC_ZC_MAX && !graphed;
+    const bool zc = nb <= CC_ZC_MAX;
     const cc_query_meta *qmeta_dev = ln.d_qmeta;  // small chunks: filled by cc_k_pack_hot from the pinned buffer
     if (!zc) LANE_CHK(hipMemcpyAsync(ln.d_qmeta, ln.h_meta, sizeof(cc_query_meta) * nb, hipMemcpyHostToDevice, ls));
     rc = launch_query_prep(db, ln, d_qdesc + b0, nb, zc);
@@ -1327,17 +1213,15 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
       lane_abort(db, ln);
       break;
     }
-    if (!graphed) {  // the caller's stream goes on once the descriptors have been read (graphed: once the chain is through)
-      LANE_CHK(hipEventRecord(ln.prep, ls));
-      LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
-    }
+    // the caller's stream goes on once the descriptors have been read
+    LANE_CHK(hipEventRecord(ln.prep, ls));
+    LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
     if (ev) LANE_CHK(hipEventRecord(ev[0], ls));
     int max_keys = 0;
     for (int l = 0; l < nql; l++) max_keys = db->n_keys[l] > max_keys ? db->n_keys[l] : max_keys;
     const bool tiled = db->tune.knn_mode == 2 || (db->tune.knn_mode == 1 && max_keys >= CC_KNN_TILE_MIN_KEYS);
     if (tiled) {
       int *ord = ln.d_knn_order;
-      if (ln.d_knn_phase) LANE_CHK(hipMemsetAsync(ln.d_knn_phase, 0, sizeof(long long) * 8 * CC_NQLEV * cc_db::KQB * CC_NPIV, ls));
       for (int s0 = 0; s0 < nb; s0 += cc_db::KQB) {  // the search order of a sub-chunk is built in LDS (cc_k_knn_order)
         const int ns = nb - s0 < cc_db::KQB ? nb - s0 : cc_db::KQB;
         const cc_hot_desc_t *qh = ln.d_qhot + s0;
@@ -1345,12 +1229,7 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
         cc_knn_hit_t *hs = ln.d_hits + (size_t)s0 * NS * CC_KNN_MAX;
         int *hc = ln.d_hit_cnt + (size_t)s0 * NS;
         hipLaunchKernelGGL(cc_k_knn_order, dim3(nql), dim3(1024), CC_KNN_ORDER_LDS, ls, KP, qh, ns, ord, hc);
-        if (ln.d_knn_phase && s0 == 0)
-          hipLaunchKernelGGL(cc_k_knn_tile<true>, dim3(nql * ns * CC_NPIV), dim3(64 * CC_KNN_TW), 0, ls, KP, qh, qm, ns, (const int *)ord, hs,
-                             hc, ln.d_knn_phase);
-        else
-          hipLaunchKernelGGL(cc_k_knn_tile<false>, dim3(nql * ns * CC_NPIV), dim3(64 * CC_KNN_TW), 0, ls, KP, qh, qm, ns, (const int *)ord, hs,
-                             hc, (long long *)nullptr);
+        hipLaunchKernelGGL(cc_k_knn_tile, dim3(nql * ns * CC_NPIV), dim3(64 * CC_KNN_TW), 0, ls, KP, qh, qm, ns, (const int *)ord, hs, hc);
       }
     } else {
       if (chunk_vis)
@@ -1371,33 +1250,6 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
     if (!zc) {
       LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
       LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
-    }
-    if (graphed) {
-      hipGraph_t g = nullptr;
-      LANE_CHK(hipStreamEndCapture(ls, &g));
-      bool ok = false;
-      if (ln.gexec) {
-        hipGraphNode_t bad_node = nullptr;
-        hipGraphExecUpdateResult res;
-        ok = hipGraphExecUpdate(ln.gexec, g, &bad_node, &res) == hipSuccess;
-        if (!ok) {
-          (void)hipGetLastError();
-          hipGraphExecDestroy(ln.gexec);
-          ln.gexec = nullptr;
-        }
-      }
-      if (!ok) {
-        const hipError_t ei = hipGraphInstantiate(&ln.gexec, g, nullptr, nullptr, 0);
-        if (ei != hipSuccess) {
-          hipGraphDestroy(g);
-          lane_abort(db, ln);
-          return set_err(CC_EHIP, "hipGraphInstantiate", ei);
-        }
-      }
-      hipGraphDestroy(g);
-      LANE_CHK(hipGraphLaunch(ln.gexec, ls));
-      LANE_CHK(hipEventRecord(ln.prep, ls));
-      LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
     }
     LANE_CHK(hipEventRecord(ln.fin, ls));
     for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];
@@ -1620,9 +1472,6 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
     CP.size_class[i] = db->tune.a_class[i];
     CP.cstl_class[i] = db->tune.b2_class[i];
   }
-#ifdef CC_TUNE
-  CP.ablate = db->tune.ablate;
-#endif
   int rc = launch_query_prep(db, ln, d_qdesc, 1);
   if (rc != CC_OK) return rc;
   {  // a hint must name contours that exist on BOTH sides (the reference would CHECK-fail on the missing view): the query
@@ -1691,29 +1540,3 @@ int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hi
   return cc_db_check_hints(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr);
 }
 
-#ifdef CC_TUNE_GMM_CLK
-// tuning aid (never in the product build): the per-problem clocks of cc_k_gmm_refine since the last call; returns the count
-extern "C" int cc_tune_gmm_clk_read(unsigned long long *out, int cap) {
-  int n = 0;
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(cc_gmm_clk_n), sizeof(int)) != hipSuccess) return -1;
-  n = n < CC_GMM_CLK_CAP ? n : CC_GMM_CLK_CAP;
-  n = n < cap ? n : cap;
-  if (n > 0 && hipMemcpyFromSymbol(out, HIP_SYMBOL(cc_gmm_clk), sizeof(unsigned long long) * 4 * (size_t)n) != hipSuccess) return -1;
-  const int z = 0;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(cc_gmm_clk_n), &z, sizeof(int)) != hipSuccess) return -1;
-  return n;
-}
-extern "C" int cc_tune_gmm_clk2_read(unsigned long long *out, int n) {  // call BEFORE cc_tune_gmm_clk_read (which resets the count)
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  if (n > 0 && hipMemcpyFromSymbol(out, HIP_SYMBOL(cc_gmm_clk2), sizeof(unsigned long long) * 4 * (size_t)n) != hipSuccess) return -1;
-  return n;
-}
-extern "C" int cc_tune_gmm_scan_clk_read(unsigned long long *out8) {
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(cc_gmm_scan_clk), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-  const unsigned long long z8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyToSymbol(HIP_SYMBOL(cc_gmm_scan_clk), z8, sizeof(z8)) != hipSuccess) return -1;
-  return 0;
-}
-#endif

@@ -86,7 +86,6 @@ struct cc_ctx {
   hipEvent_t off_ev[NSLOT] = {nullptr, nullptr, nullptr, nullptr};
   bool off_busy[NSLOT] = {false, false, false, false};
   int off_next = 0;
-  long long *d_phase_clk = nullptr;  // tuning aid: per-scan phase timestamps of cc_k_contours (CC_K2_PHASES=1)
   // the per-scan loop (cc_scan_*): own stream, pinned + device point staging, a pool of device descriptor slots
   hipStream_t s_loop = nullptr;       // per-scan loop: descriptor fetches, cc_db_query_scan / cc_db_add_scan
   // per-scan loop: cc_scan_ingest (copy of the points, K1, K2) goes to the next of CC_NCHAN channels -- own stream, device point
@@ -126,11 +125,6 @@ struct cc_ctx {
   std::vector<cc_scan_desc_t *> slot_free, slot_blocks;
   std::vector<int> slot_block_n;  // slots per block
   size_t lds1 = 0, lds2 = 0;
-  int k1_div = 0;  // CC_K1_DIV=1: keep the IEEE divisions even for power-of-two resolutions (A/B aid)
-  int k1_nosplit = 0;  // CC_K1_NOSPLIT=1: one workgroup per scan also for calls of a few scans (A/B aid)
-  int k1_wgs = 0;      // CC_K1_WGS: workgroups of a many-scan K1 launch, each taking scans b, b + grid, ... (0 = one per scan, the default:
-                       // 256 persistent workgroups make K1 0.55 -> 0.49 ms inside the pipelined step and K2 1.15 -> 1.22, the step 1.79 -> 1.82)
-  int k1_dense = 0;    // CC_K1_DENSE=1: K1 writes the dense image / positions of every scan (A/B aid; round 5's behaviour)
   // optional per-kernel timing (cc_profile_*)
   bool prof = false;
   std::vector<hipEvent_t> ev;  // triplets (before K1, between, after K2)
@@ -269,46 +263,10 @@ static hipError_t stream_take(int device, hipStream_t *out) {
   }
   return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
-// A query lane's stream.  CC_QUERY_CUS = "a/b" (a of every b CUs of each XCD) or "xa/b" (a of every b XCDs) keeps the
-// lanes' kernels off the other CUs (hipExtStreamCreateWithCUMask; bit i of the mask is CU i / 8 of XCD i % 8: the driver
-// deals the bits out to the XCDs in turn): in a pipelined loop the ingest stream is the critical path and its big
-// workgroups (79-158 KB of LDS) wait for CUs that many small query workgroups keep occupied.  Unset: the pool's stream.
-static std::vector<hipStream_t> g_masked_streams;  // (never pooled: their mask is part of them)
-static hipError_t lane_stream_take(int device, hipStream_t *out) {
-  const char *e = getenv("CC_QUERY_CUS");
-  if (e && *e && *e != '-') {
-    const bool by_xcd = e[0] == 'x';
-    int a = 0, b = 0;
-    if (sscanf(by_xcd ? e + 1 : e, "%d/%d", &a, &b) == 2 && a > 0 && b >= a) {
-      hipDeviceProp_t pr;
-      if (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) {
-        const int n_cu = pr.multiProcessorCount, n_xcd = 8;
-        std::vector<uint32_t> words((size_t)(n_cu + 31) / 32, 0u);
-        for (int i = 0; i < n_cu; i++) {
-          const int unit = by_xcd ? i % n_xcd : i / n_xcd;
-          if (unit % b < a) words[(size_t)i / 32] |= 1u << (i % 32);
-        }
-        const hipError_t r = hipExtStreamCreateWithCUMask(out, (uint32_t)words.size(), words.data());
-        if (r == hipSuccess) {
-          std::lock_guard<std::mutex> lk(g_rt_mu);
-          g_masked_streams.push_back(*out);
-        }
-        return r;
-      }
-    }
-  }
-  return stream_take(device, out);
-}
 static void stream_give(int device, hipStream_t s) {
   hipStreamSynchronize(s);
   if (device >= 0 && device < CC_RT_MAX_DEV) {
     std::lock_guard<std::mutex> lk(g_rt_mu);
-    for (size_t i = 0; i < g_masked_streams.size(); i++)
-      if (g_masked_streams[i] == s) {
-        g_masked_streams.erase(g_masked_streams.begin() + (long)i);
-        hipStreamDestroy(s);
-        return;
-      }
     if (g_stream_pool[device].size() < 32) {
       g_stream_pool[device].push_back(s);
       return;
@@ -366,28 +324,12 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
     CREATE_CHK(hipHostMalloc((void **)&c->h_off[i], sizeof(long long) * ((max_batch_scans > CC_SCAN_BATCH_MAX ? max_batch_scans : CC_SCAN_BATCH_MAX) + 1), hipHostMallocDefault));
     CREATE_CHK(hipEventCreateWithFlags(&c->off_ev[i], hipEventDisableTiming));
   }
-  if (getenv("CC_K2_PHASES"))  // (a channel launch brings up to CC_SCAN_BATCH_MAX scans whatever max_batch_scans is)
-    CREATE_CHK(hipMalloc(&c->d_phase_clk, sizeof(long long) * CC_K2_NCLK * (size_t)(max_batch_scans > CC_SCAN_BATCH_MAX ? max_batch_scans : CC_SCAN_BATCH_MAX)));
   c->lds1 = ((nc * 4 + 15) & ~(size_t)15) + ((nc + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15);
   c->lds2 = CC_K2_LDS_BYTES(nc);
-  {
-    const char *e = getenv("CC_K2_LDS_PAD");  // tuning aid, read once: extra bytes asked for (above 80 KB one scan per CU instead of two)
-    if (e && atoi(e) > 0 && atoi(e) <= 65536) c->lds2 += (size_t)atoi(e);
-  }
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
-  {
-    const char *e = getenv("CC_K1_DIV");  // tuning aid, read once
-    c->k1_div = (e && atoi(e) == 1) ? 1 : 0;
-    const char *e2 = getenv("CC_K1_NOSPLIT");
-    c->k1_nosplit = (e2 && atoi(e2) == 1) ? 1 : 0;
-    const char *e4 = getenv("CC_K1_WGS");
-    c->k1_wgs = (e4 && atoi(e4) > 0) ? atoi(e4) : 0;
-    const char *e3 = getenv("CC_K1_DENSE");
-    c->k1_dense = (e3 && atoi(e3) == 1) ? 1 : 0;
-  }
   if (nc > (size_t)CC_MAX_CELLS) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: grid larger than 150 x 150 cells");
@@ -414,46 +356,6 @@ int cc_profile_read(cc_ctx *c, double ms_out[2], int *n_launches) {
   if (!c || !ms_out) return set_err(CC_EINVAL, "cc_profile_read: bad argument");
   HIPCHK(hipSetDevice(c->device));
   if (prof_flush(c) != CC_OK) return set_err(CC_EHIP, "cc_profile_read: event sync failed");
-  if (c->d_phase_clk) {  // tuning aid: mean phase durations of the last launch, in microseconds (100 MHz wall clock)
-    std::vector<long long> h(CC_K2_NCLK * (size_t)c->max_batch);
-    HIPCHK(hipMemcpy(h.data(), c->d_phase_clk, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-    const int n = c->max_batch < 256 ? c->max_batch : 256;
-    double ph[9] = {0}, sub[8] = {0}, lv[6] = {0}, sa[4] = {0};
-    for (int i = 0; i < n; i++) {
-      const long long *p = &h[(size_t)i * CC_K2_NCLK];
-      ph[0] += p[1] * 0.01;
-      ph[1] += p[2] * 0.01;
-      ph[2] += p[3] * 0.01;
-      ph[3] += (p[5] - p[4]) * 0.01;
-      ph[4] += (p[6] - p[5]) * 0.01;
-      ph[5] += (p[7] - p[6]) * 0.01;
-      ph[6] += (p[8] - p[7]) * 0.01;
-      ph[7] += (p[8] - p[0]) * 0.01;
-      sub[0] += (p[9] - p[0]) * 0.01;    // fill + active list
-      sub[1] += (p[11] - p[10]) * 0.01;  // list starts + member lists
-      sub[2] += (p[12] - p[11]) * 0.01;  // lane walk
-      sub[3] += (p[4] - p[12]) * 0.01;   // eight-lane walk
-      sub[4] += p[14] * 0.01;            // keys: RoI lists
-      sub[5] += p[15] * 0.01;            // keys: division sums
-      for (int j = 0; j < 6; j++) lv[j] += p[16 + j] * 0.01;
-      sa[0] += (p[22] - p[0]) * 0.01;
-      sa[1] += (p[23] - p[22]) * 0.01;
-      sa[2] += (p[24] - p[23]) * 0.01;
-      sa[3] += (p[9] - p[24]) * 0.01;
-    }
-    fprintf(stderr, "[cc_k_contours phases, mean us over %d scans] ccl %.1f  enum+bbox %.1f  walk %.1f  order+sort %.1f  emit %.1f  keys %.1f  bci %.1f  | total %.1f\n",
-            n, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n, ph[5] / n, ph[6] / n, ph[7] / n);
-    fprintf(stderr, "[cc_k_contours sub-phases] fill+list %.1f | walk: member lists %.1f  lane walk %.1f  eight-lane walk %.1f | keys: RoI lists %.1f  division sums %.1f\n",
-            sub[0] / n, sub[1] / n, sub[2] / n, sub[3] / n, sub[4] / n, sub[5] / n);
-    {
-      cc_k2_big_queue hq;
-      HIPCHK(hipMemcpy(&hq, c->main.d_midq, sizeof(hq), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[cc_k_contours] scans handed to the mid path so far: %d (configuration %d, cells / slots %d, components %d, list padding %d)\n", hq.total, hq.why[0], hq.why[1], hq.why[2], hq.why[3]);
-    }
-    fprintf(stderr, "[cc_k_contours list stage A] levels %.1f  chunk ballots %.1f  prefix %.1f  entries + run labels %.1f\n", sa[0] / n, sa[1] / n, sa[2] / n, sa[3] / n);
-    fprintf(stderr, "[cc_k_contours level loop, summed over the levels] unions %.1f  flatten+count %.1f  kept roots %.1f  rank %.1f  bbox/area %.1f  records %.1f\n",
-            lv[0] / n, lv[1] / n, lv[2] / n, lv[3] / n, lv[4] / n, lv[5] / n);
-  }
   ms_out[0] = c->ms_acc[0];
   ms_out[1] = c->ms_acc[1];
   if (n_launches) *n_launches = c->launches;
@@ -463,14 +365,6 @@ int cc_profile_read(cc_ctx *c, double ms_out[2], int *n_launches) {
 }
 
 int cc_destroy(cc_ctx *c) {
-#ifdef CC_TUNE_K1_CLK
-  {
-    unsigned long long h[8] = {0};
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(cc_k1_clk), sizeof h) == hipSuccess)
-      fprintf(stderr, "[cc_k_rasterize clocks, ticks of 10 ns summed over workgroups (thread 0)] init %llu | A %llu | barrier %llu | B %llu | barrier %llu | emit %llu\n", h[0], h[1], h[2],
-              h[3], h[4], h[5]);
-  }
-#endif
   if (!c) return CC_OK;
   hipSetDevice(c->device);
   for (auto &e : c->ev) hipEventDestroy(e);
@@ -488,7 +382,6 @@ int cc_destroy(cc_ctx *c) {
     if (c->h_off[i]) hipHostFree(c->h_off[i]);
     if (c->off_ev[i]) hipEventDestroy(c->off_ev[i]);
   }
-  hipFree(c->d_phase_clk);
   if (c->s_loop) {
     stream_give(c->device, c->s_loop);
   }
@@ -529,10 +422,8 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const float *d_xyzi, const i
     c->off_busy[slot] = true;
     const float4 *pts = (const float4 *)d_xyzi + h_offsets[b0];
     // K1's dense image / positions: for the debug outputs, for a configuration K2's list kernel hands on as a whole
-    // (min_cont_cell_cnt_ > 3), CC_K1_DENSE=1 (tuning aid); otherwise only for scans whose active cells overflow the list
-    // CC_K1_WGS: fewer K1 workgroups, each keeping its CU for scans b, b + grid, ... (k_rasterize.h; tuning aid)
-    const int k1_grid = (c->k1_wgs > 0 && nb > c->k1_wgs) ? c->k1_wgs : nb;
-    const int want_dense = ((dbg && (dbg->d_bev || dbg->d_pix_rc)) || c->dcfg.min_cont_cell_cnt > 3 || c->k1_dense) ? 1 : 0;
+    // (min_cont_cell_cnt_ > 3); otherwise only for scans whose active cells overflow the list
+    const int want_dense = ((dbg && (dbg->d_bev || dbg->d_pix_rc)) || c->dcfg.min_cont_cell_cnt > 3) ? 1 : 0;
     if (dbg && dbg->d_pix_rc)
       hipLaunchKernelGGL(cc_k_fill_f32, dim3(512), dim3(256), 0, stream, (float *)S.d_pix, -1.f, nc * 2 * nb);
     hipEvent_t *pe = nullptr;
@@ -542,7 +433,7 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const float *d_xyzi, const i
       c->ev_used += 3;
       HIPCHK(hipEventRecord(pe[0], stream));
     }
-    if (nb <= CC_K1_SPLIT_MAX_SCANS && !c->k1_nosplit) {
+    if (nb <= CC_K1_SPLIT_MAX_SCANS) {
       // a handful of scans (the per-scan loop brings one): CC_K1_SPLIT workgroups per scan sweep a range of its points each,
       // a second small kernel combines the ranges (first range wins ties: file order)
       if (!S.k1_part.key) {
@@ -551,24 +442,24 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const float *d_xyzi, const i
         HIPCHK(hipMalloc(&S.k1_part.idx, sizeof(int) * np * nc));
         HIPCHK(hipMalloc(&S.k1_part.red, sizeof(unsigned) * np * 2));
       }
-      if (c->dcfg.reso_pow2 && !c->k1_div)
+      if (c->dcfg.reso_pow2)
         hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
-                           (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense, nb * CC_K1_SPLIT);
+                           (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
       else
         hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
-                           (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense, nb * CC_K1_SPLIT);
+                           (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
       hipLaunchKernelGGL(cc_k_rasterize_merge, dim3(nb), dim3(1024), 0, stream, c->dcfg, pts, (const long long *)S.d_offsets, S.k1_part, S.d_bev,
                          S.d_pix, S.d_k1, S.list, want_dense);
-    } else if (c->dcfg.reso_pow2 && !c->k1_div)
-      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true>), dim3(k1_grid), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts, (const long long *)S.d_offsets,
-                         S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense, nb);
+    } else if (c->dcfg.reso_pow2)
+      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts, (const long long *)S.d_offsets,
+                         S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
     else
-      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false>), dim3(k1_grid), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts, (const long long *)S.d_offsets,
-                         S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense, nb);
+      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts, (const long long *)S.d_offsets,
+                         S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
     if (pe) HIPCHK(hipEventRecord(pe[1], stream));
     int16_t *lab = (dbg && dbg->d_labels) ? dbg->d_labels + (size_t)b0 * CC_NLEV * nc : nullptr;
     hipLaunchKernelGGL(cc_k_contours, dim3(nb), dim3(CC_K2_BLOCK), (size_t)CC_K2L_LDS_BYTES, stream, c->dcfg, (const float *)S.d_bev,
-                       (const float2 *)S.d_pix, (const cc_k1_scan_out *)S.d_k1, S.d_scr, d_out + b0, lab, c->d_phase_clk, S.d_midq, S.list);
+                       (const float2 *)S.d_pix, (const cc_k1_scan_out *)S.d_k1, S.d_scr, d_out + b0, lab, S.d_midq, S.list);
     // the scans the list kernel handed on (more active cells / components than its LDS tables hold): the original body.
     // Its workgroups need 78 KB of LDS each to START, even those that find the queue empty and leave at once: behind a
     // pipelined ingest 512 of them waited 0.13 ms for their turns (the other streams' kernels hold the LDS).  So the

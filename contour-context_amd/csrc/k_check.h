@@ -64,15 +64,7 @@ struct cc_check_params {
   cc_score_t lb;
   int size_class[3];  // stage A: overlap counts that separate the four size classes of the check list (CC_A_CLASSES)
   int cstl_class[3];  // compaction: constellation lengths that separate the four size classes of stage B2's list (CC_B2_CLASSES)
-#ifdef CC_TUNE
-  int ablate;  // tuning aid (CC_ABLATE): stage B1 stops after its n-th part (1..5), stage B2 after part n - 10 (11..13)
-#endif
 };
-#ifdef CC_TUNE
-#define CC_ABLATE_AT(n) if (P.ablate == (n)) continue
-#else
-#define CC_ABLATE_AT(n)
-#endif
 
 struct cc_chk_item {  // a check that passed stage A
   int q, t;  // t: slot * CC_KNN_MAX + j in the low 16 bits, the two point tables' sizes above (see cc_k_check_a)
@@ -509,8 +501,8 @@ __device__ __forceinline__ void cc_b1_sort(cc_b1_lds<PPM> &L, int npp, int ntp, 
 // Two instances: <CC_PP_SMALL, false> handles every check with <= 64 potential pairs and lists the others;
 // <CC_PP_MAX, true> then runs only those.
 // grid = any (grid-stride over the device-side list), block = 64
-template <int PPM, bool REDO, int WPE = 4>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8)))
+template <int PPM, bool REDO>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
 cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
               const cc_chk_item *__restrict__ items, int *__restrict__ redo_idx, int *__restrict__ cnt, cc_cstl_item *__restrict__ cstl,
               int *__restrict__ pass_cnt, int *__restrict__ scores /*see cc_k_check_a; or nullptr*/,
@@ -564,7 +556,6 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       }
     }
     cc_group_sync();
-    CC_ABLATE_AT(1);
     // src points are sorted by bit_pos: the partners of a tgt point are the contiguous range [lo, hi)
     int npp_all = 0;
     for (int r0 = 0; r0 < ntp; r0 += G) {
@@ -599,7 +590,6 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       if (k < ntp) L.g.off[k] = (unsigned short)(npp_all + incl - cnt_k);
       npp_all += cc_group_sum_i(cnt_k);
     }
-    CC_ABLATE_AT(2);
     int flags = 0;
     int npp = npp_all;
     if (npp > PPM) {
@@ -617,9 +607,7 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       continue;
     }
     cc_b1_gen_pairs<PPM>(L, ntp, sl);
-    CC_ABLATE_AT(3);
     cc_b1_sort<PPM>(L, npp, ntp, sl);
-    CC_ABLATE_AT(4);
     // circular window of width pi/16 (contour_mng.h:344-357): for each start p1 the furthest p2, then the first start
     // that attains the maximum length (what the two-pointer loop records)
     const float angular_range = (float)(3.14159265358979323846 / 16);
@@ -654,7 +642,6 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       beg = 0;
     }
     if (sc && sl == 0) sc[2] = longest;
-    CC_ABLATE_AT(5);
     if (longest < P.lb.i_in_ang_rng) continue;
     // hand the constellation over to stage B2: the window pairs in sorted order, then the anchors (cstl_in order)
     int n_in = longest + 1;
@@ -695,7 +682,6 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       drec->flags = CC_DYN_PAIR(ncs, 0);  // checkConstellCorrespSim returns i_orie_sim = 0 when it stops here (contour_mng.h:1168)
       if (ncs < P.lb.i_indiv_sim) dyn_ok[(size_t)q * CC_CHK_STRIDE + t] = 2;
     }
-    CC_ABLATE_AT(6);
     if (ncs < P.lb.i_indiv_sim) continue;
     if (sl == 0) {
       out->q = q;
@@ -815,7 +801,6 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       }
     }
     int ncs = ncs_in;
-    CC_ABLATE_AT(11);
     cc_group_sync();
     // part 2: the "shaft" (contour_mng.h:1173-1184).  The reference scans the (i, j<i) pairs of the first <=10 entries in
     // order, replacing the running (normalised) src vector whenever the candidate is LONGER THAN THE RUNNING VECTOR'S NORM
@@ -886,7 +871,6 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
         }
       }
     }
-    CC_ABLATE_AT(12);
     // orientation test per pair (order-independent), then the order-dependent swap-to-back removal (contour_mng.h:1186-1201)
     unsigned long long rmm = 0ull;
 #pragma unroll
@@ -938,7 +922,6 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       ncs = L.misc[0];
     }
     if (sc && sl == 0) sc[4] = ncs;
-    CC_ABLATE_AT(13);
     if (ncs < P.lb.i_orie_sim) {
       if (dyn && sl == 0) {
         pass[(size_t)q * CC_CHK_STRIDE + t].flags = CC_DYN_PAIR(n_in, ncs);

@@ -70,7 +70,6 @@ struct cc_k2_big_queue {  // filled by the fast launch, drained by the slow one 
   int why[4];   // ... by reason (list kernel: configuration, cells / slots, components per level, list padding)
   int scan[1];  // [max_batch] follows
 };
-#define CC_K2_NCLK 32    // phase-clock slots per scan (tuning aid)
 #define CC_K2_OWN 6       // list entries a thread keeps in registers (beyond: read from the scratch block; a street scene has
                           // 3-4 k active cells: with four per thread half of them were re-read from the scratch block -- an L2 round
                           // trip -- in every pass of every level)
@@ -200,29 +199,6 @@ __device__ __noinline__ int cc_k2_drop_small(int min_cnt, int n_kept, unsigned *
   return n_new;
 }
 
-// optional phase timestamps (tuning aid): phase_clk[scan*CC_K2_NCLK + i], written by thread 0; the macros below expect
-// `phase_clk`, `scan`, `tid`, `tmark`, `tsub` in scope
-#define CC_K2_STAMP(i)                                                                     \
-  do {                                                                                     \
-    if (phase_clk && threadIdx.x == 0) phase_clk[(size_t)scan * CC_K2_NCLK + (i)] = (long long)wall_clock64(); \
-  } while (0)
-#define CC_K2_SUBLAP(j)                                                                   \
-  do {                                                                                    \
-    if (phase_clk) {                                                                      \
-      const long long now_ = (long long)wall_clock64();                                   \
-      if (tid == 0) phase_clk[(size_t)scan * CC_K2_NCLK + 16 + (j)] += now_ - tsub; \
-      tsub = now_;                                                                        \
-    }                                                                                     \
-  } while (0)
-#define CC_K2_LAP(acc)                                     \
-  do {                                                     \
-    if (phase_clk) {                                       \
-      const long long now_ = (long long)wall_clock64();    \
-      acc += now_ - tmark;                                 \
-      tmark = now_;                                        \
-    }                                                      \
-  } while (0)
-
 // How the back half (ordering, emit, keys, BCI) looks up the level count of a cell: the cell-indexed level image of the
 // original front half, or the list front half's occupancy bit map + per-entry level bytes.
 struct cc_k2_levmap {
@@ -248,13 +224,12 @@ __device__ __forceinline__ int cc_k2_lev_at(const cc_k2_levmap &M, int cell) {
 template <int NC, bool BIG, bool LISTED>
 __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *__restrict__ pix, const cc_k1_scan_out *__restrict__ k1_out,
                                            cc_k2_scratch_t<NC> *__restrict__ scr, cc_k2_big_tables *__restrict__ bigtab, int scan,
-                                           cc_scan_desc_t *__restrict__ desc_out, int16_t *__restrict__ labels_dbg, long long *__restrict__ phase_clk,
+                                           cc_scan_desc_t *__restrict__ desc_out, int16_t *__restrict__ labels_dbg,
                                            char *R, const int *n_lev_in, int flags_in, const cc_k2_levmap &lm) {
   const int n_cell = cfg.n_cell, n_col = cfg.n_col, n_row = cfg.n_row;
   const int tid = threadIdx.x, nt = blockDim.x;
   const int wave_id = tid >> 6, lane = tid & 63, n_waves = nt >> 6;
   cc_scan_desc_t *desc = desc_out + scan;
-  long long tmark = 0;
   // =========================== phase "order": region R re-carved ===========================
   int n_lev[CC_NLEV];
   for (int l = 0; l < CC_NLEV; l++) n_lev[l] = n_lev_in[l];
@@ -328,7 +303,6 @@ __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *
     if (lane == 0) sh2[l] = tot;
   }
   __syncthreads();
-  CC_K2_STAMP(5);
   // emit sorted contour tables + header
   for (int l = 0; l < CC_NLEV; l++) {
     const int n = n_lev[l] < CC_MAXC ? n_lev[l] : CC_MAXC;
@@ -381,7 +355,6 @@ __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *
   }
   __syncthreads();
 
-  CC_K2_STAMP(6);
   // =========================== phase "keys" (contour_mng.h:693-830) ===========================
   // R2 layout: divs f32 [36][35] (5040) | cntp int[36] | valid int[36] | acc int[36] | bci tmp | bci pts
   float *divs = (float *)R2;
@@ -428,8 +401,6 @@ __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *
     float *ldist = (float *)R;
     unsigned char *lhi = (unsigned char *)(R + (size_t)CC_KEYS_GRP * CC_KEYS_CAP * 4);
     int *lcnt = (int *)(R + (size_t)CC_KEYS_GRP * CC_KEYS_CAP * 5);
-    long long acc_klist = 0, acc_kexp = 0;
-    tmark = phase_clk ? (long long)wall_clock64() : 0;
     // groups of CC_KEYS_GRP VALID anchors (a street scene has ~18 of the 36: one group)
     for (int g0 = 0; g0 < NV; g0 += CC_KEYS_GRP) {
       for (int av = g0 + wave_id; av < g0 + CC_KEYS_GRP && av < NV; av += n_waves) {
@@ -538,7 +509,6 @@ __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *
         if (lane == 0) lcnt[av - g0] = n;
       }
       __syncthreads();
-      CC_K2_LAP(acc_klist);
       // Four lanes per (anchor, division) (round 6; one before): 36 x 35 sums of up to 400 f64 exp each kept 420 of the 512
       // lanes busy for two rounds of anchors.  The quad's lanes take the list's cells i, i + 1, i + 2, i + 3, every lane adds
       // the four products in list order (the first lane's sum is the one kept): the same f32 additions in the same order --
@@ -576,11 +546,6 @@ __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *
         }
       }
       __syncthreads();
-      CC_K2_LAP(acc_kexp);
-    }
-    if (phase_clk && tid == 0) {
-      phase_clk[(size_t)scan * CC_K2_NCLK + 14] = acc_klist;
-      phase_clk[(size_t)scan * CC_K2_NCLK + 15] = acc_kexp;
     }
   }
   for (int t = tid; t < NA * CC_KEY_DIM; t += nt) {
@@ -607,7 +572,6 @@ __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *
   }
   __syncthreads();
 
-  CC_K2_STAMP(7);
   // =========================== phase "BCI" (contour_mng.h:848-883) ===========================
   struct bci_tmp {
     int ok;
@@ -725,7 +689,6 @@ __device__ __forceinline__ void cc_k2_back(const cc_dev_cfg &cfg, const float2 *
     dst[1] = __float_as_uint(r);
     dst[2] = __float_as_uint(th);
   }
-  CC_K2_STAMP(8);
 }
 
 // The kernel body.  NC = components per level it handles exactly; BIG = the per-component tables live in `bigtab` (global)
@@ -734,9 +697,8 @@ template <int NC, bool BIG>
 __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *__restrict__ bev_in, const float2 *__restrict__ pix_in,
                                            const cc_k1_scan_out *__restrict__ k1_out, cc_k2_scratch_t<NC> *__restrict__ scr,
                                            cc_k2_big_tables *__restrict__ bigtab, cc_k2_big_queue *__restrict__ queue, int scan,
-                                           cc_scan_desc_t *__restrict__ desc_out, int16_t *__restrict__ labels_dbg, long long *__restrict__ phase_clk,
+                                           cc_scan_desc_t *__restrict__ desc_out, int16_t *__restrict__ labels_dbg,
                                            char *smem) {
-  CC_K2_STAMP(0);
   const int n_cell = cfg.n_cell, n_col = cfg.n_col, n_row = cfg.n_row;
   const int tid = threadIdx.x, nt = blockDim.x;
 
@@ -836,14 +798,7 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
     }                                                                            \
   }
 
-  CC_K2_STAMP(9);
   int prev_n = 0;
-  long long acc_ccl = 0, acc_enum = 0, acc_walk = 0, tmark = phase_clk ? (long long)wall_clock64() : 0;
-  // per pass of the level loop, summed over the levels: accumulated in the clock block itself (thread 0), so that the
-  // production launch (phase_clk == nullptr) carries no accumulator registers for it
-  long long tsub = tmark;
-  if (phase_clk && tid == 0)
-    for (int j = 0; j < 6; j++) phase_clk[(size_t)scan * CC_K2_NCLK + 16 + j] = 0;
   unsigned *w_minc = W + NC, *w_maxc = W + 2 * NC, *w_area = W + 3 * NC, *w_cB = W + 4 * NC;
   // "has a second cell" / "has a third cell" bit per root (the kept test of a level), over the working arrays
   unsigned *bitA = (unsigned *)(R + 45056), *bitB = bitA + ((n_cell + 31) >> 5);
@@ -936,7 +891,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
         }
       }
     __syncthreads();
-    CC_K2_SUBLAP(0);
     // (b) every cell is pointed at its root (a concurrent find that passes through the cell meets either its old parent or
     //     the root: both lead to the root); the owned cells' finds advance hop by hop TOGETHER (eight LDS reads in flight,
     //     not eight chains one after the other).  Which roots own >= min_cont_cell_cnt_ (3) cells: a member that is not the
@@ -997,8 +951,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
         }
       }
     __syncthreads();
-    CC_K2_SUBLAP(1);
-    CC_K2_LAP(acc_ccl);
     // (c) kept roots, numbered by cell index = raster order of their first cells.  The active list IS in raster order: a
     //     kept root's number is the count of kept roots before it in the list -- ballots per 64-entry stretch (thread t's
     //     u-th cell is entry u * nt + t: a wave's u-th cells are one stretch) and a prefix sum over the stretches.  (Round 4:
@@ -1025,7 +977,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
         if (lane == 0) scnt[(ib >> 6) + wave_id] = (unsigned char)__popcll(m);
       }
     __syncthreads();
-    CC_K2_SUBLAP(2);
     // every wave makes the whole prefix array (identical values from all of them) and then reads its own entries
     int n_kept = 0;
     {
@@ -1082,7 +1033,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
       }
     if (n_kept > NC) n_kept = NC;
     __syncthreads();
-    CC_K2_SUBLAP(3);
     // (d) per component: area, column range, last cell of the raster order, first member column of the second row
     //     (the root IS the first cell: first row and its first member column need no search), and for the walk the
     //     component index of every member cell (list position -> index, in the scratch block)
@@ -1134,8 +1084,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
         __syncthreads();
       }
     }
-    CC_K2_SUBLAP(4);
-    CC_K2_LAP(acc_enum);
     // (e) component records; parents of the level above (processed in the previous iteration): index of the root that
     //     owns the child's root cell
     for (int k = tid; k < prev_n; k += nt) {
@@ -1167,7 +1115,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
     if (tid == 0) sh[8 + l] = n_kept;
     prev_n = n_kept;
     __syncthreads();
-    CC_K2_SUBLAP(5);
   }
   // More components on a level than this instance numbers: the scan goes to the slow path (cc_k_contours_big), which
   // redoes it with room for CC_NC_BIG per level; nothing of this workgroup's output is kept (block-uniform exit).
@@ -1211,7 +1158,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
       n_tot += sh[8 + l];
     }
     lev_base[CC_NLEV] = n_tot;
-    CC_K2_STAMP(10);
     for (int l = wave_id; l < CC_NLEV; l += n_waves) {  // list starts: exclusive prefix sum of the areas, each rounded up to a multiple of 8
       const int n = sh[8 + l];
       int run = 0;
@@ -1264,7 +1210,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
     }
     __threadfence_block();
     __syncthreads();
-    CC_K2_STAMP(11);
     for (int w = tid; w < n_tot; w += nt) {
       int l = 0;
       for (int e = 1; e < CC_NLEV; e++) l += (w >= lev_base[e]) ? 1 : 0;
@@ -1361,7 +1306,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
       scr->cont[l][k] = cvw;
     }
     __syncthreads();
-    CC_K2_STAMP(12);
     // The large components (a street scene's ground-connected blob holds a few thousand cells): one lane adding nine running
     // values per cell is ~75 cycles per cell whatever the other 63 lanes do, and the phase lasted as long as the largest
     // component.  Every running sum is a sequential chain of its own, so EIGHT LANES share a component, one sum each
@@ -1470,13 +1414,6 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
     }
     __syncthreads();
   }
-  CC_K2_LAP(acc_walk);
-  if (phase_clk && tid == 0) {
-    phase_clk[(size_t)scan * CC_K2_NCLK + 1] = acc_ccl;
-    phase_clk[(size_t)scan * CC_K2_NCLK + 2] = acc_enum;
-    phase_clk[(size_t)scan * CC_K2_NCLK + 3] = acc_walk;
-  }
-  CC_K2_STAMP(4);
   __threadfence_block();
   __syncthreads();
   int n_lev_f[CC_NLEV];
@@ -1490,5 +1427,5 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
   lm.g_rc = nullptr;
   lm.g_pix = nullptr;
   lm.n_act = 0;
-  cc_k2_back<NC, BIG, false>(cfg, pix, k1_out, scr, bigtab, scan, desc_out, labels_dbg, phase_clk, R, n_lev_f, flags_f, lm);
+  cc_k2_back<NC, BIG, false>(cfg, pix, k1_out, scr, bigtab, scan, desc_out, labels_dbg, R, n_lev_f, flags_f, lm);
 }

@@ -113,8 +113,7 @@ __device__ __forceinline__ void cc_uf_union_h(uint16_t *LAB, unsigned a, unsigne
 __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const float *__restrict__ bev_in, const float2 *__restrict__ pix_in,
                                                  cc_k2_scratch *__restrict__ scr, cc_k2_big_queue *__restrict__ midq, int scan,
                                                  cc_scan_desc_t *__restrict__ desc_out, int16_t *__restrict__ labels_dbg,
-                                                 long long *__restrict__ phase_clk, char *smem, int *n_lev_out, const cc_k1_list_out &list) {
-  CC_K2_STAMP(0);
+                                                 char *smem, int *n_lev_out, const cc_k1_list_out &list) {
   const int n_cell = cfg.n_cell, n_col = cfg.n_col;
   const int tid = threadIdx.x, nt = blockDim.x;
   const int wave_id = cc_wave_id(), lane = tid & 63, n_waves = nt >> 6;
@@ -152,9 +151,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
 
   const float *bev = bev_in + (size_t)scan * n_cell;
   const float2 *pix = pix_in + (size_t)scan * n_cell;
-  long long acc_ccl = 0, acc_enum = 0, acc_walk = 0, tmark = phase_clk ? (long long)wall_clock64() : 0, tsub = tmark;
-  if (phase_clk && tid == 0)
-    for (int j = 0; j < 6; j++) phase_clk[(size_t)scan * CC_K2_NCLK + 16 + j] = 0;
 
   // ---- (A) the scan's active cells come as a raster-ordered list from K1 (k_rasterize.h: cc_k1_emit -- it has every cell's
   //      height in LDS when it writes the image): (row, col) and level count per entry.  Here: the occupancy bit map and
@@ -185,7 +181,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
       for (int i = tid; i < CC_NLEV * n_cell; i += nt) labels_dbg[(size_t)scan * CC_NLEV * n_cell + i] = (int16_t)-1;
   }
   __syncthreads();
-  CC_K2_STAMP(22);
   for (int i = tid; i < n_act; i += nt) {
     const unsigned rcv = rc[i];
     const int c = (int)(rcv >> 8) * n_col + (int)(rcv & 255u);
@@ -198,7 +193,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     if (lane == 0) ssum[q] = (uint16_t)v;
   }
   __syncthreads();
-  CC_K2_STAMP(23);
   {
     const unsigned long long lane_le = lane_lt | (1ull << lane);
     int spre;  // slots before stretch `lane` (every wave makes the prefix for itself: <= 48 stretches, one lane each)
@@ -215,7 +209,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
       if (b < n_chunk) cbase[b] = (uint16_t)(run + incl - v);
       run += cc_wave_scan_total(incl);
     }
-    CC_K2_STAMP(24);
     for (int q = wave_id; q < n_str; q += n_waves) {
       const int i = q * 64 + lane;
       const bool valid = i < n_act;
@@ -243,9 +236,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
   }
   if (tid == 0) off[n_act] = (uint16_t)n_slot;
   __syncthreads();
-  CC_K2_STAMP(9);
-  tmark = phase_clk ? (long long)wall_clock64() : 0;
-  tsub = tmark;
 
   // ---- (B) 8-connected labelling of all level sets: one union per (adjacent pair, level both cells are in).  Backward
   //      neighbours only (W, NW, N, NE): W is the previous entry if its cell is; the row above through the bit map.  Labels
@@ -345,7 +335,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     }
   }
   __syncthreads();
-  CC_K2_SUBLAP(0);
   // ---- (C) every slot is pointed at its root (an entry's finds advance hop by hop together); which roots own >= 3 cells:
   //      a member that is not the root sets the root's bit in A, and in B if A was set already
   const int need = cfg.min_cont_cell_cnt < 3 ? cfg.min_cont_cell_cnt : 3;
@@ -375,8 +364,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     }
   }
   __syncthreads();
-  CC_K2_SUBLAP(1);
-  CC_K2_LAP(acc_ccl);
   // ---- (D) kept roots, numbered per level in raster order of their first cells: ballots per 64-entry stretch (a wave
   //      takes every n_waves-th stretch), a prefix over the <= 48 stretches per level in registers (one lane per stretch,
   //      every wave makes it for itself), then the same ballots again give the numbers.
@@ -392,7 +379,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     }
   }
   __syncthreads();
-  CC_K2_SUBLAP(2);
   int nk[CC_NLEV], pre[CC_NLEV];
   bool too_many = false;
 #pragma unroll
@@ -416,7 +402,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     }
   }
   __syncthreads();
-  CC_K2_SUBLAP(3);
   // ---- (E) component index of every slot, in place (a kept root carries 0x8000 | index; a member of a kept component
   //      reads it from its root and carries it from here on); members counted per component; a root's parent is the
   //      component its own cell belongs to one level down (the same entry's previous slot)
@@ -452,14 +437,11 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     }
   }
   __syncthreads();
-  CC_K2_SUBLAP(4);
-  CC_K2_LAP(acc_enum);
   // ---- (F) member lists: list starts (prefix of the areas, each rounded up to two entries: 4-byte aligned lists), then a
   //      wave per level sweeps the list, 64 entries at a time, and gives every member its rank inside its component
   //      (entries of one component meet through ballots; a running write pointer per component) -- a stable counting sort,
   //      so every list is in raster order
 #define CC_K2L_NK(l_) ((l_) == 0 ? nk[0] : (l_) == 1 ? nk[1] : (l_) == 2 ? nk[2] : (l_) == 3 ? nk[3] : (l_) == 4 ? nk[4] : nk[5])
-  CC_K2_STAMP(10);
   for (int l = wave_id; l < CC_NLEV; l += n_waves) {
     const int n = CC_K2L_NK(l);
     int run = 0;
@@ -574,7 +556,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     }
   }
   __syncthreads();
-  CC_K2_STAMP(11);
   // ---- (G) raster-order running statistics (contour_mng.cpp:317-331): ONE LANE per component walks its member list, eight
   //      members per step -- their heights / positions fetched before any is added, the tail of the last step masked to +0.0
   //      (every sum starts at +0.0 and never becomes -0.0, so x + 0.0 == x bit for bit) -- and finishes with calcStatVals;
@@ -695,7 +676,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
     finish_stats(l, k, a, ml, rec);
     finish_shape(l, k, a, ml, c0, c1, cB);
   }
-  CC_K2_STAMP(12);
   // The large components (a street scene's ground-connected blob): EIGHT LANES share one, one running sum each (a product
   // a * b with (a, b) picked per lane, 1.0 for the plain sums: the same values added in the same order), the f32 height sum
   // by every lane; lane 0 of the eight collects the sums and finishes.
@@ -761,13 +741,6 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
       if (on && role == 0) finish_stats(l, k, a, ml, rec);
     }
   }
-  CC_K2_LAP(acc_walk);
-  if (phase_clk && tid == 0) {
-    phase_clk[(size_t)scan * CC_K2_NCLK + 1] = acc_ccl;
-    phase_clk[(size_t)scan * CC_K2_NCLK + 2] = acc_enum;
-    phase_clk[(size_t)scan * CC_K2_NCLK + 3] = acc_walk;
-  }
-  CC_K2_STAMP(4);
 #pragma unroll
   for (int l = 0; l < CC_NLEV; l++) n_lev_out[l] = nk[l];
   return true;
@@ -781,13 +754,13 @@ __device__ __forceinline__ bool cc_k2_front_list(const cc_dev_cfg &cfg, const fl
 __global__ void __launch_bounds__(CC_K2_BLOCK, 4)
 cc_k_contours(cc_dev_cfg cfg, const float *__restrict__ bev_in, const float2 *__restrict__ pix_in,
               const cc_k1_scan_out *__restrict__ k1_out, cc_k2_scratch *__restrict__ scratch_all,
-              cc_scan_desc_t *__restrict__ desc_out, int16_t *__restrict__ labels_dbg, long long *__restrict__ phase_clk,
+              cc_scan_desc_t *__restrict__ desc_out, int16_t *__restrict__ labels_dbg,
               cc_k2_big_queue *__restrict__ midq, cc_k1_list_out list) {
   HIP_DYNAMIC_SHARED(char, smem)
   const int scan = (int)blockIdx.x;
   cc_k2_scratch *scr = scratch_all + scan;
   int n_lev[CC_NLEV];
-  if (!cc_k2_front_list(cfg, bev_in, pix_in, scr, midq, scan, desc_out, labels_dbg, phase_clk, smem, n_lev, list)) return;
+  if (!cc_k2_front_list(cfg, bev_in, pix_in, scr, midq, scan, desc_out, labels_dbg, smem, n_lev, list)) return;
   __threadfence_block();
   __syncthreads();
   cc_k2_levmap lm;
@@ -798,7 +771,7 @@ cc_k_contours(cc_dev_cfg cfg, const float *__restrict__ bev_in, const float2 *__
   lm.g_rc = list.rc + (size_t)scan * CC_LIST_CAP;
   lm.g_pix = list.pix + (size_t)scan * CC_LIST_CAP;
   lm.n_act = list.hdr[scan].x;
-  cc_k2_back<CC_NC, false, true>(cfg, pix_in + (size_t)scan * cfg.n_cell, k1_out, scr, nullptr, scan, desc_out, labels_dbg, phase_clk,
+  cc_k2_back<CC_NC, false, true>(cfg, pix_in + (size_t)scan * cfg.n_cell, k1_out, scr, nullptr, scan, desc_out, labels_dbg,
                                  smem + CC_K2L_O_REST, n_lev, 0, lm);
 }
 
@@ -860,7 +833,7 @@ cc_k_contours_mid(cc_dev_cfg cfg, float *bev_io, float2 *pix_io /*written here f
       __syncthreads();
       if (threadIdx.x == 0) list.hdr[scan].z = 1;
     }
-    cc_k2_body<CC_NC, false>(cfg, bev_io, pix_io, k1_out, scratch_all + scan, nullptr, bigq, scan, desc_out, labels_dbg, nullptr, smem);
+    cc_k2_body<CC_NC, false>(cfg, bev_io, pix_io, k1_out, scratch_all + scan, nullptr, bigq, scan, desc_out, labels_dbg, smem);
   }
 }
 
@@ -889,8 +862,6 @@ cc_k_contours_big(cc_dev_cfg cfg, const float *__restrict__ bev_in, const float2
       return;
     }
     cc_k2_body<CC_NC_BIG, true>(cfg, bev_in, pix_in, k1_out, &slots[blockIdx.x].scr, &slots[blockIdx.x].tab, nullptr, queue->scan[k], desc_out,
-                                labels_dbg, nullptr, smem);
+                                labels_dbg, smem);
   }
 }
-
-#undef CC_K2_STAMP

@@ -431,14 +431,6 @@ __device__ __forceinline__ void cc_gsync() {
 // evaluation, pool record) runs on full lanes.  Round 3 tested every pair in f64 and balloted once per tgt: K5's largest
 // part on contour-rich scans (0.66 ms of cc_k_gmm_init per 1 024 KITTI-shaped queries).
 #define CC_GMM_TCHUNK 64
-#ifdef CC_TUNE_GMM_CLK
-__device__ unsigned long long cc_gmm_scan_clk[8];  // tuning aid: cycles of the scan's parts, summed over the 64-lane problems (fill, f32 sweep, f64 tests, filing, flush, count)
-#define CC_CLK_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define CC_CLK_ADD(i, a, b) do { clk_acc[i] += (b) - (a); } while (0)
-#else
-#define CC_CLK_T(v)
-#define CC_CLK_ADD(i, a, b)
-#endif
 #define CC_GMM_LIST_CAP 256
 #define CC_GMM_PRE_MARGIN 0.01f
 struct alignas(16) cc_gmm_scan_lds {
@@ -474,9 +466,6 @@ template <int G, typename Flush>
 __device__ __forceinline__ int cc_gmm_scan_pairs(const cc_gmm_feat *__restrict__ fsrc, const cc_gmm_feat *__restrict__ ftgt, double tx, double ty,
                                                  double ct0, double st0, cc_gmm_scan_lds &L, int sl, Flush flush) {
   int cnt = 0, total = 0;
-#ifdef CC_TUNE_GMM_CLK
-  unsigned long long clk_acc[6] = {0, 0, 0, 0, 0, 0};
-#endif
   // The tgt chunks of all levels in one sequence, each chunk's (mean, major axis) values requested a chunk ahead: what a
   // chunk boundary costs is then the LDS hand-over, not a memory round trip.  A lane holds TPL tgts of the next chunk.
   constexpr int TPL = CC_GMM_TCHUNK / G;
@@ -528,7 +517,6 @@ __device__ __forceinline__ int cc_gmm_scan_pairs(const cc_gmm_feat *__restrict__
   while (li < CC_GMM_LEVELS) {
     const int ns = cnt_of(ns4, li), ntg = cnt_of(nt4, li);
     const int tn = ntg - t0 < CC_GMM_TCHUNK ? ntg - t0 : CC_GMM_TCHUNK;
-    CC_CLK_T(c_f0);
     cc_gsync<G>();  // the previous chunk is no longer read
 #pragma unroll
     for (int u = 0; u < TPL; u++) {
@@ -544,13 +532,9 @@ __device__ __forceinline__ int cc_gmm_scan_pairs(const cc_gmm_feat *__restrict__
     int li_n = li, t0_n = t0;
     next_chunk(li_n, t0_n);
     request(li_n, t0_n);
-    CC_CLK_T(c_f1);
-    CC_CLK_ADD(0, c_f0, c_f1);
     for (int s0 = 0; s0 < ns; s0 += G) {
       const int si = s0 + sl;
       unsigned long long mask = 0ull;
-      CC_CLK_T(c_p0);
-      unsigned long long c_p1v = 0;
       const float cmx = pmx, cmy = pmy, smaj = pmaj;
       if (si + G < ns) {
         const cc_ell *ps = &fsrc->ell[li][si + G];
@@ -583,9 +567,6 @@ __device__ __forceinline__ int cc_gmm_scan_pairs(const cc_gmm_feat *__restrict__
           cand |= (unsigned long long)((cc_brev(~m8) >> 24) & 0xffu) << tb;
         }
         if (!pre_ok) cand = tn >= 64 ? ~0ull : (1ull << tn) - 1ull;
-#ifdef CC_TUNE_GMM_CLK
-        c_p1v = __builtin_readcyclecounter();
-#endif
         // pass 2: the reference's f64 expression on the candidates (a handful per lane)
         while (cand) {
           const int tj = __ffsll((unsigned long long)cand) - 1;
@@ -593,23 +574,15 @@ __device__ __forceinline__ int cc_gmm_scan_pairs(const cc_gmm_feat *__restrict__
           if (tj < tn && cc_gmm_pair_near(sx - (double)L.Tx[tj], sy - (double)L.Ty[tj], smaj, L.Tm[tj])) mask |= 1ull << tj;
         }
       }
-      CC_CLK_T(c_p2);
-#ifdef CC_TUNE_GMM_CLK
-      if (c_p1v) { CC_CLK_ADD(1, c_p0, c_p1v); CC_CLK_ADD(2, c_p1v, c_p2); }
-#endif
       const int c = __popcll(mask);
       const int incl = cc_gscan_incl<G>(c, sl);
       const int tot = cc_gbcast_i<G>(incl, G - 1);
       if (tot == 0) continue;
       if (cnt + tot > CC_GMM_LIST_CAP) {
-        CC_CLK_T(c_q0);
         flush(cnt, false);
-        CC_CLK_T(c_q1);
-        CC_CLK_ADD(4, c_q0, c_q1);
         total += cnt;
         cnt = 0;
       }
-      CC_CLK_T(c_p3);
       if (tot <= CC_GMM_LIST_CAP) {
         int pos = cnt + incl - c;
         while (mask) {
@@ -618,8 +591,6 @@ __device__ __forceinline__ int cc_gmm_scan_pairs(const cc_gmm_feat *__restrict__
           L.code[pos++] = (unsigned)((li << 18) | (si << 9) | (t0 + tj));
         }
         cnt += tot;
-        CC_CLK_T(c_p4);
-        CC_CLK_ADD(3, c_p3, c_p4);
       } else {  // one (src chunk, tgt chunk) block with more hits than the list holds: lane by lane (a lane has <= 64)
         for (int l = 0; l < G; l++) {
           const int cl = cc_gbcast_i<G>(c, l);
@@ -644,15 +615,7 @@ __device__ __forceinline__ int cc_gmm_scan_pairs(const cc_gmm_feat *__restrict__
     li = li_n;
     t0 = t0_n;
   }
-  CC_CLK_T(c_q2);
   if (cnt > 0) flush(cnt, true);
-  CC_CLK_T(c_q3);
-  CC_CLK_ADD(4, c_q2, c_q3);
-  CC_CLK_ADD(5, 0ull, 1ull);
-#ifdef CC_TUNE_GMM_CLK
-  if (G == 64 && sl == 0)
-    for (int i = 0; i < 6; i++) atomicAdd(&cc_gmm_scan_clk[i], clk_acc[i]);
-#endif
   return total + cnt;
 }
 
@@ -828,12 +791,6 @@ __device__ __forceinline__ void cc_gmm_eval(const cc_gsrc &Q, int np, int sl, co
   auto add_term = [&](const cc_graw &w) {
     const cc_gpair P = cc_gmm_make_pair(w);
     const cc_gterm t = cc_gmm_term(P, p[0], p[1], c, s, c2, s2, exp_tab);
-#ifdef CC_TUNE_GMM_TWICE  // tuning aid: the pair arithmetic twice (what it costs = this build's K5 minus the product's)
-    {
-      const cc_gterm t2 = cc_gmm_term(P, p[0] + 1e-9, p[1], c * 1.000000001, s, c2 * 1.000000001, s2, exp_tab);  // nothing in common with the first but the loads
-      a += 1e-300 * (t2.v + t2.gx + t2.gy + t2.gt);
-    }
-#endif
     a += t.v;
     ax += t.gx;
     ay += t.gy;
@@ -866,11 +823,7 @@ __device__ __forceinline__ void cc_gmm_eval(const cc_gsrc &Q, int np, int sl, co
   if (sl < ng) w = load(sl);
   for (int j = sl; j < ng; j += G) {
     cc_graw n = w;
-#ifdef CC_TUNE_GMM_NOLOAD
-    if (j + G < ng && p[0] == 1.2345e-300) n = load(j + G);
-#else
     if (j + G < ng) n = load(j + G);
-#endif
     add_term(w);
     w = n;
   }
@@ -961,17 +914,7 @@ struct cc_gmm_ctx {  // what a line-search evaluation needs
   cc_gsrc Q;
   const double *exp_tab;  // cc_exp2_tab64 in LDS
   int np, sl;
-#ifdef CC_TUNE_GMM_CLK
-  unsigned long long *ev_clk;  // tuning aid: cycles spent in evaluations, their count
-  int *n_ev;
-#endif
 };
-#ifdef CC_TUNE_GMM_CLK  // tuning aid: per refined problem {np | G << 20 | iterations << 40 | evaluations << 48, cycles, cycles in evaluations, cycles filing pairs}
-#define CC_GMM_CLK_CAP 65536
-__device__ unsigned long long cc_gmm_clk[CC_GMM_CLK_CAP * 4];
-__device__ unsigned long long cc_gmm_clk2[CC_GMM_CLK_CAP * 4];  // wall clock (100 MHz) at start / end, HW_ID, -
-__device__ int cc_gmm_clk_n;
-#endif
 // ---- Ceres 2.x line search pieces (see oracle/orc_gmm.h for the provenance notes) ----
 struct cc_fs {  // FunctionSample; vector_x is not kept (it is pos + x * dir, recomputed where needed)
   double x, value, gradient;
@@ -1240,14 +1183,7 @@ __device__ __forceinline__ void cc_ls_eval(const cc_gmm_ctx &S, const double pos
   o->x = x;
   double vx[3];
   for (int i = 0; i < 3; i++) vx[i] = pos[i] + x * dir[i];
-#ifdef CC_TUNE_GMM_CLK
-  const unsigned long long t_ev = __builtin_readcyclecounter();
-#endif
   cc_gmm_eval<G>(S.Q, S.np, S.sl, vx, &o->value, o->vg, S.exp_tab);
-#ifdef CC_TUNE_GMM_CLK
-  *S.ev_clk += __builtin_readcyclecounter() - t_ev;
-  *S.n_ev += 1;
-#endif
   o->value_ok = isfinite(o->value);
   o->grad_ok = o->value_ok && isfinite(o->vg[0]) && isfinite(o->vg[1]) && isfinite(o->vg[2]);
   o->gradient = dir[0] * o->vg[0] + dir[1] * o->vg[1] + dir[2] * o->vg[2];
@@ -1420,19 +1356,9 @@ cc_k_gmm_refine(const cc_gmm_problem *__restrict__ probs, const int *__restrict_
       continue;
     }
     S.Q.glb = pool + (size_t)off * CC_GRAW_BYTES;
-#ifdef CC_TUNE_GMM_CLK
-    const unsigned long long t_p0 = __builtin_readcyclecounter();
-    const unsigned long long t_w0 = wall_clock64();
-    unsigned long long ev_clk = 0;
-    int n_ev = 0;
-#endif
     S.exp_tab = exp_tab;
     S.np = np;
     S.sl = sl;
-#ifdef CC_TUNE_GMM_CLK
-    S.ev_clk = &ev_clk;
-    S.n_ev = &n_ev;
-#endif
     cc_gsync<G>();  // the previous problem's records in LDS are no longer read
     double x[3] = {pb.tf[0], pb.tf[1], pb.tf[2]};
     double cost, g[3];
@@ -1440,9 +1366,6 @@ cc_k_gmm_refine(const cc_gmm_problem *__restrict__ probs, const int *__restrict_
     cc_gmm_eval_first<G>(codes, R.code_seg, fsrc, ftgt, S.Q, sl, x, &cost, g, exp_tab);
     __threadfence_block();  // the records are read back by other lanes of the problem
     cc_gsync<G>();
-#ifdef CC_TUNE_GMM_CLK
-    const unsigned long long t_p1 = __builtin_readcyclecounter();
-#endif
     const double denom = sqrt(fsrc->ac * ftgt->ac);
     {
     // ---- calcCorrelation (correlation.h:206-238): LineSearchMinimizer, LBFGS rank 20, Wolfe/cubic, <= 10 iterations
@@ -1555,22 +1478,6 @@ cc_k_gmm_refine(const cc_gmm_problem *__restrict__ probs, const int *__restrict_
     R.tf_opt[2] = x[2];
     }
     if (sl == 0) results[pidx] = R;
-#ifdef CC_TUNE_GMM_CLK
-    if (sl == 0) {
-      const unsigned long long t_p2 = __builtin_readcyclecounter();
-      const int e = atomicAdd(&cc_gmm_clk_n, 1);
-      if (e < CC_GMM_CLK_CAP) {
-        cc_gmm_clk[e * 4 + 0] = (unsigned long long)np | ((unsigned long long)G << 20) | ((unsigned long long)R.iterations << 40) | ((unsigned long long)n_ev << 48);
-        cc_gmm_clk[e * 4 + 1] = t_p2 - t_p0;
-        cc_gmm_clk[e * 4 + 2] = ev_clk;
-        cc_gmm_clk[e * 4 + 3] = t_p1 - t_p0;
-        cc_gmm_clk2[e * 4 + 0] = t_w0;
-        cc_gmm_clk2[e * 4 + 1] = wall_clock64();
-        cc_gmm_clk2[e * 4 + 2] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
-        cc_gmm_clk2[e * 4 + 3] = (unsigned long long)blockIdx.x;
-      }
-    }
-#endif
   }
 }
 // tidyUpCandidates' order-changing compaction (contour_db.h:580-592) followed by fineOptimize's std::sort on the

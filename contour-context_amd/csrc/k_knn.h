@@ -884,21 +884,11 @@ __device__ __forceinline__ float cc_knn_cut(unsigned long long *buf, int cnt, in
   return nub;
 }
 
-// grid = n_q_levels * ceil(nq * CC_NPIV / CC_KNN_TQ), block = 64 * CC_KNN_TW.  PH: the phase timers (tuning aid) are compiled in.
-template <bool PH>
+// grid = n_q_levels * ceil(nq * CC_NPIV / CC_KNN_TQ), block = 64 * CC_KNN_TW.
 __global__ void __launch_bounds__(64 * CC_KNN_TW)
 cc_k_knn_tile(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta, int nq,
-              const int *__restrict__ ordbuf /*cc_k_knn_order's output*/, cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt,
-              long long *__restrict__ phase_clk /*tuning aid (CC_KNN_PHASES=1), else nullptr: [grid][8] ticks of 10 ns*/) {
+              const int *__restrict__ ordbuf /*cc_k_knn_order's output*/, cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt) {
   __shared__ cc_knn_tlds L;
-  long long pc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // setup | step | barrier | pass | cut-back | results | rounds | passes
-  long long pt_ = PH ? wall_clock64() : 0;
-#define CC_KNN_TICK(slot)                      \
-  if (PH) {                                    \
-    const long long now_ = wall_clock64();     \
-    pc_[slot] += now_ - pt_;                   \
-    pt_ = now_;                                \
-  }
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // one workgroup slot per search and layer (at most that many groups; most slots exit at once), layers interleaved
   const int ll = blockIdx.x % P.n_q_levels, w = blockIdx.x / P.n_q_levels;
@@ -1040,10 +1030,8 @@ cc_k_knn_tile(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_
     }                                                                    \
   }
   if (mine) CC_KNN_TFETCH()
-  CC_KNN_TICK(0)
   int n_pass_ = 0;  // passes so far (workgroup-uniform)
   for (int par = 0;; par ^= 1) {
-    if (PH) pc_[6]++;
     if (has_left) {  // the rest of the last step's pairs first (the pass in between has emptied the queue)
       unsigned m = m_left;
       while (__ballot(m != 0u) != 0ull && wn + 64 <= CC_KNN_TWL) {
@@ -1149,9 +1137,7 @@ cc_k_knn_tile(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_
       L.wn[par][wave] = wn;
       L.go[par][wave] = (mine || has_left) ? 1 : 0;
     }
-    CC_KNN_TICK(1)
     __syncthreads();
-    CC_KNN_TICK(2)
     // ---- the queues: worked off once CC_KNN_TPASS pairs are pending, or when the walk is over
     int cum[CC_KNN_TW + 1];  // queue w holds the pairs cum[w] .. cum[w + 1] of the round's list
     cum[0] = 0;
@@ -1207,8 +1193,6 @@ cc_k_knn_tile(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_
           }
         }
         __syncthreads();
-        if (PH) pc_[7]++;
-        CC_KNN_TICK(3)
         // cut back the buffers that filled up: wave w looks after the searches w, w + 4, ...
         const int cnt_l = L.st[j].cnt, tight_l = L.st[j].tight;  // lane (j, kq): search j's
         unsigned long long due = __ballot(kq == 0 && j < ns && (j & (CC_KNN_TW - 1)) == wave && (cnt_l >= CC_KNN_TTRIG || (!tight_l && cnt_l >= nnk)));
@@ -1225,7 +1209,6 @@ cc_k_knn_tile(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_
           }
         }
         __syncthreads();
-        CC_KNN_TICK(4)
       }
       wn = 0;
       ubj = L.st[j].ub;
@@ -1260,8 +1243,4 @@ cc_k_knn_tile(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_
     }
     if (lane == 0) hit_cnt[slot] = mm;
   }
-  CC_KNN_TICK(5)
-#undef CC_KNN_TICK
-  if (PH && phase_clk && tid == 0)
-    for (int i = 0; i < 8; i++) phase_clk[(size_t)blockIdx.x * 8 + i] = pc_[i];
 }

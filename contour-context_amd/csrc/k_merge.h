@@ -64,14 +64,8 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
            const int *__restrict__ pass_cnt, cc_cand_out *__restrict__ cands_all, cc_qstate *__restrict__ qstate,
            cc_gmm_problem *__restrict__ probs /*[nq][CC_MAXCAND]: problem of candidate k of query q*/,
            int *__restrict__ prob_list /*dense list of the problems that exist*/, int *__restrict__ n_prob,
-           long long *__restrict__ phase /*tuning aid (CC_MERGE_PHASES=1): [nq][8] ticks per stage, else nullptr*/,
            cc_cand_post *__restrict__ post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
   __shared__ cc_merge_lds L;
-#define CC_MERGE_STAMP(i)                                                                                   \
-  do {                                                                                                      \
-    if (phase && threadIdx.x == 0) phase[(size_t)blockIdx.x * 8 + (i)] = (long long)wall_clock64();          \
-  } while (0)
-  CC_MERGE_STAMP(0);
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (q >= nq) return;
   const unsigned char *okp = pass_ok + (size_t)q * CC_CHK_STRIDE;
@@ -98,7 +92,6 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
     }
   }
   __syncthreads();
-  CC_MERGE_STAMP(1);
   // the candidate scans of the listed checks: gathers from the pass records, four per lane in flight
   for (int i0 = 0; i0 < n; i0 += 4 * CC_MERGE_BLOCK) {
     int g[4];
@@ -117,7 +110,6 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
     }
   }
   __syncthreads();
-  CC_MERGE_STAMP(2);
   // ---- thread the checks of one scan together; number the candidates in first-appearance order.  64 checks per round:
   //      (1) each lane looks its scan up among the candidates of the earlier rounds (four per LDS read; ~60 candidates per
   //      query, against a backwards scan over up to all the ~270 earlier checks), (2) the round's checks of the same scan
@@ -180,7 +172,6 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
     st.flags = 0;
     qstate[q] = st;
   }
-  CC_MERGE_STAMP(3);
   // ---- one lane per candidate
   cc_dcand *c = &L.st[tid];
   for (int k = tid; k < nc; k += CC_MERGE_BLOCK) {
@@ -330,7 +321,6 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
   }
   // ---- dense problem list: ordered ranks within the query, one global atomic per query
   __syncthreads();
-  CC_MERGE_STAMP(4);
   int n_want = 0;
   for (int b0 = 0; b0 < nc; b0 += CC_MERGE_BLOCK) {
     const int k = b0 + tid;
@@ -342,11 +332,5 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
   if (tid == 0) L.base = n_want ? atomicAdd(n_prob, n_want) : 0;
   __syncthreads();
   for (int i = tid; i < n_want; i += CC_MERGE_BLOCK) prob_list[L.base + i] = q * CC_MAXCAND + (int)L.ord[i];
-  CC_MERGE_STAMP(5);
-  if (phase && tid == 0) {
-    phase[(size_t)blockIdx.x * 8 + 6] = n;
-    phase[(size_t)blockIdx.x * 8 + 7] = nc;
-  }
-#undef CC_MERGE_STAMP
 }
 

@@ -30,18 +30,6 @@ __device__ __forceinline__ void cc_k1_field(int cell, int n_w3, int &w, int &sh)
   sh = f * CC_K1_IDX_BITS;
 }
 
-#ifdef CC_TUNE_K1_CLK  // tuning aid: where a workgroup's time goes (10-ns ticks summed over the workgroups; printed by cc_destroy)
-__device__ unsigned long long cc_k1_clk[8];
-#define CC_K1_STAMP(slot)                                                  \
-  {                                                                        \
-    const long long now_ = (long long)wall_clock64();                      \
-    k1_acc_[slot] += now_ - k1_t_;                                         \
-    k1_t_ = now_;                                                          \
-  }
-#else
-#define CC_K1_STAMP(slot)
-#endif
-
 struct cc_k1_scan_out {
   float max_bin_val, min_bin_val;
   int n_pix;
@@ -177,11 +165,7 @@ __device__ __forceinline__ int cc_k1_emit(const cc_dev_cfg &cfg, KeyFn keyfn, Id
         key[e] = cc[e] >= 0 ? keyfn(cc[e]) : KEY_EMPTY;
       }
 #pragma unroll
-#ifdef CC_TUNE_K1_NOB
-      for (int e = 0; e < CC_K1_LB; e++) xy[e] = *(const float2 *)(P + (cc[e] >= 0 ? idxfn(cc[e]) % n_pts : 0));
-#else
       for (int e = 0; e < CC_K1_LB; e++) xy[e] = *(const float2 *)(P + (cc[e] >= 0 ? idxfn(cc[e]) : 0));  // (an active cell has an owner: n_pts > 0)
-#endif
 #pragma unroll
       for (int e = 0; e < CC_K1_LB; e++) {
         const int i = i0 + e * nt + tid, c = cc[e];
@@ -205,7 +189,7 @@ __device__ __forceinline__ int cc_k1_emit(const cc_dev_cfg &cfg, KeyFn keyfn, Id
   // (2) the dense image, the continuous position of every occupied cell, the list entries at their raster-order positions.
   // CC_K1_EB cells per thread at a time: their keys and owners first, the owners' records requested TOGETHER, then the
   // outputs -- one cell at a time every thread waited for its record 22 times in a row, a quarter of the kernel (round 6,
-  // -DCC_TUNE_K1_CLK).  A cell without an owner asks for the scan's first record and drops it.
+  // measured with clock probes).  A cell without an owner asks for the scan's first record and drops it.
   for (int c0 = 0; c0 < n_cell; c0 += nt * CC_K1_EB) {  // block-uniform trip counts: the ballots see whole waves
     unsigned key[CC_K1_EB];
     float2 xy[CC_K1_EB];
@@ -269,7 +253,7 @@ template <int CC_K1_U, bool CC_K1_POW2, bool PART = false>
 __global__ void __launch_bounds__(1024)
 cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *__restrict__ offsets,
                float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
-               int want_dense, int n_units /*scans (PART: scans * CC_K1_SPLIT); workgroup b takes units b, b + gridDim.x, ...*/) {
+               int want_dense) {
   HIP_DYNAMIC_SHARED(char, smem)
   const int n_cell = cfg.n_cell;
   unsigned *hmax = (unsigned *)smem;
@@ -281,14 +265,7 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
   static_assert(CC_LIST_CAP * 2 >= 4 * 1024 && CC_K1_EMIT_TAB_BYTES % 4 == 0, "cc_k_rasterize: the idle words fit the list's cells");
 
   const int tid = threadIdx.x, nt = blockDim.x;
-#ifdef CC_TUNE_K1_CLK
-  long long k1_t_ = 0, k1_acc_[6] = {0, 0, 0, 0, 0, 0};
-#endif
-  // A workgroup takes units b, b + gridDim.x, ...: the host normally launches one per unit; CC_K1_WGS brings fewer, each
-  // keeping its CU (a K1 workgroup needs one to itself) for several scans -- measured: K1's own in-step time falls, K2's rises
-  // by as much (profiles/r6/notes_negative_results.md).
-  for (int unit = (int)blockIdx.x; unit < n_units; unit += (int)gridDim.x) {
-  if (unit != (int)blockIdx.x) __syncthreads();  // the previous scan's output pass has read the grid
+  const int unit = (int)blockIdx.x;  // a scan (PART: a range of one)
   const int scan = PART ? unit / CC_K1_SPLIT : unit;
   long long p0 = offsets[scan];
   int n_pts = (int)(offsets[scan + 1] - p0);
@@ -301,9 +278,6 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
   }
   const float4 *P = pts + p0;
 
-#ifdef CC_TUNE_K1_CLK
-  k1_t_ = (long long)wall_clock64();
-#endif
   const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
   for (int i = tid; i < n_cell; i += nt) hmax[i] = KEY_EMPTY;
   for (int i = tid; i < n_w3; i += nt) idx3[i] = ~0ull;
@@ -314,7 +288,6 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
     red[2] = 0;
   }
   __syncthreads();
-  CC_K1_STAMP(0)
 
   // ---- one sweep over the stream, in chunks of CC_K1_U * blockDim points held in registers ----
   // step A (all lanes): atomicMax of the chunk's heights; a point that RAISES a cell's maximum erases the cell's
@@ -403,13 +376,10 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
         cc_k1_field(cell[u], n_w3, w, sh);
         atomicOr(&idx3[w], CC_K1_IDX_MASK << sh);
       }
-    CC_K1_STAMP(1)
-    __syncthreads();
-    CC_K1_STAMP(2)
-    // step B: which of this lane's points hold their cell's maximum (four reads in flight), then ONE loop in which a lane
+      __syncthreads();
+      // step B: which of this lane's points hold their cell's maximum (four reads in flight), then ONE loop in which a lane
     // works off its winners one CAS attempt per turn -- a retry and the next winner's first attempt share a turn
     unsigned pend = 0u;
-#ifndef CC_TUNE_K1_NOB  // (tuning aid: the sweep without its index pass -- wrong owners, for timing only)
     {
       unsigned hm[CC_K1_U];
 #pragma unroll
@@ -417,7 +387,6 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
 #pragma unroll
       for (int u = 0; u < CC_K1_U; u++) pend |= (cell[u] >= 0 && key[u] == hm[u] && key[u] != KEY_EMPTY) ? (1u << u) : 0u;
     }
-#endif
     {
       bool busy = false;
       int w = 0, sh = 0;
@@ -445,10 +414,8 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
         }
       }
     }
-    CC_K1_STAMP(3)
-    __syncthreads();
-    CC_K1_STAMP(4)
-  }
+      __syncthreads();
+    }
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned b2 = (unsigned)__shfl_xor((int)kmin, o);
     kmin = b2 < kmin ? b2 : kmin;
@@ -478,7 +445,7 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
       part.red[(size_t)unit * 2] = red[0];
       part.red[(size_t)unit * 2 + 1] = red[1];
     }
-    continue;
+    return;
   }
   // ---- outputs ----
   float *bev = bev_out + (size_t)scan * n_cell;
@@ -503,12 +470,6 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
     o.pad = 0;
     scan_out[scan] = o;
   }
-  CC_K1_STAMP(5)
-  }  // units of this workgroup
-#ifdef CC_TUNE_K1_CLK
-  if (tid == 0)
-    for (int i = 0; i < 6; i++) atomicAdd(&cc_k1_clk[i], (unsigned long long)k1_acc_[i]);
-#endif
 }
 
 // The ranges of a scan combined: a cell's height is the largest of the ranges' keys and its point the one of the FIRST

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Tuning aid (round 5): isolated K1 / K2 times of one 1 024-scan ingest launch per workload, K2's phase clocks
-(CC_K2_PHASES=1) and a digest of the descriptors -- the digest of a changed kernel must equal the digest of the kernel it
+"""Tuning aid (round 5): isolated K1 / K2 times of one 1 024-scan ingest launch per workload and a digest of the
+descriptors -- the digest of a changed kernel must equal the digest of the kernel it
 replaces (bit-exact descriptors at full size, without the oracle in the loop).
     python profiles/k2_probe.py [sparse,dense,kitti] [n_scans] [repeats]   -> one JSON line per workload"""
 import hashlib
@@ -12,8 +12,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if not os.environ.get("CC_PROBE_NOPHASES"):   # the phase clocks cost time themselves (a clock read is a memory operation): true kernel times come without them
-    os.environ.setdefault("CC_K2_PHASES", "1")
 import torch  # noqa: E402
 import cc_amd  # noqa: E402
 
@@ -45,8 +43,6 @@ def main():
         torch.cuda.synchronize()
         ms = (C.c_double * 2)()
         nl = C.c_int()
-        sys.stderr.write("[%s] " % wname)
-        sys.stderr.flush()
         lib.cc_profile_read(ctx.h, ms, C.byref(nl))
         lib.cc_profile_enable(ctx.h, 0)
         d = cc.desc_to_numpy(out)

@@ -125,7 +125,6 @@ static inline void __syncthreads() { emu::co_wait(emu::t_block->bar, (int)emu::t
 static inline void __threadfence_block() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 static inline void __threadfence() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 static inline int __lane_id() { return emu::t_cur->lane; }
-static inline long long wall_clock64() { return 0; }
 
 // ---- cross-lane (wave = 64).  All 64 lanes of the wave must call these together. ----
 // A lane can only reach its (n+2)-th collective (which reuses buffer n%2) after passing the barrier of collective
@@ -357,29 +356,17 @@ static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s
 static inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { *s = nullptr; return hipSuccess; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = 0; return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-struct hipDeviceProp_t { int multiProcessorCount; };
-static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) { p->multiProcessorCount = 0; return hipSuccess; }
-static inline hipError_t hipExtStreamCreateWithCUMask(hipStream_t *s, unsigned, const unsigned *) { *s = nullptr; return hipSuccess; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = nullptr; return hipSuccess; }
 static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : 1; }
 static inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-// graphs: the harness runs every launch at once, so a "captured" chain has already run when the capture ends
+// stream capture: what lane_abort's guard compiles against (the harness never captures)
 typedef void *hipGraph_t;
-typedef void *hipGraphExec_t;
-typedef void *hipGraphNode_t;
-enum hipStreamCaptureMode { hipStreamCaptureModeGlobal, hipStreamCaptureModeThreadLocal, hipStreamCaptureModeRelaxed };
-enum hipGraphExecUpdateResult { hipGraphExecUpdateSuccess };
 enum hipStreamCaptureStatus { hipStreamCaptureStatusNone, hipStreamCaptureStatusActive };
 static inline hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *s) { *s = hipStreamCaptureStatusNone; return hipSuccess; }
-static inline hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipSuccess; }
 static inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t *g) { *g = nullptr; return hipSuccess; }
-static inline hipError_t hipGraphInstantiate(hipGraphExec_t *e, hipGraph_t, hipGraphNode_t *, char *, size_t) { *e = (void *)1; return hipSuccess; }
-static inline hipError_t hipGraphExecUpdate(hipGraphExec_t, hipGraph_t, hipGraphNode_t *, hipGraphExecUpdateResult *) { return hipSuccess; }
 static inline hipError_t hipGraphDestroy(hipGraph_t) { return hipSuccess; }
-static inline hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
-static inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipSuccess; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
 struct hipFuncAttributes { int numRegs = 0; size_t sharedSizeBytes = 0; };
