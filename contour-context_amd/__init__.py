@@ -43,7 +43,7 @@ _lib = None
 
 # every symbol include/cont2_amd.h declares
 EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_db_cfg", "cc_default_thresholds",
-           "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_db_create", "cc_db_destroy", "cc_db_size",
+           "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
            "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_hot_ptr", "cc_db_feat_ptr", "cc_pack_scans", "cc_db_add_packed",
            "cc_packed_sizes", "cc_db_bucket_state", "cc_est_sens_tf",
            "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
@@ -69,6 +69,7 @@ def lib():
         _lib.cc_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_destroy.argtypes = [C.c_void_p]
         _lib.cc_db_size.argtypes = [C.c_void_p]
+        _lib.cc_db_knn_stride.argtypes = [C.c_void_p]
         _lib.cc_db_add_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.cc_db_add_scans_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_query_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
@@ -239,6 +240,11 @@ class Database:
     def __len__(self):
         return lib().cc_db_size(self.h)
 
+    @property
+    def knn_stride(self):
+        """Last dimension of the hit array query(want_knn=True) returns: KNN_MAX for nnk <= KNN_MAX, else KNN_MAX_LARGE."""
+        return lib().cc_db_knn_stride(self.h)
+
     def add_scans(self, desc, ts, seeds):
         """desc: torch uint8 CUDA [n, DESC_BYTES]; ts float64 [n]; seeds int32 [n] (the reference passes the scan's
         assigned seq to pushAndBalance, batch_bin_test.cpp:236)."""
@@ -270,8 +276,9 @@ class Database:
         assert qdesc.is_cuda and qdesc.is_contiguous() and len(epochs) == nq
         res = np.zeros(nq, L.query_result_dt)
         knn = cnt = None
+        ks = self.knn_stride
         if want_knn:
-            knn = torch.zeros((nq, L.NQLEV, L.NPIV, L.KNN_MAX, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=qdesc.device)
+            knn = torch.zeros((nq, L.NQLEV, L.NPIV, ks, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=qdesc.device)
             cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=qdesc.device)
         stream = torch.cuda.current_stream(qdesc.device).cuda_stream
         _chk(lib().cc_db_query_batch(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
@@ -279,7 +286,7 @@ class Database:
                                      cnt.data_ptr() if want_knn else None, stream), "cc_db_query_batch",
              tolerate=(CC_ECAPACITY,) if allow_flagged else ())
         if want_knn:
-            return res, knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, L.KNN_MAX), cnt.cpu().numpy()
+            return res, knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy()
         return res
 
     def query_submit(self, qdesc, epochs, lb=None, ub=None):

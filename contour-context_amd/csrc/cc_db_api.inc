@@ -169,6 +169,8 @@ struct cc_db {
   static const int QB = 1024;  // queries per chunk (one launch chain): every chain pays ~20 launches and ~20 kernel tails,
                                // a quarter of a 512-query chain's time (measured: 256 / 384 / 512 queries per chunk
                                // 354 / 396 / 440 k scans/s)
+  int kmax = CC_KNN_MAX;  // hits per search of the query kernels: CC_KNN_MAX, or CC_KNN_MAX_LARGE when nnk > CC_KNN_MAX (the _l instances)
+  int qb_max = QB;        // queries per chunk: QB * CC_KNN_MAX / kmax, so that a lane's per-slot buffers keep their byte size
   static const int KQB = 1024;  // ... of which the tiled K3 takes this many at a time (round 3: 512 -- two launches per chunk, each as long as
                                 // its widest group; one launch lets the second half's groups fill in behind the first half's stragglers)
   static_assert(KQB * CC_NPIV <= CC_KNN_ORDER_CAP, "cc_k_knn_order sorts a sub-chunk's searches of one layer in LDS");
@@ -193,7 +195,7 @@ struct cc_db {
   } tune;
   ScanLite *d_lite = nullptr;
   ScanLite *h_lite_zc = nullptr;  // [CC_ZC_MAX] pinned, device-visible: cc_k_extract writes a small append's records straight to the host
-  unsigned short *d_perm_tab = nullptr;  // what std::sort does to n equal keys, for every n <= CC_MAXCAND (cc_tidy_order)
+  unsigned short *d_perm_tab = nullptr;  // what std::sort does to n equal keys, for every n <= the candidate capacity (cc_tidy_order)
   // cc_db_add_scans_prepare: batches whose records are packed and whose keys are on their way to the host, in order
   struct Prepared {
     const cc_scan_desc_t *d_desc = nullptr;
@@ -302,6 +304,8 @@ static void db_free(cc_db *db) {
 // Everything a query lane owns (stream, events, ~0.85 GB of device scratch at QB = 1024: the pair pool alone is QB * 8192
 // pairs * 80 B = 640 MiB), allocated when the lane comes into use: at cc_db_create for the default two lanes, in
 // cc_db_set_lanes for more.  A handle that uses one lane (the class mirror's per-setting stores) pays for one.
+// The per-slot buffers are sized QB * CC_CHK_STRIDE (hits: QB * NS * CC_KNN_MAX): a large-k database (nnk > CC_KNN_MAX) runs
+// chunks of qb_max = QB * CC_KNN_MAX / CC_KNN_MAX_LARGE = 256 queries with four times the slots each, in the same bytes.
 static int lane_env_int(const char *name, int lo, int hi, int dflt) {
   const char *e = getenv(name);
   if (!e) return dflt;
@@ -387,8 +391,8 @@ static int lane_alloc(cc_db *db, cc_qlane &ln) {
 
 int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db **out) {
   if (!ctx || !cfg || !out || capacity_scans < 1) return set_err(CC_EINVAL, "cc_db_create: bad argument");
-  if (cfg->n_q_levels < 1 || cfg->n_q_levels > CC_NQLEV || cfg->nnk < 1 || cfg->nnk > CC_KNN_MAX)
-    return set_err(CC_EINVAL, "cc_db_create: unsupported ContourDBConfig (q_levels_ <= 3, nnk_ <= 64)");
+  if (cfg->n_q_levels < 1 || cfg->n_q_levels > CC_NQLEV || cfg->nnk < 1 || cfg->nnk > CC_KNN_MAX_LARGE)
+    return set_err(CC_EINVAL, "cc_db_create: unsupported ContourDBConfig (q_levels_ <= 3, 1 <= nnk_ <= CC_KNN_MAX_LARGE = 256)");
   for (int i = 0; i < cfg->n_q_levels; i++)
     if (cfg->q_levels[i] < 1 || cfg->q_levels[i] > CC_HOT_LEVELS) return set_err(CC_EINVAL, "cc_db_create: q_levels_ must be within 1..4");
   if (cfg->max_fine_opt < 1) return set_err(CC_EINVAL, "cc_db_create: max_fine_opt_ must be positive");
@@ -407,6 +411,8 @@ int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db 
     }                                       \
   } while (0)
   db->cfg = *cfg;
+  db->kmax = cfg->nnk > CC_KNN_MAX ? CC_KNN_MAX_LARGE : CC_KNN_MAX;
+  db->qb_max = cc_db::QB * CC_KNN_MAX / db->kmax;
   db->cap = capacity_scans;
   db->cap_k = capacity_scans * CC_NPIV;
   DB_CHK(hipMalloc(&db->d_hot, sizeof(cc_hot_desc_t) * (size_t)db->cap));
@@ -433,8 +439,11 @@ int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db 
     // fineOptimize sorts candidates whose correlation_ is still 0 (contour_db.h:604-610): with a comparator that never
     // says "less", std::sort is a permutation that depends on the length alone.  One row per length, made by std::sort
     // itself (the libstdc++ the reference is built with; csrc/cc_sort.h replays the same algorithm where keys matter).
-    std::vector<unsigned short> tab((size_t)CC_MAXCAND * (CC_MAXCAND + 1) / 2);
-    for (int n = 1; n <= CC_MAXCAND; n++) {
+    // (the large-k table, up to 4 608 candidates, is 21 MB; its rows for n <= CC_MAXCAND are the common table, which the
+    // hint flow's 64-stride kernels read)
+    const int mc = CC_CHK_STRIDE_K(db->kmax);
+    std::vector<unsigned short> tab((size_t)mc * (mc + 1) / 2);
+    for (int n = 1; n <= mc; n++) {
       unsigned short *row = tab.data() + (size_t)n * (n - 1) / 2;
       for (int i = 0; i < n; i++) row[i] = (unsigned short)i;
       std::sort(row, row + n, [](unsigned short, unsigned short) { return false; });
@@ -460,6 +469,7 @@ int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db 
   db->tune.knn_mode = env_int("CC_KNN_MODE", 0, 2, db->tune.knn_mode);
   db->add_timers = getenv("CC_ADD_TIMERS") != nullptr;
   db->tune.chunk = env_int("CC_CHUNK", 64, cc_db::QB, db->tune.chunk);
+  db->tune.chunk = db->tune.chunk < db->qb_max ? db->tune.chunk : db->qb_max;
   auto env_triple = [](const char *name, int (&v)[3]) {
     const char *e = getenv(name);
     int a, b, c;
@@ -553,6 +563,7 @@ int cc_db_set_lanes(cc_db *db, int n) {
 }
 
 int cc_db_size(const cc_db *db) { return db ? db->n_scans : 0; }
+int cc_db_knn_stride(const cc_db *db) { return db ? db->kmax : 0; }
 
 void cc_packed_sizes(size_t *hot_bytes, size_t *feat_bytes) {
   if (hot_bytes) *hot_bytes = sizeof(cc_hot_desc_t);
@@ -985,9 +996,12 @@ static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q,
 
 // The launches of one chunk after the retrieval: checks (K4), proposal merge (K4b), correlation (K5), selection (K6).
 // ev: profiling events [2..5] or nullptr; d_scores: per-check gate scores (hint flow) or nullptr.
+// km: hits per search in ln.d_hits (db->kmax for queries; CC_KNN_MAX for the hint flow): picks the kernel instances.
 static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_params &CP, const cc_score_t *lb, const cc_score_t *ub,
-                                int max_fine_opt, hipEvent_t *ev, int *d_scores, bool zc /*results and counters straight into the lane's pinned host buffers*/) {
+                                int max_fine_opt, hipEvent_t *ev, int *d_scores, bool zc /*results and counters straight into the lane's pinned host buffers*/,
+                                int km) {
   hipStream_t ls = ln.stream;
+  const bool lg = km != CC_KNN_MAX;
   // dynamic thresholds (the mode at submission): the stages leave their scores in the pass records, cc_k_check_dyn replays the
   // checks in order, cc_k_select<true> / cc_k_final<true> the post bars
   const bool dyn = db->dyn_thres != 0;
@@ -995,24 +1009,24 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
   cc_pass_rec *const dpass = dyn ? ln.d_pass : nullptr;
   unsigned char *const dok = dyn ? ln.d_pass_ok : nullptr;
   const cc_hot_desc_t *qh = ln.d_qhot, *dh = db->d_hot;
-  const size_t n_slots = (size_t)nb * CC_CHK_STRIDE;
-  hipLaunchKernelGGL(cc_k_check_a, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), 0, ls, CP, qh, dh, nb, (const cc_knn_hit_t *)ln.d_hits,
+  const size_t n_slots = (size_t)nb * CC_CHK_STRIDE_K(km);
+  hipLaunchKernelGGL(lg ? cc_k_check_a_l : cc_k_check_a, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), 0, ls, CP, qh, dh, nb, (const cc_knn_hit_t *)ln.d_hits,
                      (const int *)ln.d_hit_cnt, ln.d_items, ln.d_cnt, ln.d_pass_ok, ln.d_pass_cnt, d_scores, dpass);
-  hipLaunchKernelGGL((cc_k_check_b1<CC_PP_SMALL, false>), dim3(db->tune.b1), dim3(64), 0, ls, CP, qh, dh, (const cc_chk_item *)ln.d_items,
+  hipLaunchKernelGGL((lg ? cc_k_check_b1_l<CC_PP_SMALL, false> : cc_k_check_b1<CC_PP_SMALL, false>), dim3(db->tune.b1), dim3(64), 0, ls, CP, qh, dh, (const cc_chk_item *)ln.d_items,
                      ln.d_redo, ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
-  hipLaunchKernelGGL((cc_k_check_b1<CC_PP_MAX, true>), dim3((db->tune.b1 + 3) / 4), dim3(64), 0, ls, CP, qh, dh, (const cc_chk_item *)ln.d_items, ln.d_redo,
+  hipLaunchKernelGGL((lg ? cc_k_check_b1_l<CC_PP_MAX, true> : cc_k_check_b1<CC_PP_MAX, true>), dim3((db->tune.b1 + 3) / 4), dim3(64), 0, ls, CP, qh, dh, (const cc_chk_item *)ln.d_items, ln.d_redo,
                      ln.d_cnt, ln.d_cstl, ln.d_pass_cnt, d_scores, dpass, dok);
   hipLaunchKernelGGL(cc_k_compact_cstl, dim3((unsigned)((n_slots + CC_CHKA_BLOCK - 1) / CC_CHKA_BLOCK)), dim3(CC_CHKA_BLOCK), 0, ls, CP, (const cc_cstl_item *)ln.d_cstl, ln.d_cnt,
                      ln.d_cstl_idx);
-  hipLaunchKernelGGL(cc_k_check_b2, dim3(db->tune.b2), dim3(64), 0, ls, CP, qh, dh, (const cc_cstl_item *)ln.d_cstl,
+  hipLaunchKernelGGL(lg ? cc_k_check_b2_l : cc_k_check_b2, dim3(db->tune.b2), dim3(64), 0, ls, CP, qh, dh, (const cc_cstl_item *)ln.d_cstl,
                      (const int *)ln.d_cstl_idx, (const int *)ln.d_cnt, ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt, d_scores, dyn ? 1 : 0);
-  hipLaunchKernelGGL(cc_k_check_c, dim3((db->tune.b2 + 3) / 4), dim3(256), 0, ls, (const cc_cstl_item *)ln.d_cstl,
+  hipLaunchKernelGGL(lg ? cc_k_check_c_l : cc_k_check_c, dim3((db->tune.b2 + 3) / 4), dim3(256), 0, ls, (const cc_cstl_item *)ln.d_cstl,
                      (const int *)ln.d_cstl_idx, (const int *)ln.d_cnt, ln.d_pass, (const unsigned char *)ln.d_pass_ok);
   if (dyn)
-    hipLaunchKernelGGL(cc_k_check_dyn, dim3(nb), dim3(64), 0, ls, nb, *lb, *ub, (const cc_pass_rec *)ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt,
+    hipLaunchKernelGGL(lg ? cc_k_check_dyn_l : cc_k_check_dyn, dim3(nb), dim3(64), 0, ls, nb, *lb, *ub, (const cc_pass_rec *)ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt,
                        d_scores);
   if (ev) HIPCHK(hipEventRecord(ev[2], ls));
-  hipLaunchKernelGGL(cc_k_merge, dim3(nb), dim3(CC_MERGE_BLOCK), 0, ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
+  hipLaunchKernelGGL(lg ? cc_k_merge_l : cc_k_merge, dim3(nb), dim3(CC_MERGE_BLOCK), 0, ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
                      (const unsigned char *)ln.d_pass_ok, (const int *)ln.d_pass_cnt, ln.d_cands, ln.d_qstate, ln.d_prob, ln.d_prob_list,
                      ln.d_nprob, dyn ? ln.d_cpost : (cc_cand_post *)nullptr);
   if (ev) HIPCHK(hipEventRecord(ev[3], ls));
@@ -1020,7 +1034,7 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
   hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
                      (const int *)ln.d_nprob, (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, ln.d_gres,
                      cc_gmm_code_pool{ln.d_codes, ln.code_cap, ln.d_heads + 9, ln.d_nprob + 3, ln.pool_cap});
-  hipLaunchKernelGGL(dyn ? cc_k_select<true> : cc_k_select<false>, dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
+  hipLaunchKernelGGL(lg ? (dyn ? cc_k_select_l<true> : cc_k_select_l<false>) : (dyn ? cc_k_select<true> : cc_k_select<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
                      (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, ln.d_sel, ln.prob_cap,
                      ln.d_nprob + 1, ln.d_heads + 8, (const unsigned short *)db->d_perm_tab, ln.d_sel + 3 * (size_t)ln.prob_cap, ln.d_heads + 12,
                      ln.d_nprob + 3, ln.d_pool_off, (const cc_cand_post *)ln.d_cpost, ln.d_tidy, *lb, *ub);
@@ -1034,7 +1048,7 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
                      ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
                      (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
   if (ev) HIPCHK(hipEventRecord(ev[4], ls));
-  hipLaunchKernelGGL(dyn ? cc_k_final<true> : cc_k_final<false>, dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
+  hipLaunchKernelGGL(lg ? (dyn ? cc_k_final_l<true> : cc_k_final_l<false>) : (dyn ? cc_k_final<true> : cc_k_final<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
                      (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
                      (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
                      zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy);
@@ -1162,8 +1176,8 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
   // batches deep, and an append in between has to wait for the chunks that still read the view buffer it rewrites
   // (measured on the online loop with 512-scan sub-batches and four lanes: 188 k against 265 k scans/s).
   int qb = (((nq + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
-  if (!db->sync_call && nq >= cc_db::QB) qb = cc_db::QB;
-  qb = qb > db->tune.chunk ? db->tune.chunk : qb;
+  if (!db->sync_call && nq >= db->qb_max) qb = db->qb_max;
+  qb = qb > db->tune.chunk ? db->tune.chunk : qb;  // (tune.chunk <= qb_max)
   // A HIP call that fails once part of a chunk's chain is queued: the lane is drained (its pinned staging buffers must not
   // be reused under copies still in flight) and the handle is marked failed, as the appends do.
 #define LANE_CHK(call)                        \
@@ -1219,7 +1233,8 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
     if (ev) LANE_CHK(hipEventRecord(ev[0], ls));
     int max_keys = 0;
     for (int l = 0; l < nql; l++) max_keys = db->n_keys[l] > max_keys ? db->n_keys[l] : max_keys;
-    const bool tiled = db->tune.knn_mode == 2 || (db->tune.knn_mode == 1 && max_keys >= CC_KNN_TILE_MIN_KEYS);
+    // (a large-k database always walks: the tiled search has no large-k instance)
+    const bool tiled = db->kmax == CC_KNN_MAX && (db->tune.knn_mode == 2 || (db->tune.knn_mode == 1 && max_keys >= CC_KNN_TILE_MIN_KEYS));
     if (tiled) {
       int *ord = ln.d_knn_order;
       for (int s0 = 0; s0 < nb; s0 += cc_db::KQB) {  // the search order of a sub-chunk is built in LDS (cc_k_knn_order)
@@ -1231,6 +1246,9 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
         hipLaunchKernelGGL(cc_k_knn_order, dim3(nql), dim3(1024), CC_KNN_ORDER_LDS, ls, KP, qh, ns, ord, hc);
         hipLaunchKernelGGL(cc_k_knn_tile, dim3(nql * ns * CC_NPIV), dim3(64 * CC_KNN_TW), 0, ls, KP, qh, qm, ns, (const int *)ord, hs, hc);
       }
+    } else if (db->kmax != CC_KNN_MAX) {
+      hipLaunchKernelGGL(chunk_vis ? cc_k_knn_l<true> : cc_k_knn_l<false>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot,
+                         qmeta_dev, ln.d_hits, ln.d_hit_cnt);
     } else {
       if (chunk_vis)
         hipLaunchKernelGGL(cc_k_knn<true>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot, qmeta_dev,
@@ -1240,12 +1258,12 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
                          ln.d_hits, ln.d_hit_cnt);
     }
     if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc);
+    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc, db->kmax);
     if (rc != CC_OK) {
       lane_abort(db, ln);
       break;
     }
-    if (d_knn) LANE_CHK(hipMemcpyAsync(d_knn + (size_t)b0 * NS * CC_KNN_MAX, ln.d_hits, sizeof(cc_knn_hit_t) * (size_t)nb * NS * CC_KNN_MAX, hipMemcpyDeviceToDevice, ls));
+    if (d_knn) LANE_CHK(hipMemcpyAsync(d_knn + (size_t)b0 * NS * db->kmax, ln.d_hits, sizeof(cc_knn_hit_t) * (size_t)nb * NS * db->kmax, hipMemcpyDeviceToDevice, ls));
     if (d_knn_cnt) LANE_CHK(hipMemcpyAsync(d_knn_cnt + (size_t)b0 * NS, ln.d_hit_cnt, sizeof(int) * nb * NS, hipMemcpyDeviceToDevice, ls));
     if (!zc) {
       LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
@@ -1483,7 +1501,7 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
       if (h_hints[i].seq_tgt >= ql.n_cont[h_hints[i].level - 1])
         return set_err(CC_EINVAL, "cc_db_check_hints: hint names a contour of the query scan that does not exist");
   }
-  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false);
+  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false, CC_KNN_MAX);  // any database: 64-stride
   if (rc != CC_OK) return rc;
   std::vector<int> sc((size_t)CC_CHK_STRIDE * CC_NSCORE);
   std::vector<unsigned char> ok(CC_CHK_STRIDE);

@@ -24,7 +24,11 @@
 #define CC_PP_MAX 256      // potential (src,tgt) neighbour pairs per check (large instance of stage B1)
 #define CC_PP_SMALL 64     // ... handled by the common, high-occupancy instance
 #define CC_CSTL_MAX 64     // pairs kept in a constellation
-#define CC_CHK_STRIDE (CC_NQLEV * CC_NPIV * CC_KNN_MAX)  // dense check slots per query: slot * CC_KNN_MAX + j
+#define CC_CHK_STRIDE_K(km) (CC_NQLEV * CC_NPIV * (km))  // dense check slots per query: slot * km + j, km = hits per search
+#define CC_CHK_STRIDE CC_CHK_STRIDE_K(CC_KNN_MAX)          // ... of the common instances (nnk <= 64); 4 608 for the large-k ones
+// a check slot travels in the low 16 bits of cc_chk_item::t, and cc_k_merge keeps slots and list positions in u16 / short
+static_assert(CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) < 32768 && CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) % 64 == 0,
+              "check slots of the large-k instances: 16-bit packing, whole waves");
 #define CC_NSCORE 5  // per-check gate scores (hint flow): ovlp_sum, max_one, in_ang_rng, indiv_sim, orie_sim
 
 // A KNN hit names the candidate's anchor (level, seq); the query's anchor is implied by the slot.  In the hint flow
@@ -116,18 +120,18 @@ __device__ __forceinline__ float cc_norm2f(float x, float y) { return sqrtf(x * 
 // ~11.5 ns apart whatever else the chip does -- profiles/r6/micro/atomic_convoy.hip; with 256-thread workgroups the 4 608
 // atomics of a chunk WERE this kernel: 55 of its 69 us)
 #define CC_CHKA_BLOCK 1024
-__global__ void __launch_bounds__(CC_CHKA_BLOCK)
-cc_k_check_a(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
-             int nq, const cc_knn_hit_t *__restrict__ hits, const int *__restrict__ hit_cnt, cc_chk_item *__restrict__ items,
-             int *__restrict__ cnt, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt /*[nq][4]*/,
-             int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] or nullptr: per-check gate scores (hint flow)*/,
-             cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/) {
+template <int KM>
+__device__ __forceinline__ void cc_check_a_body(cc_check_params P, const cc_hot_desc_t *qhot, const cc_hot_desc_t *db_hot,
+                                                int nq, const cc_knn_hit_t *hits, const int *hit_cnt, cc_chk_item *items,
+                                                int *cnt, unsigned char *pass_ok, int *pass_cnt /*[nq][4]*/,
+                                                int *scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] or nullptr: per-check gate scores (hint flow)*/,
+                                                cc_pass_rec *dyn /*dynamic thresholds: the pass records, else nullptr*/) {
   const int NS = CC_NQLEV * CC_NPIV;
   const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int q = (int)(gt / CC_CHK_STRIDE), t = (int)(gt - (size_t)q * CC_CHK_STRIDE);
-  const bool in_range = q < nq;  // whole waves: CC_CHK_STRIDE is a multiple of 64 (no early return: barriers below)
+  const int q = (int)(gt / CC_CHK_STRIDE_K(KM)), t = (int)(gt - (size_t)q * CC_CHK_STRIDE_K(KM));
+  const bool in_range = q < nq;  // whole waves: CC_CHK_STRIDE_K(KM) is a multiple of 64 (no early return: barriers below)
   const int lane = threadIdx.x & 63;
-  const int slot = t / CC_KNN_MAX, j = t - slot * CC_KNN_MAX;
+  const int slot = t / KM, j = t - slot * KM;
   bool anchor_ok = false, keep = false;
   int sc_sum = 0, sc_max = 0, npts = 0;
   cc_knn_hit_t h;
@@ -135,7 +139,7 @@ cc_k_check_a(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc
   h.level = h.seq = 0;
   h.dist_sq = 0.f;
   if (in_range && j < hit_cnt[q * NS + slot]) {
-    h = hits[((size_t)q * NS + slot) * CC_KNN_MAX + j];
+    h = hits[((size_t)q * NS + slot) * KM + j];
     const int seq_tgt = CC_HIT_SEQ_TGT(h, slot), li = CC_HIT_LEVEL(h) - 1;
     const cc_hot_desc_t *src = db_hot + h.gidx, *tgt = qhot + q;
     // the rings are fetched next to the contour rows (both addresses follow from the hit alone): one dependent round trip
@@ -211,10 +215,28 @@ cc_k_check_a(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc
     const unsigned long long mine = bk == 0 ? mb0 : (bk == 1 ? mb1 : (bk == 2 ? mb2 : mb3));
     cc_chk_item it;
     it.q = q;
-    it.t = t | (npts << 16);  // slot position (11 bits) | points of the src table << 16 | of the tgt table << 24
+    it.t = t | (npts << 16);  // slot position (11 bits, 13 in the large-k instance) | points of the src table << 16 | of the tgt table << 24
     it.h = h;
     items[pos + __popcll(mine & ((1ull << lane) - 1ull))] = it;
   }
+}
+
+__global__ void __launch_bounds__(CC_CHKA_BLOCK)
+cc_k_check_a(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
+             int nq, const cc_knn_hit_t *__restrict__ hits, const int *__restrict__ hit_cnt, cc_chk_item *__restrict__ items,
+             int *__restrict__ cnt, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt /*[nq][4]*/,
+             int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] or nullptr: per-check gate scores (hint flow)*/,
+             cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/) {
+  cc_check_a_body<CC_KNN_MAX>(P, qhot, db_hot, nq, hits, hit_cnt, items, cnt, pass_ok, pass_cnt, scores, dyn);
+}
+// the large-k instance (64 < nnk <= CC_KNN_MAX_LARGE): hits [.][CC_KNN_MAX_LARGE], CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) slots per query
+__global__ void __launch_bounds__(CC_CHKA_BLOCK)
+cc_k_check_a_l(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
+               int nq, const cc_knn_hit_t *__restrict__ hits, const int *__restrict__ hit_cnt, cc_chk_item *__restrict__ items,
+               int *__restrict__ cnt, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt /*[nq][4]*/,
+               int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] or nullptr: per-check gate scores (hint flow)*/,
+               cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/) {
+  cc_check_a_body<CC_KNN_MAX_LARGE>(P, qhot, db_hot, nq, hits, hit_cnt, items, cnt, pass_ok, pass_cnt, scores, dyn);
 }
 
 // ---- stage B1 -------------------------------------------------------------------------------------------------------
@@ -501,12 +523,11 @@ __device__ __forceinline__ void cc_b1_sort(cc_b1_lds<PPM> &L, int npp, int ntp, 
 // Two instances: <CC_PP_SMALL, false> handles every check with <= 64 potential pairs and lists the others;
 // <CC_PP_MAX, true> then runs only those.
 // grid = any (grid-stride over the device-side list), block = 64
-template <int PPM, bool REDO>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
-cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
-              const cc_chk_item *__restrict__ items, int *__restrict__ redo_idx, int *__restrict__ cnt, cc_cstl_item *__restrict__ cstl,
-              int *__restrict__ pass_cnt, int *__restrict__ scores /*see cc_k_check_a; or nullptr*/,
-              cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/, unsigned char *__restrict__ dyn_ok) {
+template <int PPM, bool REDO, int KM>
+__device__ __forceinline__ void cc_check_b1_body(cc_check_params P, const cc_hot_desc_t *qhot, const cc_hot_desc_t *db_hot,
+                                                 const cc_chk_item *items, int *redo_idx, int *cnt, cc_cstl_item *cstl,
+                                                 int *pass_cnt, int *scores /*see cc_k_check_a; or nullptr*/,
+                                                 cc_pass_rec *dyn /*dynamic thresholds: the pass records, else nullptr*/, unsigned char *dyn_ok) {
   __shared__ cc_b1_lds<PPM> LG[CC_CHKB_GPW];
   const int G = CC_G;
   const int sub = threadIdx.x / CC_G, sl = threadIdx.x % CC_G;
@@ -530,9 +551,9 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
     // the check's constellation record sits at the check's own list position; n_in = 0 until (unless) it passes
     cc_cstl_item *out = cstl + (REDO ? redo_idx[i] : i);
     if (sl == 0) out->n_in = 0;
-    const int slot = t / CC_KNN_MAX;
+    const int slot = t / KM;
     const int level = CC_HIT_LEVEL(h), seq_src = h.seq, seq_tgt = CC_HIT_SEQ_TGT(h, slot);
-    int *sc = scores ? scores + ((size_t)q * CC_CHK_STRIDE + t) * CC_NSCORE : nullptr;
+    int *sc = scores ? scores + ((size_t)q * CC_CHK_STRIDE_K(KM) + t) * CC_NSCORE : nullptr;
     const cc_bci_t *bs = &db_hot[h.gidx].bcis[level - 1][seq_src];
     const cc_bci_t *bt = &qhot[q].bcis[level - 1][seq_tgt];
     // point tables as 8-byte words: a table is 40 x 12 B = 60 words at an 8-byte aligned offset, four words per lane; only
@@ -651,7 +672,7 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       if (sl == 0) atomicOr((unsigned *)&pass_cnt[q * 4 + 0], (unsigned)CC_QF_CHECK_CAP);
     }
     if (sl == 0) atomicAdd(&pass_cnt[q * 4 + 2], 1);
-    cc_pass_rec *drec = dyn ? dyn + (size_t)q * CC_CHK_STRIDE + t : nullptr;  // a stage-2 passer: its scores for the replay
+    cc_pass_rec *drec = dyn ? dyn + (size_t)q * CC_CHK_STRIDE_K(KM) + t : nullptr;  // a stage-2 passer: its scores for the replay
     if (drec && sl == 0) drec->pad |= CC_DYN_RNG(longest);
     // (3/4, first part) the individual similarity of the window pairs and the anchors (contour_mng.h:1138-1160) is
     // decided here, where the pairs are at hand: a check that keeps too few pairs ends without a record (a third of those
@@ -680,7 +701,7 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
     if (sc && sl == 0) sc[3] = ncs;
     if (drec && sl == 0) {
       drec->flags = CC_DYN_PAIR(ncs, 0);  // checkConstellCorrespSim returns i_orie_sim = 0 when it stops here (contour_mng.h:1168)
-      if (ncs < P.lb.i_indiv_sim) dyn_ok[(size_t)q * CC_CHK_STRIDE + t] = 2;
+      if (ncs < P.lb.i_indiv_sim) dyn_ok[(size_t)q * CC_CHK_STRIDE_K(KM) + t] = 2;
     }
     if (ncs < P.lb.i_indiv_sim) continue;
     if (sl == 0) {
@@ -694,6 +715,23 @@ cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       out->flags = flags;
     }
   }
+}
+
+template <int PPM, bool REDO>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
+cc_k_check_b1(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
+              const cc_chk_item *__restrict__ items, int *__restrict__ redo_idx, int *__restrict__ cnt, cc_cstl_item *__restrict__ cstl,
+              int *__restrict__ pass_cnt, int *__restrict__ scores /*see cc_k_check_a; or nullptr*/,
+              cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/, unsigned char *__restrict__ dyn_ok) {
+  cc_check_b1_body<PPM, REDO, CC_KNN_MAX>(P, qhot, db_hot, items, redo_idx, cnt, cstl, pass_cnt, scores, dyn, dyn_ok);
+}
+template <int PPM, bool REDO>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
+cc_k_check_b1_l(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
+                const cc_chk_item *__restrict__ items, int *__restrict__ redo_idx, int *__restrict__ cnt, cc_cstl_item *__restrict__ cstl,
+                int *__restrict__ pass_cnt, int *__restrict__ scores /*see cc_k_check_a; or nullptr*/,
+                cc_pass_rec *__restrict__ dyn /*dynamic thresholds: the pass records, else nullptr*/, unsigned char *__restrict__ dyn_ok) {
+  cc_check_b1_body<PPM, REDO, CC_KNN_MAX_LARGE>(P, qhot, db_hot, items, redo_idx, cnt, cstl, pass_cnt, scores, dyn, dyn_ok);
 }
 
 // The constellations that passed, as a dense index list for stage B2 (order irrelevant: results are slot-indexed).
@@ -755,11 +793,11 @@ __device__ __forceinline__ int cc_shaft_i(int pr) {
 }
 
 // grid = any (grid-stride over the device-side list), block = 64
-__global__ void __launch_bounds__(64)
-cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
-              const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl_idx, const int *__restrict__ cnt,
-              cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt,
-              int *__restrict__ scores, int dyn /*dynamic thresholds: the scores into the pass records*/) {
+template <int KM>
+__device__ __forceinline__ void cc_check_b2_body(cc_check_params P, const cc_hot_desc_t *qhot, const cc_hot_desc_t *db_hot,
+                                                 const cc_cstl_item *cstl, const int *cstl_idx, const int *cnt,
+                                                 cc_pass_rec *pass, unsigned char *pass_ok, int *pass_cnt,
+                                                 int *scores, int dyn /*dynamic thresholds: the scores into the pass records*/) {
   __shared__ cc_b2_lds LG[CC_CHKB_GPW];
   const int G = CC_G;
   const int sub = threadIdx.x / CC_G, sl = threadIdx.x % CC_G;
@@ -769,7 +807,7 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
     const cc_cstl_item *it = cstl + cstl_idx[i];
     const int q = it->q, t = it->t, gidx = it->gidx, n_in = it->n_in;
     int flags = it->flags;
-    int *sc = scores ? scores + ((size_t)q * CC_CHK_STRIDE + t) * CC_NSCORE : nullptr;
+    int *sc = scores ? scores + ((size_t)q * CC_CHK_STRIDE_K(KM) + t) * CC_NSCORE : nullptr;
     const cc_hot_desc_t *src = db_hot + gidx, *tgt = qhot + q;
     cc_group_sync();  // the previous constellation's reads of the group's LDS are done
     // (3/4) the pairs that passed the individual similarity (stage B1's tail), in cstl_in order: their centres into LDS
@@ -924,8 +962,8 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
     if (sc && sl == 0) sc[4] = ncs;
     if (ncs < P.lb.i_orie_sim) {
       if (dyn && sl == 0) {
-        pass[(size_t)q * CC_CHK_STRIDE + t].flags = CC_DYN_PAIR(n_in, ncs);
-        pass_ok[(size_t)q * CC_CHK_STRIDE + t] = 2;
+        pass[(size_t)q * CC_CHK_STRIDE_K(KM) + t].flags = CC_DYN_PAIR(n_in, ncs);
+        pass_ok[(size_t)q * CC_CHK_STRIDE_K(KM) + t] = 2;
       }
       continue;
     }
@@ -1008,7 +1046,7 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       r10 = sn2 / nrm;
     }
     cc_group_sync();
-    cc_pass_rec *rec = &pass[(size_t)q * CC_CHK_STRIDE + t];
+    cc_pass_rec *rec = &pass[(size_t)q * CC_CHK_STRIDE_K(KM) + t];
     if (sl == 0) {
       atomicAdd(&pass_cnt[q * 4 + 3], 1);
       rec->q = q;
@@ -1025,10 +1063,25 @@ cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const c
       rec->cs[0] = r00;
       rec->cs[1] = r10;
       rec->cs[2] = 0.0;
-      pass_ok[(size_t)q * CC_CHK_STRIDE + t] = 1;
+      pass_ok[(size_t)q * CC_CHK_STRIDE_K(KM) + t] = 1;
     }
     if (sl < 7) rec->bits[sl] = L.bitsw[sl];
   }
+}
+
+__global__ void __launch_bounds__(64)
+cc_k_check_b2(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
+              const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl_idx, const int *__restrict__ cnt,
+              cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt,
+              int *__restrict__ scores, int dyn /*dynamic thresholds: the scores into the pass records*/) {
+  cc_check_b2_body<CC_KNN_MAX>(P, qhot, db_hot, cstl, cstl_idx, cnt, pass, pass_ok, pass_cnt, scores, dyn);
+}
+__global__ void __launch_bounds__(64)
+cc_k_check_b2_l(cc_check_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_hot_desc_t *__restrict__ db_hot,
+                const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl_idx, const int *__restrict__ cnt,
+                cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok, int *__restrict__ pass_cnt,
+                int *__restrict__ scores, int dyn /*dynamic thresholds: the scores into the pass records*/) {
+  cc_check_b2_body<CC_KNN_MAX_LARGE>(P, qhot, db_hot, cstl, cstl_idx, cnt, pass, pass_ok, pass_cnt, scores, dyn);
 }
 
 // Stage C (one lane per constellation): T_pass's angle atan2(R10, R00) and the rotation rebuilt from it, as the reference
@@ -1042,6 +1095,26 @@ cc_k_check_c(const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl
     const cc_cstl_item *it = cstl + cstl_idx[i];
     const size_t slot = (size_t)it->q * CC_CHK_STRIDE + it->t;
     if (pass_ok[slot] != 1) continue;  // (2: failed stage 3 under the initial bars, dynamic thresholds)
+    cc_pass_rec *rec = &pass[slot];
+    const double r00 = rec->cs[0], r10 = rec->cs[1];
+    const double th = atan2(r10, r00);
+    const double c_ = cos(th), s_2 = sin(th);
+    rec->tf[2] = th;
+    rec->cs[0] = c_;
+    rec->cs[1] = s_2;
+    rec->cs[2] = atan2(s_2, c_);
+  }
+}
+// the large-k instance: the same with CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) slots per query (kept apart: a shared template
+// body compiles the common instance differently)
+__global__ void __launch_bounds__(256)
+cc_k_check_c_l(const cc_cstl_item *__restrict__ cstl, const int *__restrict__ cstl_idx, const int *__restrict__ cnt,
+               cc_pass_rec *__restrict__ pass, const unsigned char *__restrict__ pass_ok) {
+  const int n = cnt[CC_CNT_CSTL];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const cc_cstl_item *it = cstl + cstl_idx[i];
+    const size_t slot = (size_t)it->q * CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) + it->t;
+    if (pass_ok[slot] != 1) continue;
     cc_pass_rec *rec = &pass[slot];
     const double r00 = rec->cs[0], r10 = rec->cs[1];
     const double th = atan2(r10, r00);
@@ -1072,15 +1145,15 @@ __device__ __forceinline__ T cc_dyn_bar(T bar, T v, T ub) {  // alignLB, then al
 }
 
 // grid = nq, block = 64
-__global__ void __launch_bounds__(64)
-cc_k_check_dyn(int nq, cc_score_t lb, cc_score_t ub, const cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok,
-               int *__restrict__ pass_cnt, int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] (hint flow) or nullptr*/) {
+template <int KM>
+__device__ __forceinline__ void cc_check_dyn_body(int nq, cc_score_t lb, cc_score_t ub, const cc_pass_rec *pass, unsigned char *pass_ok,
+                                                  int *pass_cnt, int *scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] (hint flow) or nullptr*/) {
   const int q = blockIdx.x, lane = threadIdx.x;
   if (q >= nq) return;
   int b0 = lb.i_ovlp_sum, b1 = lb.i_ovlp_max_one, b2 = lb.i_in_ang_rng, b3 = lb.i_indiv_sim, b4 = lb.i_orie_sim;
   int c2 = 0, c3 = 0;
-  for (int w0 = 0; w0 < CC_CHK_STRIDE; w0 += 64) {
-    const size_t slot = (size_t)q * CC_CHK_STRIDE + w0 + lane;
+  for (int w0 = 0; w0 < CC_CHK_STRIDE_K(KM); w0 += 64) {
+    const size_t slot = (size_t)q * CC_CHK_STRIDE_K(KM) + w0 + lane;
     const bool cand = pass_ok[slot] != 0;  // passed stage 2 under the initial bars
     if (!__ballot(cand) && !scores) continue;
     int s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
@@ -1131,4 +1204,15 @@ cc_k_check_dyn(int nq, cc_score_t lb, cc_score_t ub, const cc_pass_rec *__restri
     pass_cnt[q * 4 + 2] = c2;
     pass_cnt[q * 4 + 3] = c3;
   }
+}
+
+__global__ void __launch_bounds__(64)
+cc_k_check_dyn(int nq, cc_score_t lb, cc_score_t ub, const cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok,
+               int *__restrict__ pass_cnt, int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] (hint flow) or nullptr*/) {
+  cc_check_dyn_body<CC_KNN_MAX>(nq, lb, ub, pass, pass_ok, pass_cnt, scores);
+}
+__global__ void __launch_bounds__(64)
+cc_k_check_dyn_l(int nq, cc_score_t lb, cc_score_t ub, const cc_pass_rec *__restrict__ pass, unsigned char *__restrict__ pass_ok,
+                 int *__restrict__ pass_cnt, int *__restrict__ scores /*[nq][CC_CHK_STRIDE][CC_NSCORE] (hint flow) or nullptr*/) {
+  cc_check_dyn_body<CC_KNN_MAX_LARGE>(nq, lb, ub, pass, pass_ok, pass_cnt, scores);
 }

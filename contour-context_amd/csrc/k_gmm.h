@@ -1489,51 +1489,62 @@ cc_k_gmm_refine(const cc_gmm_problem *__restrict__ probs, const int *__restrict_
 //   sort: a comparator that is always false makes libstdc++'s introsort a fixed permutation of its n inputs (median and
 //     partition swaps that never look at the values; the final insertion sort moves nothing): perm_tab holds it for
 //     every n (built on the host with std::sort itself, cc_db_create), row n at offset n (n - 1) / 2.
-// idx[0..n) = the candidates in the order fineOptimize sees them; returns n.  scr: CC_MAXCAND u16 of LDS scratch.
+// idx[0..n) = the candidates in the order fineOptimize sees them; returns n.  scr: MC u16 of LDS scratch, MC = the candidate
+// capacity (CC_MAXCAND, or CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) in the large-k instances).
+template <int MC>
 __device__ __forceinline__ int cc_tidy_order(int nc, const unsigned char *has, unsigned short *idx, unsigned short *scr,
                                              const unsigned short *__restrict__ perm_tab, int lane) {
   const unsigned long long lt = (1ull << lane) - 1ull;
   int n = 0;
   for (int k0 = 0; k0 < nc; k0 += 64) n += __popcll(__ballot(k0 + lane < nc && has[k0 + lane]));
   // front part: positions < n without an estimate, ascending -> scr[0..nf); back part: positions >= n with one,
-  // ascending -> scr[CC_MAXCAND - 1 - j] (read back descending)
+  // ascending -> scr[MC - 1 - j] (read back descending)
   int nf = 0, nb = 0;
   for (int k0 = 0; k0 < nc; k0 += 64) {
     const int k = k0 + lane;
     const bool fr = k < n && !has[k], bk = k >= n && k < nc && has[k];
     const unsigned long long mf = __ballot(fr), mb = __ballot(bk);
     if (fr) scr[nf + __popcll(mf & lt)] = (unsigned short)k;
-    if (bk) scr[CC_MAXCAND - 1 - (nb + __popcll(mb & lt))] = (unsigned short)k;
+    if (bk) scr[MC - 1 - (nb + __popcll(mb & lt))] = (unsigned short)k;
     nf += __popcll(mf);
     nb += __popcll(mb);
   }
   __syncthreads();
   // nf == nb; the a-th front gap takes the a-th estimate from the back, i.e. the (nb - 1 - a)-th in ascending order
-  unsigned short mine[CC_MAXCAND / 64];
+  if constexpr (MC / 64 > CC_MAXCAND / 64) {  // large-k: 72 u16 per lane would not stay in registers; scr is free again
+    for (int a = lane; a < nf; a += 64) idx[scr[a]] = scr[MC - 1 - (nb - 1 - a)];  // idx was the identity
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) scr[i] = idx[perm_tab[(size_t)n * (n - 1) / 2 + i]];
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) idx[i] = scr[i];
+    __syncthreads();
+  } else {
+    unsigned short mine[MC / 64];
 #pragma unroll
-  for (int u = 0; u < CC_MAXCAND / 64; u++) {
-    const int i = u * 64 + lane;
-    mine[u] = 0;
-    if (i < n) {
-      const int p = (int)perm_tab[(size_t)n * (n - 1) / 2 + i];  // position (after the compaction) that the sort puts at i
-      mine[u] = (unsigned short)p;
+    for (int u = 0; u < MC / 64; u++) {
+      const int i = u * 64 + lane;
+      mine[u] = 0;
+      if (i < n) {
+        const int p = (int)perm_tab[(size_t)n * (n - 1) / 2 + i];  // position (after the compaction) that the sort puts at i
+        mine[u] = (unsigned short)p;
+      }
     }
-  }
-  __syncthreads();
-  for (int a = lane; a < nf; a += 64) idx[scr[a]] = scr[CC_MAXCAND - 1 - (nb - 1 - a)];  // idx was the identity
-  __syncthreads();
+    __syncthreads();
+    for (int a = lane; a < nf; a += 64) idx[scr[a]] = scr[MC - 1 - (nb - 1 - a)];  // idx was the identity
+    __syncthreads();
 #pragma unroll
-  for (int u = 0; u < CC_MAXCAND / 64; u++) {
-    const int i = u * 64 + lane;
-    if (i < n) mine[u] = idx[mine[u]];
-  }
-  __syncthreads();
+    for (int u = 0; u < MC / 64; u++) {
+      const int i = u * 64 + lane;
+      if (i < n) mine[u] = idx[mine[u]];
+    }
+    __syncthreads();
 #pragma unroll
-  for (int u = 0; u < CC_MAXCAND / 64; u++) {
-    const int i = u * 64 + lane;
-    if (i < n) idx[i] = mine[u];
+    for (int u = 0; u < MC / 64; u++) {
+      const int i = u * 64 + lane;
+      if (i < n) idx[i] = mine[u];
+    }
+    __syncthreads();
   }
-  __syncthreads();
   return n;
 }
 
@@ -1581,22 +1592,21 @@ __device__ __forceinline__ void cc_post_walk(int nc, unsigned char *has, const i
 // Their GMM problems are appended to sel_list.  One wave per query.
 // DYN (dynamic thresholds): the survivors come from cc_post_walk and are handed to cc_k_final<true> in `tidy`.
 // ------------------------------------------------------------------------------------------------
-template <bool DYN>
-__global__ void __launch_bounds__(64)
-cc_k_select(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
-            const cc_gmm_result *__restrict__ gres, int *__restrict__ sel_list /*[3][sel_stride]*/, int sel_stride,
-            int *__restrict__ n_sel /*[2]*/, int *__restrict__ n_sel_wide, const unsigned short *__restrict__ perm_tab,
-            int *__restrict__ cls_list /*[CC_GMM_NCLS][sel_stride]: the long problems by length class*/, int *__restrict__ cls_cnt /*[CC_GMM_NCLS]*/,
-            int *__restrict__ pool_head, int *__restrict__ pool_off /*[problem slot]: where a selected problem's records go in the pair pool*/,
-            const cc_cand_post *__restrict__ post, unsigned char *__restrict__ tidy /*[nq][CC_MAXCAND]*/, cc_score_t lb, cc_score_t ub /*DYN only*/) {
-  __shared__ unsigned short idx[CC_MAXCAND];
-  __shared__ unsigned short scr[CC_MAXCAND];
-  __shared__ unsigned char has[CC_MAXCAND];
-  __shared__ int gm[CC_MAXCAND];
+template <bool DYN, int KM>
+__device__ __forceinline__ void cc_select_body(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *cands_all, const cc_qstate *qstate,
+                                               const cc_gmm_result *gres, int *sel_list /*[3][sel_stride]*/, int sel_stride,
+                                               int *n_sel /*[2]*/, int *n_sel_wide, const unsigned short *perm_tab,
+                                               int *cls_list /*[CC_GMM_NCLS][sel_stride]: the long problems by length class*/, int *cls_cnt /*[CC_GMM_NCLS]*/,
+                                               int *pool_head, int *pool_off /*[problem slot]: where a selected problem's records go in the pair pool*/,
+                                               const cc_cand_post *post, unsigned char *tidy /*[nq][CC_MAXCAND]*/, cc_score_t lb, cc_score_t ub /*DYN only*/) {
+  __shared__ unsigned short idx[CC_CHK_STRIDE_K(KM)];
+  __shared__ unsigned short scr[CC_CHK_STRIDE_K(KM)];
+  __shared__ unsigned char has[CC_CHK_STRIDE_K(KM)];
+  __shared__ int gm[CC_CHK_STRIDE_K(KM)];
   __shared__ int s_off[4];
   const int q = blockIdx.x, lane = threadIdx.x;
   if (q >= nq) return;
-  const cc_cand_out *cands = cands_all + (size_t)q * CC_MAXCAND;
+  const cc_cand_out *cands = cands_all + (size_t)q * CC_CHK_STRIDE_K(KM);
   const int nc = qstate[q].n_cand;
   for (int k = lane; k < nc; k += 64) {
     const int g = cands[k].gmm_idx;
@@ -1608,9 +1618,9 @@ cc_k_select(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restri
   if constexpr (DYN) {
     cc_post_walk(nc, has, gm, post, gres, lb, ub, lane);
     __syncthreads();
-    for (int k = lane; k < nc; k += 64) tidy[(size_t)q * CC_MAXCAND + k] = has[k];
+    for (int k = lane; k < nc; k += 64) tidy[(size_t)q * CC_CHK_STRIDE_K(KM) + k] = has[k];
   }
-  const int n = cc_tidy_order(nc, has, idx, scr, perm_tab, lane);
+  const int n = cc_tidy_order<CC_CHK_STRIDE_K(KM)>(nc, has, idx, scr, perm_tab, lane);
   if (n <= 0) return;
   const int pre = max_fine_opt < n ? max_fine_opt : n;
   // three lists by pair count: the 16-lane refinement instance, the 64-lane one, and the problems in between, which go to
@@ -1678,32 +1688,52 @@ cc_k_select(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restri
   }
 }
 
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_select(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+            const cc_gmm_result *__restrict__ gres, int *__restrict__ sel_list /*[3][sel_stride]*/, int sel_stride,
+            int *__restrict__ n_sel /*[2]*/, int *__restrict__ n_sel_wide, const unsigned short *__restrict__ perm_tab,
+            int *__restrict__ cls_list /*[CC_GMM_NCLS][sel_stride]: the long problems by length class*/, int *__restrict__ cls_cnt /*[CC_GMM_NCLS]*/,
+            int *__restrict__ pool_head, int *__restrict__ pool_off /*[problem slot]: where a selected problem's records go in the pair pool*/,
+            const cc_cand_post *__restrict__ post, unsigned char *__restrict__ tidy /*[nq][CC_MAXCAND]*/, cc_score_t lb, cc_score_t ub /*DYN only*/) {
+  cc_select_body<DYN, CC_KNN_MAX>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, sel_list, sel_stride, n_sel, n_sel_wide, perm_tab, cls_list, cls_cnt, pool_head, pool_off, post, tidy, lb, ub);
+}
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_select_l(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+              const cc_gmm_result *__restrict__ gres, int *__restrict__ sel_list /*[3][sel_stride]*/, int sel_stride,
+              int *__restrict__ n_sel /*[2]*/, int *__restrict__ n_sel_wide, const unsigned short *__restrict__ perm_tab,
+              int *__restrict__ cls_list /*[CC_GMM_NCLS][sel_stride]: the long problems by length class*/, int *__restrict__ cls_cnt /*[CC_GMM_NCLS]*/,
+              int *__restrict__ pool_head, int *__restrict__ pool_off /*[problem slot]: where a selected problem's records go in the pair pool*/,
+              const cc_cand_post *__restrict__ post, unsigned char *__restrict__ tidy /*[nq][CC_MAXCAND]*/, cc_score_t lb, cc_score_t ub /*DYN only*/) {
+  cc_select_body<DYN, CC_KNN_MAX_LARGE>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, sel_list, sel_stride, n_sel, n_sel_wide, perm_tab, cls_list, cls_cnt, pool_head, pool_off, post, tidy, lb, ub);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K6: per query, the rest of tidyUpCandidates (correlation bar + order-changing compaction, contour_db.h:560-592) and
 // fineOptimize (contour_db.h:604-648): std::sort on the still-all-zero correlation_ (replayed), take the first
 // max_fine_opt_, adopt their refined score/pose, re-sort those, return the best.  One lane per query.
 // DYN (dynamic thresholds): the survivors are those cc_k_select<true> left in `tidy`.
 // ------------------------------------------------------------------------------------------------
-template <bool DYN>
-__global__ void __launch_bounds__(64)
-cc_k_final(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
-           const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
-           const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
-           const int *__restrict__ nprob /*the chunk's problem counters and pool head*/, int *__restrict__ nprob_host /*or nullptr: copy them there*/,
-           const unsigned char *__restrict__ tidy /*DYN only*/) {
+template <bool DYN, int KM>
+__device__ __forceinline__ void cc_final_body(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *cands_all, const cc_qstate *qstate,
+                                              const cc_gmm_result *gres, const int *pass_cnt, const int *hit_cnt,
+                                              const cc_hot_desc_t *qhot, cc_query_result_t *out, const unsigned short *perm_tab,
+                                              const int *nprob /*the chunk's problem counters and pool head*/, int *nprob_host /*or nullptr: copy them there*/,
+                                              const unsigned char *tidy /*DYN only*/) {
   // one wave per query: lanes fetch the per-candidate inputs and order the candidates in parallel (cc_tidy_order), lane 0
   // replays the short order-dependent rest on LDS
-  __shared__ unsigned short idx[CC_MAXCAND];
-  __shared__ unsigned short scr[CC_MAXCAND];
-  __shared__ unsigned char has[CC_MAXCAND];
-  __shared__ float corr_o[CC_MAXCAND];
-  __shared__ int gm[CC_MAXCAND];
+  __shared__ unsigned short idx[CC_CHK_STRIDE_K(KM)];
+  __shared__ unsigned short scr[CC_CHK_STRIDE_K(KM)];
+  __shared__ unsigned char has[CC_CHK_STRIDE_K(KM)];
+  __shared__ float corr_o[CC_CHK_STRIDE_K(KM)];
+  __shared__ int gm[CC_CHK_STRIDE_K(KM)];
   __shared__ int s_tot;
   __shared__ unsigned stk[CC_SORT_STACK];
   const int q = blockIdx.x, lane = threadIdx.x;
   if (q >= nq) return;
   if (nprob_host && q == 0 && lane < 4) nprob_host[lane] = nprob[lane];  // small chunks: no copy command behind the chain
-  const cc_cand_out *cands = cands_all + (size_t)q * CC_MAXCAND;
+  const cc_cand_out *cands = cands_all + (size_t)q * CC_CHK_STRIDE_K(KM);
   const int nc = qstate[q].n_cand;
   // what lane 0 needs of the query's counters, fetched up front (every load it would issue later is a round trip)
   const int pc0 = pass_cnt[q * 4 + 0], pc1 = pass_cnt[q * 4 + 1], pc2 = pass_cnt[q * 4 + 2], pc3 = pass_cnt[q * 4 + 3];
@@ -1716,7 +1746,7 @@ cc_k_final(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restric
     bool h = false;
     float co = 0.f;
     if (g >= 0) {
-      h = DYN ? tidy[(size_t)q * CC_MAXCAND + k] != 0 : !((float)gres[g].corr_init < corr_lb);
+      h = DYN ? tidy[(size_t)q * CC_CHK_STRIDE_K(KM) + k] != 0 : !((float)gres[g].corr_init < corr_lb);
       co = (float)gres[g].corr_opt;
       gfl |= gres[g].flags;
     }
@@ -1731,7 +1761,7 @@ cc_k_final(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restric
   __syncthreads();
   // two-pointer compaction of candidates_ (has = corr_est_ != nullptr), contour_db.h:580-592, and the first std::sort:
   // every anch_props_[0].correlation_ is still 0 -> the comparator is always false
-  const int n = cc_tidy_order(nc, has, idx, scr, perm_tab, lane);
+  const int n = cc_tidy_order<CC_CHK_STRIDE_K(KM)>(nc, has, idx, scr, perm_tab, lane);
   if (lane != 0) return;
   cc_query_result_t r;
   r.n_res = 0;
@@ -1764,4 +1794,23 @@ cc_k_final(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restric
     }
   }
   out[q] = r;
+}
+
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_final(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+           const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
+           const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
+           const int *__restrict__ nprob /*the chunk's problem counters and pool head*/, int *__restrict__ nprob_host /*or nullptr: copy them there*/,
+           const unsigned char *__restrict__ tidy /*DYN only*/) {
+  cc_final_body<DYN, CC_KNN_MAX>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy);
+}
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_final_l(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+             const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
+             const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
+             const int *__restrict__ nprob /*the chunk's problem counters and pool head*/, int *__restrict__ nprob_host /*or nullptr: copy them there*/,
+             const unsigned char *__restrict__ tidy /*DYN only*/) {
+  cc_final_body<DYN, CC_KNN_MAX_LARGE>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy);
 }

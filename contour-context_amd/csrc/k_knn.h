@@ -1,6 +1,8 @@
 // K3 -- retrieval: maintenance of the per-layer sorted key view and the k-nearest-key search with the reference's
 // visibility rules.  Replaces LayerDB::layerKNNSearch / TreeBucket::knnSearch / nanoflann kNN (src/cont2/contour_db.cpp:319-403).
 #pragma once
+#include <type_traits>
+
 #include "cc_dev.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -27,6 +29,12 @@
 // are pending when the buffer is reduced (255 at nnk = CC_KNN_MAX = 64).
 #define CC_KNN_CAP 256
 static_assert(2 * CC_KNN_MAX - 1 + 128 <= CC_KNN_CAP && CC_KNN_MAX <= 64, "cc_k_knn: pending candidates must fit the LDS buffer");
+// ... and of the large-k instance (cc_k_knn_l: 64 < nnk <= CC_KNN_MAX_LARGE): 639 pending at nnk = 256.  Its reduction sorts up
+// to 16 entries per lane (1 024) in registers; only the first cnt entries are ever read from the buffer, and only the first nnk
+// written back.
+#define CC_KNN_CAP_LARGE 640
+static_assert(2 * CC_KNN_MAX_LARGE - 1 + 128 <= CC_KNN_CAP_LARGE && CC_KNN_CAP_LARGE <= 16 * 64,
+              "cc_k_knn_l: pending candidates must fit the LDS buffer and the largest sorting network");
 
 struct cc_knn_params {
   const float *skeys[CC_NQLEV];       // SoA [CC_KEY_DIM + 1][cap_k], sorted by dim 0 (ties: insertion order); last row = |key|^2
@@ -319,20 +327,52 @@ __device__ __forceinline__ float cc_knn_reduce(unsigned long long *buf, int cnt,
   return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)(v[0] >> 32), nnk - 1));
 }
 
+// The same for nnk up to 64 R (large-k instance): the best nnk of the cnt <= 64 R pending candidates, sorted, at buf[0..nnk);
+// v keeps the whole sorted list (position p in v[p / 64] of lane p % 64).  Returns the nnk-th best distance when cnt >= nnk.
+template <int R>
+__device__ __forceinline__ float cc_knn_reduce_l(unsigned long long *buf, int cnt, int nnk, int lane, unsigned long long (&v)[R]) {
+  cc_wave_sync();
+#pragma unroll
+  for (int a = 0; a < R; a++) v[a] = (a * 64 + lane < cnt) ? buf[a * 64 + lane] : ~0ull;
+  cc_wave_bitonic_u64<R>(v, lane);
+  cc_wave_sync();
+  float kth = __uint_as_float(0x7F800000u);
+#pragma unroll
+  for (int a = 0; a < R; a++) {
+    if (a * 64 + lane < nnk) buf[a * 64 + lane] = v[a];
+    if (a == (nnk - 1) >> 6) kth = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)(v[a] >> 32), (nnk - 1) & 63));
+  }
+  return kth;
+}
+
+// f(std::integral_constant<int, R>) with the smallest network of cc_knn_reduce_l that holds cnt <= 1 024 entries
+template <typename F>
+__device__ __forceinline__ void cc_knn_by_width(int cnt, F &&f) {
+  if (cnt <= 128)
+    f(std::integral_constant<int, 2>());
+  else if (cnt <= 256)
+    f(std::integral_constant<int, 4>());
+  else if (cnt <= 512)
+    f(std::integral_constant<int, 8>());
+  else
+    f(std::integral_constant<int, 16>());
+}
+
 // grid = nq * CC_NQLEV * CC_NPIV, block = 64 (one wave per anchor key).  VIS: the chunk has a query at an epoch at which some
 // bucket's kd-tree does not index its whole range (cc_query_meta::idx_full): that instance tests every candidate key against
 // its bucket's indexed interval; the common instance carries none of it (the test in the shared loop cost the walk 8 %:
 // the kernel sits at its scalar-register limit).
-template <bool VIS>
-__global__ void __launch_bounds__(64)
-cc_k_knn(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta,
-         cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt) {
-  __shared__ unsigned long long buf[CC_KNN_CAP];
+// KM: the hit capacity per search (CC_KNN_MAX for nnk <= 64: cc_k_knn; CC_KNN_MAX_LARGE: cc_k_knn_l), the stride of `hits`.
+template <bool VIS, int KM>
+__device__ __forceinline__ void cc_knn_walk(cc_knn_params P, const cc_hot_desc_t *qhot, const cc_query_meta *qmeta,
+                                            cc_knn_hit_t *hits, int *hit_cnt) {
+  static_assert(KM == CC_KNN_MAX || KM == CC_KNN_MAX_LARGE, "cc_knn_walk: the two instances");
+  __shared__ unsigned long long buf[KM == CC_KNN_MAX ? CC_KNN_CAP : CC_KNN_CAP_LARGE];
   const int lane = threadIdx.x;
   const int slot = blockIdx.x % (CC_NQLEV * CC_NPIV);
   const int q = blockIdx.x / (CC_NQLEV * CC_NPIV);
   const int ll = slot / CC_NPIV, seq = slot - ll * CC_NPIV;
-  cc_knn_hit_t *out = hits + (size_t)blockIdx.x * CC_KNN_MAX;
+  cc_knn_hit_t *out = hits + (size_t)blockIdx.x * KM;
   if (ll >= P.n_q_levels) {
     if (lane == 0) hit_cnt[blockIdx.x] = 0;
     return;
@@ -495,8 +535,15 @@ cc_k_knn(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query
       cnt += __popcll(m);
     }
     if (cnt >= 2 * nnk || (!tightened && cnt >= nnk)) {  // keep the best nnk (by distance, then key id); the radius follows
-      unsigned long long first;
-      ub = cnt <= 128 ? cc_knn_reduce<2>(buf, cnt, nnk, lane, first) : cc_knn_reduce<4>(buf, cnt, nnk, lane, first);
+      if constexpr (KM == CC_KNN_MAX) {
+        unsigned long long first;
+        ub = cnt <= 128 ? cc_knn_reduce<2>(buf, cnt, nnk, lane, first) : cc_knn_reduce<4>(buf, cnt, nnk, lane, first);
+      } else {
+        cc_knn_by_width(cnt, [&](auto r_) {
+          unsigned long long v[decltype(r_)::value];
+          ub = cc_knn_reduce_l(buf, cnt, nnk, lane, v);
+        });
+      }
       cnt = nnk;
       tightened = true;
       cc_wave_sync();
@@ -506,7 +553,27 @@ cc_k_knn(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query
       if (open[dir]) open[dir] = last_in[dir] && (tightened ? (far2[dir] <= ub) : (far2[dir] < ub));
   }
 #undef CC_KNN_FETCH
-  {
+  if constexpr (KM != CC_KNN_MAX) {  // up to KM / 64 hits per lane, straight from the sorted registers
+    const int mm = cnt < nnk ? cnt : nnk;
+    cc_knn_by_width(cnt, [&](auto r_) {
+      constexpr int R = decltype(r_)::value;
+      unsigned long long v[R];
+      cc_knn_reduce_l(buf, cnt, nnk, lane, v);
+#pragma unroll
+      for (int a = 0; a < (R < KM / 64 ? R : KM / 64); a++) {
+        if (a * 64 + lane < mm) {
+          const unsigned id = (unsigned)(v[a] & 0xFFFFFFFFu);
+          cc_knn_hit_t h;
+          h.gidx = P.kgidx[ll][id];
+          h.level = (int16_t)level;
+          h.seq = (int16_t)P.kseq[ll][id];
+          h.dist_sq = __uint_as_float((unsigned)(v[a] >> 32));
+          out[a * 64 + lane] = h;
+        }
+      }
+    });
+    if (lane == 0) hit_cnt[blockIdx.x] = mm;
+  } else {
     unsigned long long first;
     if (cnt <= 128)
       cc_knn_reduce<2>(buf, cnt, nnk, lane, first);
@@ -524,6 +591,21 @@ cc_k_knn(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query
     }
     if (lane == 0) hit_cnt[blockIdx.x] = mm;
   }
+}
+
+template <bool VIS>
+__global__ void __launch_bounds__(64)
+cc_k_knn(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta,
+         cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt) {
+  cc_knn_walk<VIS, CC_KNN_MAX>(P, qhot, qmeta, hits, hit_cnt);
+}
+
+// the large-k instance (64 < nnk <= CC_KNN_MAX_LARGE): hits [.][CC_KNN_MAX_LARGE]
+template <bool VIS>
+__global__ void __launch_bounds__(64)
+cc_k_knn_l(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta,
+           cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt) {
+  cc_knn_walk<VIS, CC_KNN_MAX_LARGE>(P, qhot, qmeta, hits, hit_cnt);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -41,35 +41,37 @@ struct cc_qstate {
   int n_cand;  // candidates_.size() before tidyUpCandidates
   int flags;
 };
+template <int STR>  // check slots per query: CC_CHK_STRIDE, or CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) for the large-k instance
 struct alignas(16) cc_merge_lds {
-  cc_dcand st[CC_MERGE_BLOCK];             // lane-private candidate state
-  alignas(16) int gid[CC_CHK_STRIDE];      // candidate scan of the i-th passing check (read four at a time)
-  unsigned short ord[CC_CHK_STRIDE];       // its check slot
-  short next[CC_CHK_STRIDE];               // next passing check naming the same scan, -1 = none
-  unsigned short firstrec[CC_CHK_STRIDE];  // first passing check of candidate k (candidates in first-appearance order)
-  alignas(16) int cg[CC_CHK_STRIDE + 4];   // candidate k's scan (+ four sentinels behind the last one)
-  unsigned short clast[CC_CHK_STRIDE];     // candidate k's last check so far
+  cc_dcand st[CC_MERGE_BLOCK];   // lane-private candidate state
+  alignas(16) int gid[STR];      // candidate scan of the i-th passing check (read four at a time)
+  unsigned short ord[STR];       // its check slot
+  short next[STR];               // next passing check naming the same scan, -1 = none
+  unsigned short firstrec[STR];  // first passing check of candidate k (candidates in first-appearance order)
+  alignas(16) int cg[STR + 4];   // candidate k's scan (+ four sentinels behind the last one)
+  unsigned short clast[STR];     // candidate k's last check so far
   int base;
-  unsigned char want[CC_CHK_STRIDE];       // candidate k goes on to the correlation
-  float tperc[CC_HOT_LEVELS][CC_NDIST];    // cont_perc_ of the query's top contours: cell_cnt * 1.0f / layer_cell_cnt
+  unsigned char want[STR];       // candidate k goes on to the correlation
+  float tperc[CC_HOT_LEVELS][CC_NDIST];  // cont_perc_ of the query's top contours: cell_cnt * 1.0f / layer_cell_cnt
 };
 
-static_assert(CC_CHK_STRIDE % CC_MERGE_BLOCK == 0, "merge scan split");
+static_assert(CC_CHK_STRIDE % CC_MERGE_BLOCK == 0 && CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) % CC_MERGE_BLOCK == 0, "merge scan split");
+static_assert(CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) <= 32767, "check slots and list positions are kept in u16 / short");
 static_assert(CC_MERGE_BLOCK == 64, "the list building below uses wave ballots");
 
 // grid = nq, block = CC_MERGE_BLOCK
-__global__ void __launch_bounds__(CC_MERGE_BLOCK)
-cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__restrict__ qdesc,
-           const cc_hot_desc_t *__restrict__ db_desc, const cc_pass_rec *__restrict__ pass, const unsigned char *__restrict__ pass_ok,
-           const int *__restrict__ pass_cnt, cc_cand_out *__restrict__ cands_all, cc_qstate *__restrict__ qstate,
-           cc_gmm_problem *__restrict__ probs /*[nq][CC_MAXCAND]: problem of candidate k of query q*/,
-           int *__restrict__ prob_list /*dense list of the problems that exist*/, int *__restrict__ n_prob,
-           cc_cand_post *__restrict__ post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
-  __shared__ cc_merge_lds L;
+template <int KM>
+__device__ __forceinline__ void cc_merge_body(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *qdesc,
+                                              const cc_hot_desc_t *db_desc, const cc_pass_rec *pass, const unsigned char *pass_ok,
+                                              const int *pass_cnt, cc_cand_out *cands_all, cc_qstate *qstate,
+                                              cc_gmm_problem *probs /*[nq][CC_MAXCAND]: problem of candidate k of query q*/,
+                                              int *prob_list /*dense list of the problems that exist*/, int *n_prob,
+                                              cc_cand_post *post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
+  __shared__ cc_merge_lds<CC_CHK_STRIDE_K(KM)> L;
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (q >= nq) return;
-  const unsigned char *okp = pass_ok + (size_t)q * CC_CHK_STRIDE;
-  const cc_pass_rec *recs = pass + (size_t)q * CC_CHK_STRIDE;
+  const unsigned char *okp = pass_ok + (size_t)q * CC_CHK_STRIDE_K(KM);
+  const cc_pass_rec *recs = pass + (size_t)q * CC_CHK_STRIDE_K(KM);
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   if (tid < CC_HOT_LEVELS * CC_NDIST) {  // visible after the barrier of the list building below
     const int l = tid / CC_NDIST, t_ = tid - l * CC_NDIST;
@@ -79,15 +81,17 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
   // ---- ordered list of the passing checks (slot order = the reference's iteration order): 64 slots per round, the
   //      flags of all rounds fetched up front (coalesced byte loads), positions from ballots
   int n = 0;
-  {
-    unsigned char okv[CC_CHK_STRIDE / 64];
+  // (the large-k instance fetches the flags of 18 rounds at a time: the common instance's whole window)
+  constexpr int NU = CC_CHK_STRIDE / 64;
+  for (int u0 = 0; u0 < CC_CHK_STRIDE_K(KM) / 64; u0 += NU) {
+    unsigned char okv[NU];
 #pragma unroll
-    for (int u = 0; u < CC_CHK_STRIDE / 64; u++) okv[u] = okp[u * 64 + lane];
+    for (int u = 0; u < NU; u++) okv[u] = okp[(u0 + u) * 64 + lane];
 #pragma unroll
-    for (int u = 0; u < CC_CHK_STRIDE / 64; u++) {
+    for (int u = 0; u < NU; u++) {
       const bool ok = okv[u] != 0;
       const unsigned long long m = __ballot(ok);
-      if (ok) L.ord[n + __popcll(m & lt_mask)] = (unsigned short)(u * 64 + lane);
+      if (ok) L.ord[n + __popcll(m & lt_mask)] = (unsigned short)((u0 + u) * 64 + lane);
       n += __popcll(m);
     }
   }
@@ -294,7 +298,7 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
       if (!(neg < (double)lb.neg_est_dist)) {
         // the candidate's correlation problem has a fixed place (no shared counter on this path: a single-address
         // atomic per candidate would serialise the chunk); the dense list is built once per query below
-        gi = q * CC_MAXCAND + k;
+        gi = q * CC_CHK_STRIDE_K(KM) + k;
         cc_gmm_problem pb;
         pb.q = q;
         pb.gidx = c->gidx;
@@ -317,7 +321,7 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
     o.nprops = c->nprops;
     o.gmm_idx = gi;
     o.pad = 0;
-    cands_all[(size_t)q * CC_MAXCAND + k] = o;
+    cands_all[(size_t)q * CC_CHK_STRIDE_K(KM) + k] = o;
   }
   // ---- dense problem list: ordered ranks within the query, one global atomic per query
   __syncthreads();
@@ -331,6 +335,26 @@ cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__r
   }
   if (tid == 0) L.base = n_want ? atomicAdd(n_prob, n_want) : 0;
   __syncthreads();
-  for (int i = tid; i < n_want; i += CC_MERGE_BLOCK) prob_list[L.base + i] = q * CC_MAXCAND + (int)L.ord[i];
+  for (int i = tid; i < n_want; i += CC_MERGE_BLOCK) prob_list[L.base + i] = q * CC_CHK_STRIDE_K(KM) + (int)L.ord[i];
+}
+
+__global__ void __launch_bounds__(CC_MERGE_BLOCK)
+cc_k_merge(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__restrict__ qdesc,
+           const cc_hot_desc_t *__restrict__ db_desc, const cc_pass_rec *__restrict__ pass, const unsigned char *__restrict__ pass_ok,
+           const int *__restrict__ pass_cnt, cc_cand_out *__restrict__ cands_all, cc_qstate *__restrict__ qstate,
+           cc_gmm_problem *__restrict__ probs /*[nq][CC_MAXCAND]: problem of candidate k of query q*/,
+           int *__restrict__ prob_list /*dense list of the problems that exist*/, int *__restrict__ n_prob,
+           cc_cand_post *__restrict__ post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
+  cc_merge_body<CC_KNN_MAX>(nq, lb, n_row, n_col, qdesc, db_desc, pass, pass_ok, pass_cnt, cands_all, qstate, probs, prob_list, n_prob, post);
+}
+// the large-k instance (64 < nnk <= CC_KNN_MAX_LARGE): 4 608 check slots per query, 106 176 B of LDS (one query per CU)
+__global__ void __launch_bounds__(CC_MERGE_BLOCK)
+cc_k_merge_l(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__restrict__ qdesc,
+             const cc_hot_desc_t *__restrict__ db_desc, const cc_pass_rec *__restrict__ pass, const unsigned char *__restrict__ pass_ok,
+             const int *__restrict__ pass_cnt, cc_cand_out *__restrict__ cands_all, cc_qstate *__restrict__ qstate,
+             cc_gmm_problem *__restrict__ probs /*[nq][CC_MAXCAND]: problem of candidate k of query q*/,
+             int *__restrict__ prob_list /*dense list of the problems that exist*/, int *__restrict__ n_prob,
+             cc_cand_post *__restrict__ post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
+  cc_merge_body<CC_KNN_MAX_LARGE>(nq, lb, n_row, n_col, qdesc, db_desc, pass, pass_ok, pass_cnt, cands_all, qstate, probs, prob_list, n_prob, post);
 }
 

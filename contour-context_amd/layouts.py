@@ -8,6 +8,7 @@ import numpy as np
 
 NLEV, KEY_DIM, NPIV, NDIST = 6, 10, 6, 10
 BCI_LAYERS, BCI_MAXPTS, MAXC, MAX_CELLS, NQLEV, KNN_MAX = 4, 40, 320, 22500, 3, 64
+KNN_MAX_LARGE = 256  # nnk upper bound; a database with nnk > KNN_MAX returns hits [nq][NQLEV][NPIV][KNN_MAX_LARGE]
 
 contour_dt = np.dtype([
     ("level", "<i2"), ("poi", "<i2", (2,)), ("cell_cnt", "<i2"),

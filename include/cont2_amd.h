@@ -34,7 +34,8 @@ extern "C" {
 #define CC_MAXC 320        /* stored contours per level per scan (sorted, largest first)        */
 #define CC_MAX_CELLS 22500 /* n_row_*n_col_ upper bound (150x150), LDS-resident BEV             */
 #define CC_NQLEV 3         /* q_levels_.size() upper bound ([1,2,3], yaml :11)                  */
-#define CC_KNN_MAX 64      /* nnk_ upper bound (shipped 50)                                     */
+#define CC_KNN_MAX 64      /* nnk_ of the common kernels and d_knn stride up to it (shipped 50) */
+#define CC_KNN_MAX_LARGE 256 /* nnk_ upper bound: 64 < nnk_ <= 256 runs the large-k instances  */
 #define CC_GMM_LEVELS 4    /* GMMOptConfig::levels_ = {1,2,3,4}, correlation.h:18               */
 
 /* Status codes.  Every entry point returns one; cc_last_error() (thread-local text) explains a non-zero one.
@@ -330,10 +331,14 @@ int cc_scan_on_device(const cc_scan *scan); /* 1: the descriptor still sits in a
 int cc_scan_release(cc_scan *scan);
 
 /* ---------------------------------------------------------------------- database -------- */
-/* Replaces ContourDB::ContourDB (contour_db.h:680-684). */
+/* Replaces ContourDB::ContourDB (contour_db.h:680-684).  1 <= cfg->nnk <= CC_KNN_MAX_LARGE: a database with
+ * nnk > CC_KNN_MAX runs the large-k instances of the query kernels, in chunks of 256 queries. */
 int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db **out);
 int cc_db_destroy(cc_db *db);
 int cc_db_size(const cc_db *db);
+/* The last dimension of d_knn (cc_db_query_batch / cc_db_query_submit): CC_KNN_MAX when nnk <= CC_KNN_MAX, else
+ * CC_KNN_MAX_LARGE.  0 for NULL. */
+int cc_db_knn_stride(const cc_db *db);
 
 /* Replaces ContourDB::addScan + ContourDB::pushAndBalance (contour_db.h:814-843) and
  * LayerDB::rebuild (src/cont2/contour_db.cpp:63-317) for n consecutive scans:
@@ -367,7 +372,8 @@ int cc_db_add_scans_prepare(cc_db *db, const cc_scan_desc_t *d_desc, int n, void
  * reference loop scan i queries epoch i (batch_bin_test.cpp:179 runs before :234-237).
  *   d_qdesc : [nq] query descriptors (device)
  *   h_res   : [nq] results (host)
- *   d_knn   : optional [nq][CC_NQLEV][CC_NPIV][CC_KNN_MAX] hits + d_knn_cnt [nq][3][6] i32
+ *   d_knn   : optional [nq][CC_NQLEV][CC_NPIV][stride] hits, stride = cc_db_knn_stride(db) (CC_KNN_MAX when
+ *             nnk <= CC_KNN_MAX), + d_knn_cnt [nq][3][6] i32
  *             (parity/debug; NULL to skip)
  *   thres_lb: the bars of the four gates and of the post-checks (CandidateScoreEnsemble sim_lb, contour_db.h:374-596)
  *   thres_ub: validated like CandidateManager's ctor does (lb.strictSmaller(ub), contour_db.h:365-367: CC_EINVAL otherwise).
