@@ -43,7 +43,7 @@ _lib = None
 
 # every symbol include/cont2_amd.h declares
 EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_db_cfg", "cc_default_thresholds",
-           "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
+           "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_ingest_points", "cc_ingest_points_host", "cc_scan_ingest_points", "cc_scan_ingest_points_batch", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
            "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_hot_ptr", "cc_db_feat_ptr", "cc_pack_scans", "cc_db_add_packed",
            "cc_packed_sizes", "cc_db_bucket_state", "cc_est_sens_tf",
            "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
@@ -66,6 +66,10 @@ def lib():
         _lib.cc_ingest_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.cc_ingest_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_ingest_host_bev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.cc_ingest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.cc_ingest_points_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.cc_scan_ingest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.cc_scan_ingest_points_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.cc_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_destroy.argtypes = [C.c_void_p]
         _lib.cc_db_size.argtypes = [C.c_void_p]
@@ -118,6 +122,29 @@ class IngestDebug(C.Structure):
 
 DESC_BYTES = L.scan_desc_dt.itemsize
 
+POINT_LAYOUTS = {"xyzi": (16, 0), "xyz": (12, 0)}   # names Context.ingest takes for cc_point_layout_t {stride_bytes, xyz_offset}
+
+
+def _point_layout(layout):
+    """None, "xyz" / "xyzi" or a (stride_bytes, xyz_offset) pair -> L.PointLayout or None (the library checks the values)."""
+    if layout is None:
+        return None
+    if isinstance(layout, str):
+        if layout not in POINT_LAYOUTS:
+            raise ValueError("unknown point layout %r (known: %s, or a (stride_bytes, xyz_offset) pair)" % (layout, sorted(POINT_LAYOUTS)))
+        layout = POINT_LAYOUTS[layout]
+    return L.PointLayout(int(layout[0]), int(layout[1]))
+
+
+def _scan_tf(tf, n):
+    """[n, 3, 4] or [n, 12] -> contiguous f32 [n, 12] (host), or None"""
+    if tf is None:
+        return None
+    tf = np.ascontiguousarray(np.asarray(tf, np.float32).reshape(len(tf), -1))
+    if tf.shape != (n, 12):
+        raise ValueError("tf must hold a 3 x 4 matrix per scan: [%d, 3, 4] or [%d, 12], got %s" % (n, n, tf.shape))
+    return tf
+
 
 def comm_from_env():
     """cc_comm_create_from_env: (handle, rank, world) from RANK / WORLD_SIZE / LOCAL_RANK / MASTER_PORT (one node)."""
@@ -169,11 +196,14 @@ class Context:
         except Exception:
             pass
 
-    def ingest(self, xyzi, offsets, out=None, debug=False):
-        """xyzi: torch float32 CUDA tensor [total_points, 4]; offsets: int64 host array [n+1].
+    def ingest(self, xyzi, offsets, out=None, debug=False, layout=None, tf=None):
+        """xyzi: torch float32 CUDA tensor [total_points, 4]; offsets: int64 host array [n+1] (in points).
+        layout: where x, y, z sit in a record -- None / "xyzi" (16-byte KITTI records), "xyz" (packed, 12 bytes) or a
+        (stride_bytes, xyz_offset) pair; with a layout `xyzi` is any contiguous CUDA tensor holding the records (cc_ingest_points).
+        tf: one row-major 3 x 4 f32 matrix per scan ([n, 3, 4] or [n, 12], host), applied to every point while it is loaded.
         Returns a torch uint8 CUDA tensor [n, DESC_BYTES] (array of cc_scan_desc_t) (+ debug dict)."""
         import torch
-        assert xyzi.is_cuda and xyzi.dtype == torch.float32 and xyzi.is_contiguous()
+        assert xyzi.is_cuda and xyzi.is_contiguous() and (layout is not None or xyzi.dtype == torch.float32)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(offsets) - 1
         if out is None:
@@ -186,8 +216,13 @@ class Context:
             st = IngestDebug(dbg["bev"].data_ptr(), dbg["pix_rc"].data_ptr(), dbg["labels"].data_ptr())
             dbg_p = C.addressof(st)
         stream = torch.cuda.current_stream(xyzi.device).cuda_stream
-        _chk(lib().cc_ingest_batch(self.h, xyzi.data_ptr(), offsets.ctypes.data, n, out.data_ptr(), dbg_p, stream),
-             "cc_ingest_batch")
+        if layout is None and tf is None:
+            _chk(lib().cc_ingest_batch(self.h, xyzi.data_ptr(), offsets.ctypes.data, n, out.data_ptr(), dbg_p, stream),
+                 "cc_ingest_batch")
+        else:
+            lay, tfa = _point_layout(layout), _scan_tf(tf, n)
+            _chk(lib().cc_ingest_points(self.h, xyzi.data_ptr(), C.addressof(lay) if lay is not None else None, offsets.ctypes.data, n,
+                                        tfa.ctypes.data if tfa is not None else None, out.data_ptr(), dbg_p, stream), "cc_ingest_points")
         return (out, dbg) if debug else out
 
     def pack(self, desc):
@@ -202,12 +237,20 @@ class Context:
         _chk(lib().cc_pack_scans(self.h, desc.data_ptr(), n, hot.data_ptr(), feat.data_ptr(), stream), "cc_pack_scans")
         return hot, feat
 
-    def ingest_host(self, xyzi, offsets):
-        xyzi = np.ascontiguousarray(xyzi, np.float32)
+    def ingest_host(self, xyzi, offsets, layout=None, tf=None):
+        """Host records in, host descriptors out.  layout / tf: as for ingest(); with a layout `xyzi` is a contiguous numpy
+        array of any dtype holding the records as they are."""
         offsets = np.ascontiguousarray(offsets, np.int64)
         n = len(offsets) - 1
         out = np.zeros(n, L.scan_desc_dt)
-        _chk(lib().cc_ingest_host(self.h, xyzi.ctypes.data, offsets.ctypes.data, n, out.ctypes.data), "cc_ingest_host")
+        if layout is None and tf is None:
+            xyzi = np.ascontiguousarray(xyzi, np.float32)
+            _chk(lib().cc_ingest_host(self.h, xyzi.ctypes.data, offsets.ctypes.data, n, out.ctypes.data), "cc_ingest_host")
+            return out
+        xyzi = np.ascontiguousarray(xyzi, np.float32) if layout is None else np.ascontiguousarray(xyzi)
+        lay, tfa = _point_layout(layout), _scan_tf(tf, n)
+        _chk(lib().cc_ingest_points_host(self.h, xyzi.ctypes.data, C.addressof(lay) if lay is not None else None, offsets.ctypes.data, n,
+                                         tfa.ctypes.data if tfa is not None else None, out.ctypes.data, None), "cc_ingest_points_host")
         return out
 
 

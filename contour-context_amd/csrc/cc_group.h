@@ -256,6 +256,25 @@ __device__ __forceinline__ T cc_group_bcast(T v, int src) {
 }
 #endif
 
+// three consecutive f32 from a 4-byte aligned address as ONE 12-byte load (global_load_dwordx3).  Read as a struct of three
+// floats the compiler splits it into two overlapping 8-byte loads; a 3-vector whose alignment is lowered to 4 stays whole.
+#ifndef CC_EMU
+typedef float cc_v3u __attribute__((ext_vector_type(3), aligned(4)));
+__device__ __forceinline__ void cc_load3f(const char *p, float &x, float &y, float &z) {
+  const cc_v3u v = *(const cc_v3u *)p;
+  x = v.x;
+  y = v.y;
+  z = v.z;
+}
+#else
+__device__ __forceinline__ void cc_load3f(const char *p, float &x, float &y, float &z) {
+  const float *f = (const float *)p;
+  x = f[0];
+  y = f[1];
+  z = f[2];
+}
+#endif
+
 // value of lane Q of this lane's quad (lanes 4 k .. 4 k + 3)
 #ifndef CC_EMU
 template <int Q>

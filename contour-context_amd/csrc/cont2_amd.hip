@@ -66,6 +66,7 @@ struct cc_ctx {
     cc_k1_part k1_part;  // scratch of the split rasterisation (calls of <= CC_K1_SPLIT_MAX_SCANS scans), allocated at first use
     cc_k2_scratch *d_scr = nullptr;
     long long *d_offsets = nullptr;
+    float *d_tf = nullptr;  // [cap][12]: the per-scan transforms of a call that brings some (cc_ingest_points)
     // the slow path of K2 (scans with more than CC_MAXC components on a level): queue filled by the fast launch, a few
     // workgroups with CC_NC_BIG-sized tables in global memory
     int n_bigslots = 0;
@@ -80,12 +81,14 @@ struct cc_ctx {
   };
   static const int N_BIG_SLOTS = 8;
   Scratch main;
-  // pinned staging ring for the per-chunk point offsets: a slot is reused only after the copy that read it has finished
+  // pinned staging ring for the per-chunk point offsets (and, behind them, the chunk's 12 floats per scan of a call with
+  // transforms): a slot is reused only after the copies that read it have finished
   static const int NSLOT = 4;
   long long *h_off[NSLOT] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t off_ev[NSLOT] = {nullptr, nullptr, nullptr, nullptr};
   bool off_busy[NSLOT] = {false, false, false, false};
   int off_next = 0;
+  int off_cap = 0;  // scans a slot holds
   // the per-scan loop (cc_scan_*): own stream, pinned + device point staging, a pool of device descriptor slots
   hipStream_t s_loop = nullptr;       // per-scan loop: descriptor fetches, cc_db_query_scan / cc_db_add_scan
   // per-scan loop: cc_scan_ingest (copy of the points, K1, K2) goes to the next of CC_NCHAN channels -- own stream, device point
@@ -156,6 +159,7 @@ static int scratch_alloc(cc_ctx *c, cc_ctx::Scratch &S, int cap, int n_bigslots)
   HIPCHK(hipMalloc(&S.d_k1, sizeof(cc_k1_scan_out) * cap));
   HIPCHK(hipMalloc(&S.d_scr, sizeof(cc_k2_scratch) * cap));
   HIPCHK(hipMalloc(&S.d_offsets, sizeof(long long) * (cap + 1)));
+  HIPCHK(hipMalloc(&S.d_tf, sizeof(float) * 12 * (size_t)cap));
   HIPCHK(hipMalloc(&S.d_bigq, sizeof(cc_k2_big_queue) + sizeof(int) * (size_t)cap));
   HIPCHK(hipMemset(S.d_bigq, 0, sizeof(cc_k2_big_queue)));  // the slow launch leaves it empty again
   HIPCHK(hipMalloc(&S.d_midq, sizeof(cc_k2_big_queue) + sizeof(int) * (size_t)cap));
@@ -181,6 +185,7 @@ static void scratch_free(cc_ctx::Scratch &S) {
   hipFree(S.k1_part.red);
   hipFree(S.d_scr);
   hipFree(S.d_offsets);
+  hipFree(S.d_tf);
   hipFree(S.d_bigq);
   hipFree(S.d_midq);
   if (S.h_mid_seen) hipHostFree(S.h_mid_seen);
@@ -320,8 +325,9 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
     cc_destroy(c);
     return CC_EHIP;  // (the message is set)
   }
+  c->off_cap = max_batch_scans > CC_SCAN_BATCH_MAX ? max_batch_scans : CC_SCAN_BATCH_MAX;
   for (int i = 0; i < cc_ctx::NSLOT; i++) {
-    CREATE_CHK(hipHostMalloc((void **)&c->h_off[i], sizeof(long long) * ((max_batch_scans > CC_SCAN_BATCH_MAX ? max_batch_scans : CC_SCAN_BATCH_MAX) + 1), hipHostMallocDefault));
+    CREATE_CHK(hipHostMalloc((void **)&c->h_off[i], (sizeof(long long) + sizeof(float) * 12) * (size_t)(c->off_cap + 1), hipHostMallocDefault));
     CREATE_CHK(hipEventCreateWithFlags(&c->off_ev[i], hipEventDisableTiming));
   }
   c->lds1 = ((nc * 4 + 15) & ~(size_t)15) + ((nc + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15);
@@ -330,6 +336,15 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
+#define CC_K1_REC_ATTR(STRIDE)                                                                                                                                    \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1)); \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
+  CC_K1_REC_ATTR(12)
+  CC_K1_REC_ATTR(16)
+  CC_K1_REC_ATTR(0)
+#undef CC_K1_REC_ATTR
   if (nc > (size_t)CC_MAX_CELLS) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: grid larger than 150 x 150 cells");
@@ -398,14 +413,37 @@ __global__ void cc_k_fill_f32(float *p, float v, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// cc_ingest_batch on the scratch set S (c->ing_mu held by the caller)
-static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const float *d_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *d_out,
-                     const cc_ingest_debug_t *dbg, hipStream_t stream) {
+// The layout a call works with: the caller's, or {16, 0}; CC_EINVAL (nothing queued, no state touched) for one the loaders do not take.
+// base: the DEVICE pointer the kernels will read (4-byte aligned), or nullptr where the records are copied to device memory first.
+static int point_layout(const cc_point_layout_t *layout, const void *base, const char *who, cc_point_layout_t *out) {
+  cc_point_layout_t l;
+  l.stride_bytes = 16;
+  l.xyz_offset = 0;
+  if (layout) l = *layout;
+  const char *why = nullptr;
+  if (l.stride_bytes % 4 != 0 || l.xyz_offset % 4 != 0) why = "stride_bytes and xyz_offset must be multiples of 4";
+  else if (l.xyz_offset < 0 || l.stride_bytes < 12 || l.xyz_offset > l.stride_bytes - 12) why = "xyz_offset + 12 must not exceed stride_bytes";
+  else if (l.stride_bytes > CC_POINT_STRIDE_MAX) why = "stride_bytes above CC_POINT_STRIDE_MAX";
+  else if (((uintptr_t)base & 3u) != 0) why = "the points must be 4-byte aligned";
+  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
+  *out = l;
+  return CC_OK;
+}
+static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
+// an error text that names the entry point the caller called (the old entry points are thin calls of the new ones' bodies)
+#define CC_WHO(text) (std::string(who) + text).c_str()
+
+// cc_ingest_points on the scratch set S (c->ing_mu held by the caller; `lay` has passed point_layout).  h_tf: [n_scans][12] or nullptr.
+static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_point_layout_t lay, const float *h_tf, const int64_t *h_offsets, int n_scans,
+                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, hipStream_t stream, const char *who) {
   HIPCHK(hipSetDevice(c->device));
+  // KITTI records without a transform take the float4 kernels (16-byte loads: the base must be aligned for them); everything
+  // else one of the record loaders' instances
+  const bool kitti = lay.stride_bytes == 16 && lay.xyz_offset == 0 && !h_tf && ((uintptr_t)d_points & 15u) == 0;
   for (int i = 0; i < n_scans; i++) {
     const int64_t n = h_offsets[i + 1] - h_offsets[i];
-    if (!(n > 10)) return set_err(CC_EINVAL, "cc_ingest_batch: scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)");
-    if (n >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, "cc_ingest_batch: scan with >= 2^21 points");
+    if (!(n > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
+    if (n >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": scan with >= 2^21 points"));
   }
   const size_t nc = (size_t)c->dcfg.n_cell;
   if (S.has_last && S.last_stream != stream) HIPCHK(hipStreamWaitEvent(stream, S.ev_last, 0));
@@ -418,9 +456,17 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const float *d_xyzi, const i
     long long *off = c->h_off[slot];
     for (int i = 0; i <= nb; i++) off[i] = (long long)(h_offsets[b0 + i] - h_offsets[b0]);
     HIPCHK(hipMemcpyAsync(S.d_offsets, off, sizeof(long long) * (nb + 1), hipMemcpyHostToDevice, stream));
+    if (h_tf) {  // the chunk's transforms ride in the same slot, behind the offsets
+      float *tfs = (float *)(off + c->off_cap + 1);
+      memcpy(tfs, h_tf + (size_t)b0 * 12, sizeof(float) * 12 * (size_t)nb);
+      HIPCHK(hipMemcpyAsync(S.d_tf, tfs, sizeof(float) * 12 * (size_t)nb, hipMemcpyHostToDevice, stream));
+    }
     HIPCHK(hipEventRecord(c->off_ev[slot], stream));
     c->off_busy[slot] = true;
-    const float4 *pts = (const float4 *)d_xyzi + h_offsets[b0];
+    const float4 *pts = (const float4 *)d_points + h_offsets[b0];  // (the float4 kernels')
+    const char *rpts = (const char *)d_points + (long long)h_offsets[b0] * lay.stride_bytes + lay.xyz_offset;
+    const float *d_tf = h_tf ? S.d_tf : nullptr;
+    const int rstride = lay.stride_bytes;
     // K1's dense image / positions: for the debug outputs, for a configuration K2's list kernel hands on as a whole
     // (min_cont_cell_cnt_ > 3); otherwise only for scans whose active cells overflow the list
     const int want_dense = ((dbg && (dbg->d_bev || dbg->d_pix_rc)) || c->dcfg.min_cont_cell_cnt > 3) ? 1 : 0;
@@ -442,14 +488,46 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const float *d_xyzi, const i
         HIPCHK(hipMalloc(&S.k1_part.idx, sizeof(int) * np * nc));
         HIPCHK(hipMalloc(&S.k1_part.red, sizeof(unsigned) * np * 2));
       }
-      if (c->dcfg.reso_pow2)
-        hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
-                           (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
-      else
-        hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
-                           (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
-      hipLaunchKernelGGL(cc_k_rasterize_merge, dim3(nb), dim3(1024), 0, stream, c->dcfg, pts, (const long long *)S.d_offsets, S.k1_part, S.d_bev,
-                         S.d_pix, S.d_k1, S.list, want_dense);
+      if (kitti) {
+        if (c->dcfg.reso_pow2)
+          hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
+                             (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
+        else
+          hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
+                             (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
+        hipLaunchKernelGGL(cc_k_rasterize_merge, dim3(nb), dim3(1024), 0, stream, c->dcfg, pts, (const long long *)S.d_offsets, S.k1_part, S.d_bev,
+                           S.d_pix, S.d_k1, S.list, want_dense);
+      } else {
+#define CC_K1_REC_SPLIT(STRIDE)                                                                                                                              \
+  {                                                                                                                                                          \
+    if (c->dcfg.reso_pow2)                                                                                                                                   \
+      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
+                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);                      \
+    else                                                                                                                                                     \
+      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
+                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);                      \
+    hipLaunchKernelGGL((cc_k_rasterize_merge_rec<STRIDE>), dim3(nb), dim3(1024), 0, stream, c->dcfg, rpts, rstride, d_tf, (const long long *)S.d_offsets,    \
+                       S.k1_part, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);                                                                             \
+  }
+        if (rstride == 12) CC_K1_REC_SPLIT(12)
+        else if (rstride == 16) CC_K1_REC_SPLIT(16)
+        else CC_K1_REC_SPLIT(0)
+#undef CC_K1_REC_SPLIT
+      }
+    } else if (!kitti) {
+#define CC_K1_REC_WHOLE(STRIDE)                                                                                                                \
+  {                                                                                                                                            \
+    if (c->dcfg.reso_pow2)                                                                                                                     \
+      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
+                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);     \
+    else                                                                                                                                       \
+      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
+                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);     \
+  }
+      if (rstride == 12) CC_K1_REC_WHOLE(12)
+      else if (rstride == 16) CC_K1_REC_WHOLE(16)
+      else CC_K1_REC_WHOLE(0)
+#undef CC_K1_REC_WHOLE
     } else if (c->dcfg.reso_pow2)
       hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts, (const long long *)S.d_offsets,
                          S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
@@ -492,27 +570,55 @@ int cc_ingest_batch(cc_ctx *c, const float *d_xyzi, const int64_t *h_offsets, in
                     const cc_ingest_debug_t *dbg, void *stream_) {
   if (!c || !d_xyzi || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, "cc_ingest_batch: bad argument");
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);  // offsets ring, K1/K2 scratch, ev_last: one call at a time
-  return ingest_on(c, c->main, d_xyzi, h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_);
+  return ingest_on(c, c->main, d_xyzi, CC_LAYOUT_KITTI, nullptr, h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_batch");
 }
+
+static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
+                              cc_scan_desc_t *h_out, float *h_bev, const char *who);
 
 int cc_ingest_host(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out) {
   return cc_ingest_host_bev(c, h_xyzi, h_offsets, n_scans, h_out, nullptr);
 }
 
+int cc_ingest_points(cc_ctx *c, const void *d_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
+                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
+  if (!c || !d_points || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, "cc_ingest_points: bad argument");
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, d_points, "cc_ingest_points", &lay);
+  if (rcl != CC_OK) return rcl;
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+  return ingest_on(c, c->main, d_points, lay, h_tf, h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_points");
+}
+
 int cc_ingest_host_bev(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out, float *h_bev) {
-  if (!c || !h_xyzi || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, "cc_ingest_host: bad argument");
+  return ingest_points_host(c, h_xyzi, nullptr, h_offsets, n_scans, nullptr, h_out, h_bev, "cc_ingest_host");
+}
+
+int cc_ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
+                          cc_scan_desc_t *h_out, float *h_bev) {
+  return ingest_points_host(c, h_points, layout, h_offsets, n_scans, h_tf, h_out, h_bev, "cc_ingest_points_host");
+}
+
+static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
+                              cc_scan_desc_t *h_out, float *h_bev, const char *who) {
+  if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records are copied to aligned device memory)
+  if (rcl != CC_OK) return rcl;
   HIPCHK(hipSetDevice(c->device));
   const int64_t base = h_offsets[0], total = h_offsets[n_scans] - base;
   const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
-  float *d_x = nullptr, *d_b = nullptr;
+  const size_t pts_bytes = (size_t)lay.stride_bytes * (size_t)total;
+  char *d_x = nullptr;
+  float *d_b = nullptr;
   cc_scan_desc_t *d_o = nullptr;
-  HIPCHK(hipMalloc(&d_x, sizeof(float) * 4 * (size_t)total));
+  HIPCHK(hipMalloc(&d_x, pts_bytes));
   hipError_t e = hipMalloc(&d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans);
   if (e == hipSuccess && h_bev) e = hipMalloc(&d_b, bev_bytes);
   if (e != hipSuccess) {
     hipFree(d_x);
     hipFree(d_o);
-    return set_err(CC_EHIP, "cc_ingest_host: hipMalloc", e);
+    return set_err(CC_EHIP, CC_WHO(": hipMalloc"), e);
   }
   cc_ingest_debug_t dbg;
   dbg.d_bev = d_b;
@@ -521,19 +627,22 @@ int cc_ingest_host_bev(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets,
   int rc = CC_OK;
   std::vector<int64_t> off(n_scans + 1);
   for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
-  e = hipMemcpy(d_x, h_xyzi + 4 * base, sizeof(float) * 4 * (size_t)total, hipMemcpyHostToDevice);
-  if (e != hipSuccess) rc = set_err(CC_EHIP, "cc_ingest_host: H2D", e);
-  if (rc == CC_OK) rc = cc_ingest_batch(c, d_x, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr);
+  e = hipMemcpy(d_x, (const char *)h_points + (size_t)lay.stride_bytes * (size_t)base, pts_bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) rc = set_err(CC_EHIP, CC_WHO(": H2D"), e);
+  if (rc == CC_OK) {
+    std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+    rc = ingest_on(c, c->main, d_x, lay, h_tf, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
+  }
   if (rc == CC_OK) {
     e = hipMemcpy(h_out, d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans, hipMemcpyDeviceToHost);
     if (e == hipSuccess && h_bev) e = hipMemcpy(h_bev, d_b, bev_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(CC_EHIP, "cc_ingest_host: D2H", e);
+    if (e != hipSuccess) rc = set_err(CC_EHIP, CC_WHO(": D2H"), e);
   }
   if (rc == CC_OK)
     for (int i = 0; i < n_scans; i++)
       if (h_out[i].flags & (CC_DESC_INEXACT_COMPONENTS | CC_DESC_INEXACT_KEYS)) {
-        rc = set_err(CC_ECAPACITY, "cc_ingest_host: a scan exceeds a fixed capacity of the contour kernel (more than CC_MAXC components on "
-                                   "a level, or an over-full key RoI): its descriptor is not exact");
+        rc = set_err(CC_ECAPACITY, CC_WHO(": a scan exceeds a fixed capacity of the contour kernel (more than CC_MAXC components on "
+                                   "a level, or an over-full key RoI): its descriptor is not exact"));
         break;
       }
   hipFree(d_x);
@@ -649,22 +758,39 @@ int cc_stage_points_cancel(cc_ctx *c, const float *staged) {
   return set_err(CC_EINVAL, "cc_stage_points_cancel: not a staging buffer of this context");
 }
 
+static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
+                              const char *who);
+
 int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_bev, cc_scan **out) {
-  if (!c || !h_xyzi || !out || n_points < 1) return set_err(CC_EINVAL, "cc_scan_ingest: bad argument");
+  return scan_ingest_points(c, h_xyzi, nullptr, n_points, nullptr, want_bev, out, "cc_scan_ingest");
+}
+
+int cc_scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out) {
+  return scan_ingest_points(c, h_xyzi, layout, n_points, h_tf, want_bev, out, "cc_scan_ingest_points");
+}
+
+static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
+                              const char *who) {
+  if (!c || !h_xyzi || !out || n_points < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records go through a staging buffer to aligned device memory)
+  if (rcl != CC_OK) return rcl;
+  const size_t n_bytes = (size_t)n_points * (size_t)lay.stride_bytes;   // the records travel as they are
+  const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);  // d_pts, the slots, the scratch behind cc_ingest_batch
   HIPCHK(hipSetDevice(c->device));
   int slot = -1;
   for (int i = 0; i < cc_ctx::NPTS; i++)
     if (c->h_pts[i] && h_xyzi == c->h_pts[i]) slot = i;
   if (slot < 0) {
-    float *dst = stage_slot_locked(c, n_points, cc_ctx::OWN_SLOT, lk);  // waits for the slot's holder and its previous copy, grows the buffers if need be
-    if (!dst) return set_err(CC_EHIP, "cc_scan_ingest: staging buffer");
-    memcpy(dst, h_xyzi, sizeof(float) * 4 * (size_t)n_points);
+    float *dst = stage_slot_locked(c, n_stage, cc_ctx::OWN_SLOT, lk);  // waits for the slot's holder and its previous copy, grows the buffers if need be
+    if (!dst) return set_err(CC_EHIP, CC_WHO(": staging buffer"));
+    memcpy(dst, h_xyzi, n_bytes);
     slot = cc_ctx::OWN_SLOT;
   } else if (!c->pts_handed[slot] || c->pts_owner[slot] != std::this_thread::get_id()) {
-    return set_err(CC_EINVAL, "cc_scan_ingest: the staging buffer was not handed to this thread by cc_stage_points* (or was ingested already)");
-  } else if (n_points > c->pts_cap) {
-    return set_err(CC_EINVAL, "cc_scan_ingest: more points than were staged");
+    return set_err(CC_EINVAL, CC_WHO(": the staging buffer was not handed to this thread by cc_stage_points* (or was ingested already)"));
+  } else if (n_stage > c->pts_cap) {
+    return set_err(CC_EINVAL, CC_WHO(": more points than were staged"));
   }
   // whatever happens below, the buffer is no longer the caller's: the next thread waiting for the slot may have it once this
   // call has queued (or given up on) the copy
@@ -682,7 +808,7 @@ int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_be
   cc_ctx::Channel &ch = c->chan[c->chan_next];
   c->chan_next = (c->chan_next + 1) % cc_ctx::NCHAN;
   if (want_bev && !ch.d_bev_copy) HIPCHK(hipMalloc(&ch.d_bev_copy, sizeof(float) * (size_t)c->dcfg.n_cell));
-  HIPCHK(hipMemcpyAsync(ch.d_pts, c->h_pts[slot], sizeof(float) * 4 * (size_t)n_points, hipMemcpyHostToDevice, ch.s));
+  HIPCHK(hipMemcpyAsync(ch.d_pts, c->h_pts[slot], n_bytes, hipMemcpyHostToDevice, ch.s));
   HIPCHK(hipEventRecord(c->pts_ev[slot], ch.s));
   c->pts_busy[slot] = true;
   cc_scan *sc = new cc_scan();  // from here on every failure path gives the handle (and, once taken, the descriptor slot) back
@@ -699,7 +825,7 @@ int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_be
       const hipError_t e_ = hipMalloc(&blk, sizeof(cc_scan_desc_t) * nblk);
       if (e_ != hipSuccess) {
         delete sc;
-        return set_err(CC_EHIP, "cc_scan_ingest: descriptor slots", e_);
+        return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_);
       }
       c->slot_blocks.push_back(blk);
       c->slot_block_n.push_back(nblk);
@@ -722,7 +848,7 @@ int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_be
   dbg.d_bev = want_bev ? ch.d_bev_copy : nullptr;
   dbg.d_pix_rc = nullptr;
   dbg.d_labels = nullptr;
-  const int rc = ingest_on(c, ch.scr, ch.d_pts, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s);
+  const int rc = ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
   if (rc != CC_OK) {
     give_back();
     return rc;
@@ -731,12 +857,12 @@ int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_be
     sc->h_bev = (float *)malloc(sizeof(float) * (size_t)c->dcfg.n_cell);
     if (!sc->h_bev) {
       give_back();
-      return set_err(CC_ENOMEM, "cc_scan_ingest: out of host memory");
+      return set_err(CC_ENOMEM, CC_WHO(": out of host memory"));
     }
     const hipError_t e_ = hipMemcpyAsync(sc->h_bev, ch.d_bev_copy, sizeof(float) * (size_t)c->dcfg.n_cell, hipMemcpyDeviceToHost, ch.s);
     if (e_ != hipSuccess) {
       give_back();
-      return set_err(CC_EHIP, "cc_scan_ingest: copy of the BEV image", e_);
+      return set_err(CC_EHIP, CC_WHO(": copy of the BEV image"), e_);
     }
     sc->bev_pending = true;
   }
@@ -745,7 +871,7 @@ int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_be
   if (e_ != hipSuccess) {
     hipStreamSynchronize(ch.s);  // the queued kernels write the slot
     give_back();
-    return set_err(CC_EHIP, "cc_scan_ingest: ready event", e_);
+    return set_err(CC_EHIP, CC_WHO(": ready event"), e_);
   }
   *out = sc;
   return CC_OK;
@@ -769,9 +895,26 @@ cc_k_scatter_desc(cc_desc_out_tab tab, int n, const cc_scan_desc_t *__restrict__
   for (int i = part * 256 + (int)threadIdx.x; i < nv; i += CC_SCATTER_BLOCKS * 256) out[i] = in[i];
 }
 
+static int scan_ingest_points_batch(cc_ctx *c, const void *const *h_xyzi, const cc_point_layout_t *layout, const int64_t *n_points, int n, const float *h_tf,
+                                    cc_scan **out, const char *who);
+
 int cc_scan_ingest_batch(cc_ctx *c, const float *const *h_xyzi, const int64_t *n_points, int n, cc_scan **out) {
+  return scan_ingest_points_batch(c, (const void *const *)h_xyzi, nullptr, n_points, n, nullptr, out, "cc_scan_ingest_batch");
+}
+
+int cc_scan_ingest_points_batch(cc_ctx *c, const void *const *h_xyzi, const cc_point_layout_t *layout, const int64_t *n_points, int n, const float *h_tf,
+                                cc_scan **out) {
+  return scan_ingest_points_batch(c, h_xyzi, layout, n_points, n, h_tf, out, "cc_scan_ingest_points_batch");
+}
+
+static int scan_ingest_points_batch(cc_ctx *c, const void *const *h_xyzi, const cc_point_layout_t *layout, const int64_t *n_points, int n, const float *h_tf,
+                                    cc_scan **out, const char *who) {
   if (!c || !h_xyzi || !n_points || !out || n < 1 || n > CC_SCAN_BATCH_MAX)
-    return set_err(CC_EINVAL, "cc_scan_ingest_batch: bad argument (1..CC_SCAN_BATCH_MAX scans)");
+    return set_err(CC_EINVAL, CC_WHO(": bad argument (1..CC_SCAN_BATCH_MAX scans)"));
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, nullptr, who, &lay);  // (staging buffers are aligned)
+  if (rcl != CC_OK) return rcl;
+  const size_t stride = (size_t)lay.stride_bytes;
   static_assert(sizeof(cc_scan_desc_t) % 8 == 0, "cc_k_scatter_desc copies 8 bytes per lane");
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);
   HIPCHK(hipSetDevice(c->device));
@@ -784,11 +927,12 @@ int cc_scan_ingest_batch(cc_ctx *c, const float *const *h_xyzi, const int64_t *n
     for (int k = 0; k < cc_ctx::NPTS; k++)
       if (c->h_pts[k] && h_xyzi[i] == c->h_pts[k]) slot[i] = k;
     if (slot[i] < 0 || !c->pts_handed[slot[i]] || c->pts_owner[slot[i]] != me)
-      return set_err(CC_EINVAL, "cc_scan_ingest_batch: every buffer must be a staging buffer handed to this thread by cc_stage_points*");
+      return set_err(CC_EINVAL, CC_WHO(": every buffer must be a staging buffer handed to this thread by cc_stage_points*"));
     for (int k = 0; k < i; k++)
-      if (slot[k] == slot[i]) return set_err(CC_EINVAL, "cc_scan_ingest_batch: the same staging buffer twice");
-    if (n_points[i] < 1 || n_points[i] > c->pts_cap) return set_err(CC_EINVAL, "cc_scan_ingest_batch: more points than were staged");
-    if (!(n_points[i] > 10)) return set_err(CC_EINVAL, "cc_scan_ingest_batch: scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)");
+      if (slot[k] == slot[i]) return set_err(CC_EINVAL, CC_WHO(": the same staging buffer twice"));
+    if (n_points[i] < 1 || (int64_t)(((size_t)n_points[i] * stride + 15) / 16) > c->pts_cap)
+      return set_err(CC_EINVAL, CC_WHO(": more points than were staged"));
+    if (!(n_points[i] > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
     off[i + 1] = off[i] + n_points[i];
   }
   // from here on the buffers are no longer the caller's, whatever happens
@@ -804,7 +948,7 @@ int cc_scan_ingest_batch(cc_ctx *c, const float *const *h_xyzi, const int64_t *n
   cc_ctx::Channel &ch = c->chan[c->chan_next];
   c->chan_next = (c->chan_next + 1) % cc_ctx::NCHAN;
   // the channel's point buffer, scratch set and descriptor row grow to a batch's size the first time a batch comes by
-  if (ch.d_pts_cap < off[n] || ch.scr.cap < n || !ch.d_desc_tmp) {
+  if (ch.d_pts_cap < (int64_t)((stride * (size_t)off[n] + 15) / 16) || ch.scr.cap < n || !ch.d_desc_tmp) {
     HIPCHK(hipStreamSynchronize(ch.s));
     if (ch.d_pts_cap < (int64_t)CC_SCAN_BATCH_MAX * c->pts_cap) {
       hipFree(ch.d_pts);
@@ -821,7 +965,7 @@ int cc_scan_ingest_batch(cc_ctx *c, const float *const *h_xyzi, const int64_t *n
     if (!ch.d_desc_tmp) HIPCHK(hipMalloc(&ch.d_desc_tmp, sizeof(cc_scan_desc_t) * CC_SCAN_BATCH_MAX));
   }
   for (int i = 0; i < n; i++) {
-    HIPCHK(hipMemcpyAsync(ch.d_pts + 4 * (size_t)off[i], c->h_pts[slot[i]], sizeof(float) * 4 * (size_t)n_points[i], hipMemcpyHostToDevice, ch.s));
+    HIPCHK(hipMemcpyAsync((char *)ch.d_pts + stride * (size_t)off[i], c->h_pts[slot[i]], stride * (size_t)n_points[i], hipMemcpyHostToDevice, ch.s));
     HIPCHK(hipEventRecord(c->pts_ev[slot[i]], ch.s));
     c->pts_busy[slot[i]] = true;
   }
@@ -855,7 +999,7 @@ int cc_scan_ingest_batch(cc_ctx *c, const float *const *h_xyzi, const int64_t *n
             c->slot_free.push_back(sc[k]->d_desc);
             delete sc[k];
           }
-          return set_err(CC_EHIP, "cc_scan_ingest_batch: descriptor slots", e_);
+          return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_);
         }
         c->slot_blocks.push_back(blk);
         c->slot_block_n.push_back(nblk);
@@ -869,7 +1013,7 @@ int cc_scan_ingest_batch(cc_ctx *c, const float *const *h_xyzi, const int64_t *n
       n_have = i + 1;
     }
   }
-  const int rc = ingest_on(c, ch.scr, ch.d_pts, off, n, ch.d_desc_tmp, nullptr, ch.s);
+  const int rc = ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, n, ch.d_desc_tmp, nullptr, ch.s, who);
   if (rc != CC_OK) {
     give_back();
     return rc;
@@ -883,7 +1027,7 @@ int cc_scan_ingest_batch(cc_ctx *c, const float *const *h_xyzi, const int64_t *n
   if (e_ != hipSuccess) {
     hipStreamSynchronize(ch.s);  // the queued kernels write the slots
     give_back();
-    return set_err(CC_EHIP, "cc_scan_ingest_batch: launch / ready events", e_);
+    return set_err(CC_EHIP, CC_WHO(": launch / ready events"), e_);
   }
   for (int i = 0; i < n; i++) out[i] = sc[i];
   return CC_OK;

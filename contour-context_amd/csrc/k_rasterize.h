@@ -1,7 +1,8 @@
 // K1 -- BEV rasterisation.  Replaces ContourManager::makeBEV (contour_mng.h:505-556) for a batch
 // of scans: one workgroup per scan, the 150x150 max-height grid lives in LDS.
 //
-//   sweep : stream the scan's (x,y,z,i) records ONCE with coalesced 16-B loads, a register-held chunk at a time:
+//   sweep : stream the scan's points ONCE (KITTI (x,y,z,i) records, or the caller's own records through a point loader, below;
+//           an optional per-scan 3 x 4 transform is applied as they arrive), a register-held chunk at a time:
 //           LDS atomicMax of the order-preserving height key per cell               (90 KB LDS), then, among the
 //           chunk's points whose height equals the cell maximum, keep the smallest point index -- the reference
 //           updates a cell only on `bev < height` (strict), so the FIRST point in file order wins ties
@@ -10,7 +11,8 @@
 //   out   : dense bev image + continuous (row_f,col_f) of the winning point per occupied cell
 //           (pointToContRowCol, contour_mng.h:468-472), max/min accepted height, #occupied cells.
 //
-// Roofline: HBM.  Algorithmic bytes = 16 B x points = what the sweep reads.
+// Roofline: HBM.  Algorithmic bytes = 16 B x points = what the sweep reads of KITTI records.  Other layouts:
+// DESIGN.md 3.0 has the measured rows (the byte ratio of a layout is not its speed).
 #pragma once
 #include "cc_dev.h"
 #include "cc_group.h"
@@ -84,13 +86,79 @@ struct cc_k1_list_out {
 #define CC_K1_EMIT_TAB_BYTES (CC_K1_NCHUNK * 2 * 3 + 16)  // u16 entries per chunk | u16 entries before the chunk | u16 slots per chunk | totals
 #define CC_K1_EMIT_LDS_BYTES (CC_K1_EMIT_TAB_BYTES + CC_LIST_CAP * 2)  // ... | u16 cell of every list entry
 
+// ---- point loaders: where a scan's points lie and how they become (x, y, z) ----
+// The kernels read points in three places -- the sweep's prefetched chunk and the two owner re-reads of the output pass -- and all
+// three go through one of these.  load(j) only ISSUES the read of point j (the sweep keeps the next chunk's records in flight
+// while it resolves this one in LDS); xyz() turns a record that has arrived into the coordinates everything downstream sees, and
+// owner_xy(j) is both for the owner of a cell: the same loads and the same operations, so the output pass gets the bits the sweep saw.
+//   cc_ld_kitti       : float4 (x, y, z, intensity) records, 16-byte aligned, no transform -- what cc_ingest_batch takes
+//   cc_ld_rec<STRIDE> : three consecutive f32 at the start of records STRIDE bytes apart (0: the stride is a run-time value), base
+//                       and stride multiples of 4: one 12-byte load per point.  An optional per-scan rigid transform (row-major
+//                       3 x 4, workgroup-uniform, held in scalar registers) is applied as x' = ((m00 x + m01 y) + m02 z) + m03,
+//                       every product and sum rounded once (the library is built with -ffp-contract=off).
+struct cc_xyz {
+  float x, y, z;
+};
+struct cc_ld_kitti {
+  typedef float4 rec;
+  const float4 *__restrict__ P;
+  __device__ __forceinline__ void advance(long long n) { P += n; }
+  __device__ __forceinline__ rec load(int j) const { return P[j]; }
+  __device__ __forceinline__ static rec zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  __device__ __forceinline__ void xyz(const rec &q, float &x, float &y, float &z) const {
+    x = q.x;
+    y = q.y;
+    z = q.z;
+  }
+  __device__ __forceinline__ float2 owner_xy(int j) const { return *(const float2 *)(P + j); }
+};
+template <int STRIDE>
+struct cc_ld_rec {
+  typedef cc_xyz rec;
+  const char *__restrict__ B;  // x of the first point
+  unsigned stride;             // bytes; a scan has fewer than 2^21 points and a record at most CC_POINT_STRIDE_MAX = 2^8 bytes: j * stride < 2^29
+  bool has_tf;                 // a RUN-TIME, workgroup-uniform switch (not a template one): every instance carries the branch and m[]
+  float m[12];
+  // tf: [n_scans][12] or nullptr.  The twelve values are the same for the whole workgroup: handed to the compiler as scalars.
+  __device__ __forceinline__ cc_ld_rec(const char *base, int stride_bytes, const float *__restrict__ tf, int scan)
+      : B(base), stride(STRIDE ? (unsigned)STRIDE : (unsigned)stride_bytes), has_tf(tf != nullptr) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) m[i] = has_tf ? __int_as_float(cc_uniform_i(__float_as_int(tf[(size_t)scan * 12 + i]))) : 0.f;
+  }
+  __device__ __forceinline__ void advance(long long n) { B += n * (long long)stride; }
+  __device__ __forceinline__ rec load(int j) const {
+    cc_xyz q;
+    cc_load3f(B + (unsigned)j * stride, q.x, q.y, q.z);
+    return q;
+  }
+  __device__ __forceinline__ static rec zero() { return cc_xyz{0.f, 0.f, 0.f}; }
+  __device__ __forceinline__ void xyz(const rec &q, float &x, float &y, float &z) const {
+    x = q.x;
+    y = q.y;
+    z = q.z;
+    if (has_tf) {  // workgroup-uniform
+      const float tx = ((m[0] * q.x + m[1] * q.y) + m[2] * q.z) + m[3];
+      const float ty = ((m[4] * q.x + m[5] * q.y) + m[6] * q.z) + m[7];
+      const float tz = ((m[8] * q.x + m[9] * q.y) + m[10] * q.z) + m[11];
+      x = tx;
+      y = ty;
+      z = tz;
+    }
+  }
+  __device__ __forceinline__ float2 owner_xy(int j) const {
+    float x, y, z;
+    xyz(load(j), x, y, z);
+    return make_float2(x, y);
+  }
+};
+
 // The output pass shared by the one-sweep kernel and the merge kernel.  keyfn(c) / idxfn(c): the cell's height key and the
 // scan-relative index of the point that owns it (asked for occupied cells only).  Two sweeps over the cells, a wave
 // on 64 consecutive cells at a time: (1) active cells per chunk (one ballot), prefix by wave 0; (2) the
 // dense image, the continuous position of every occupied cell, and the list entries at their raster-order positions.
 // Returns this thread's count of occupied cells.  tab: CC_K1_EMIT_LDS_BYTES of LDS.
-template <typename KeyFn, typename IdxFn>
-__device__ __forceinline__ int cc_k1_emit(const cc_dev_cfg &cfg, KeyFn keyfn, IdxFn idxfn, const float4 *__restrict__ P, float *__restrict__ bev,
+template <typename KeyFn, typename IdxFn, typename LD>
+__device__ __forceinline__ int cc_k1_emit(const cc_dev_cfg &cfg, KeyFn keyfn, IdxFn idxfn, const LD &P, float *__restrict__ bev,
                                           float2 *__restrict__ pix, const cc_k1_list_out &L, int scan, char *tab, int n_pts, int want_dense, unsigned *kmax_out /*LDS: the largest cell key is max-ed into it (nullptr: not wanted)*/) {
   const int n_cell = cfg.n_cell, tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
   const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
@@ -165,7 +233,7 @@ __device__ __forceinline__ int cc_k1_emit(const cc_dev_cfg &cfg, KeyFn keyfn, Id
         key[e] = cc[e] >= 0 ? keyfn(cc[e]) : KEY_EMPTY;
       }
 #pragma unroll
-      for (int e = 0; e < CC_K1_LB; e++) xy[e] = *(const float2 *)(P + (cc[e] >= 0 ? idxfn(cc[e]) : 0));  // (an active cell has an owner: n_pts > 0)
+      for (int e = 0; e < CC_K1_LB; e++) xy[e] = P.owner_xy(cc[e] >= 0 ? idxfn(cc[e]) : 0);  // (an active cell has an owner: n_pts > 0)
 #pragma unroll
       for (int e = 0; e < CC_K1_LB; e++) {
         const int i = i0 + e * nt + tid, c = cc[e];
@@ -203,7 +271,7 @@ __device__ __forceinline__ int cc_k1_emit(const cc_dev_cfg &cfg, KeyFn keyfn, Id
       const int c = c0 + e * nt + tid;
       const bool need = dense ? key[e] != KEY_EMPTY : cc_funkey(key[e]) > cfg.lv_grads[0];
       const int own = need ? idxfn(c) : 0;
-      xy[e] = n_pts > 0 ? *(const float2 *)(P + own) : make_float2(0.f, 0.f);
+      xy[e] = n_pts > 0 ? P.owner_xy(own) : make_float2(0.f, 0.f);
     }
 #pragma unroll
     for (int e = 0; e < CC_K1_EB; e++) {
@@ -249,12 +317,11 @@ __device__ __forceinline__ int cc_k1_emit(const cc_dev_cfg &cfg, KeyFn keyfn, Id
 }
 
 // grid = n_scans (PART: n_scans * CC_K1_SPLIT), block = multiple of 64.  dynamic LDS: n_cell*4 + ((n_cell+2)/3)*8 + 16 + CC_K1_EMIT_LDS_BYTES bytes.
-template <int CC_K1_U, bool CC_K1_POW2, bool PART = false>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *__restrict__ offsets,
-               float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
-               int want_dense) {
-  HIP_DYNAMIC_SHARED(char, smem)
+// The body of the sweep kernels.  P: the loader of the call's points, positioned at the first point of the call's first scan.
+template <int CC_K1_U, bool CC_K1_POW2, bool PART, typename LD>
+__device__ __forceinline__ void cc_k1_sweep(char *smem, const cc_dev_cfg &cfg, LD P, const long long *__restrict__ offsets,
+                                            float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out,
+                                            const cc_k1_part &part, const cc_k1_list_out &list_out, int want_dense) {
   const int n_cell = cfg.n_cell;
   unsigned *hmax = (unsigned *)smem;
   const int n_w3 = (n_cell + 2) / 3;
@@ -276,7 +343,7 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
     n_pts = n_pts - idx_base < per ? n_pts - idx_base : per;
     p0 += idx_base;
   }
-  const float4 *P = pts + p0;
+  P.advance(p0);
 
   const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
   for (int i = tid; i < n_cell; i += nt) hmax[i] = KEY_EMPTY;
@@ -304,14 +371,14 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
   // its point when it uses it: a load under a branch is waited for where the branch ends (round 6: the prefetch below was
   // no prefetch for two of the four loads).
   const int last = n_pts > 0 ? n_pts - 1 : 0;
-  float4 q[CC_K1_U];
+  typename LD::rec q[CC_K1_U];
 #pragma unroll
-  for (int u = 0; u < CC_K1_U; u++) q[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int u = 0; u < CC_K1_U; u++) q[u] = LD::zero();
   if (n_pts > 0) {
 #pragma unroll
     for (int u = 0; u < CC_K1_U; u++) {
       const int j = tid + u * nt;
-      q[u] = P[j < last ? j : last];
+      q[u] = P.load(j < last ? j : last);
     }
   }
   for (int base = 0; base < n_pts; base += chunk) {
@@ -319,8 +386,10 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
     unsigned key[CC_K1_U];
 #pragma unroll
     for (int u = 0; u < CC_K1_U; u++) {
-      const int c = cc_point_cell<CC_K1_POW2>(cfg, q[u].x, q[u].y);
-      const float h = cfg.lidar_height + q[u].z;
+      float px, py, pz;
+      P.xyz(q[u], px, py, pz);
+      const int c = cc_point_cell<CC_K1_POW2>(cfg, px, py);
+      const float h = cfg.lidar_height + pz;
       key[u] = cc_fkey(h);
       // a NaN height never updates a cell or the max/min in the reference (`bev < NaN`, `max < NaN`, `min > NaN` are
       // all false, contour_mng.h:517-524): such a point is dropped here
@@ -332,7 +401,7 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
 #pragma unroll
     for (int u = 0; u < CC_K1_U; u++) {
       const int j = base + chunk + tid + u * nt;
-      q[u] = P[j < last ? j : last];
+      q[u] = P.load(j < last ? j : last);
     }
     // Consecutive records are neighbouring azimuth steps of one laser: close to the sensor dozens of them fall into
     // the same cell, and same-address LDS atomics of a wave are served one after the other.  So the lanes of a 16-lane
@@ -472,18 +541,41 @@ cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *
   }
 }
 
+// KITTI float4 records, no transform (cc_ingest_batch; the other entry points with the default layout and no transform)
+template <int CC_K1_U, bool CC_K1_POW2, bool PART = false>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *__restrict__ offsets,
+               float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
+               int want_dense) {
+  HIP_DYNAMIC_SHARED(char, smem)
+  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_kitti{pts}, offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+}
+
+// Records of another shape and / or a per-scan transform (cc_ingest_points and its siblings).  STRIDE: 12 (packed xyz), 16 (KITTI
+// records with a transform, or not 16-byte aligned), 0 (run-time stride).  pts: x of the call's first point; tf: [n_scans][12] or nullptr.
+template <int CC_K1_U, bool CC_K1_POW2, bool PART, int STRIDE>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_rec(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, const float *__restrict__ tf, const long long *__restrict__ offsets,
+                   float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
+                   int want_dense) {
+  HIP_DYNAMIC_SHARED(char, smem)
+  const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;
+  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_rec<STRIDE>(pts, stride, tf, scan), offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+}
+
 // The ranges of a scan combined: a cell's height is the largest of the ranges' keys and its point the one of the FIRST
 // range that reaches it -- ranges are in file order and each holds the first of its own points, so this is the first point
 // of the scan at that height: the reference's strict `bev < height` update (contour_mng.h:517) as in the one-sweep kernel.
 // grid = n_scans, block = multiple of 64
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_merge(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *__restrict__ offsets, cc_k1_part part,
-                     float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
+template <typename LD>
+__device__ __forceinline__ void cc_k1_merge(const cc_dev_cfg &cfg, LD P, const long long *__restrict__ offsets, const cc_k1_part &part,
+                                            float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out,
+                                            const cc_k1_list_out &list_out, int want_dense) {
   __shared__ unsigned red[3];
   __shared__ __attribute__((aligned(16))) char emit_tab[CC_K1_EMIT_LDS_BYTES];
   const int scan = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, n_cell = cfg.n_cell;
   const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
-  const float4 *P = pts + offsets[scan];
+  P.advance(offsets[scan]);
   if (tid == 0) {
     unsigned mx = cc_fkey(CC_BEV_EMPTY), mn = cc_fkey(-CC_BEV_EMPTY);
     for (int p = 0; p < CC_K1_SPLIT; p++) {
@@ -534,4 +626,16 @@ cc_k_rasterize_merge(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long 
     o.pad = 0;
     scan_out[scan] = o;
   }
+}
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_merge(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *__restrict__ offsets, cc_k1_part part,
+                     float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
+  cc_k1_merge(cfg, cc_ld_kitti{pts}, offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
+}
+template <int STRIDE>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_merge_rec(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, const float *__restrict__ tf, const long long *__restrict__ offsets,
+                         cc_k1_part part, float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out,
+                         cc_k1_list_out list_out, int want_dense) {
+  cc_k1_merge(cfg, cc_ld_rec<STRIDE>(pts, stride, tf, (int)blockIdx.x), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
 }

@@ -303,6 +303,30 @@ class ContourManager {
     str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
   }
 
+  // Mirror-only: makeBEV for a cloud that is not in the frame the BEV is built in (a tilted or offset sensor, a base-frame
+  // extrinsic, a roll / pitch compensated scan).  T_bev_sensor: row-major 3 x 4 [R | t], applied on the device while the
+  // rasteriser loads the points, x' = ((m00 x + m01 y) + m02 z) + m03 in f32 (cc_scan_ingest_points, include/cont2_amd.h): no
+  // transformed copy of the cloud, and no repack either -- the cloud's own records go to the device as they are (x, y, z must
+  // be three consecutive floats of PointType).
+  template <typename PointType>
+  void makeBEV(typename pcl::PointCloud<PointType>::ConstPtr &ptr_gapc, const float (&T_bev_sensor)[12], std::string str_id = "") {
+    CC_CHECK(ptr_gapc);
+    CC_CHECK(ptr_gapc->size() > 10);
+    CC_CHECK(!scan_);
+    static_assert(sizeof(PointType) % 4 == 0 && sizeof(PointType) <= CC_POINT_STRIDE_MAX, "makeBEV: a record the rasteriser's loaders do not take");
+    const PointType &p0 = ptr_gapc->points[0];
+    const char *base = reinterpret_cast<const char *>(&p0);
+    CC_CHECK(reinterpret_cast<const char *>(&p0.y) == reinterpret_cast<const char *>(&p0.x) + 4);
+    CC_CHECK(reinterpret_cast<const char *>(&p0.z) == reinterpret_cast<const char *>(&p0.x) + 8);
+    cc_point_layout_t lay;
+    lay.stride_bytes = (int32_t)sizeof(PointType);
+    lay.xyz_offset = (int32_t)(reinterpret_cast<const char *>(&p0.x) - base);
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_points(ctx, base, &lay, (int64_t)ptr_gapc->size(), T_bev_sensor, want_images_ ? 1 : 0, &scan_) != CC_OK) die();
+    str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
+  }
+
   // Mirror-only: the evaluator's .bin reader (tools/pointcloud_util.h:9-47: at most 1 000 000 floats, x y z i records,
   // intensity dropped) without the intermediate cloud.  A KITTI record IS a staging record (the kernels never read the
   // fourth float), so the file is read straight into the context's pinned buffer.  Returns the number of points.

@@ -62,6 +62,11 @@ class ManagerCfg(C.Structure):
                 ("point_sigma", C.c_float), ("com_bias_thres", C.c_float)]
 
 
+class PointLayout(C.Structure):
+    """cc_point_layout_t: where the three consecutive f32 (x, y, z) of a point sit.  (16, 0) KITTI, (12, 0) packed xyz."""
+    _fields_ = [("stride_bytes", C.c_int32), ("xyz_offset", C.c_int32)]
+
+
 class SimCfg(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ta_cell_cnt", "tp_cell_cnt", "tp_eigval", "ta_h_bar", "ta_rcom", "tp_rcom")]
 

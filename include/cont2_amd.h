@@ -266,7 +266,9 @@ int cc_profile_read(cc_ctx *ctx, double ms_out[2], int *n_launches);
  *   d_xyzi     : [total_points][4] f32 KITTI layout (x,y,z,intensity), device memory
  *   h_offsets  : [n_scans+1] point offsets of each scan into d_xyzi (host memory)
  *   d_out      : [n_scans] cc_scan_desc_t, device memory
- * Scans with <= 10 points violate CHECK_GT(size,10) (contour_mng.h:507) -> CC_EINVAL. */
+ * Scans with <= 10 points violate CHECK_GT(size,10) (contour_mng.h:507) -> CC_EINVAL.
+ * d_xyzi should be 16-byte aligned: the float4 kernels load 16-byte records.  A base that is only 4-byte aligned is taken
+ * by the record-loader kernels of cc_ingest_points instead (same results, 12-byte loads). */
 int cc_ingest_batch(cc_ctx *ctx, const float *d_xyzi, const int64_t *h_offsets, int n_scans,
                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream);
 
@@ -279,6 +281,40 @@ int cc_ingest_host(cc_ctx *ctx, const float *h_xyzi, const int64_t *h_offsets, i
  * (contour_mng.h:573-586, 1039-1049, 1286-1311; the SAVE_MID_FILE artefacts of the drivers).  h_bev may be NULL. */
 int cc_ingest_host_bev(cc_ctx *ctx, const float *h_xyzi, const int64_t *h_offsets, int n_scans,
                        cc_scan_desc_t *h_out, float *h_bev);
+
+/* ---- points in the caller's own record shape, with an optional per-scan transform ----
+ * The rasteriser reads the records where they lie (no repack pass) and, if asked to, moves every point by a per-scan 3 x 4
+ * matrix while it does (sensor extrinsics, roll / pitch compensation: no transformed copy of the cloud).  Everything behind
+ * the rasteriser is unchanged.
+ *   layout : where the three consecutive f32 (x, y, z) of a point sit.  {16, 0} = KITTI records / PCL PointXYZ,
+ *            {12, 0} = packed xyz, {32, 0} = PCL PointXYZI (what each costs is measured in DESIGN.md 3.0),
+ *            {48, 8} = some driver's PointCloud2 record, ...  NULL means {16, 0}.
+ *            stride_bytes and xyz_offset are multiples of 4, xyz_offset + 12 <= stride_bytes <= CC_POINT_STRIDE_MAX, and the base
+ *            pointer is 4-byte aligned (CC_EINVAL otherwise, nothing is queued).  CC_POINT_STRIDE_MAX is 256: PointCloud2
+ *            records of the common drivers are 16 to 48 bytes, padded PCL types up to 64, and 2^21 points of 256 bytes keep a
+ *            point's byte offset inside its scan below 2^32.  Records that are not 4-byte aligned (22-byte Velodyne
+ *            packets), f64 or integer coordinates and structure-of-arrays inputs are not supported.
+ *   h_offsets : [n_scans+1], in POINTS: scan i starts h_offsets[i] * stride_bytes bytes behind d_points (with 12-byte records
+ *            a scan starts 4-byte aligned, not 16).  The limits on a scan (more than 10 points, fewer than 2^21) count points.
+ *   h_tf   : [n_scans][12] f32 host memory, row-major 3 x 4 (m00 m01 m02 m03 | m10 .. | m20 ..), or NULL for none.  Copied
+ *            before the call returns.  x' = ((m00*x + m01*y) + m02*z) + m03 in f32, every product and every sum rounded
+ *            once, rows 1 and 2 likewise; the matrix is applied as given (not checked to be orthonormal).  Cell, blind-zone
+ *            test, height, max / min height and the continuous position of a cell's point all see (x', y', z') only.
+ * With layout NULL or {16, 0}, h_tf NULL and a 16-byte aligned d_points the call IS cc_ingest_batch (same kernels).  Like
+ * cc_ingest_batch the call only queues work on `stream`; cc_profile_enable brackets its kernels the same way. */
+#define CC_POINT_STRIDE_MAX 256
+typedef struct {
+  int32_t stride_bytes; /* distance between consecutive points */
+  int32_t xyz_offset;   /* byte offset of x inside a record; y and z follow */
+} cc_point_layout_t;
+int cc_ingest_points(cc_ctx *ctx, const void *d_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans,
+                     const float *h_tf, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream);
+/* The same from host records (cc_ingest_host_bev's shape: one H2D copy of the records as they are, results copied back;
+ * h_bev may be NULL).  The host calls (this one and cc_scan_ingest_points*) copy stride_bytes * points bytes: the buffer must
+ * hold WHOLE records up to the end of the last one, also where x, y, z end before the record does.  The host pointer need not
+ * be aligned. */
+int cc_ingest_points_host(cc_ctx *ctx, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans,
+                          const float *h_tf, cc_scan_desc_t *h_out, float *h_bev);
 
 /* ---- the per-scan loop (test/batch_bin_test.cpp:131-237 at sensor rate) ----
  * A cc_scan is ONE scan's descriptor kept on the device between ContourManager::makeContoursRecurs (contour_mng.h:588),
@@ -323,6 +359,15 @@ int cc_scan_ingest(cc_ctx *ctx, const float *h_xyzi, int64_t n_points, int want_
  * latencies whatever it holds), out[i] are ordinary scan handles.  All or nothing: on an error no handle is returned.
  * cc_scan_ready: 1 once the scan's ingest has finished on the device, 0 while it is in flight (never blocks). */
 int cc_scan_ingest_batch(cc_ctx *ctx, const float *const *h_xyzi, const int64_t *n_points, int n, cc_scan **out);
+/* The two calls above for records of another shape and / or with a transform (layout, h_tf: as for cc_ingest_points; one
+ * layout per call, h_tf = 12 floats per scan or NULL).  The records go to the device as they are: no repack on the host.
+ * Staging: a buffer handed out by cc_stage_points* for n_points holds 16 * n_points BYTES, whatever is written there; a
+ * caller with records of stride_bytes stages (n * stride_bytes + 15) / 16 "points" for a scan of n and may write
+ * n * stride_bytes bytes (CC_EINVAL when a scan's bytes exceed what was staged). */
+int cc_scan_ingest_points(cc_ctx *ctx, const void *h_points, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf,
+                          int want_bev, cc_scan **out);
+int cc_scan_ingest_points_batch(cc_ctx *ctx, const void *const *h_points, const cc_point_layout_t *layout, const int64_t *n_points, int n,
+                                const float *h_tf, cc_scan **out);
 int cc_scan_ready(const cc_scan *scan);
 int cc_scan_desc(cc_scan *scan, const cc_scan_desc_t **h_desc);
 int cc_scan_bev(cc_scan *scan, const float **h_bev);
