@@ -43,7 +43,8 @@ _lib = None
 
 # every symbol include/cont2_amd.h declares
 EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_db_cfg", "cc_default_thresholds",
-           "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_ingest_points", "cc_ingest_points_host", "cc_scan_ingest_points", "cc_scan_ingest_points_batch", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
+           "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_ingest_points", "cc_ingest_points_host", "cc_scan_ingest_points", "cc_scan_ingest_points_batch",
+           "cc_ingest_segments", "cc_ingest_segments_host", "cc_scan_ingest_segments", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
            "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_hot_ptr", "cc_db_feat_ptr", "cc_pack_scans", "cc_db_add_packed",
            "cc_packed_sizes", "cc_db_bucket_state", "cc_est_sens_tf",
            "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
@@ -70,6 +71,9 @@ def lib():
         _lib.cc_ingest_points_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.cc_scan_ingest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_scan_ingest_points_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.cc_ingest_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.cc_ingest_segments_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.cc_scan_ingest_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _lib.cc_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_destroy.argtypes = [C.c_void_p]
         _lib.cc_db_size.argtypes = [C.c_void_p]
@@ -144,6 +148,42 @@ def _scan_tf(tf, n):
     if tf.shape != (n, 12):
         raise ValueError("tf must hold a 3 x 4 matrix per scan: [%d, 3, 4] or [%d, 12], got %s" % (n, n, tf.shape))
     return tf
+
+
+def _segment_table(scans, device):
+    """[[(points, layout, tf), ...], ...] -> (array of L.PointSegment, int32 [n + 1] first-segment indices).  points: contiguous CUDA
+    tensors (device=True) or numpy arrays holding the records as they are; None or an empty one for a segment without points."""
+    n_seg = sum(len(sc) for sc in scans)
+    arr = (L.PointSegment * max(n_seg, 1))()
+    scan_segs = np.zeros(len(scans) + 1, np.int32)
+    k = 0
+    for i, sc in enumerate(scans):
+        for (pts, layout, tf) in sc:
+            g = arr[k]
+            lay = _point_layout(layout)
+            stride = 16 if lay is None else lay.stride_bytes
+            if lay is not None:
+                g.layout = lay
+            if pts is not None:
+                if device:
+                    assert pts.is_cuda and pts.is_contiguous()
+                    nbytes, ptr = pts.numel() * pts.element_size(), pts.data_ptr()
+                else:
+                    assert pts.flags["C_CONTIGUOUS"]
+                    nbytes, ptr = pts.nbytes, pts.ctypes.data
+                if stride <= 0 or nbytes % stride != 0:
+                    raise ValueError("segment %d of scan %d: %d bytes are not whole records of %d bytes" % (k - scan_segs[i], i, nbytes, stride))
+                g.n_points = nbytes // stride
+                g.points = ptr if nbytes else None
+            if tf is not None:
+                tf = np.asarray(tf, np.float32).reshape(-1)
+                if tf.shape != (12,):
+                    raise ValueError("a segment's tf is a 3 x 4 matrix (12 values)")
+                g.has_tf = 1
+                g.tf[:] = tf.tolist()
+            k += 1
+        scan_segs[i + 1] = k
+    return arr, scan_segs
 
 
 def comm_from_env():
@@ -224,6 +264,37 @@ class Context:
             _chk(lib().cc_ingest_points(self.h, xyzi.data_ptr(), C.addressof(lay) if lay is not None else None, offsets.ctypes.data, n,
                                         tfa.ctypes.data if tfa is not None else None, out.data_ptr(), dbg_p, stream), "cc_ingest_points")
         return (out, dbg) if debug else out
+
+    def ingest_segments(self, scans, out=None, debug=False):
+        """Every scan from an ordered list of point segments, each with its own record shape and transform (cc_ingest_segments):
+        scans = [[(points, layout, tf), ...], ...] with `points` a contiguous CUDA tensor holding the segment's records (read in
+        place; the tensors of one call may be separate allocations), `layout` as ingest() takes it and `tf` a 3 x 4 / 12-value
+        array or None.  The result is ingest()'s for the cloud T_0(segment 0) ++ T_1(segment 1) ++ ... of every scan.
+        Returns a torch uint8 CUDA tensor [n, DESC_BYTES] (+ debug dict)."""
+        import torch
+        arr, scan_segs = _segment_table(scans, device=True)
+        n = len(scans)
+        dev = next((p.device for sc in scans for (p, _l, _t) in sc if p is not None), torch.device("cuda", self.device))
+        if out is None:
+            out = torch.empty((n, DESC_BYTES), dtype=torch.uint8, device=dev)
+        dbg_p, dbg = None, None
+        if debug:
+            dbg = {"bev": torch.empty((n, self.n_cell), dtype=torch.float32, device=dev),
+                   "pix_rc": torch.empty((n, self.n_cell, 2), dtype=torch.float32, device=dev),
+                   "labels": torch.empty((n, L.NLEV, self.n_cell), dtype=torch.int16, device=dev)}
+            st = IngestDebug(dbg["bev"].data_ptr(), dbg["pix_rc"].data_ptr(), dbg["labels"].data_ptr())
+            dbg_p = C.addressof(st)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _chk(lib().cc_ingest_segments(self.h, C.addressof(arr), scan_segs.ctypes.data, n, out.data_ptr(), dbg_p, stream), "cc_ingest_segments")
+        return (out, dbg) if debug else out
+
+    def ingest_segments_host(self, scans):
+        """ingest_segments() from host records (numpy arrays of any dtype holding the records as they are): host descriptors out."""
+        arr, scan_segs = _segment_table(scans, device=False)
+        out = np.zeros(len(scans), L.scan_desc_dt)
+        _chk(lib().cc_ingest_segments_host(self.h, C.addressof(arr), scan_segs.ctypes.data, len(scans), out.ctypes.data, None),
+             "cc_ingest_segments_host")
+        return out
 
     def pack(self, desc):
         """Full descriptors (torch uint8 CUDA [n, DESC_BYTES]) -> (hot [n, HOT_BYTES], feat [n, FEAT_BYTES]): the compact

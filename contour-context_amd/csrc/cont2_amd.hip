@@ -67,6 +67,7 @@ struct cc_ctx {
     cc_k2_scratch *d_scr = nullptr;
     long long *d_offsets = nullptr;
     float *d_tf = nullptr;  // [cap][12]: the per-scan transforms of a call that brings some (cc_ingest_points)
+    char *d_seg = nullptr;  // a chunk's segment table (cc_ingest_segments): int scan_seg[cap + 1], then up to cap * CC_SEG_MAX cc_k1_seg; allocated at first use
     // the slow path of K2 (scans with more than CC_MAXC components on a level): queue filled by the fast launch, a few
     // workgroups with CC_NC_BIG-sized tables in global memory
     int n_bigslots = 0;
@@ -89,6 +90,8 @@ struct cc_ctx {
   bool off_busy[NSLOT] = {false, false, false, false};
   int off_next = 0;
   int off_cap = 0;  // scans a slot holds
+  char *h_seg[NSLOT] = {nullptr, nullptr, nullptr, nullptr};  // the same ring's slots for a chunk's segment table (cc_ingest_segments), grown to what a chunk needs
+  size_t h_seg_cap[NSLOT] = {0, 0, 0, 0};
   // the per-scan loop (cc_scan_*): own stream, pinned + device point staging, a pool of device descriptor slots
   hipStream_t s_loop = nullptr;       // per-scan loop: descriptor fetches, cc_db_query_scan / cc_db_add_scan
   // per-scan loop: cc_scan_ingest (copy of the points, K1, K2) goes to the next of CC_NCHAN channels -- own stream, device point
@@ -186,6 +189,7 @@ static void scratch_free(cc_ctx::Scratch &S) {
   hipFree(S.d_scr);
   hipFree(S.d_offsets);
   hipFree(S.d_tf);
+  hipFree(S.d_seg);
   hipFree(S.d_bigq);
   hipFree(S.d_midq);
   if (S.h_mid_seen) hipHostFree(S.h_mid_seen);
@@ -345,6 +349,11 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
   CC_K1_REC_ATTR(16)
   CC_K1_REC_ATTR(0)
 #undef CC_K1_REC_ATTR
+  const int lds1_seg = (int)(c->lds1 + CC_K1_SEG_LDS_BYTES);  // (the segment table sits behind the layout of the other instances)
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
   if (nc > (size_t)CC_MAX_CELLS) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: grid larger than 150 x 150 cells");
@@ -395,6 +404,7 @@ int cc_destroy(cc_ctx *c) {
   scratch_free(c->main);
   for (int i = 0; i < cc_ctx::NSLOT; i++) {
     if (c->h_off[i]) hipHostFree(c->h_off[i]);
+    if (c->h_seg[i]) hipHostFree(c->h_seg[i]);
     if (c->off_ev[i]) hipEventDestroy(c->off_ev[i]);
   }
   if (c->s_loop) {
@@ -433,9 +443,16 @@ static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
 // an error text that names the entry point the caller called (the old entry points are thin calls of the new ones' bodies)
 #define CC_WHO(text) (std::string(who) + text).c_str()
 
+// A checked cc_*_segments call (segs_check below) as ingest_on takes it: one entry per segment with the DEVICE address of its first
+// x; the scans' point totals are the call's h_offsets.
+struct seg_call {
+  const cc_k1_seg *segs;
+  const int32_t *scan_segs;  // [n_scans + 1]
+};
 // cc_ingest_points on the scratch set S (c->ing_mu held by the caller; `lay` has passed point_layout).  h_tf: [n_scans][12] or nullptr.
+// sg: nullptr, or the call's segments -- d_points, lay and h_tf are not looked at then (cc_ingest_segments).
 static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_point_layout_t lay, const float *h_tf, const int64_t *h_offsets, int n_scans,
-                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, hipStream_t stream, const char *who) {
+                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, hipStream_t stream, const char *who, const seg_call *sg = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   // KITTI records without a transform take the float4 kernels (16-byte loads: the base must be aligned for them); everything
   // else one of the record loaders' instances
@@ -461,10 +478,29 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
       memcpy(tfs, h_tf + (size_t)b0 * 12, sizeof(float) * 12 * (size_t)nb);
       HIPCHK(hipMemcpyAsync(S.d_tf, tfs, sizeof(float) * 12 * (size_t)nb, hipMemcpyHostToDevice, stream));
     }
+    cc_k1_segs d_segs = {nullptr, nullptr};
+    if (sg) {  // the chunk's segment table rides in the same slot of the ring: scan_seg[nb + 1] relative to the chunk's first segment, then the entries
+      const int s0 = sg->scan_segs[b0], ns = sg->scan_segs[b0 + nb] - s0;
+      const size_t ent_off = (sizeof(int) * (size_t)(nb + 1) + 7) & ~(size_t)7, bytes = ent_off + sizeof(cc_k1_seg) * (size_t)ns;
+      if (!S.d_seg) HIPCHK(hipMalloc(&S.d_seg, ((sizeof(int) * (size_t)(S.cap + 1) + 7) & ~(size_t)7) + sizeof(cc_k1_seg) * CC_SEG_MAX * (size_t)S.cap));
+      if (c->h_seg_cap[slot] < bytes) {
+        if (c->h_seg[slot]) hipHostFree(c->h_seg[slot]);
+        c->h_seg[slot] = nullptr;
+        c->h_seg_cap[slot] = 0;
+        HIPCHK(hipHostMalloc((void **)&c->h_seg[slot], bytes * 2, hipHostMallocDefault));
+        c->h_seg_cap[slot] = bytes * 2;
+      }
+      int *ss = (int *)c->h_seg[slot];
+      for (int i = 0; i <= nb; i++) ss[i] = sg->scan_segs[b0 + i] - s0;
+      memcpy(c->h_seg[slot] + ent_off, sg->segs + s0, sizeof(cc_k1_seg) * (size_t)ns);
+      HIPCHK(hipMemcpyAsync(S.d_seg, c->h_seg[slot], bytes, hipMemcpyHostToDevice, stream));
+      d_segs.scan_seg = (const int *)S.d_seg;
+      d_segs.seg = (const cc_k1_seg *)(S.d_seg + ent_off);
+    }
     HIPCHK(hipEventRecord(c->off_ev[slot], stream));
     c->off_busy[slot] = true;
-    const float4 *pts = (const float4 *)d_points + h_offsets[b0];  // (the float4 kernels')
-    const char *rpts = (const char *)d_points + (long long)h_offsets[b0] * lay.stride_bytes + lay.xyz_offset;
+    const float4 *pts = sg ? nullptr : (const float4 *)d_points + h_offsets[b0];  // (the float4 kernels')
+    const char *rpts = sg ? nullptr : (const char *)d_points + (long long)h_offsets[b0] * lay.stride_bytes + lay.xyz_offset;
     const float *d_tf = h_tf ? S.d_tf : nullptr;
     const int rstride = lay.stride_bytes;
     // K1's dense image / positions: for the debug outputs, for a configuration K2's list kernel hands on as a whole
@@ -488,7 +524,16 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
         HIPCHK(hipMalloc(&S.k1_part.idx, sizeof(int) * np * nc));
         HIPCHK(hipMalloc(&S.k1_part.red, sizeof(unsigned) * np * 2));
       }
-      if (kitti) {
+      if (sg) {
+        if (c->dcfg.reso_pow2)
+          hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream,
+                             c->dcfg, d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
+        else
+          hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream,
+                             c->dcfg, d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
+        hipLaunchKernelGGL(cc_k_rasterize_merge_seg, dim3(nb), dim3(1024), 0, stream, c->dcfg, d_segs, (const long long *)S.d_offsets, S.k1_part, S.d_bev,
+                           S.d_pix, S.d_k1, S.list, want_dense);
+      } else if (kitti) {
         if (c->dcfg.reso_pow2)
           hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
                              (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
@@ -514,6 +559,13 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
         else CC_K1_REC_SPLIT(0)
 #undef CC_K1_REC_SPLIT
       }
+    } else if (sg) {
+      if (c->dcfg.reso_pow2)
+        hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, false>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream, c->dcfg,
+                           d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
+      else
+        hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, false>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream, c->dcfg,
+                           d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
     } else if (!kitti) {
 #define CC_K1_REC_WHOLE(STRIDE)                                                                                                                \
   {                                                                                                                                            \
@@ -599,6 +651,18 @@ int cc_ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout
   return ingest_points_host(c, h_points, layout, h_offsets, n_scans, h_tf, h_out, h_bev, "cc_ingest_points_host");
 }
 
+// the results of a host call back to the host (blocking copies: they wait for the call's kernels); CC_ECAPACITY for an inexact descriptor
+static int host_results(const cc_scan_desc_t *d_o, const float *d_b, size_t bev_bytes, int n_scans, cc_scan_desc_t *h_out, float *h_bev, const char *who) {
+  hipError_t e = hipMemcpy(h_out, d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && h_bev) e = hipMemcpy(h_bev, d_b, bev_bytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return set_err(CC_EHIP, CC_WHO(": D2H"), e);
+  for (int i = 0; i < n_scans; i++)
+    if (h_out[i].flags & (CC_DESC_INEXACT_COMPONENTS | CC_DESC_INEXACT_KEYS))
+      return set_err(CC_ECAPACITY, CC_WHO(": a scan exceeds a fixed capacity of the contour kernel (more than CC_MAXC components on "
+                                          "a level, or an over-full key RoI): its descriptor is not exact"));
+  return CC_OK;
+}
+
 static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
                               cc_scan_desc_t *h_out, float *h_bev, const char *who) {
   if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
@@ -633,18 +697,117 @@ static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_la
     std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
     rc = ingest_on(c, c->main, d_x, lay, h_tf, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
   }
-  if (rc == CC_OK) {
-    e = hipMemcpy(h_out, d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_bev) e = hipMemcpy(h_bev, d_b, bev_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(CC_EHIP, CC_WHO(": D2H"), e);
+  if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
+  hipFree(d_x);
+  hipFree(d_o);
+  hipFree(d_b);
+  return rc;
+}
+
+// ---- scans made of segments (cc_ingest_segments and its siblings) ----
+// Everything the header promises to check, before anything is queued or read.  tab: one entry per segment, `base` = the caller's
+// pointer + xyz_offset (the host calls replace it with where the records went on the device); q_off: the scans' point totals as offsets.
+static int segs_check(const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, const char *who, std::vector<cc_k1_seg> &tab,
+                      std::vector<int64_t> &q_off) {
+  q_off.assign(1, 0);
+  for (int i = 0; i < n_scans; i++) {
+    const int64_t ns = (int64_t)h_scan_segs[i + 1] - h_scan_segs[i];
+    if (h_scan_segs[i] < 0 || ns < 1 || ns > CC_SEG_MAX) return set_err(CC_EINVAL, CC_WHO(": a scan has 1 .. CC_SEG_MAX segments"));
+    int64_t total = 0;
+    for (int k = h_scan_segs[i]; k < h_scan_segs[i + 1]; k++) {
+      const cc_point_segment_t &g = h_segs[k];
+      if (g.n_points < 0 || g.n_points >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": a segment's n_points is negative or >= 2^21"));
+      if (g.n_points > 0 && !g.points) return set_err(CC_EINVAL, CC_WHO(": a segment with points has a NULL pointer"));
+      cc_point_layout_t lay;
+      const bool dflt = g.layout.stride_bytes == 0 && g.layout.xyz_offset == 0;
+      const int rcl = point_layout(dflt ? nullptr : &g.layout, g.n_points > 0 ? g.points : nullptr, who, &lay);
+      if (rcl != CC_OK) return rcl;
+      cc_k1_seg e;
+      e.base = (const char *)g.points + lay.xyz_offset;
+      e.stride = (unsigned)lay.stride_bytes;
+      e.first = (int)total;
+      e.n = (int)g.n_points;
+      e.has_tf = g.has_tf != 0;
+      for (int m = 0; m < 12; m++) e.m[m] = g.has_tf ? g.tf[m] : 0.f;
+      tab.push_back(e);
+      total += g.n_points;
+      if (total >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": scan with >= 2^21 points"));
+    }
+    if (!(total > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
+    q_off.push_back(q_off.back() + total);
   }
-  if (rc == CC_OK)
-    for (int i = 0; i < n_scans; i++)
-      if (h_out[i].flags & (CC_DESC_INEXACT_COMPONENTS | CC_DESC_INEXACT_KEYS)) {
-        rc = set_err(CC_ECAPACITY, CC_WHO(": a scan exceeds a fixed capacity of the contour kernel (more than CC_MAXC components on "
-                                   "a level, or an over-full key RoI): its descriptor is not exact"));
-        break;
-      }
+  return CC_OK;
+}
+
+int cc_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, cc_scan_desc_t *d_out,
+                       const cc_ingest_debug_t *dbg, void *stream_) {
+  const char *who = "cc_ingest_segments";
+  if (!c || !h_segs || !h_scan_segs || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  std::vector<cc_k1_seg> tab;
+  std::vector<int64_t> q_off;
+  const int rcs = segs_check(h_segs, h_scan_segs, n_scans, who, tab, q_off);
+  if (rcs != CC_OK) return rcs;
+  std::vector<int32_t> ss(n_scans + 1);
+  for (int i = 0; i <= n_scans; i++) ss[i] = h_scan_segs[i] - h_scan_segs[0];  // (tab begins with the call's first segment)
+  const seg_call sg = {tab.data(), ss.data()};
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+  return ingest_on(c, c->main, nullptr, CC_LAYOUT_KITTI, nullptr, q_off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who, &sg);
+}
+
+// Where the records of the checked segments `tab` (host pointers) go in ONE buffer: every segment at a 16-byte boundary, whole records.
+// Returns the buffer's bytes; off[k]: segment k's place.
+static size_t segs_place(const cc_point_segment_t *h_segs, const std::vector<cc_k1_seg> &tab, std::vector<size_t> &off) {
+  size_t bytes = 0;
+  for (size_t k = 0; k < tab.size(); k++) {
+    off.push_back(bytes);
+    bytes += ((size_t)h_segs[k].n_points * tab[k].stride + 15) & ~(size_t)15;
+  }
+  return bytes;
+}
+
+int cc_ingest_segments_host(cc_ctx *c, const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, cc_scan_desc_t *h_out, float *h_bev) {
+  const char *who = "cc_ingest_segments_host";
+  if (!c || !h_segs || !h_scan_segs || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  std::vector<cc_k1_seg> tab;
+  std::vector<int64_t> q_off;
+  const int rcs = segs_check(h_segs, h_scan_segs, n_scans, who, tab, q_off);
+  if (rcs != CC_OK) return rcs;
+  h_segs += h_scan_segs[0];
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<size_t> off;
+  const size_t pts_bytes = segs_place(h_segs, tab, off);
+  const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
+  char *d_x = nullptr;
+  float *d_b = nullptr;
+  cc_scan_desc_t *d_o = nullptr;
+  HIPCHK(hipMalloc(&d_x, pts_bytes));
+  hipError_t e = hipMalloc(&d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans);
+  if (e == hipSuccess && h_bev) e = hipMalloc(&d_b, bev_bytes);
+  if (e != hipSuccess) {
+    hipFree(d_x);
+    hipFree(d_o);
+    return set_err(CC_EHIP, CC_WHO(": hipMalloc"), e);
+  }
+  for (size_t k = 0; k < tab.size() && e == hipSuccess; k++) {
+    if (tab[k].n > 0) e = hipMemcpy(d_x + off[k], h_segs[k].points, (size_t)tab[k].n * tab[k].stride, hipMemcpyHostToDevice);
+    tab[k].base = d_x + off[k] + (tab[k].base - (const char *)h_segs[k].points);
+  }
+  // (the rows of a descriptor that its counts do not cover are not written by the kernels: zero here, so that the call's bytes are
+  // those of cc_ingest_segments into zeroed memory)
+  if (e == hipSuccess) e = hipMemset(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans);
+  int rc = e == hipSuccess ? CC_OK : set_err(CC_EHIP, CC_WHO(": H2D"), e);
+  cc_ingest_debug_t dbg;
+  dbg.d_bev = d_b;
+  dbg.d_pix_rc = nullptr;
+  dbg.d_labels = nullptr;
+  if (rc == CC_OK) {
+    std::vector<int32_t> ss(n_scans + 1);
+    for (int i = 0; i <= n_scans; i++) ss[i] = h_scan_segs[i] - h_scan_segs[0];
+    const seg_call sg = {tab.data(), ss.data()};
+    std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+    rc = ingest_on(c, c->main, nullptr, CC_LAYOUT_KITTI, nullptr, q_off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who, &sg);
+  }
+  if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
   hipFree(d_x);
   hipFree(d_o);
   hipFree(d_b);
@@ -759,7 +922,7 @@ int cc_stage_points_cancel(cc_ctx *c, const float *staged) {
 }
 
 static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who);
+                              const char *who, const cc_point_segment_t *h_segs = nullptr, int n_segs = 0);
 
 int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_bev, cc_scan **out) {
   return scan_ingest_points(c, h_xyzi, nullptr, n_points, nullptr, want_bev, out, "cc_scan_ingest");
@@ -769,13 +932,31 @@ int cc_scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t
   return scan_ingest_points(c, h_xyzi, layout, n_points, h_tf, want_bev, out, "cc_scan_ingest_points");
 }
 
+int cc_scan_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, int n_segs, int want_bev, cc_scan **out) {
+  if (!h_segs) return set_err(CC_EINVAL, "cc_scan_ingest_segments: bad argument");
+  return scan_ingest_points(c, nullptr, nullptr, 0, nullptr, want_bev, out, "cc_scan_ingest_segments", h_segs, n_segs);
+}
+
+// h_segs: nullptr, or the scan's n_segs host segments (cc_scan_ingest_segments; h_xyzi, layout, n_points and h_tf are not looked at then):
+// their records go to the staging buffer one segment after the other, each at a 16-byte boundary.
 static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who) {
-  if (!c || !h_xyzi || !out || n_points < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  cc_point_layout_t lay;
-  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records go through a staging buffer to aligned device memory)
-  if (rcl != CC_OK) return rcl;
-  const size_t n_bytes = (size_t)n_points * (size_t)lay.stride_bytes;   // the records travel as they are
+                              const char *who, const cc_point_segment_t *h_segs, int n_segs) {
+  if (!c || (!h_xyzi && !h_segs) || !out || (!h_segs && n_points < 1)) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  cc_point_layout_t lay = CC_LAYOUT_KITTI;
+  std::vector<cc_k1_seg> seg_tab;
+  std::vector<int64_t> seg_qoff;
+  std::vector<size_t> seg_place;
+  const int32_t seg_scan[2] = {0, n_segs};
+  size_t seg_bytes = 0;
+  if (h_segs) {
+    const int rcs = segs_check(h_segs, seg_scan, 1, who, seg_tab, seg_qoff);
+    if (rcs != CC_OK) return rcs;
+    seg_bytes = segs_place(h_segs, seg_tab, seg_place);
+  } else {
+    const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records go through a staging buffer to aligned device memory)
+    if (rcl != CC_OK) return rcl;
+  }
+  const size_t n_bytes = h_segs ? seg_bytes : (size_t)n_points * (size_t)lay.stride_bytes;   // the records travel as they are
   const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);  // d_pts, the slots, the scratch behind cc_ingest_batch
   HIPCHK(hipSetDevice(c->device));
@@ -785,7 +966,12 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
   if (slot < 0) {
     float *dst = stage_slot_locked(c, n_stage, cc_ctx::OWN_SLOT, lk);  // waits for the slot's holder and its previous copy, grows the buffers if need be
     if (!dst) return set_err(CC_EHIP, CC_WHO(": staging buffer"));
-    memcpy(dst, h_xyzi, n_bytes);
+    if (h_segs) {
+      for (int k = 0; k < n_segs; k++)
+        if (seg_tab[k].n > 0) memcpy((char *)dst + seg_place[k], h_segs[k].points, (size_t)seg_tab[k].n * seg_tab[k].stride);
+    } else {
+      memcpy(dst, h_xyzi, n_bytes);
+    }
     slot = cc_ctx::OWN_SLOT;
   } else if (!c->pts_handed[slot] || c->pts_owner[slot] != std::this_thread::get_id()) {
     return set_err(CC_EINVAL, CC_WHO(": the staging buffer was not handed to this thread by cc_stage_points* (or was ingested already)"));
@@ -848,7 +1034,17 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
   dbg.d_bev = want_bev ? ch.d_bev_copy : nullptr;
   dbg.d_pix_rc = nullptr;
   dbg.d_labels = nullptr;
-  const int rc = ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
+  if (h_segs) {  // a pool slot holds an earlier scan's rows: zero, as cc_ingest_segments_host does, for the same bytes
+    const hipError_t e_ = hipMemsetAsync(sc->d_desc, 0, sizeof(cc_scan_desc_t), ch.s);
+    if (e_ != hipSuccess) {
+      give_back();
+      return set_err(CC_EHIP, CC_WHO(": hipMemsetAsync"), e_);
+    }
+  }
+  for (int k = 0; k < n_segs; k++) seg_tab[k].base = (const char *)ch.d_pts + seg_place[k] + (seg_tab[k].base - (const char *)h_segs[k].points);
+  const seg_call sg = {seg_tab.data(), seg_scan};
+  const int rc = h_segs ? ingest_on(c, ch.scr, nullptr, lay, nullptr, seg_qoff.data(), 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, &sg)
+                        : ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
   if (rc != CC_OK) {
     give_back();
     return rc;

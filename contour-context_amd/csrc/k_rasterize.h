@@ -639,3 +639,351 @@ cc_k_rasterize_merge_rec(cc_dev_cfg cfg, const char *__restrict__ pts, int strid
                          cc_k1_list_out list_out, int want_dense) {
   cc_k1_merge(cfg, cc_ld_rec<STRIDE>(pts, stride, tf, (int)blockIdx.x), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
 }
+
+// ---- a scan made of several SEGMENTS (cc_ingest_segments): records in up to CC_SEG_MAX places, each with its own stride and its own
+// optional transform; the scan is their points one after the other, and a point's index -- what the 21-bit fields hold, what step B
+// min-reduces and what "the first range wins" in the merge kernel is about -- is its index in THAT sequence.  So the tie rule holds
+// across segments with the logic above: the sweep only has to hand cc_k1_resolve the right j0.
+struct cc_k1_seg {
+  const char *base;  // x of the segment's first point
+  unsigned stride;   // bytes between records
+  int first;         // index within the scan of the segment's first point
+  int n;             // points (0: the segment is skipped)
+  int has_tf;
+  float m[12];       // row-major 3 x 4, read when has_tf != 0
+};
+struct cc_k1_segs {
+  const cc_k1_seg *seg;  // the call's segments, scan after scan
+  const int *scan_seg;   // [n_scans + 1]: scan i is made of the segments scan_seg[i] .. scan_seg[i + 1] - 1
+};
+#define CC_K1_SEG_LDS_BYTES (CC_SEG_MAX * (int)sizeof(cc_k1_seg))  // a scan's table in LDS, behind cc_k1_sweep's layout: 2 304 of the 5 504 bytes K1 leaves of a CU's LDS at 150 x 150
+
+// The scan's table to LDS (a barrier has to follow); returns the number of its segments.
+__device__ __forceinline__ int cc_k1_seg_table(cc_k1_seg *T, const cc_k1_segs &segs, int scan) {
+  const int s0 = segs.scan_seg[scan], n_seg = segs.scan_seg[scan + 1] - s0;
+  const unsigned *__restrict__ src = (const unsigned *)(segs.seg + s0);
+  unsigned *dst = (unsigned *)T;
+  for (int i = threadIdx.x; i < n_seg * (int)(sizeof(cc_k1_seg) / 4); i += blockDim.x) dst[i] = src[i];
+  return n_seg;
+}
+
+// The pieces of cc_k1_sweep's chunk loop as functions, for cc_k1_sweep_seg below, which runs them once per piece of a scan.  (cc_k1_sweep
+// keeps its own text: built from these functions its instances came out with another register allocation and schedule, and the
+// existing kernels are not to move -- a change to one of the two has to be made in the other.)
+// The cells and height keys of the chunk's points that have arrived in q[]: lane tid (of nt) holds the points tid + u * nt of the
+// chunk, of which the first n_left exist.  kmin: the smallest key of an accepted point.
+template <int CC_K1_U, bool CC_K1_POW2, typename LD>
+__device__ __forceinline__ void cc_k1_cells(const cc_dev_cfg &cfg, const LD &P, const typename LD::rec (&q)[CC_K1_U], int n_left, int (&cell)[CC_K1_U],
+                                            unsigned (&key)[CC_K1_U], unsigned &kmin, const int tid, const int nt) {
+#pragma unroll
+  for (int u = 0; u < CC_K1_U; u++) {
+    float px, py, pz;
+    P.xyz(q[u], px, py, pz);
+    const int c = cc_point_cell<CC_K1_POW2>(cfg, px, py);
+    const float h = cfg.lidar_height + pz;
+    key[u] = cc_fkey(h);
+    // a NaN height never updates a cell or the max/min in the reference (`bev < NaN`, `max < NaN`, `min > NaN` are
+    // all false, contour_mng.h:517-524): such a point is dropped here
+    cell[u] = ((h == h) & (tid + u * nt < n_left)) ? c : -1;
+    const unsigned kb = cell[u] >= 0 ? key[u] : 0xFFFFFFFFu;
+    kmin = kb < kmin ? kb : kmin;
+  }
+}
+
+// Steps A and B (cc_k1_sweep) for one chunk; j0: the scan-relative index of the chunk's first point.  Two barriers.
+template <int CC_K1_U>
+__device__ __forceinline__ void cc_k1_resolve(unsigned *hmax, unsigned long long *idx3, unsigned *idle, int n_w3, const int (&cell)[CC_K1_U],
+                                              const unsigned (&key)[CC_K1_U], int j0, const int tid, const int nt) {
+  const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
+  // Consecutive records are neighbouring azimuth steps of one laser: close to the sensor dozens of them fall into
+  // the same cell, and same-address LDS atomics of a wave are served one after the other.  So the lanes of a 16-lane
+  // row first combine their heights per run of equal cells (segmented max over DPP row shifts), and only the last
+  // lane of a run goes to the LDS, with the run's maximum.  Which lanes continue their left neighbour's run is ONE wave
+  // mask; the masks of the wider steps ("the 2, 4, 8 lanes to my left are in my run") and the senders' come from it with
+  // scalar shifts (round 6: a compare of shifted cells per step before) -- a step is a DPP max and a select.
+  unsigned kr[CC_K1_U], was[CC_K1_U];
+#pragma unroll
+  for (int u = 0; u < CC_K1_U; u++) {
+    const int c1 = cell[u] + 1;  // 0 = rejected point (and what a row shift reads beyond the row's end: a run ends at its row's end)
+    unsigned k = cell[u] >= 0 ? key[u] : 0u;  // (rejected lanes form runs of their own, of zeros)
+    const unsigned long long m1 = __ballot(cc_row_shr<1>(c1) == c1);
+    const unsigned long long m2 = m1 & (m1 << 1), m4 = m2 & (m2 << 2), m8 = m4 & (m4 << 4);
+    {
+      const unsigned ok = (unsigned)cc_row_shr<1>((int)k);
+      k = cc_mask_lane(m1) ? (ok > k ? ok : k) : k;
+    }
+    {
+      const unsigned ok = (unsigned)cc_row_shr<2>((int)k);
+      k = cc_mask_lane(m2) ? (ok > k ? ok : k) : k;
+    }
+    {
+      const unsigned ok = (unsigned)cc_row_shr<4>((int)k);
+      k = cc_mask_lane(m4) ? (ok > k ? ok : k) : k;
+    }
+    {
+      const unsigned ok = (unsigned)cc_row_shr<8>((int)k);
+      k = cc_mask_lane(m8) ? (ok > k ? ok : k) : k;
+    }
+    const unsigned long long last_of_run = ~(m1 >> 1) | 0x8000800080008000ull;
+    kr[u] = cc_mask_lane(last_of_run) ? k : 0u;  // 0: this lane sends nothing (no height maps to key 0; a rejected lane holds 0)
+  }
+  // the chunk's atomics leave together (round 6: one after the other, each waited for, they were four LDS round trips)
+#pragma unroll
+  for (int u = 0; u < CC_K1_U; u++) was[u] = atomicMax(kr[u] ? &hmax[cell[u]] : &idle[tid], kr[u]);
+#pragma unroll
+  for (int u = 0; u < CC_K1_U; u++)
+    if (was[u] < kr[u]) {
+      int w, sh;
+      cc_k1_field(cell[u], n_w3, w, sh);
+      atomicOr(&idx3[w], CC_K1_IDX_MASK << sh);
+    }
+  __syncthreads();
+  // step B: which of this lane's points hold their cell's maximum (four reads in flight), then ONE loop in which a lane
+  // works off its winners one CAS attempt per turn -- a retry and the next winner's first attempt share a turn
+  unsigned pend = 0u;
+  {
+    unsigned hm[CC_K1_U];
+#pragma unroll
+    for (int u = 0; u < CC_K1_U; u++) hm[u] = hmax[cell[u] >= 0 ? cell[u] : 0];
+#pragma unroll
+    for (int u = 0; u < CC_K1_U; u++) pend |= (cell[u] >= 0 && key[u] == hm[u] && key[u] != KEY_EMPTY) ? (1u << u) : 0u;
+  }
+  {
+    bool busy = false;
+    int w = 0, sh = 0;
+    unsigned long long j = 0ull, old = 0ull;
+    while (pend || busy) {
+      if (!busy) {
+        const int u = __ffs(pend) - 1;
+        pend &= pend - 1u;
+        int c = cell[0];
+#pragma unroll
+        for (int v = 1; v < CC_K1_U; v++) c = u == v ? cell[v] : c;
+        cc_k1_field(c, n_w3, w, sh);
+        j = (unsigned long long)(j0 + tid + u * nt);
+        old = idx3[w];
+        busy = true;
+      }
+      const unsigned long long cur = (old >> sh) & CC_K1_IDX_MASK;
+      if (j >= cur) {
+        busy = false;
+      } else {
+        const unsigned long long nw = (old & ~(CC_K1_IDX_MASK << sh)) | (j << sh);
+        const unsigned long long got = atomicCAS(&idx3[w], old, nw);
+        busy = got != old;
+        old = got;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// What follows a sweep: the min key, then (PART) the range's grid to the scratch or the output pass.  n_pts: the points this workgroup swept.
+template <bool PART, typename LD>
+__device__ __forceinline__ void cc_k1_finish(const cc_dev_cfg &cfg, const LD &P, unsigned *hmax, unsigned long long *idx3, unsigned *red, char *emit_tab, int n_w3,
+                                             unsigned kmin, int unit, int scan, int n_pts, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
+                                             cc_k1_scan_out *__restrict__ scan_out, const cc_k1_part &part, const cc_k1_list_out &list_out, int want_dense,
+                                             const int tid, const int nt) {
+  const int n_cell = cfg.n_cell;
+  const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned b2 = (unsigned)__shfl_xor((int)kmin, o);
+    kmin = b2 < kmin ? b2 : kmin;
+  }
+  if ((tid & 63) == 0) atomicMin(&red[1], kmin);
+  __syncthreads();
+
+  if (PART) {  // this range's grid to the scratch; cc_k_rasterize_merge combines the ranges
+    unsigned *pk = part.key + (size_t)unit * n_cell;
+    int *pj = part.idx + (size_t)unit * n_cell;
+    unsigned kmx = KEY_EMPTY;
+    for (int c = tid; c < n_cell; c += nt) {
+      const unsigned k = hmax[c];
+      kmx = k > kmx ? k : kmx;
+      pk[c] = k;
+      int w, sh;
+      cc_k1_field(c, n_w3, w, sh);
+      pj[c] = k != KEY_EMPTY ? (int)((idx3[w] >> sh) & CC_K1_IDX_MASK) : -1;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned a = (unsigned)__shfl_xor((int)kmx, o);
+      kmx = a > kmx ? a : kmx;
+    }
+    if ((tid & 63) == 0) atomicMax(&red[0], kmx);
+    __syncthreads();
+    if (tid == 0) {
+      part.red[(size_t)unit * 2] = red[0];
+      part.red[(size_t)unit * 2 + 1] = red[1];
+    }
+    return;
+  }
+  // ---- outputs ----
+  float *bev = bev_out + (size_t)scan * n_cell;
+  float2 *pix = pix_out + (size_t)scan * n_cell;
+  int npix = cc_k1_emit(
+      cfg,
+      [&](int c) { return hmax[c]; },
+      [&](int c) {
+        int w, sh;
+        cc_k1_field(c, n_w3, w, sh);
+        return (int)((idx3[w] >> sh) & CC_K1_IDX_MASK);
+      },
+      P, bev, pix, list_out, scan, emit_tab, n_pts, want_dense, &red[0]);
+  npix = cc_wave_sum(npix);
+  if ((tid & 63) == 0) atomicAdd(&red[2], (unsigned)npix);
+  __syncthreads();
+  if (tid == 0) {
+    cc_k1_scan_out o;
+    o.max_bin_val = cc_funkey(red[0]);
+    o.min_bin_val = cc_funkey(red[1]);
+    o.n_pix = (int)red[2];
+    o.pad = 0;
+    scan_out[scan] = o;
+  }
+}
+
+// The output pass' loader: the owner of a cell is known by its index within the scan -- its segment is the last one that begins at
+// or before it (a search over at most CC_SEG_MAX prefix sums; empty segments share their successor's `first` and are passed over),
+// and the point is moved by THAT segment's matrix, per lane, with cc_ld_rec::xyz's operations in its order.
+struct cc_ld_segs {
+  const cc_k1_seg *T;  // LDS
+  int n_seg;
+  __device__ __forceinline__ void advance(long long) {}
+  __device__ __forceinline__ float2 owner_xy(int j) const {
+    int s = 0;
+    for (int i = 1; i < n_seg; i++) s += j >= T[i].first ? 1 : 0;
+    const cc_k1_seg &g = T[s];
+    float x, y, z;
+    cc_load3f(g.base + (unsigned)(j - g.first) * g.stride, x, y, z);
+    const float tx = ((g.m[0] * x + g.m[1] * y) + g.m[2] * z) + g.m[3];
+    const float ty = ((g.m[4] * x + g.m[5] * y) + g.m[6] * z) + g.m[7];
+    return g.has_tf ? make_float2(tx, ty) : make_float2(x, y);
+  }
+};
+
+// The record loader seated on segment s, lo points into it.  Workgroup-uniform like cc_ld_rec's arguments: stride and matrix stay scalars.
+__device__ __forceinline__ cc_ld_rec<0> cc_k1_seg_loader(const cc_k1_seg *T, int s, int lo) {
+  const cc_k1_seg &g = T[s];
+  cc_ld_rec<0> P(cc_uniform_ptr(g.base), cc_uniform_i((int)g.stride), cc_uniform_i(g.has_tf) ? g.m : nullptr, 0);
+  P.advance(lo);
+  return P;
+}
+
+// cc_k1_sweep for a scan of segments.  The workgroup's range of the scan (all of it; PART: one of CC_K1_SPLIT ranges, which may begin
+// and end inside segments) is cut into PIECES, one per segment that has points in it, and the chunk loop restarts with every piece:
+// stride and matrix are what they are in cc_ld_rec -- scalars, re-seated between pieces -- at the price of one partly filled chunk
+// per piece.  The prefetch stays unconditional across pieces: a piece's last chunk requests the first records of the NEXT piece (the
+// base, the stride and the clamp are selected as scalars; the load itself is under no branch).  tab_off: where the table goes in smem.
+template <int CC_K1_U, bool CC_K1_POW2, bool PART>
+__device__ __forceinline__ void cc_k1_sweep_seg(char *smem, int tab_off, const cc_dev_cfg &cfg, const cc_k1_segs &segs, const long long *__restrict__ offsets,
+                                                float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out,
+                                                const cc_k1_part &part, const cc_k1_list_out &list_out, int want_dense) {
+  const int n_cell = cfg.n_cell;
+  unsigned *hmax = (unsigned *)smem;  // (cc_k1_sweep's layout)
+  const int n_w3 = (n_cell + 2) / 3;
+  unsigned long long *idx3 = (unsigned long long *)(smem + (((size_t)n_cell * 4 + 15) & ~(size_t)15));
+  unsigned *red = (unsigned *)(idx3 + n_w3);
+  char *emit_tab = (char *)(red + 4);
+  unsigned *idle = (unsigned *)(emit_tab + CC_K1_EMIT_TAB_BYTES);
+  cc_k1_seg *T = (cc_k1_seg *)(smem + tab_off);
+
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int unit = (int)blockIdx.x;
+  const int scan = PART ? unit / CC_K1_SPLIT : unit;
+  int n_pts = (int)(offsets[scan + 1] - offsets[scan]);  // of the whole scan: the segments' counts added up
+  int idx_base = 0;
+  if (PART) {  // the same ranges as cc_k1_sweep's
+    const int per = (n_pts + CC_K1_SPLIT - 1) / CC_K1_SPLIT, pi = unit % CC_K1_SPLIT;
+    idx_base = pi * per < n_pts ? pi * per : n_pts;
+    n_pts = n_pts - idx_base < per ? n_pts - idx_base : per;
+  }
+  const int n_seg = cc_k1_seg_table(T, segs, scan);
+  const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
+  for (int i = tid; i < n_cell; i += nt) hmax[i] = KEY_EMPTY;
+  for (int i = tid; i < n_w3; i += nt) idx3[i] = ~0ull;
+  idle[tid] = 0u;
+  if (tid == 0) {
+    red[0] = cc_fkey(CC_BEV_EMPTY);
+    red[1] = cc_fkey(-CC_BEV_EMPTY);
+    red[2] = 0;
+  }
+  __syncthreads();
+
+  // the first segment from s on with points in the range: `lo` points into it, cnt of them (n_seg: none left)
+  const int q0 = idx_base, q1 = idx_base + n_pts;
+  auto piece = [&](int s, int &lo, int &cnt) {
+    for (; s < n_seg; s++) {
+      const int f = T[s].first, hi = q1 - f < T[s].n ? q1 - f : T[s].n;
+      lo = q0 > f ? q0 - f : 0;
+      cnt = hi - lo;
+      if (cnt > 0) break;
+    }
+    lo = cc_uniform_i(lo);
+    cnt = cc_uniform_i(cnt);
+    return cc_uniform_i(s);
+  };
+  unsigned kmin = cc_fkey(-CC_BEV_EMPTY);
+  const int chunk = CC_K1_U * nt;
+  int lo = 0, cnt = 0;
+  int s = piece(0, lo, cnt);
+  if (s < n_seg) {
+    cc_ld_rec<0> P = cc_k1_seg_loader(T, s, lo);
+    cc_xyz q[CC_K1_U];
+#pragma unroll
+    for (int u = 0; u < CC_K1_U; u++) {
+      const int j = tid + u * nt;
+      q[u] = P.load(j < cnt - 1 ? j : cnt - 1);
+    }
+    while (s < n_seg) {
+      int lo2 = 0, cnt2 = 0;
+      const int s2 = piece(s + 1, lo2, cnt2);
+      // what this piece's last chunk prefetches: the next piece's first records (the last piece: its own last record, dropped)
+      const char *nB = P.B;
+      unsigned nstride = P.stride;
+      int nlast = cnt - 1;
+      if (s2 < n_seg) {
+        nstride = (unsigned)cc_uniform_i((int)T[s2].stride);
+        nB = cc_uniform_ptr(T[s2].base) + (long long)lo2 * (long long)nstride;
+        nlast = cnt2 - 1;
+      }
+      const int j_piece = cc_uniform_i(T[s].first) + lo;  // index within the scan of the piece's first point
+      for (int base = 0; base < cnt; base += chunk) {
+        int cell[CC_K1_U];
+        unsigned key[CC_K1_U];
+        cc_k1_cells<CC_K1_U, CC_K1_POW2>(cfg, P, q, cnt - base, cell, key, kmin, tid, nt);
+        const bool more = base + chunk < cnt;
+        const char *lB = more ? P.B : nB;
+        const unsigned lstride = more ? P.stride : nstride;
+        const int l0 = more ? base + chunk : 0, llast = more ? cnt - 1 : nlast;
+#pragma unroll
+        for (int u = 0; u < CC_K1_U; u++) {
+          const int j = l0 + tid + u * nt;
+          cc_load3f(lB + (unsigned)(j < llast ? j : llast) * lstride, q[u].x, q[u].y, q[u].z);
+        }
+        cc_k1_resolve<CC_K1_U>(hmax, idx3, idle, n_w3, cell, key, j_piece + base, tid, nt);
+      }
+      s = s2;
+      lo = lo2;
+      cnt = cnt2;
+      if (s < n_seg) P = cc_k1_seg_loader(T, s, lo);
+    }
+  }
+  cc_k1_finish<PART>(cfg, cc_ld_segs{T, n_seg}, hmax, idx3, red, emit_tab, n_w3, kmin, unit, scan, n_pts, bev_out, pix_out, scan_out, part, list_out, want_dense, tid, nt);
+}
+
+// grid, block as cc_k_rasterize; dynamic LDS: tab_off (cc_k_rasterize's bytes) + CC_K1_SEG_LDS_BYTES
+template <int CC_K1_U, bool CC_K1_POW2, bool PART>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_seg(cc_dev_cfg cfg, cc_k1_segs segs, int tab_off, const long long *__restrict__ offsets, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
+                   cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out, int want_dense) {
+  HIP_DYNAMIC_SHARED(char, smem)
+  cc_k1_sweep_seg<CC_K1_U, CC_K1_POW2, PART>(smem, tab_off, cfg, segs, offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+}
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_merge_seg(cc_dev_cfg cfg, cc_k1_segs segs, const long long *__restrict__ offsets, cc_k1_part part, float *__restrict__ bev_out,
+                         float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
+  __shared__ cc_k1_seg T[CC_SEG_MAX];
+  const int n_seg = cc_k1_seg_table(T, segs, (int)blockIdx.x);
+  __syncthreads();
+  cc_k1_merge(cfg, cc_ld_segs{T, n_seg}, offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
+}

@@ -327,6 +327,52 @@ class ContourManager {
     str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
   }
 
+  // Mirror-only: ONE BEV from several clouds, each in a frame of its own -- the sensors of a multi-LiDAR rig with their extrinsics,
+  // or the last few sweeps with their odometry poses (a local submap).  The scan is the clouds' points one after the other in the
+  // order given, each moved by its own T_bev_sensor as in the overload above (nullptr: the cloud is in the BEV's frame already);
+  // among points of equal height in a cell the first one in that order owns the cell.  The clouds' own records go to the device as
+  // they are and are rasterised where they land (cc_scan_ingest_segments, include/cont2_amd.h): no transformed or concatenated
+  // copy.  A cloud may be empty (a sensor that dropped a frame); together they must hold more than 10 points.
+  template <typename PointType>
+  struct BevSegment {
+    typename pcl::PointCloud<PointType>::ConstPtr cloud;
+    const float (*T_bev_sensor)[12] = nullptr;
+  };
+  template <typename PointType>
+  void makeBEV(const std::vector<BevSegment<PointType>> &segments, std::string str_id = "") {
+    CC_CHECK(!segments.empty() && segments.size() <= (size_t)CC_SEG_MAX);
+    CC_CHECK(!scan_);
+    static_assert(sizeof(PointType) % 4 == 0 && sizeof(PointType) <= CC_POINT_STRIDE_MAX, "makeBEV: a record the rasteriser's loaders do not take");
+    std::vector<cc_point_segment_t> segs(segments.size());
+    size_t total = 0;
+    for (size_t i = 0; i < segments.size(); i++) {
+      const auto &cloud = segments[i].cloud;
+      CC_CHECK(cloud);
+      cc_point_segment_t &g = segs[i];
+      memset(&g, 0, sizeof(g));
+      g.n_points = (int64_t)cloud->size();
+      g.layout.stride_bytes = (int32_t)sizeof(PointType);
+      if (cloud->size() > 0) {
+        const PointType &p0 = cloud->points[0];
+        const char *base = reinterpret_cast<const char *>(&p0);
+        CC_CHECK(reinterpret_cast<const char *>(&p0.y) == reinterpret_cast<const char *>(&p0.x) + 4);
+        CC_CHECK(reinterpret_cast<const char *>(&p0.z) == reinterpret_cast<const char *>(&p0.x) + 8);
+        g.points = base;
+        g.layout.xyz_offset = (int32_t)(reinterpret_cast<const char *>(&p0.x) - base);
+      }
+      if (segments[i].T_bev_sensor) {
+        g.has_tf = 1;
+        memcpy(g.tf, *segments[i].T_bev_sensor, sizeof(g.tf));
+      }
+      total += cloud->size();
+    }
+    CC_CHECK(total > 10);
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_segments(ctx, segs.data(), (int)segs.size(), want_images_ ? 1 : 0, &scan_) != CC_OK) die();
+    str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(segments[0].cloud->header.stamp);
+  }
+
   // Mirror-only: the evaluator's .bin reader (tools/pointcloud_util.h:9-47: at most 1 000 000 floats, x y z i records,
   // intensity dropped) without the intermediate cloud.  A KITTI record IS a staging record (the kernels never read the
   // fourth float), so the file is read straight into the context's pinned buffer.  Returns the number of points.

@@ -67,6 +67,18 @@ class PointLayout(C.Structure):
     _fields_ = [("stride_bytes", C.c_int32), ("xyz_offset", C.c_int32)]
 
 
+SEG_MAX = 32  # CC_SEG_MAX: segments per scan of cc_ingest_segments
+
+
+class PointSegment(C.Structure):
+    """cc_point_segment_t: n_points records at `points` (layout {0, 0} stands for {16, 0}) with an optional row-major 3 x 4 matrix."""
+    _fields_ = [("points", C.c_void_p), ("n_points", C.c_int64), ("layout", PointLayout), ("has_tf", C.c_int32), ("pad_", C.c_int32),
+                ("tf", C.c_float * 12)]
+
+
+assert C.sizeof(PointSegment) == 80 and PointSegment.tf.offset == 32
+
+
 class SimCfg(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ta_cell_cnt", "tp_cell_cnt", "tp_eigval", "ta_h_bar", "ta_rcom", "tp_rcom")]
 

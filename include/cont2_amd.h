@@ -316,6 +316,47 @@ int cc_ingest_points(cc_ctx *ctx, const void *d_points, const cc_point_layout_t 
 int cc_ingest_points_host(cc_ctx *ctx, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans,
                           const float *h_tf, cc_scan_desc_t *h_out, float *h_bev);
 
+/* ---- a scan from several point SEGMENTS, each with its own record shape and its own transform ----
+ * A multi-LiDAR rig (every sensor its own driver, buffer, record shape and extrinsics) or a local submap (the last few sweeps, each
+ * with its odometry pose) into ONE max-height image / ONE descriptor, without a pass that transforms and concatenates the
+ * clouds first: the rasteriser sweeps the segments where they lie, one after the other.  No reference counterpart.
+ * A scan is an ordered list of 1 .. CC_SEG_MAX segments; a segment is n_points records at `points` of layout
+ * {stride_bytes, xyz_offset} with an optional row-major 3 x 4 f32 matrix.  The scan's result -- descriptor, bev, pix_rc, labels,
+ * every byte -- is the one cc_ingest_batch gives for the cloud
+ *     Q = T_0(segment 0) ++ T_1(segment 1) ++ ... ++ T_{S-1}(segment S-1)
+ * (++: concatenation in the order given; T_s: the operation cc_ingest_points documents for h_tf, or the identity on the bits for
+ * a segment without a matrix).  In particular: among points of equal height in one cell the FIRST point of Q owns the cell,
+ * whichever segment it is in -- a segment listed earlier wins over one listed later; max / min height, n_pix, the blind zone
+ * and the map's border see the moved points only.
+ * Checked before anything is queued or read (CC_EINVAL, the context stays as it was): 1 .. CC_SEG_MAX segments per scan;
+ * n_points >= 0 (0: a sensor that dropped a frame; `points` may be NULL then); the scan's TOTAL point count is what the limits
+ * on a scan count (more than 10, fewer than 2^21: a point's index within Q has 21 bits); every segment's layout passes
+ * cc_ingest_points' rules; every non-empty segment's pointer is non-NULL and 4-byte aligned (the host calls too).
+ * What the kernels cost next to cc_ingest_points': DESIGN.md 3.0. */
+#define CC_SEG_MAX 32
+typedef struct {
+  const void *points;       /* first record of the segment (device or host pointer, see the call) */
+  int64_t n_points;
+  cc_point_layout_t layout; /* {0, 0} stands for {16, 0}, like a NULL layout of cc_ingest_points */
+  int32_t has_tf, pad_;
+  float tf[12];             /* row-major 3 x 4, read when has_tf != 0 */
+} cc_point_segment_t;       /* 80 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cc_point_segment_t) == 80 && offsetof(cc_point_segment_t, tf) == 32, "cc_point_segment_t: 80 bytes, tf at 32");
+#else
+_Static_assert(sizeof(cc_point_segment_t) == 80 && offsetof(cc_point_segment_t, tf) == 32, "cc_point_segment_t: 80 bytes, tf at 32");
+#endif
+/* scan i = the segments h_segs[h_scan_segs[i] .. h_scan_segs[i + 1]); `points` are DEVICE pointers, read in place; the segments
+ * of one call may lie in different allocations.  h_segs and h_scan_segs are copied before the call returns.  Queues work on
+ * `stream` like cc_ingest_points (calls with more scans than the context's max_batch_scans go in chunks; cc_profile_enable
+ * brackets the kernels the same way). */
+int cc_ingest_segments(cc_ctx *ctx, const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, cc_scan_desc_t *d_out,
+                       const cc_ingest_debug_t *dbg, void *stream);
+/* The same from HOST records: the segments' records are copied to the device as they are (whole records, one staging pass),
+ * results copied back; h_bev may be NULL. */
+int cc_ingest_segments_host(cc_ctx *ctx, const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, cc_scan_desc_t *h_out,
+                            float *h_bev);
+
 /* ---- the per-scan loop (test/batch_bin_test.cpp:131-237 at sensor rate) ----
  * A cc_scan is ONE scan's descriptor kept on the device between ContourManager::makeContoursRecurs (contour_mng.h:588),
  * ContourDB::queryRangedKNN (contour_db.h:698) and ContourDB::addScan (:814): the class mirror's ContourManager holds one.
@@ -368,6 +409,9 @@ int cc_scan_ingest_points(cc_ctx *ctx, const void *h_points, const cc_point_layo
                           int want_bev, cc_scan **out);
 int cc_scan_ingest_points_batch(cc_ctx *ctx, const void *const *h_points, const cc_point_layout_t *layout, const int64_t *n_points, int n,
                                 const float *h_tf, cc_scan **out);
+/* cc_scan_ingest_points for ONE scan made of n_segs host segments (cc_point_segment_t above; the records go through the context's
+ * own staging buffer): an ordinary scan handle comes out. */
+int cc_scan_ingest_segments(cc_ctx *ctx, const cc_point_segment_t *h_segs, int n_segs, int want_bev, cc_scan **out);
 int cc_scan_ready(const cc_scan *scan);
 int cc_scan_desc(cc_scan *scan, const cc_scan_desc_t **h_desc);
 int cc_scan_bev(cc_scan *scan, const float **h_bev);
