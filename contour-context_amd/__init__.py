@@ -23,7 +23,7 @@ import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
 _SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_contours.h", "k_contours_list.h",
-         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
+         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_verify.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 
 def build(force=False, verbose=False):
@@ -50,6 +50,7 @@ EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_
            "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
            "cc_db_add_scan_host", "cc_db_query_host", "cc_db_set_lanes", "cc_db_set_dynamic_thres",
            "cc_db_add_scans_host", "cc_db_query_batch_host", "cc_db_check_hints", "cc_db_check_hints_host", "cc_db_debug_passes",
+           "cc_db_verify_submit", "cc_db_verify_batch", "cc_db_verify_batch_host",
            "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
            "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
            "cc_comm_unique_id", "cc_comm_create", "cc_comm_create_from_env", "cc_comm_rank", "cc_comm_world", "cc_comm_allgather_packed", "cc_comm_destroy"]
@@ -100,6 +101,9 @@ def lib():
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.cc_db_check_hints_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_void_p]
+        for f in ("cc_db_verify_submit", "cc_db_verify_batch"):
+            getattr(_lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        _lib.cc_db_verify_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
         _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
         _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
     return _lib
@@ -454,6 +458,78 @@ class Database:
         _chk(lib().cc_db_check_hints(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
                                      int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream), "cc_db_check_hints")
         return res[0], sc
+
+    def _verify_args(self, qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt):
+        import torch
+        if lb is None:
+            lb, ub = L.default_thresholds()
+        assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
+        if isinstance(cands, np.ndarray):
+            rows = np.asarray(cands, np.int64).reshape(len(cands), -1)
+        else:
+            rows = [list(c) for c in cands]
+        n = len(rows)
+        tab = np.full((n, L.VERIFY_CANDS_MAX), -1, np.int32)
+        for i, c in enumerate(rows):
+            if len(c) > L.VERIFY_CANDS_MAX:
+                if any(int(v) != -1 for v in c[L.VERIFY_CANDS_MAX:]):
+                    raise ValueError("item %d: more than VERIFY_CANDS_MAX = %d candidates" % (i, L.VERIFY_CANDS_MAX))
+                c = c[:L.VERIFY_CANDS_MAX]
+            tab[i, :len(c)] = c
+        if qidx is not None:
+            qidx = np.ascontiguousarray(qidx, np.int32)
+            if len(qidx) != n:
+                raise ValueError("qidx must name one descriptor per item")
+        mask = 0
+        for lv in levels:
+            if not 1 <= int(lv) <= 4:
+                raise ValueError("hint levels are 1..4")
+            mask |= 1 << (int(lv) - 1)
+        if mask == 0:
+            raise ValueError("no hint level given")
+        cfg = L.VerifyCfg(mask, int(self.cfg.max_fine_opt if max_fine_opt is None else max_fine_opt), float(max_key_dist_sq), 0)
+        return tab, qidx, cfg, lb, ub
+
+    def verify(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
+               want_hints=False, allow_flagged=False):
+        """Score candidates the caller proposes, in one batch (cc_db_verify_batch).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES];
+        cands: int array [n, <= 8] padded with -1, or a list of lists of DB indices; item i is descriptor qidx[i] (None: i)
+        against cands[i].  The hint list of an item is generated on the device: every (candidate, level, candidate anchor,
+        query anchor) whose keys are non-zero and at most max_key_dist_sq apart (float("inf"): no bound), candidate outermost.
+        max_fine_opt: None = the database's.  Returns the cc_query_result_t array (cand_gidx is a DB index; n_knn_hits the number
+        of hints), plus a list of L.hint_dt arrays, one per item, when want_hints is set.  allow_flagged: as for query()."""
+        import torch
+        tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
+        n = len(tab)
+        res = np.zeros(n, L.query_result_dt)
+        d_h = d_n = None
+        if want_hints:
+            d_h = torch.zeros((max(n, 1), L.HINT_MAX, L.hint_dt.itemsize), dtype=torch.uint8, device=qdesc.device)
+            d_n = torch.zeros(max(n, 1), dtype=torch.int32, device=qdesc.device)
+        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+        _chk(lib().cc_db_verify_batch(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
+                                      tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
+                                      d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream),
+             "cc_db_verify_batch", tolerate=(CC_ECAPACITY,) if allow_flagged else ())
+        if want_hints:
+            cnt = d_n.cpu().numpy()
+            allh = d_h.cpu().numpy().view(L.hint_dt).reshape(-1, L.HINT_MAX)
+            return res, [allh[i, :cnt[i]].copy() for i in range(n)]
+        return res
+
+    def verify_submit(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None):
+        """Asynchronous form of verify(): queues the batch and returns the result array, which is only valid after query_wait()
+        (cc_db_verify_submit; verify and query chunks share the lanes and are collected together)."""
+        import torch
+        tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
+        res = np.zeros(len(tab), L.query_result_dt)
+        self._pending = getattr(self, "_pending", [])
+        self._pending.append(res)  # the library writes into it until query_wait
+        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+        _chk(lib().cc_db_verify_submit(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
+                                       tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
+                                       None, None, stream), "cc_db_verify_submit")
+        return res
 
     def debug_passes(self, cap=1152):
         """Constellations of the last check_hints call that passed all gates: numpy array of L.pass_dbg_dt."""

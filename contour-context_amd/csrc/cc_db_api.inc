@@ -33,10 +33,10 @@ __global__ void __launch_bounds__(256)
 cc_k_pack_hot(const cc_scan_desc_t *__restrict__ desc, int n, cc_hot_desc_t *__restrict__ hot,
               int *__restrict__ z_heads /*[CC_N_HEADS] or nullptr*/, int *__restrict__ z_pass_cnt /*[n][4] or nullptr*/,
               const cc_query_meta *__restrict__ meta_src /*small query chunks: the epoch records in pinned host memory, or nullptr*/,
-              cc_query_meta *__restrict__ meta_dst) {
+              cc_query_meta *__restrict__ meta_dst, const int *__restrict__ sel /*[n] record i comes from desc[sel[i]] (verify chunks), or nullptr: from desc[i]*/) {
   const int i = blockIdx.x;
   if (i >= n) return;
-  const cc_scan_desc_t *d = desc + i;
+  const cc_scan_desc_t *d = desc + (sel ? sel[i] : i);
   cc_hot_desc_t *o = hot + i;
   const int tid = threadIdx.x, nt = blockDim.x;
   // small query chunks: the query's epoch record comes over with this kernel instead of a copy command in front of the chain
@@ -121,6 +121,9 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   cc_query_meta *h_meta = nullptr;
   cc_query_result_t *h_results = nullptr;
   int *h_nprob = nullptr;             // [4]
+  // verify chunks (cc_db_verify_submit), allocated with the first one: per item the descriptor it reads and its candidates
+  int *d_vin = nullptr;               // [QB] descriptor index | [QB][CC_VERIFY_CANDS_MAX] candidate lists
+  int *h_vin = nullptr;               // the same, pinned: filled by the submit, one copy per chunk
 };
 
 struct cc_db {
@@ -279,6 +282,8 @@ static void db_free(cc_db *db) {
     hipHostFree(ln.h_meta);
     hipHostFree(ln.h_results);
     hipHostFree(ln.h_nprob);
+    hipFree(ln.d_vin);
+    if (ln.h_vin) hipHostFree(ln.h_vin);
     if (ln.done) hipEventDestroy(ln.done);
     if (ln.prep) hipEventDestroy(ln.prep);
     if (ln.fin) hipEventDestroy(ln.fin);
@@ -328,6 +333,24 @@ static int lane_alloc_dyn(cc_qlane &ln) {
     ln.d_cpost = nullptr;
   }
   return e == hipSuccess ? CC_OK : set_err(CC_EHIP, "lane_alloc_dyn: hipMalloc", e);
+}
+// the item table of a lane's verify chunks (36 KB), allocated with the lane's first one
+static int lane_alloc_verify(cc_qlane &ln) {
+  if (ln.d_vin) return CC_OK;
+  const size_t bytes = sizeof(int) * (size_t)cc_db::QB * (1 + CC_VERIFY_CANDS_MAX);
+  if (!ln.h_vin) {
+    const hipError_t e = hipHostMalloc((void **)&ln.h_vin, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      ln.h_vin = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_verify: hipHostMalloc", e);
+    }
+  }
+  const hipError_t e = hipMalloc(&ln.d_vin, bytes);
+  if (e != hipSuccess) {
+    ln.d_vin = nullptr;
+    return set_err(CC_EHIP, "lane_alloc_verify: hipMalloc", e);
+  }
+  return CC_OK;
 }
 static int lane_alloc(cc_db *db, cc_qlane &ln) {
   if (ln.d_qmeta) return db->dyn_thres ? lane_alloc_dyn(ln) : CC_OK;  // (an earlier call may have failed on the dynamic buffers)
@@ -634,8 +657,8 @@ int cc_pack_scans(cc_ctx *ctx, const cc_scan_desc_t *d_desc, int n, void *d_hot_
   hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(cc_k_pack_hot, dim3(n), dim3(256), 0, stream, d_desc, n, (cc_hot_desc_t *)d_hot_out, (int *)nullptr, (int *)nullptr,
-                     (const cc_query_meta *)nullptr, (cc_query_meta *)nullptr);
-  hipLaunchKernelGGL(cc_k_gmm_prep, dim3(n), dim3(CC_GMM_PREP_BLOCK), 0, stream, d_desc, n, (cc_gmm_feat *)d_feat_out);
+                     (const cc_query_meta *)nullptr, (cc_query_meta *)nullptr, (const int *)nullptr);
+  hipLaunchKernelGGL(cc_k_gmm_prep, dim3(n), dim3(CC_GMM_PREP_BLOCK), 0, stream, d_desc, n, (cc_gmm_feat *)d_feat_out, (const int *)nullptr);
   HIPCHK(hipGetLastError());
   return CC_OK;
 }
@@ -984,12 +1007,13 @@ static bool thres_strict_smaller(const cc_score_t *lb, const cc_score_t *ub) {
 }
 
 // hot records and correlation inputs of a chunk's query scans + the per-chunk list heads
-static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q, int nb, bool meta_from_host = false) {
+// d_sel: verify chunks -- query record i of the chunk is built from d_q[d_sel[i]] (else from d_q[i])
+static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q, int nb, bool meta_from_host = false, const int *d_sel = nullptr) {
   (void)db;
   hipStream_t ls = ln.stream;
   hipLaunchKernelGGL(cc_k_pack_hot, dim3(nb), dim3(256), 0, ls, d_q, nb, ln.d_qhot, ln.d_heads, ln.d_pass_cnt,  // d_heads = d_nprob[4] | d_cnt[4]
-                     meta_from_host ? (const cc_query_meta *)ln.h_meta : (const cc_query_meta *)nullptr, ln.d_qmeta);
-  hipLaunchKernelGGL(cc_k_gmm_prep, dim3(nb), dim3(CC_GMM_PREP_BLOCK), 0, ls, d_q, nb, ln.d_qfeat);
+                     meta_from_host ? (const cc_query_meta *)ln.h_meta : (const cc_query_meta *)nullptr, ln.d_qmeta, d_sel);
+  hipLaunchKernelGGL(cc_k_gmm_prep, dim3(nb), dim3(CC_GMM_PREP_BLOCK), 0, ls, d_q, nb, ln.d_qfeat, d_sel);
   HIPCHK(hipGetLastError());
   return CC_OK;
 }
@@ -1558,3 +1582,154 @@ int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hi
   return cc_db_check_hints(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr);
 }
 
+// ---- verification of caller-proposed candidates (k_verify.h) ----
+// The batched form of the hint flow: item i is query descriptor h_qidx[i] against <= CC_VERIFY_CANDS_MAX database scans.  The
+// check table of a chunk is written by cc_k_hints_expand in the place of the KNN search; everything after it is the query
+// path's chain, chunked over the lanes and collected like cc_db_query_submit's chunks.
+static int verify_validate(const cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands,
+                           int n, const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, const cc_query_result_t *h_res) {
+  if (!db || !d_qdesc || n_desc < 0 || n < 0 || (n > 0 && !h_cands) || !cfg || !lb || !ub || !h_res)
+    return set_err(CC_EINVAL, "cc_db_verify: bad argument");
+  if (!h_qidx && n != n_desc) return set_err(CC_EINVAL, "cc_db_verify: without h_qidx item i reads descriptor i, so n must equal n_desc");
+  if (cfg->max_fine_opt < 1) return set_err(CC_EINVAL, "cc_db_verify: max_fine_opt must be positive");
+  if (cfg->level_mask < 0 || cfg->level_mask > 15) return set_err(CC_EINVAL, "cc_db_verify: level_mask must be within 0..15 (bit level-1 of levels 1..4)");
+  if (!(cfg->max_key_dist_sq >= 0.f)) return set_err(CC_EINVAL, "cc_db_verify: max_key_dist_sq must be >= 0 (INFINITY: no bound)");
+  if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_verify: thresholds must satisfy lb.strictSmaller(ub)");
+  for (int i = 0; i < n; i++) {
+    if (h_qidx && (h_qidx[i] < 0 || h_qidx[i] >= n_desc)) return set_err(CC_EINVAL, "cc_db_verify: query descriptor index out of range");
+    const int32_t *c = h_cands + (size_t)i * CC_VERIFY_CANDS_MAX;
+    bool ended = false;
+    for (int k = 0; k < CC_VERIFY_CANDS_MAX; k++) {
+      if (c[k] == -1) {
+        ended = true;
+        continue;
+      }
+      if (ended) return set_err(CC_EINVAL, "cc_db_verify: a candidate list continues after its first -1");
+      if (c[k] < 0 || c[k] >= db->n_scans) return set_err(CC_EINVAL, "cc_db_verify: candidate scan not in the DB");
+      for (int j = 0; j < k; j++)
+        if (c[j] == c[k]) return set_err(CC_EINVAL, "cc_db_verify: a candidate is listed twice in one item");
+    }
+  }
+  return CC_OK;
+}
+
+int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                        const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                        cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_) {
+  {  // everything that can be refused is refused before anything is queued or collected
+    const int vrc = verify_validate(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
+    if (vrc != CC_OK) return vrc;
+  }
+  DB_POISON_CHK(db, "cc_db_verify_submit");
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(db->device));
+  cc_check_params CP;
+  CP.sim = db->cfg.cont_sim;
+  CP.lb = *lb;
+  for (int i = 0; i < 3; i++) {
+    CP.size_class[i] = db->tune.a_class[i];
+    CP.cstl_class[i] = db->tune.b2_class[i];
+  }
+  cc_verify_params VP;
+  VP.level_mask = cfg->level_mask ? cfg->level_mask : 0xF;
+  VP.max_key_dist_sq = cfg->max_key_dist_sq;
+  // chunks over the lanes exactly as cc_db_query_submit cuts a query batch (the comments there); a large-k database's lanes
+  // take qb_max = 256 items, and the chain is the 64-stride one on any database, as in the hint flow
+  hipEvent_t e_start = db->lane[0].done;
+  HIPCHK(hipEventRecord(e_start, stream));
+  for (int i = 0; i < db->n_lanes; i++) {
+    HIPCHK(hipStreamWaitEvent(db->lane[i].stream, e_start, 0));
+    if (db->add_done) HIPCHK(hipStreamWaitEvent(db->lane[i].stream, db->add_done, 0));  // an append queued on another stream
+  }
+  int rc = CC_OK;
+  int qb = (((n + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
+  if (!db->sync_call && n >= db->qb_max) qb = db->qb_max;
+  qb = qb > db->tune.chunk ? db->tune.chunk : qb;
+#define LANE_CHK(call)                        \
+  do {                                        \
+    hipError_t e_ = (call);                   \
+    if (e_ != hipSuccess) {                   \
+      lane_abort(db, ln);                     \
+      return set_err(CC_EHIP, #call, e_);     \
+    }                                         \
+  } while (0)
+  for (int b0 = 0; b0 < n && rc == CC_OK; b0 += qb) {
+    const int nb = n - b0 < qb ? n - b0 : qb;
+    cc_qlane &ln = db->lane[db->next_lane];
+    db->next_lane = (db->next_lane + 1) % db->n_lanes;
+    rc = lane_finish(db, ln);
+    if (rc != CC_OK) break;
+    rc = lane_alloc_verify(ln);
+    if (rc != CC_OK) break;
+    if (db->dyn_thres) {
+      rc = lane_alloc_dyn(ln);
+      if (rc != CC_OK) break;
+    }
+    hipStream_t ls = ln.stream;
+    int *h_sel = ln.h_vin, *h_cl = ln.h_vin + nb;  // the chunk's table, packed: [nb] | [nb][CC_VERIFY_CANDS_MAX]
+    for (int i = 0; i < nb; i++) h_sel[i] = h_qidx ? h_qidx[b0 + i] : b0 + i;
+    memcpy(h_cl, h_cands + (size_t)b0 * CC_VERIFY_CANDS_MAX, sizeof(int) * (size_t)nb * CC_VERIFY_CANDS_MAX);
+    ln.profiled = db->prof && (db->prof_tick++ % db->prof_every) == 0;
+    hipEvent_t *ev = ln.profiled ? ln.pev : nullptr;
+    const bool zc = nb <= CC_ZC_MAX;  // cc_k_final writes the results of a small chunk straight into the lane's pinned buffer
+    LANE_CHK(hipMemcpyAsync(ln.d_vin, ln.h_vin, sizeof(int) * (size_t)nb * (1 + CC_VERIFY_CANDS_MAX), hipMemcpyHostToDevice, ls));
+    rc = launch_query_prep(db, ln, d_qdesc, nb, false, ln.d_vin);
+    if (rc != CC_OK) {
+      lane_abort(db, ln);
+      break;
+    }
+    // the caller's stream goes on once the descriptors have been read
+    LANE_CHK(hipEventRecord(ln.prep, ls));
+    LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
+    if (ev) LANE_CHK(hipEventRecord(ev[0], ls));
+    hipLaunchKernelGGL(cc_k_hints_expand, dim3(nb), dim3(64), 0, ls, VP, (const cc_hot_desc_t *)ln.d_qhot, (const cc_hot_desc_t *)db->d_hot,
+                       (const int *)(ln.d_vin + nb), nb, ln.d_hits, ln.d_hit_cnt, d_hints ? d_hints + (size_t)b0 * CC_HINT_MAX : (cc_hint_t *)nullptr,
+                       d_n_hints ? d_n_hints + b0 : (int32_t *)nullptr);
+    if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
+    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, cfg->max_fine_opt, ev, nullptr, zc, CC_KNN_MAX);
+    if (rc != CC_OK) {
+      lane_abort(db, ln);
+      break;
+    }
+    if (!zc) {
+      LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
+      LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
+    }
+    LANE_CHK(hipEventRecord(ln.fin, ls));
+    for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];  // (a verify chunk reads no sorted view: nothing for an append to wait for beyond this)
+    ln.busy = true;
+    ln.b0 = b0;
+    ln.nb = nb;
+    ln.h_dst = h_res;
+  }
+#undef LANE_CHK
+  return rc;
+}
+
+int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                       const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                       cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_) {
+  {  // a refused call leaves the chunks in flight where they are
+    const int vrc = verify_validate(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
+    if (vrc != CC_OK) return vrc;
+  }
+  db->sync_call = true;
+  const int rc = cc_db_verify_submit(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_);
+  db->sync_call = false;
+  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
+  return rc != CC_OK ? rc : r2;
+}
+
+int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                            const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res) {
+  {
+    const int vrc = verify_validate(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
+    if (vrc != CC_OK) return vrc;
+  }
+  if (n == 0) return CC_OK;
+  HIPCHK(hipSetDevice(db->device));
+  int rc = stage_reserve(db, n_desc);
+  if (rc != CC_OK) return rc;
+  HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)n_desc, hipMemcpyHostToDevice));
+  return cc_db_verify_batch(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr);
+}

@@ -27,6 +27,7 @@
 #include "k_check.h"
 #include "k_merge.h"
 #include "k_gmm.h"
+#include "k_verify.h"
 #include "cc_hostdb.h"
 
 #ifndef CC_INGEST_BLOCK

@@ -111,11 +111,12 @@ __device__ __forceinline__ double cc_gmm_self_term(const cc_ell &a, const cc_ell
 //     code runs on full waves.
 #define CC_GMM_PREP_BLOCK 256
 __global__ void __launch_bounds__(CC_GMM_PREP_BLOCK)
-cc_k_gmm_prep(const cc_scan_desc_t *__restrict__ desc, int n, cc_gmm_feat *__restrict__ feat) {
+cc_k_gmm_prep(const cc_scan_desc_t *__restrict__ desc, int n, cc_gmm_feat *__restrict__ feat,
+              const int *__restrict__ sel /*[n] record i comes from desc[sel[i]] (verify chunks), or nullptr: from desc[i]*/) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NW = CC_GMM_PREP_BLOCK / 64;
   if ((int)blockIdx.x >= n) return;
-  const cc_scan_desc_t *d = desc + blockIdx.x;
+  const cc_scan_desc_t *d = desc + (sel ? sel[blockIdx.x] : (int)blockIdx.x);
   cc_gmm_feat *F = feat + blockIdx.x;
   __shared__ cc_ell E[CC_GMM_ECAP_L];
   __shared__ unsigned s_q[NW][128];  // per wave: pairs waiting for the exact evaluation, (i << 16) | j, a ring

@@ -367,6 +367,46 @@ class ContourDB {
       cand_tf.push_back(T);
     }
   }
+  // Mirror-only (no reference counterpart): score candidates the CALLER proposes -- scans of this database by their index in
+  // adding order (odometry or GPS proximity, another descriptor, a re-check of accepted loops) -- instead of the ones the key
+  // search retrieves.  At most CC_VERIFY_CANDS_MAX distinct indices.  Returns what the reference demo's loop over the
+  // candidates' anchor pairs (test/kitti_read_bin_test.cpp:226-291: checkCandWithHint for every pair of existing anchors
+  // whose keys are at most 1000 apart, candidate by candidate) + tidyUpCandidates + fineOptimize(max_fine_opt_) return: one
+  // device pass (cc_db_verify_batch_host) whose hint list is generated on the device.
+  int verifyCandidates(const std::shared_ptr<const ContourManager> &q_ptr, const std::vector<int> &cand_indices,
+                       const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
+                       std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
+                       std::vector<Eigen::Isometry2d> &res_T) const {
+    res_cand.clear();
+    res_corr.clear();
+    res_T.clear();
+    CC_CHECK((int)cand_indices.size() <= CC_VERIFY_CANDS_MAX);
+    for (const int c : cand_indices) CC_CHECK(c >= 0 && c < (int)all_bevs_.size());  // (scans appended ahead of the driver are not the caller's yet)
+    if (cand_indices.empty()) return 0;
+    ensure(*q_ptr);
+    if (need_rebuild_) rebuild();
+    const cc_score_t lb = to_c(thres_lb), ub = to_c(thres_ub);
+    int32_t cands[CC_VERIFY_CANDS_MAX];
+    for (int k = 0; k < CC_VERIFY_CANDS_MAX; k++) cands[k] = k < (int)cand_indices.size() ? cand_indices[k] : -1;
+    cc_verify_cfg_t vc;
+    vc.level_mask = 0;
+    vc.max_fine_opt = cfg_.max_fine_opt_;
+    vc.max_key_dist_sq = 1000.0f;
+    vc.pad_ = 0;
+    cc_query_result_t r;
+    const int rc = cc_db_verify_batch_host(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
+    for (auto &sp : spec_) sp.collected = true;  // the synchronous call collected every chain in flight
+    if (rc != CC_OK) die_cc();
+    if (r.n_res > 0) {
+      res_cand.push_back(all_bevs_[r.cand_gidx]);
+      res_corr.push_back(r.correlation);
+      Eigen::Isometry2d T;
+      T.rotate(r.tf[2]);
+      T.pretranslate(r.tf[0], r.tf[1]);
+      res_T.push_back(T);
+    }
+    return r.n_res;
+  }
   // contour_db.h:814 and :827
   void addScan(const std::shared_ptr<ContourManager> &added, double curr_timestamp) {
     ensure(*added);

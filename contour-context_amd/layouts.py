@@ -50,6 +50,9 @@ hint_dt = np.dtype([("cand_gidx", "<i4"), ("level", "i1"), ("seq_src", "i1"), ("
 hint_score_dt = np.dtype([("i_ovlp_sum", "<i4"), ("i_ovlp_max_one", "<i4"), ("i_in_ang_rng", "<i4"), ("i_indiv_sim", "<i4"),
                           ("i_orie_sim", "<i4"), ("passed", "<i4")], align=True)
 assert hint_dt.itemsize == 8 and hint_score_dt.itemsize == 24
+HINT_MAX = NQLEV * NPIV * KNN_MAX  # CC_HINT_MAX: hints of one cc_db_check_hints call / of one item of cc_db_verify_*
+VERIFY_CANDS_MAX = 8               # CC_VERIFY_CANDS_MAX: candidates per item (8 x 4 levels x 6 x 6 anchor pairs = HINT_MAX)
+assert VERIFY_CANDS_MAX * 4 * NPIV * NPIV == HINT_MAX
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
 
@@ -93,6 +96,13 @@ class DbCfg(C.Structure):
     _fields_ = [("nnk", C.c_int32), ("max_fine_opt", C.c_int32), ("n_q_levels", C.c_int32),
                 ("q_levels", C.c_int32 * NQLEV), ("cont_sim", SimCfg), ("max_elapse", C.c_double),
                 ("min_elapse", C.c_double)]
+
+
+class VerifyCfg(C.Structure):  # cc_verify_cfg_t
+    _fields_ = [("level_mask", C.c_int32), ("max_fine_opt", C.c_int32), ("max_key_dist_sq", C.c_float), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(VerifyCfg) == 16
 
 
 def default_manager_cfg(mulran=False):

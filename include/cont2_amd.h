@@ -554,6 +554,51 @@ int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hi
                            const cc_score_t *thres_lb, const cc_score_t *thres_ub, int max_fine_opt,
                            cc_query_result_t *h_res, cc_hint_score_t *h_scores);
 
+/* Verification of candidates the CALLER proposes (odometry or GPS proximity, another descriptor, another robot's map, a
+ * re-check of accepted loops): the batched, streamed form of the hint flow.  Item i is the query scan d_qdesc[h_qidx[i]]
+ * (h_qidx NULL: d_qdesc[i], and then n == n_desc) against the database scans h_cands[i][0 .. m_i), 0 <= m_i <=
+ * CC_VERIFY_CANDS_MAX, the list ended by -1; candidates are DB indices below cc_db_size, searchable or not.  Several items
+ * may name the same descriptor: one item per (query, candidate) pair gives one verdict per pair instead of the best of a list.
+ *
+ * The hint list of an item is generated on the device, in the demo's order (test/kitti_read_bin_test.cpp:226-291 with the
+ * candidate as the outermost index): for candidate k in list order, for level 1..4 where set in level_mask, for seq_src
+ * 0..CC_NPIV-1 (the candidate's anchor), for seq_tgt 0..CC_NPIV-1 (the query's anchor) -- unless either retrieval key sums
+ * to zero (the f32 sum in index order: the anchor does not exist, contour_db.h:726) or the keys' squared f32 distance
+ * (accumulated in index order, every product and sum rounded once) exceeds max_key_dist_sq.
+ *
+ * h_res[i] is, byte for byte, what cc_db_check_hints returns for that query, that hint list, the same thresholds and
+ * max_fine_opt: n_knn_hits = the number of hints generated, cand_gidx = a DB index, n_res = 0 for an empty list.  d_hints /
+ * d_n_hints (device, optional) receive the generated lists: [n][CC_HINT_MAX] and [n].
+ *
+ * Refused with CC_EINVAL before anything is queued (the handle and the chunks in flight stay untouched): NULL arguments,
+ * n < 0, h_qidx[i] outside [0, n_desc), a candidate outside [0, cc_db_size), a candidate listed twice in one item, an entry
+ * other than -1 after the first -1, max_fine_opt < 1, level_mask outside 0..15, a NaN or negative max_key_dist_sq, thresholds
+ * that fail lb.strictSmaller(ub).
+ *
+ * Streaming: the batch is cut into chunks over the lanes exactly like cc_db_query_submit (at most 1024 items per chunk, 256
+ * on a database with nnk > CC_KNN_MAX); cc_db_query_wait / cc_db_query_collect collect verify chunks too; chunks wait for the
+ * last append on the device; the caller's stream continues once the descriptors are read; CC_QF_* flags / CC_ECAPACITY as for
+ * queries; cc_db_set_dynamic_thres applies; with cc_db_profile_enable the hint generation's time lands in ms_out[0]. */
+#define CC_VERIFY_CANDS_MAX 8 /* 8 candidates x 4 levels x 6 x 6 anchor pairs = CC_HINT_MAX check slots */
+typedef struct {
+  int32_t level_mask;    /* bit (level-1) for hint levels 1..4; 0 stands for 0xF                                    */
+  int32_t max_fine_opt;  /* >= 1, as cc_db_check_hints                                                              */
+  float max_key_dist_sq; /* anchor pairs whose keys are farther apart are not checked (the demo uses 1000.0f);
+                            INFINITY = no bound                                                                    */
+  int32_t pad_;
+} cc_verify_cfg_t;
+int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                        const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                        cc_query_result_t *h_res, cc_hint_t *d_hints, int32_t *d_n_hints, void *stream);
+/* submit + cc_db_query_wait */
+int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                       const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                       cc_query_result_t *h_res, cc_hint_t *d_hints, int32_t *d_n_hints, void *stream);
+/* ... with host descriptors: one H2D copy of them, like cc_db_query_batch_host */
+int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                            const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                            cc_query_result_t *h_res);
+
 /* Parity / debug: the constellations of the LAST cc_db_check_hints[_host] call that passed all four gates, in hint
  * order: the pose getTFFromConstell returned for each (contour_mng.h:1246-1277, before any proposal merging) and the
  * constellation it was computed from, so that a test can redo the rigid fit independently (e.g. with an SVD). */
