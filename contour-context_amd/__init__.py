@@ -51,6 +51,8 @@ EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_
            "cc_db_add_scan_host", "cc_db_query_host", "cc_db_set_lanes", "cc_db_set_dynamic_thres",
            "cc_db_add_scans_host", "cc_db_query_batch_host", "cc_db_check_hints", "cc_db_check_hints_host", "cc_db_debug_passes",
            "cc_db_verify_submit", "cc_db_verify_batch", "cc_db_verify_batch_host",
+           "cc_db_query_submit_ranked", "cc_db_query_batch_host_ranked", "cc_db_query_scan_batch_submit_ranked", "cc_db_verify_submit_ranked",
+           "cc_db_check_hints_ranked", "cc_db_verify_batch_host_ranked", "cc_db_check_hints_host_ranked",
            "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
            "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
            "cc_comm_unique_id", "cc_comm_create", "cc_comm_create_from_env", "cc_comm_rank", "cc_comm_world", "cc_comm_allgather_packed", "cc_comm_destroy"]
@@ -104,6 +106,12 @@ def lib():
         for f in ("cc_db_verify_submit", "cc_db_verify_batch"):
             getattr(_lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib.cc_db_verify_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        _lib.cc_db_query_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        _lib.cc_db_query_batch_host_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _lib.cc_db_query_scan_batch_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _lib.cc_db_verify_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        _lib.cc_db_check_hints_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
         _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
     return _lib
@@ -381,11 +389,26 @@ class Database:
         stream = torch.cuda.current_stream(desc.device).cuda_stream
         _chk(lib().cc_db_add_scans_prepare(self.h, desc.data_ptr(), desc.shape[0], stream), "cc_db_add_scans_prepare")
 
-    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False):
+    def _ranked_call(self, fn, what, tol, *args):
+        """a *_submit_ranked call followed by the wait: the synchronous ranked forms of query() and verify()"""
+        rc = fn(*args)
+        if rc != 0 and rc not in tol:  # refused or failed: the message is this call's; nothing of it may stay in flight
+            msg = lib().cc_last_error().decode()
+            lib().cc_db_query_wait(self.h)
+            e = CCError("%s failed (%d): %s" % (what, rc, msg))
+            e.rc = rc
+            raise e
+        _chk(lib().cc_db_query_wait(self.h), "cc_db_query_wait", tolerate=tol)
+
+    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None):
         """qdesc: torch uint8 CUDA [nq, DESC_BYTES]; epochs int32 [nq] (DB state each query sees).
         Returns numpy structured array of cc_query_result_t (+ knn hits / counts as torch tensors).
         allow_flagged: a query that met an internal capacity (cc_query_result_t.flags != 0) makes the library return
-        CC_ECAPACITY with every result delivered; True hands the results back (the caller looks at `flags`) instead of raising."""
+        CC_ECAPACITY with every result delivered; True hands the results back (the caller looks at `flags`) instead of raising.
+        ranked=K (1..RANK_MAX): the ranked list of every query's refined candidates as well (cc_db_query_submit_ranked): the return
+        value is followed by (cands [nq, K] of L.ranked_cand_dt, counts [nq]); entry 0 of a list is the candidate the result names.
+        The ranked form is query_submit(ranked=K) + query_wait(): a batch of a full chunk or more goes out in whole chunks, lane
+        after lane, where the plain synchronous call cuts one chunk per lane -- the same answers, scheduled differently."""
         import torch
         if lb is None:
             lb, ub = L.default_thresholds()
@@ -399,18 +422,29 @@ class Database:
             knn = torch.zeros((nq, L.NQLEV, L.NPIV, ks, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=qdesc.device)
             cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=qdesc.device)
         stream = torch.cuda.current_stream(qdesc.device).cuda_stream
-        _chk(lib().cc_db_query_batch(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
-                                     res.ctypes.data, knn.data_ptr() if want_knn else None,
-                                     cnt.data_ptr() if want_knn else None, stream), "cc_db_query_batch",
-             tolerate=(CC_ECAPACITY,) if allow_flagged else ())
+        tol = (CC_ECAPACITY,) if allow_flagged else ()
+        rk = None
+        if ranked is None:
+            _chk(lib().cc_db_query_batch(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
+                                         res.ctypes.data, knn.data_ptr() if want_knn else None,
+                                         cnt.data_ptr() if want_knn else None, stream), "cc_db_query_batch", tolerate=tol)
+        else:
+            rc_, rn_, ro = L.rank_buffers(nq, ranked)
+            rk = (rc_, rn_)
+            self._ranked_call(lib().cc_db_query_submit_ranked, "cc_db_query_submit_ranked", tol, self.h, qdesc.data_ptr(), nq, epochs.ctypes.data,
+                              C.addressof(lb), C.addressof(ub), res.ctypes.data, knn.data_ptr() if want_knn else None,
+                              cnt.data_ptr() if want_knn else None, stream, C.addressof(ro))
+        out = (res,)
         if want_knn:
-            return res, knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy()
-        return res
+            out += (knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy())
+        if rk is not None:
+            out += (rk,)
+        return out if len(out) > 1 else res
 
-    def query_submit(self, qdesc, epochs, lb=None, ub=None):
+    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None):
         """Asynchronous form of query(): queues the batch and returns the result array, which is only valid after
         query_wait() (cc_db_query_submit / cc_db_query_wait).  qdesc may be overwritten by work queued afterwards on the
-        current stream."""
+        current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait()."""
         import torch
         if lb is None:
             lb, ub = L.default_thresholds()
@@ -421,6 +455,12 @@ class Database:
         self._pending = getattr(self, "_pending", [])
         self._pending.append(res)  # the library writes into it until query_wait
         stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+        if ranked is not None:
+            rc_, rn_, ro = L.rank_buffers(nq, ranked)
+            self._pending.append((rc_, rn_))
+            _chk(lib().cc_db_query_submit_ranked(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
+                                                 res.ctypes.data, None, None, stream, C.addressof(ro)), "cc_db_query_submit_ranked")
+            return res, (rc_, rn_)
         _chk(lib().cc_db_query_submit(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
                                       res.ctypes.data, None, None, stream), "cc_db_query_submit")
         return res
@@ -442,10 +482,10 @@ class Database:
         _chk(lib().cc_db_add_packed(self.h, hot.data_ptr(), feat.data_ptr(), n, ts.ctypes.data, seeds.ctypes.data, stream),
              "cc_db_add_packed")
 
-    def check_hints(self, qdesc, hints, lb=None, ub=None, max_fine_opt=10):
+    def check_hints(self, qdesc, hints, lb=None, ub=None, max_fine_opt=10, ranked=None):
         """CandidateManager driven by explicit hints (checkCandWithHint in the given order, tidyUpCandidates, fineOptimize).
         qdesc: torch uint8 CUDA [DESC_BYTES] of the query scan; hints: array of L.hint_dt (cand_gidx = DB index).
-        Returns (cc_query_result_t record, per-hint L.hint_score_dt array)."""
+        Returns (cc_query_result_t record, per-hint L.hint_score_dt array); with ranked=K followed by (cands [1, K], counts [1])."""
         import torch
         if lb is None:
             lb, ub = L.default_thresholds()
@@ -455,6 +495,12 @@ class Database:
         res = np.zeros(1, L.query_result_dt)
         sc = np.zeros(len(hints), L.hint_score_dt)
         stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+        if ranked is not None:
+            rc_, rn_, ro = L.rank_buffers(1, ranked)
+            _chk(lib().cc_db_check_hints_ranked(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
+                                                int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream, C.addressof(ro)),
+                 "cc_db_check_hints_ranked")
+            return res[0], sc, (rc_, rn_)
         _chk(lib().cc_db_check_hints(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
                                      int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream), "cc_db_check_hints")
         return res[0], sc
@@ -491,13 +537,16 @@ class Database:
         return tab, qidx, cfg, lb, ub
 
     def verify(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
-               want_hints=False, allow_flagged=False):
+               want_hints=False, allow_flagged=False, ranked=None):
         """Score candidates the caller proposes, in one batch (cc_db_verify_batch).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES];
         cands: int array [n, <= 8] padded with -1, or a list of lists of DB indices; item i is descriptor qidx[i] (None: i)
         against cands[i].  The hint list of an item is generated on the device: every (candidate, level, candidate anchor,
         query anchor) whose keys are non-zero and at most max_key_dist_sq apart (float("inf"): no bound), candidate outermost.
         max_fine_opt: None = the database's.  Returns the cc_query_result_t array (cand_gidx is a DB index; n_knn_hits the number
-        of hints), plus a list of L.hint_dt arrays, one per item, when want_hints is set.  allow_flagged: as for query()."""
+        of hints), plus a list of L.hint_dt arrays, one per item, when want_hints is set.  allow_flagged: as for query().
+        ranked=K: followed by (cands [n, K] of L.ranked_cand_dt, counts [n]) -- every refined candidate of an item, best first
+        (cc_db_verify_submit_ranked), instead of one item per (query, candidate) pair.  Like query(ranked=K) it is the submit
+        followed by the wait, so a large batch is chunked by the streamed rule (whole chunks), not one chunk per lane."""
         import torch
         tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
         n = len(tab)
@@ -507,25 +556,47 @@ class Database:
             d_h = torch.zeros((max(n, 1), L.HINT_MAX, L.hint_dt.itemsize), dtype=torch.uint8, device=qdesc.device)
             d_n = torch.zeros(max(n, 1), dtype=torch.int32, device=qdesc.device)
         stream = torch.cuda.current_stream(qdesc.device).cuda_stream
-        _chk(lib().cc_db_verify_batch(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
-                                      tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
-                                      d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream),
-             "cc_db_verify_batch", tolerate=(CC_ECAPACITY,) if allow_flagged else ())
+        tol = (CC_ECAPACITY,) if allow_flagged else ()
+        rk = None
+        if ranked is None:
+            _chk(lib().cc_db_verify_batch(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
+                                          tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
+                                          d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream),
+                 "cc_db_verify_batch", tolerate=tol)
+        else:
+            rc_, rn_, ro = L.rank_buffers(n, ranked)
+            rk = (rc_, rn_)
+            self._ranked_call(lib().cc_db_verify_submit_ranked, "cc_db_verify_submit_ranked", tol, self.h, qdesc.data_ptr(), qdesc.shape[0],
+                              qidx.ctypes.data if qidx is not None else None, tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub),
+                              res.ctypes.data, d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream,
+                              C.addressof(ro))
+        out = (res,)
         if want_hints:
             cnt = d_n.cpu().numpy()
             allh = d_h.cpu().numpy().view(L.hint_dt).reshape(-1, L.HINT_MAX)
-            return res, [allh[i, :cnt[i]].copy() for i in range(n)]
-        return res
+            out += ([allh[i, :cnt[i]].copy() for i in range(n)],)
+        if rk is not None:
+            out += (rk,)
+        return out if len(out) > 1 else res
 
-    def verify_submit(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None):
+    def verify_submit(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
+                      ranked=None):
         """Asynchronous form of verify(): queues the batch and returns the result array, which is only valid after query_wait()
-        (cc_db_verify_submit; verify and query chunks share the lanes and are collected together)."""
+        (cc_db_verify_submit; verify and query chunks share the lanes and are collected together).  ranked=K: returns
+        (results, (cands [n, K], counts [n]))."""
         import torch
         tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
         res = np.zeros(len(tab), L.query_result_dt)
         self._pending = getattr(self, "_pending", [])
         self._pending.append(res)  # the library writes into it until query_wait
         stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+        if ranked is not None:
+            rc_, rn_, ro = L.rank_buffers(len(tab), ranked)
+            self._pending.append((rc_, rn_))
+            _chk(lib().cc_db_verify_submit_ranked(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
+                                                  tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
+                                                  None, None, stream, C.addressof(ro)), "cc_db_verify_submit_ranked")
+            return res, (rc_, rn_)
         _chk(lib().cc_db_verify_submit(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
                                        tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
                                        None, None, stream), "cc_db_verify_submit")

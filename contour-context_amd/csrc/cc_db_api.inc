@@ -124,6 +124,11 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   // verify chunks (cc_db_verify_submit), allocated with the first one: per item the descriptor it reads and its candidates
   int *d_vin = nullptr;               // [QB] descriptor index | [QB][CC_VERIFY_CANDS_MAX] candidate lists
   int *h_vin = nullptr;               // the same, pinned: filled by the submit, one copy per chunk
+  // ranked chunks (the *_ranked entry points), allocated with the first one: cc_k_final_r's lists, [nb][max_ret]
+  cc_ranked_cand_t *d_rank = nullptr; // [QB * CC_RANK_MAX]
+  cc_ranked_cand_t *h_rank = nullptr; // the same, pinned: copied out beside h_results (small chunks: written by the kernel)
+  cc_rank_out_t rank_dst = {nullptr, nullptr, 0, 0};  // where the chunk's lists go when it is collected (h_cands NULL: not a ranked chunk)
+  int rank_mfo = 0;                   // the chunk's max_fine_opt (the counts are min(max_ret, max_fine_opt, n_cand_tidy))
 };
 
 struct cc_db {
@@ -284,6 +289,8 @@ static void db_free(cc_db *db) {
     hipHostFree(ln.h_nprob);
     hipFree(ln.d_vin);
     if (ln.h_vin) hipHostFree(ln.h_vin);
+    hipFree(ln.d_rank);
+    if (ln.h_rank) hipHostFree(ln.h_rank);
     if (ln.done) hipEventDestroy(ln.done);
     if (ln.prep) hipEventDestroy(ln.prep);
     if (ln.fin) hipEventDestroy(ln.fin);
@@ -351,6 +358,38 @@ static int lane_alloc_verify(cc_qlane &ln) {
     return set_err(CC_EHIP, "lane_alloc_verify: hipMalloc", e);
   }
   return CC_OK;
+}
+// the list buffers of a lane's ranked chunks (2 x 640 KB), allocated with the lane's first one
+static int lane_alloc_rank(cc_qlane &ln) {
+  if (ln.d_rank) return CC_OK;
+  const size_t bytes = sizeof(cc_ranked_cand_t) * (size_t)cc_db::QB * CC_RANK_MAX;
+  if (!ln.h_rank) {
+    const hipError_t e = hipHostMalloc((void **)&ln.h_rank, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      ln.h_rank = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_rank: hipHostMalloc", e);
+    }
+  }
+  const hipError_t e = hipMalloc(&ln.d_rank, bytes);
+  if (e != hipSuccess) {
+    ln.d_rank = nullptr;
+    return set_err(CC_EHIP, "lane_alloc_rank: hipMalloc", e);
+  }
+  return CC_OK;
+}
+static int rank_validate(const cc_rank_out_t *rank, const char *what) {
+  if (!rank || !rank->h_cands || !rank->h_n || rank->max_ret < 1 || rank->max_ret > CC_RANK_MAX) return set_err(CC_EINVAL, what);
+  return CC_OK;
+}
+// a collected chunk's lists: rows [b0, b0 + nb) of the caller's arrays
+static void rank_deliver(const cc_qlane &ln, const cc_rank_out_t &dst, int b0, int nb, int max_fine_opt) {
+  const int mr = dst.max_ret;
+  memcpy(dst.h_cands + (size_t)b0 * mr, ln.h_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * mr);
+  for (int i = 0; i < nb; i++) {
+    const cc_query_result_t &r = ln.h_results[i];
+    const int pre = max_fine_opt < r.n_cand_tidy ? max_fine_opt : r.n_cand_tidy;
+    dst.h_n[b0 + i] = r.n_res > 0 ? (mr < pre ? mr : pre) : 0;
+  }
 }
 static int lane_alloc(cc_db *db, cc_qlane &ln) {
   if (ln.d_qmeta) return db->dyn_thres ? lane_alloc_dyn(ln) : CC_OK;  // (an earlier call may have failed on the dynamic buffers)
@@ -1023,7 +1062,7 @@ static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q,
 // km: hits per search in ln.d_hits (db->kmax for queries; CC_KNN_MAX for the hint flow): picks the kernel instances.
 static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_params &CP, const cc_score_t *lb, const cc_score_t *ub,
                                 int max_fine_opt, hipEvent_t *ev, int *d_scores, bool zc /*results and counters straight into the lane's pinned host buffers*/,
-                                int km) {
+                                int km, int max_ret = 0 /*> 0: a ranked chunk (cc_k_final_r writes the lists to the lane's rank buffer)*/) {
   hipStream_t ls = ln.stream;
   const bool lg = km != CC_KNN_MAX;
   // dynamic thresholds (the mode at submission): the stages leave their scores in the pass records, cc_k_check_dyn replays the
@@ -1072,10 +1111,17 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
                      ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
                      (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
   if (ev) HIPCHK(hipEventRecord(ev[4], ls));
-  hipLaunchKernelGGL(lg ? (dyn ? cc_k_final_l<true> : cc_k_final_l<false>) : (dyn ? cc_k_final<true> : cc_k_final<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
-                     (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
-                     (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
-                     zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy);
+  if (max_ret > 0) {  // the ranked instance replaces the plain one; a chain without `rank` launches what it always launched
+    hipLaunchKernelGGL(lg ? (dyn ? cc_k_final_rl<true> : cc_k_final_rl<false>) : (dyn ? cc_k_final_r<true> : cc_k_final_r<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
+                       (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
+                       (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
+                       zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy, zc ? ln.h_rank : ln.d_rank, max_ret);
+  } else {
+    hipLaunchKernelGGL(lg ? (dyn ? cc_k_final_l<true> : cc_k_final_l<false>) : (dyn ? cc_k_final<true> : cc_k_final<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
+                       (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
+                       (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
+                       zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy);
+  }
   if (ev) HIPCHK(hipEventRecord(ev[5], ls));
   HIPCHK(hipGetLastError());
   return CC_OK;
@@ -1097,6 +1143,7 @@ static int lane_finish(cc_db *db, cc_qlane &ln) {
   ln.busy = false;
   HIPCHK(hipStreamSynchronize(ln.stream));
   memcpy(ln.h_dst + ln.b0, ln.h_results, sizeof(cc_query_result_t) * ln.nb);
+  if (ln.rank_dst.h_cands) rank_deliver(ln, ln.rank_dst, ln.b0, ln.nb, ln.rank_mfo);
   if (ln.profiled) {
     float t[5];
     for (int k = 0; k < 5; k++) hipEventElapsedTime(&t[k], ln.pev[k], ln.pev[k + 1]);
@@ -1149,8 +1196,10 @@ int cc_db_query_collect(cc_db *db, const cc_query_result_t *h_res, int n) {
   return rc;
 }
 
-int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
-                       const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_) {
+// rank: where the chunks' ranked lists go (the *_ranked entry points, validated there), or nullptr: the plain call
+static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                             const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
+                             const cc_rank_out_t *rank) {
   if (!db || !d_qdesc || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch");
   if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch: thresholds must satisfy lb.strictSmaller(ub)");
@@ -1222,6 +1271,10 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
       rc = lane_alloc_dyn(ln);
       if (rc != CC_OK) break;
     }
+    if (rank) {
+      rc = lane_alloc_rank(ln);
+      if (rc != CC_OK) break;
+    }
     hipStream_t ls = ln.stream;
     bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
     for (int i = 0; i < nb; i++) {
@@ -1282,7 +1335,7 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
                          ln.d_hits, ln.d_hit_cnt);
     }
     if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc, db->kmax);
+    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc, db->kmax, rank ? rank->max_ret : 0);
     if (rc != CC_OK) {
       lane_abort(db, ln);
       break;
@@ -1292,6 +1345,7 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
     if (!zc) {
       LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
       LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
+      if (rank) LANE_CHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
     }
     LANE_CHK(hipEventRecord(ln.fin, ls));
     for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];
@@ -1299,9 +1353,23 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
     ln.b0 = b0;
     ln.nb = nb;
     ln.h_dst = h_res;
+    ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
+    ln.rank_mfo = db->cfg.max_fine_opt;
   }
 #undef LANE_CHK
   return rc;
+}
+
+int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                       const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_) {
+  return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, nullptr);
+}
+int cc_db_query_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                              const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
+                              const cc_rank_out_t *rank) {
+  const int vrc = rank_validate(rank, "cc_db_query_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank);
 }
 
 int cc_db_query_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
@@ -1334,15 +1402,37 @@ int cc_db_add_scans_host(cc_db *db, const cc_scan_desc_t *h_desc, int n, const d
   return cc_db_add_scans(db, db->d_stage, n, h_ts, h_seed, nullptr);
 }
 
-int cc_db_query_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
-                           const cc_score_t *ub, cc_query_result_t *h_res) {
+// rank: as for query_submit_impl.  The ranked form refuses what the chain would refuse before the descriptors are staged.
+static int query_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                 const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
   if (!db || !h_qdesc || nq < 0 || !h_epoch || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch_host: bad argument");
+  if (rank) {
+    if (!lb || !ub) return set_err(CC_EINVAL, "cc_db_query_batch_host_ranked: bad argument");
+    if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch_host_ranked: thresholds must satisfy lb.strictSmaller(ub)");
+    for (int i = 0; i < nq; i++)
+      if (h_epoch[i] < 0 || h_epoch[i] > db->n_scans) return set_err(CC_EINVAL, "cc_db_query_batch_host_ranked: epoch out of range");
+  }
   if (nq == 0) return CC_OK;
   HIPCHK(hipSetDevice(db->device));
   int rc = stage_reserve(db, nq);
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)nq, hipMemcpyHostToDevice));
-  return cc_db_query_batch(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr);
+  if (!rank) return cc_db_query_batch(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr);
+  db->sync_call = true;  // cc_db_query_batch's body with the lists
+  rc = query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank);
+  db->sync_call = false;
+  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
+  return rc != CC_OK ? rc : r2;
+}
+int cc_db_query_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                           const cc_score_t *ub, cc_query_result_t *h_res) {
+  return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, nullptr);
+}
+int cc_db_query_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                  const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
+  const int vrc = rank_validate(rank, "cc_db_query_batch_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank);
 }
 
 // The per-scan loop on a scan that is still on the device (cc_scan_ingest): the launches follow the scan's ingest on the
@@ -1442,8 +1532,8 @@ int cc_db_add_scan_batch(cc_db *db, cc_scan *const *scans, int n, const double *
   return cc_db_add_scans(db, d, n, h_ts, h_seed, db->ctx->s_loop);
 }
 
-int cc_db_query_scan_batch_submit(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
-                                  const cc_score_t *ub, cc_query_result_t *h_res) {
+static int query_scan_batch_submit_impl(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
+                                        const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
   if (!db || !scans || n < 1 || n > CC_SCAN_BATCH_MAX || !h_epoch || !lb || !ub || !h_res)
     return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit: bad argument (1..CC_SCAN_BATCH_MAX scans)");
   DB_POISON_CHK(db, "cc_db_query_scan_batch_submit");
@@ -1452,7 +1542,19 @@ int cc_db_query_scan_batch_submit(cc_db *db, cc_scan *const *scans, int n, const
   const cc_scan_desc_t *d = nullptr;
   const int rc = gather_handles(db, scans, n, 1, "cc_db_query_scan_batch_submit: null scan handle", &d);
   if (rc != CC_OK) return rc;
-  return cc_db_query_submit(db, d, n, h_epoch, lb, ub, h_res, nullptr, nullptr, db->ctx->s_loop);
+  return query_submit_impl(db, d, n, h_epoch, lb, ub, h_res, nullptr, nullptr, db->ctx->s_loop, rank);
+}
+int cc_db_query_scan_batch_submit(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
+                                  const cc_score_t *ub, cc_query_result_t *h_res) {
+  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, nullptr);
+}
+int cc_db_query_scan_batch_submit_ranked(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
+                                         const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
+  const int vrc = rank_validate(rank, "cc_db_query_scan_batch_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  if (lb && ub && !thres_strict_smaller(lb, ub))  // (before the handles are gathered: a refused call queues nothing)
+    return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit_ranked: thresholds must satisfy lb.strictSmaller(ub)");
+  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, rank);
 }
 
 int cc_db_add_scan_host(cc_db *db, const cc_scan_desc_t *h_desc, double ts, int32_t seed) {
@@ -1467,8 +1569,9 @@ int cc_db_query_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_score_t 
 
 // CandidateManager with explicit hints (single-pair flow, kitti_read_bin_test.cpp:226-291): the scoring chain of one
 // query whose check table is the caller's hint list, in the caller's order, instead of the KNN result.
-int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
-                      const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_) {
+static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                            const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_,
+                            const cc_rank_out_t *rank) {
   if (!db || !d_qdesc || n_hints < 0 || (n_hints > 0 && !h_hints) || !lb || !ub || !h_res || max_fine_opt < 1)
     return set_err(CC_EINVAL, "cc_db_check_hints: bad argument");
   DB_POISON_CHK(db, "cc_db_check_hints");
@@ -1502,6 +1605,10 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
     const int arc = lane_alloc_dyn(ln);
     if (arc != CC_OK) return arc;
   }
+  if (rank) {
+    const int arc = lane_alloc_rank(ln);
+    if (arc != CC_OK) return arc;
+  }
   HIPCHK(hipEventRecord(ln.done, stream));  // start after what the caller queued
   HIPCHK(hipStreamWaitEvent(ln.stream, ln.done, 0));
   if (db->add_done) HIPCHK(hipStreamWaitEvent(ln.stream, db->add_done, 0));  // ... and after the last append, whatever stream it used
@@ -1525,17 +1632,19 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
       if (h_hints[i].seq_tgt >= ql.n_cont[h_hints[i].level - 1])
         return set_err(CC_EINVAL, "cc_db_check_hints: hint names a contour of the query scan that does not exist");
   }
-  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false, CC_KNN_MAX);  // any database: 64-stride
+  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false, CC_KNN_MAX, rank ? rank->max_ret : 0);  // any database: 64-stride
   if (rc != CC_OK) return rc;
   std::vector<int> sc((size_t)CC_CHK_STRIDE * CC_NSCORE);
   std::vector<unsigned char> ok(CC_CHK_STRIDE);
   HIPCHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ln.stream));
+  if (rank) HIPCHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)rank->max_ret, hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(sc.data(), db->d_hint_scores, sizeof(int) * sc.size(), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(ok.data(), ln.d_pass_ok, ok.size(), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipStreamSynchronize(ln.stream));
   rc = chunk_status(ln, 1);  // CC_ECAPACITY: the result and the scores are delivered all the same (flags says what was hit)
   *h_res = ln.h_results[0];
+  if (rank) rank_deliver(ln, *rank, 0, 1, max_fine_opt);
   if (h_scores)
     for (int i = 0; i < n_hints; i++) {
       const int *p = &sc[(size_t)i * CC_NSCORE];
@@ -1547,6 +1656,18 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
       h_scores[i].passed = ok[i] == 1;
     }
   return rc;
+}
+
+int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                      const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_) {
+  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, nullptr);
+}
+int cc_db_check_hints_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                             const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_,
+                             const cc_rank_out_t *rank) {
+  const int vrc = rank_validate(rank, "cc_db_check_hints_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, rank);
 }
 
 int cc_db_debug_passes(cc_db *db, cc_pass_dbg_t *h_out, int cap, int *n_out) {
@@ -1572,14 +1693,26 @@ int cc_db_debug_passes(cc_db *db, cc_pass_dbg_t *h_out, int cap, int *n_out) {
   return CC_OK;
 }
 
-int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
-                           const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores) {
+static int check_hints_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                                 const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
+                                 const cc_rank_out_t *rank) {
   if (!db || !h_qdesc) return set_err(CC_EINVAL, "cc_db_check_hints_host: bad argument");
   HIPCHK(hipSetDevice(db->device));
   int rc = stage_reserve(db, 1);
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t), hipMemcpyHostToDevice));
-  return cc_db_check_hints(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr);
+  return check_hints_impl(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr, rank);
+}
+int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                           const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores) {
+  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr);
+}
+int cc_db_check_hints_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                                  const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
+                                  const cc_rank_out_t *rank) {
+  const int vrc = rank_validate(rank, "cc_db_check_hints_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank);
 }
 
 // ---- verification of caller-proposed candidates (k_verify.h) ----
@@ -1613,9 +1746,9 @@ static int verify_validate(const cc_db *db, const cc_scan_desc_t *d_qdesc, int n
   return CC_OK;
 }
 
-int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
-                        const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
-                        cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_) {
+static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                              const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                              cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank) {
   {  // everything that can be refused is refused before anything is queued or collected
     const int vrc = verify_validate(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
     if (vrc != CC_OK) return vrc;
@@ -1661,6 +1794,10 @@ int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, co
     if (rc != CC_OK) break;
     rc = lane_alloc_verify(ln);
     if (rc != CC_OK) break;
+    if (rank) {
+      rc = lane_alloc_rank(ln);
+      if (rc != CC_OK) break;
+    }
     if (db->dyn_thres) {
       rc = lane_alloc_dyn(ln);
       if (rc != CC_OK) break;
@@ -1686,7 +1823,7 @@ int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, co
                        (const int *)(ln.d_vin + nb), nb, ln.d_hits, ln.d_hit_cnt, d_hints ? d_hints + (size_t)b0 * CC_HINT_MAX : (cc_hint_t *)nullptr,
                        d_n_hints ? d_n_hints + b0 : (int32_t *)nullptr);
     if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, cfg->max_fine_opt, ev, nullptr, zc, CC_KNN_MAX);
+    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, cfg->max_fine_opt, ev, nullptr, zc, CC_KNN_MAX, rank ? rank->max_ret : 0);
     if (rc != CC_OK) {
       lane_abort(db, ln);
       break;
@@ -1694,6 +1831,7 @@ int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, co
     if (!zc) {
       LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
       LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
+      if (rank) LANE_CHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
     }
     LANE_CHK(hipEventRecord(ln.fin, ls));
     for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];  // (a verify chunk reads no sorted view: nothing for an append to wait for beyond this)
@@ -1701,9 +1839,23 @@ int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, co
     ln.b0 = b0;
     ln.nb = nb;
     ln.h_dst = h_res;
+    ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
+    ln.rank_mfo = cfg->max_fine_opt;
   }
 #undef LANE_CHK
   return rc;
+}
+int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                        const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                        cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_) {
+  return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, nullptr);
+}
+int cc_db_verify_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                               const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                               cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank) {
+  const int vrc = rank_validate(rank, "cc_db_verify_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank);
 }
 
 int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
@@ -1720,8 +1872,9 @@ int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, con
   return rc != CC_OK ? rc : r2;
 }
 
-int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
-                            const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res) {
+static int verify_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                                  const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                                  const cc_rank_out_t *rank) {
   {
     const int vrc = verify_validate(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
     if (vrc != CC_OK) return vrc;
@@ -1731,5 +1884,21 @@ int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc
   int rc = stage_reserve(db, n_desc);
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)n_desc, hipMemcpyHostToDevice));
-  return cc_db_verify_batch(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr);
+  if (!rank) return cc_db_verify_batch(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr);
+  db->sync_call = true;
+  rc = verify_submit_impl(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr, rank);
+  db->sync_call = false;
+  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
+  return rc != CC_OK ? rc : r2;
+}
+int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                            const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res) {
+  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr);
+}
+int cc_db_verify_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                                   const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                                   const cc_rank_out_t *rank) {
+  const int vrc = rank_validate(rank, "cc_db_verify_batch_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank);
 }

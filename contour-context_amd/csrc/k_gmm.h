@@ -10,7 +10,7 @@
 //                    reads the problem's codes and files a 56-byte record per pair (the first CC_GMM_NL in LDS, the rest in
 //                    the pair pool, unit by unit), every further evaluation streams those records.
 //                    Two instances: 16 lanes per problem (4 problems per wave) and 64 lanes for the long pair lists.
-//   cc_k_final       tidyUp compaction, fineOptimize ordering, result record
+//   cc_k_final       tidyUp compaction, fineOptimize ordering, result record (cc_k_final_r: and the ranked list of the refined ones)
 // The ellipse tables are read where they lie; the two pools are sized per query lane (cc_db_api.inc) and running out of
 // either is reported (CC_ECAPACITY), never a shorter pair list.
 #pragma once
@@ -1715,13 +1715,16 @@ cc_k_select_l(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__rest
 // fineOptimize (contour_db.h:604-648): std::sort on the still-all-zero correlation_ (replayed), take the first
 // max_fine_opt_, adopt their refined score/pose, re-sort those, return the best.  One lane per query.
 // DYN (dynamic thresholds): the survivors are those cc_k_select<true> left in `tidy`.
+// RANK (the _r instances): the first min(max_ret, pre) entries of the re-sorted list go to rank_out[q][max_ret] as well -- what
+// fineOptimize would return with ret_size = max_ret (contour_db.h:630-648); the rest of the row is zeroed.
 // ------------------------------------------------------------------------------------------------
-template <bool DYN, int KM>
+template <bool DYN, int KM, bool RANK = false>
 __device__ __forceinline__ void cc_final_body(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *cands_all, const cc_qstate *qstate,
                                               const cc_gmm_result *gres, const int *pass_cnt, const int *hit_cnt,
                                               const cc_hot_desc_t *qhot, cc_query_result_t *out, const unsigned short *perm_tab,
                                               const int *nprob /*the chunk's problem counters and pool head*/, int *nprob_host /*or nullptr: copy them there*/,
-                                              const unsigned char *tidy /*DYN only*/) {
+                                              const unsigned char *tidy /*DYN only*/, cc_ranked_cand_t *rank_out = nullptr /*RANK only: [nq][max_ret]*/,
+                                              int max_ret = 0 /*RANK only: 1..CC_RANK_MAX*/) {
   // one wave per query: lanes fetch the per-candidate inputs and order the candidates in parallel (cc_tidy_order), lane 0
   // replays the short order-dependent rest on LDS
   __shared__ unsigned short idx[CC_CHK_STRIDE_K(KM)];
@@ -1763,38 +1766,73 @@ __device__ __forceinline__ void cc_final_body(int nq, float corr_lb, int max_fin
   // two-pointer compaction of candidates_ (has = corr_est_ != nullptr), contour_db.h:580-592, and the first std::sort:
   // every anch_props_[0].correlation_ is still 0 -> the comparator is always false
   const int n = cc_tidy_order<CC_CHK_STRIDE_K(KM)>(nc, has, idx, scr, perm_tab, lane);
-  if (lane != 0) return;
-  cc_query_result_t r;
-  r.n_res = 0;
-  r.cand_gidx = -1;
-  r.correlation = 0;
-  r.tf[0] = r.tf[1] = r.tf[2] = 0;
-  r.cand_aft_check1 = pc1;
-  r.cand_aft_check2 = pc2;
-  r.cand_aft_check3 = pc3;
-  r.n_cand_pose = nc;
-  r.n_knn_hits = s_tot;
-  r.flags = (pc0 & CC_QF_CHECK_CAP) | ((gfl & 1) ? CC_QF_GMM_CAP : 0) | ((gfl & 4) ? CC_QF_DESC_CAP : 0) |
-            ((qflags & (CC_DESC_INEXACT_COMPONENTS | CC_DESC_INEXACT_KEYS)) ? CC_QF_QUERY_INEXACT : 0);
-  r.pad_ = 0;
-  r.n_cand_tidy = n;
-  if (n > 0) {
-    const int pre = max_fine_opt < n ? max_fine_opt : n;
-    // candidates beyond `pre` keep correlation_ = 0
-    ccsort::std_sort(idx, pre, [&](unsigned short a, unsigned short b) { return corr_o[a] > corr_o[b]; }, stk);
-    const int b = idx[0];
-    r.n_res = 1;
-    r.cand_gidx = cands[b].gidx;
-    r.correlation = pre > 0 ? (double)corr_o[b] : 0.0;
-    if (pre > 0) {
-      const cc_gmm_result *g = &gres[gm[b]];
-      // T_best_ = Identity.rotate(theta).pretranslate(x, y); reported as (x, y, atan2(T10, T00))
-      r.tf[0] = g->tf_opt[0];
-      r.tf[1] = g->tf_opt[1];
-      r.tf[2] = atan2(sin(g->tf_opt[2]), cos(g->tf_opt[2]));
+  auto record = [&]() {  // lane 0: the query's result record
+    cc_query_result_t r;
+    r.n_res = 0;
+    r.cand_gidx = -1;
+    r.correlation = 0;
+    r.tf[0] = r.tf[1] = r.tf[2] = 0;
+    r.cand_aft_check1 = pc1;
+    r.cand_aft_check2 = pc2;
+    r.cand_aft_check3 = pc3;
+    r.n_cand_pose = nc;
+    r.n_knn_hits = s_tot;
+    r.flags = (pc0 & CC_QF_CHECK_CAP) | ((gfl & 1) ? CC_QF_GMM_CAP : 0) | ((gfl & 4) ? CC_QF_DESC_CAP : 0) |
+              ((qflags & (CC_DESC_INEXACT_COMPONENTS | CC_DESC_INEXACT_KEYS)) ? CC_QF_QUERY_INEXACT : 0);
+    r.pad_ = 0;
+    r.n_cand_tidy = n;
+    if (n > 0) {
+      const int pre = max_fine_opt < n ? max_fine_opt : n;
+      // candidates beyond `pre` keep correlation_ = 0
+      ccsort::std_sort(idx, pre, [&](unsigned short a, unsigned short b) { return corr_o[a] > corr_o[b]; }, stk);
+      const int b = idx[0];
+      r.n_res = 1;
+      r.cand_gidx = cands[b].gidx;
+      r.correlation = pre > 0 ? (double)corr_o[b] : 0.0;
+      if (pre > 0) {
+        const cc_gmm_result *g = &gres[gm[b]];
+        // T_best_ = Identity.rotate(theta).pretranslate(x, y); reported as (x, y, atan2(T10, T00))
+        r.tf[0] = g->tf_opt[0];
+        r.tf[1] = g->tf_opt[1];
+        r.tf[2] = atan2(sin(g->tf_opt[2]), cos(g->tf_opt[2]));
+      }
     }
+    out[q] = r;
+  };
+  if constexpr (RANK) {
+    if (lane == 0) {
+      record();
+      const int pre = max_fine_opt < n ? max_fine_opt : n;  // the refined ones: nothing beyond them is listed
+      s_tot = max_ret < pre ? max_ret : pre;                // (read by record()) from here on: the entries of the list
+    }
+    __syncthreads();
+    // the list comes from lane 0's sorted idx[]; every lane of the row gathers its own candidate's record (one round trip for
+    // all of them) and writes its 40 bytes
+    const int ret = s_tot;
+    if (lane < max_ret) {
+      cc_ranked_cand_t e;
+      e.cand_gidx = 0;
+      e.flags = 0;
+      e.correlation = 0;
+      e.tf[0] = e.tf[1] = e.tf[2] = 0;
+      if (lane < ret) {
+        const int b = idx[lane];
+        const cc_gmm_result *g = &gres[gm[b]];
+        const int gf = g->flags;
+        const double t0 = g->tf_opt[0], t1 = g->tf_opt[1], t2 = g->tf_opt[2];
+        e.cand_gidx = cands[b].gidx;
+        e.flags = ((gf & 1) ? CC_QF_GMM_CAP : 0) | ((gf & 4) ? CC_QF_DESC_CAP : 0);
+        e.correlation = (double)corr_o[b];
+        e.tf[0] = t0;
+        e.tf[1] = t1;
+        e.tf[2] = atan2(sin(t2), cos(t2));
+      }
+      rank_out[(size_t)q * max_ret + lane] = e;
+    }
+    return;
   }
-  out[q] = r;
+  if (lane != 0) return;
+  record();
 }
 
 template <bool DYN>
@@ -1814,4 +1852,23 @@ cc_k_final_l(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restr
              const int *__restrict__ nprob /*the chunk's problem counters and pool head*/, int *__restrict__ nprob_host /*or nullptr: copy them there*/,
              const unsigned char *__restrict__ tidy /*DYN only*/) {
   cc_final_body<DYN, CC_KNN_MAX_LARGE>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy);
+}
+// the ranked instances (the *_ranked entry points): the same body, plus the list of the refined candidates
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_final_r(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+             const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
+             const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
+             const int *__restrict__ nprob, int *__restrict__ nprob_host, const unsigned char *__restrict__ tidy /*DYN only*/,
+             cc_ranked_cand_t *__restrict__ rank_out /*[nq][max_ret]*/, int max_ret) {
+  cc_final_body<DYN, CC_KNN_MAX, true>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy, rank_out, max_ret);
+}
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_final_rl(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+              const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
+              const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
+              const int *__restrict__ nprob, int *__restrict__ nprob_host, const unsigned char *__restrict__ tidy /*DYN only*/,
+              cc_ranked_cand_t *__restrict__ rank_out /*[nq][max_ret]*/, int max_ret) {
+  cc_final_body<DYN, CC_KNN_MAX_LARGE, true>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy, rank_out, max_ret);
 }

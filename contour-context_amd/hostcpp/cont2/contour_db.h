@@ -67,8 +67,12 @@ class ContourDB {
     std::shared_ptr<std::vector<cc_query_result_t>> block;  // the answers of the batch the scan was queued with (epoch = position of the scan)
     int idx = 0;                                             // ... this scan's among them; filled by cc_db_query_collect / _wait
     bool collected = false;
+    int max_ret = 1;                                         // setMaxReturn when the scan was queued; > 1: the batch's ranked lists
+    std::shared_ptr<std::vector<cc_ranked_cand_t>> rblock;  // [batch][max_ret]
+    std::shared_ptr<std::vector<int32_t>> nblock;           // [batch]
     cc_query_result_t *result() const { return block->data() + idx; }
   };
+  int max_ret_ = 1;  // setMaxReturn: entries queryRangedKNN / verifyCandidates hand out (fineOptimize's ret_size, contour_db.h:630)
   static constexpr int SPEC_LOW = 2;  // fewer answers than this queued ahead of the driver: a step goes out with whatever has been published
   mutable std::deque<Spec> spec_;   // scans appended ahead of the driver, oldest first (spec_[j] sits at DB index n_official + j)
   mutable bool have_thres_ = false;
@@ -212,7 +216,16 @@ class ContourDB {
       if (cc_db_add_scan_batch(db_, scans, n, ts, seed) != CC_OK) die_cc();
       t_ra_[0] += t0.toc();
       TicToc t1;
-      if (cc_db_query_scan_batch_submit(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data()) != CC_OK) die_cc();
+      std::shared_ptr<std::vector<cc_ranked_cand_t>> rblock;
+      std::shared_ptr<std::vector<int32_t>> nblock;
+      if (max_ret_ > 1) {  // the answers carry their ranked lists
+        rblock = std::make_shared<std::vector<cc_ranked_cand_t>>((size_t)n * max_ret_);
+        nblock = std::make_shared<std::vector<int32_t>>((size_t)n);
+        const cc_rank_out_t ro = {rblock->data(), nblock->data(), max_ret_, 0};
+        if (cc_db_query_scan_batch_submit_ranked(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data(), &ro) != CC_OK) die_cc();
+      } else if (cc_db_query_scan_batch_submit(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data()) != CC_OK) {
+        die_cc();
+      }
       t_ra_[1] += t1.toc();
       n_ra_++;
       n_ra_scans_ += n;
@@ -225,6 +238,9 @@ class ContourDB {
         sp.ub = last_ub_;
         sp.block = block;
         sp.idx = j;
+        sp.max_ret = max_ret_;
+        sp.rblock = rblock;
+        sp.nblock = nblock;
         spec_.push_back(std::move(sp));
       }
       pos += (size_t)n;
@@ -310,6 +326,14 @@ class ContourDB {
     cc_db_destroy(db_);
   }
 
+  // Mirror-only: how many candidates a query hands out -- what fineOptimize would return with ret_size = n instead of its
+  // hard-wired 1 (contour_db.h:630): the refined candidates by refined correlation, best first.  1 (the default) is the reference.
+  void setMaxReturn(int n) {
+    CC_CHECK(n >= 1 && n <= CC_RANK_MAX);
+    max_ret_ = n;  // (answers queued with another setting are not handed out: queryRangedKNN asks again, at the official epoch)
+  }
+  int maxReturn() const { return max_ret_; }
+
   // contour_db.h:698-703
   void queryRangedKNN(const std::shared_ptr<const ContourManager> &q_ptr, const CandidateScoreEnsemble &thres_lb,
                       const CandidateScoreEnsemble &thres_ub, std::vector<std::shared_ptr<const ContourManager>> &cand_ptrs,
@@ -320,30 +344,41 @@ class ContourDB {
     ensure(*q_ptr);
     const cc_score_t lb = to_c(thres_lb), ub = to_c(thres_ub);
     cc_query_result_t r;
+    cc_ranked_cand_t rl[CC_RANK_MAX];  // the ranked list (max_ret_ > 1)
+    int32_t rn = 0;
+    const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
     TicToc wall;
     if (need_rebuild_) rebuild();
     last_lb_ = lb;
     last_ub_ = ub;
     have_thres_ = true;
     cc_scan *qh = q_ptr->scanHandle();
-    if (!spec_.empty() && qh && spec_.front().scan == qh && same(spec_.front().lb, lb) && same(spec_.front().ub, ub)) {
+    if (!spec_.empty() && qh && spec_.front().scan == qh && same(spec_.front().lb, lb) && same(spec_.front().ub, ub) &&
+        spec_.front().max_ret == max_ret_) {
       // the answer was queued when the scan was published (at the epoch the database is officially in now); only ITS chain is
       // waited for, the queries queued behind it stay in flight
       collectOne(0);
-      r = *spec_.front().result();
+      const Spec &sp = spec_.front();
+      r = *sp.result();
+      if (max_ret_ > 1) {
+        rn = (*sp.nblock)[sp.idx];
+        std::copy(sp.rblock->begin() + (size_t)sp.idx * max_ret_, sp.rblock->begin() + (size_t)(sp.idx + 1) * max_ret_, rl);
+      }
       n_spec_hit_++;
     } else {
       n_spec_miss_++;
       const int32_t epoch = (int32_t)all_bevs_.size();  // the scans appended ahead of the driver are hidden by the epoch
       int rc;
       if (qh && cc_scan_on_device(qh)) {
-        rc = cc_db_query_scan_submit(db_, qh, epoch, &lb, &ub, &r);
+        rc = max_ret_ > 1 ? cc_db_query_scan_batch_submit_ranked(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro)
+                          : cc_db_query_scan_submit(db_, qh, epoch, &lb, &ub, &r);
         const int r2 = cc_db_query_wait(db_);
         for (auto &sp : spec_) sp.collected = true;
         if (rc == CC_OK) rc = r2;
       } else {  // a scan that was offloaded goes by its host copy
         collectSpec();
-        rc = cc_db_query_batch_host(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r);
+        rc = max_ret_ > 1 ? cc_db_query_batch_host_ranked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro)
+                          : cc_db_query_batch_host(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r);
       }
       if (rc != CC_OK) die_cc();  // CHECK(sim_lb.strictSmaller(sim_ub)) etc.; also CC_ECAPACITY (the reference has no capacities)
     }
@@ -358,7 +393,9 @@ class ContourDB {
         stp.addSample("L2 opt", (ms[3] + ms[4]) * 1e-3);
       }
     }
-    if (r.n_res > 0) {
+    if (max_ret_ > 1) {
+      for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], cand_ptrs, cand_corr, cand_tf);
+    } else if (r.n_res > 0) {
       cand_ptrs.push_back(all_bevs_[r.cand_gidx]);
       cand_corr.push_back(r.correlation);
       Eigen::Isometry2d T;
@@ -366,6 +403,17 @@ class ContourDB {
       T.pretranslate(r.tf[0], r.tf[1]);
       cand_tf.push_back(T);
     }
+  }
+  // one entry of a ranked list as the reference's result vectors hold it
+  template <class Scans>
+  static void pushRanked(const Scans &scans, const cc_ranked_cand_t &e, std::vector<std::shared_ptr<const ContourManager>> &res_cand,
+                         std::vector<double> &res_corr, std::vector<Eigen::Isometry2d> &res_T) {
+    res_cand.push_back(scans[e.cand_gidx]);
+    res_corr.push_back(e.correlation);
+    Eigen::Isometry2d T;
+    T.rotate(e.tf[2]);
+    T.pretranslate(e.tf[0], e.tf[1]);
+    res_T.push_back(T);
   }
   // Mirror-only (no reference counterpart): score candidates the CALLER proposes -- scans of this database by their index in
   // adding order (odometry or GPS proximity, another descriptor, a re-check of accepted loops) -- instead of the ones the key
@@ -377,6 +425,15 @@ class ContourDB {
                        const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
                        std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
                        std::vector<Eigen::Isometry2d> &res_T) const {
+    return verifyCandidates(q_ptr, cand_indices, thres_lb, thres_ub, res_cand, res_corr, res_T, 1);
+  }
+  // ... and the ranked list of them: up to max_ret (1..CC_RANK_MAX) of the candidates that survive, best first -- one verdict
+  // per proposed candidate from one device pass.  Returns the number of entries.
+  int verifyCandidates(const std::shared_ptr<const ContourManager> &q_ptr, const std::vector<int> &cand_indices,
+                       const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
+                       std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
+                       std::vector<Eigen::Isometry2d> &res_T, int max_ret) const {
+    CC_CHECK(max_ret >= 1 && max_ret <= CC_RANK_MAX);
     res_cand.clear();
     res_corr.clear();
     res_T.clear();
@@ -394,9 +451,17 @@ class ContourDB {
     vc.max_key_dist_sq = 1000.0f;
     vc.pad_ = 0;
     cc_query_result_t r;
-    const int rc = cc_db_verify_batch_host(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
+    cc_ranked_cand_t rl[CC_RANK_MAX];
+    int32_t rn = 0;
+    const cc_rank_out_t ro = {rl, &rn, max_ret, 0};
+    const int rc = max_ret > 1 ? cc_db_verify_batch_host_ranked(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro)
+                               : cc_db_verify_batch_host(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
     for (auto &sp : spec_) sp.collected = true;  // the synchronous call collected every chain in flight
     if (rc != CC_OK) die_cc();
+    if (max_ret > 1) {
+      for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], res_cand, res_corr, res_T);
+      return rn;
+    }
     if (r.n_res > 0) {
       res_cand.push_back(all_bevs_[r.cand_gidx]);
       res_corr.push_back(r.correlation);
@@ -637,9 +702,11 @@ class CandidateManager {
     flow_valve++;
   }
 
-  // contour_db.h:604-648: returns the number of results (0 or 1)
+  // contour_db.h:604-648: returns the number of results (0 or 1; with max_ret > 1 -- mirror-only, the reference's ret_size is
+  // hard-wired to 1 -- up to min(max_ret, max_fine_opt) refined candidates, best first)
   int fineOptimize(int max_fine_opt, std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
-                   std::vector<Eigen::Isometry2d> &res_T) {
+                   std::vector<Eigen::Isometry2d> &res_T, int max_ret = 1) {
+    CC_CHECK(max_ret >= 1 && max_ret <= CC_RANK_MAX);
     CC_CHECK(flow_valve == 1);
     flow_valve++;
     res_cand.clear();
@@ -651,6 +718,15 @@ class CandidateManager {
     ensureMine();
     std::vector<cc_hint_t> hs(hints_);
     for (auto &h : hs) h.cand_gidx = st_->pos[my_cands_[h.cand_gidx].get()];
+    if (max_ret > 1) {
+      cc_ranked_cand_t rl[CC_RANK_MAX];
+      int32_t rn = 0;
+      const cc_rank_out_t ro = {rl, &rn, max_ret, 0};
+      if (cc_db_check_hints_host_ranked(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r, nullptr, &ro) != CC_OK)
+        die();
+      for (int k = 0; k < rn; k++) ContourDB::pushRanked(st_->keep, rl[k], res_cand, res_corr, res_T);
+      return rn;
+    }
     if (cc_db_check_hints_host(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r, nullptr) != CC_OK)
       die();
     if (r.n_res > 0) {

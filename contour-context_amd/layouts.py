@@ -53,6 +53,26 @@ assert hint_dt.itemsize == 8 and hint_score_dt.itemsize == 24
 HINT_MAX = NQLEV * NPIV * KNN_MAX  # CC_HINT_MAX: hints of one cc_db_check_hints call / of one item of cc_db_verify_*
 VERIFY_CANDS_MAX = 8               # CC_VERIFY_CANDS_MAX: candidates per item (8 x 4 levels x 6 x 6 anchor pairs = HINT_MAX)
 assert VERIFY_CANDS_MAX * 4 * NPIV * NPIV == HINT_MAX
+# cc_ranked_cand_t / cc_rank_out_t (the *_ranked entry points): one refined candidate of a query's ranked list
+RANK_MAX = 16  # CC_RANK_MAX
+ranked_cand_dt = np.dtype([("cand_gidx", "<i4"), ("flags", "<i4"), ("correlation", "<f8"), ("tf", "<f8", (3,))], align=True)
+assert ranked_cand_dt.itemsize == 40
+
+
+class RankOut(C.Structure):  # cc_rank_out_t
+    _fields_ = [("h_cands", C.c_void_p), ("h_n", C.c_void_p), ("max_ret", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(RankOut) == 24
+
+
+def rank_buffers(n, max_ret):
+    """(cands [n, max_ret] of ranked_cand_dt, counts [n] int32, RankOut pointing at them) for a *_ranked call of n queries"""
+    cands = np.zeros((n, max(int(max_ret), 0)), ranked_cand_dt)
+    cnt = np.zeros(n, np.int32)
+    return cands, cnt, RankOut(cands.ctypes.data, cnt.ctypes.data, int(max_ret), 0)
+
+
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
 

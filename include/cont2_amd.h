@@ -558,7 +558,8 @@ int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hi
  * re-check of accepted loops): the batched, streamed form of the hint flow.  Item i is the query scan d_qdesc[h_qidx[i]]
  * (h_qidx NULL: d_qdesc[i], and then n == n_desc) against the database scans h_cands[i][0 .. m_i), 0 <= m_i <=
  * CC_VERIFY_CANDS_MAX, the list ended by -1; candidates are DB indices below cc_db_size, searchable or not.  Several items
- * may name the same descriptor: one item per (query, candidate) pair gives one verdict per pair instead of the best of a list.
+ * may name the same descriptor: one item per (query, candidate) pair gives one verdict per pair instead of the best of a list
+ * (cc_db_verify_submit_ranked lists every refined candidate of ONE item instead: the query's pack and prep work is done once).
  *
  * The hint list of an item is generated on the device, in the demo's order (test/kitti_read_bin_test.cpp:226-291 with the
  * candidate as the outermost index): for candidate k in list order, for level 1..4 where set in level_mask, for seq_src
@@ -598,6 +599,59 @@ int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, con
 int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                             const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
                             cc_query_result_t *h_res);
+
+/* ---- the ranked list of a query's refined candidates ----
+ * Every entry point above answers with the best candidate: fineOptimize's `ret_size = 1` (contour_db.h:604-648).  The _ranked
+ * forms return what fineOptimize would with ret_size = min(max_ret, pre_sel_size): the first entries of candidates_ after its
+ * second std::sort -- the (at most max_fine_opt) candidates that were refined, by refined correlation, best first; ties in the
+ * order that sort leaves them in.  Entry 0 is the candidate h_res reports, bit for bit; h_res itself is what the plain call
+ * returns.  Candidates that were not refined are not listed.  Other passes through the same place show up as further entries:
+ * several loop edges per key frame for a back end that weighs or switches hypotheses, one verdict per proposed candidate from
+ * ONE verify item.
+ *
+ * h_n[i] = min(max_ret, max_fine_opt, n_cand_tidy), 0 where n_res is 0; h_cands[i][0 .. h_n[i]) are the entries, the rest of
+ * the row is zeroed.  A chunk's rows arrive with its h_res rows (cc_db_query_wait / cc_db_query_collect, or the synchronous
+ * call's return), so both buffers must stay valid until then.  Everything else -- chunking, streaming, epochs, thresholds,
+ * dynamic thresholds, flags and CC_ECAPACITY -- is the plain call's.  Refused with CC_EINVAL before anything is queued: rank
+ * NULL, h_cands or h_n NULL, max_ret outside 1..CC_RANK_MAX (and whatever the plain call refuses). */
+#define CC_RANK_MAX 16
+typedef struct {
+  int32_t cand_gidx;   /* DB index, as cc_query_result_t.cand_gidx of the same entry point                             */
+  int32_t flags;       /* the CC_QF_GMM_CAP / CC_QF_DESC_CAP bits of THIS candidate's correlation problem             */
+  double correlation;  /* refined                                                                                     */
+  double tf[3];        /* (x, y, theta), as cc_query_result_t.tf                                                      */
+} cc_ranked_cand_t; /* 40 bytes */
+typedef struct {
+  cc_ranked_cand_t *h_cands; /* [n][max_ret], host; rows beyond h_n[i] are zeroed */
+  int32_t *h_n;              /* [n]                                               */
+  int32_t max_ret;           /* 1..CC_RANK_MAX                                    */
+  int32_t pad_;
+} cc_rank_out_t;
+int cc_db_query_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *thres_lb,
+                              const cc_score_t *thres_ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt,
+                              void *stream, const cc_rank_out_t *rank);
+/* synchronous, host descriptors */
+int cc_db_query_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *thres_lb,
+                                  const cc_score_t *thres_ub, cc_query_result_t *h_res, const cc_rank_out_t *rank);
+/* scan handles (n = 1: the per-scan loop's query) */
+int cc_db_query_scan_batch_submit_ranked(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *thres_lb,
+                                         const cc_score_t *thres_ub, cc_query_result_t *h_res, const cc_rank_out_t *rank);
+/* one item of <= CC_VERIFY_CANDS_MAX candidates -> one entry per candidate that survives (cand_gidx names it) */
+int cc_db_verify_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                               const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                               cc_query_result_t *h_res, cc_hint_t *d_hints, int32_t *d_n_hints, void *stream, const cc_rank_out_t *rank);
+/* synchronous; n = 1 */
+int cc_db_check_hints_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *thres_lb,
+                             const cc_score_t *thres_ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
+                             void *stream, const cc_rank_out_t *rank);
+/* the verify and hint flows with host descriptors (one H2D copy, then the calls above; both synchronous): what a caller without
+ * device memory of its own uses -- the class mirror (hostcpp/cont2/contour_db.h) */
+int cc_db_verify_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                                   const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                                   cc_query_result_t *h_res, const cc_rank_out_t *rank);
+int cc_db_check_hints_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints,
+                                  const cc_score_t *thres_lb, const cc_score_t *thres_ub, int max_fine_opt, cc_query_result_t *h_res,
+                                  cc_hint_score_t *h_scores, const cc_rank_out_t *rank);
 
 /* Parity / debug: the constellations of the LAST cc_db_check_hints[_host] call that passed all four gates, in hint
  * order: the pose getTFFromConstell returned for each (contour_mng.h:1246-1277, before any proposal merging) and the
