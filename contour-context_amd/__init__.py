@@ -23,7 +23,7 @@ import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
 _SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_contours.h", "k_contours_list.h",
-         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_verify.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
+         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 
 def build(force=False, verbose=False):
@@ -53,6 +53,9 @@ EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_
            "cc_db_verify_submit", "cc_db_verify_batch", "cc_db_verify_batch_host",
            "cc_db_query_submit_ranked", "cc_db_query_batch_host_ranked", "cc_db_query_scan_batch_submit_ranked", "cc_db_verify_submit_ranked",
            "cc_db_check_hints_ranked", "cc_db_verify_batch_host_ranked", "cc_db_check_hints_host_ranked",
+           "cc_db_query_submit_ranked_detail", "cc_db_query_batch_host_ranked_detail", "cc_db_query_scan_batch_submit_ranked_detail",
+           "cc_db_verify_submit_ranked_detail", "cc_db_verify_batch_host_ranked_detail", "cc_db_check_hints_ranked_detail",
+           "cc_db_check_hints_host_ranked_detail", "cc_est_sens_info",
            "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
            "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
            "cc_comm_unique_id", "cc_comm_create", "cc_comm_create_from_env", "cc_comm_rank", "cc_comm_world", "cc_comm_allgather_packed", "cc_comm_destroy"]
@@ -112,6 +115,11 @@ def lib():
         _lib.cc_db_verify_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
         _lib.cc_db_check_hints_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for f in ("cc_db_query_submit_ranked", "cc_db_query_batch_host_ranked", "cc_db_query_scan_batch_submit_ranked", "cc_db_verify_submit_ranked",
+                  "cc_db_check_hints_ranked"):  # the _detail siblings: one more trailing pointer
+            getattr(_lib, f + "_detail").argtypes = getattr(_lib, f).argtypes + [C.c_void_p]
+        _lib.cc_est_sens_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.cc_est_sens_info.restype = None
         _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
         _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
     return _lib
@@ -389,6 +397,15 @@ class Database:
         stream = torch.cuda.current_stream(desc.device).cuda_stream
         _chk(lib().cc_db_add_scans_prepare(self.h, desc.data_ptr(), desc.shape[0], stream), "cc_db_add_scans_prepare")
 
+    @staticmethod
+    def _detail_args(n, ranked, detail):
+        """detail=True: the h_detail buffer of a *_ranked_detail call ([n, ranked] of L.ranked_detail_dt), else None"""
+        if not detail:
+            return None
+        if ranked is None:
+            raise ValueError("detail=True needs ranked=K: the detail rows belong to the entries of the ranked list")
+        return L.rank_detail_buffer(n, ranked)
+
     def _ranked_call(self, fn, what, tol, *args):
         """a *_submit_ranked call followed by the wait: the synchronous ranked forms of query() and verify()"""
         rc = fn(*args)
@@ -400,7 +417,7 @@ class Database:
             raise e
         _chk(lib().cc_db_query_wait(self.h), "cc_db_query_wait", tolerate=tol)
 
-    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None):
+    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False):
         """qdesc: torch uint8 CUDA [nq, DESC_BYTES]; epochs int32 [nq] (DB state each query sees).
         Returns numpy structured array of cc_query_result_t (+ knn hits / counts as torch tensors).
         allow_flagged: a query that met an internal capacity (cc_query_result_t.flags != 0) makes the library return
@@ -408,8 +425,12 @@ class Database:
         ranked=K (1..RANK_MAX): the ranked list of every query's refined candidates as well (cc_db_query_submit_ranked): the return
         value is followed by (cands [nq, K] of L.ranked_cand_dt, counts [nq]); entry 0 of a list is the candidate the result names.
         The ranked form is query_submit(ranked=K) + query_wait(): a batch of a full chunk or more goes out in whole chunks, lane
-        after lane, where the plain synchronous call cuts one chunk per lane -- the same answers, scheduled differently."""
+        after lane, where the plain synchronous call cuts one chunk per lane -- the same answers, scheduled differently.
+        detail=True (with ranked=K): followed by a [nq, K] array of L.ranked_detail_dt as well -- per entry the curvature of
+        -correlation at its pose (hess, grad) and the refinement's start, initial correlation, iterations, termination and pair
+        count (cc_db_query_submit_ranked_detail).  Without ranked it is a ValueError."""
         import torch
+        det = self._detail_args(qdesc.shape[0], ranked, detail)
         if lb is None:
             lb, ub = L.default_thresholds()
         epochs = np.ascontiguousarray(epochs, np.int32)
@@ -431,21 +452,26 @@ class Database:
         else:
             rc_, rn_, ro = L.rank_buffers(nq, ranked)
             rk = (rc_, rn_)
-            self._ranked_call(lib().cc_db_query_submit_ranked, "cc_db_query_submit_ranked", tol, self.h, qdesc.data_ptr(), nq, epochs.ctypes.data,
+            fn = "cc_db_query_submit_ranked" + ("_detail" if det is not None else "")
+            self._ranked_call(getattr(lib(), fn), fn, tol, self.h, qdesc.data_ptr(), nq, epochs.ctypes.data,
                               C.addressof(lb), C.addressof(ub), res.ctypes.data, knn.data_ptr() if want_knn else None,
-                              cnt.data_ptr() if want_knn else None, stream, C.addressof(ro))
+                              cnt.data_ptr() if want_knn else None, stream, C.addressof(ro), *(() if det is None else (det.ctypes.data,)))
         out = (res,)
         if want_knn:
             out += (knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy())
         if rk is not None:
             out += (rk,)
+        if det is not None:
+            out += (det,)
         return out if len(out) > 1 else res
 
-    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None):
+    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False):
         """Asynchronous form of query(): queues the batch and returns the result array, which is only valid after
         query_wait() (cc_db_query_submit / cc_db_query_wait).  qdesc may be overwritten by work queued afterwards on the
-        current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait()."""
+        current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait();
+        with detail=True followed by the [nq, K] detail array (see query())."""
         import torch
+        det = self._detail_args(qdesc.shape[0], ranked, detail)
         if lb is None:
             lb, ub = L.default_thresholds()
         epochs = np.ascontiguousarray(epochs, np.int32)
@@ -458,6 +484,12 @@ class Database:
         if ranked is not None:
             rc_, rn_, ro = L.rank_buffers(nq, ranked)
             self._pending.append((rc_, rn_))
+            if det is not None:
+                self._pending.append(det)
+                _chk(lib().cc_db_query_submit_ranked_detail(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
+                                                            res.ctypes.data, None, None, stream, C.addressof(ro), det.ctypes.data),
+                     "cc_db_query_submit_ranked_detail")
+                return res, (rc_, rn_), det
             _chk(lib().cc_db_query_submit_ranked(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
                                                  res.ctypes.data, None, None, stream, C.addressof(ro)), "cc_db_query_submit_ranked")
             return res, (rc_, rn_)
@@ -482,11 +514,13 @@ class Database:
         _chk(lib().cc_db_add_packed(self.h, hot.data_ptr(), feat.data_ptr(), n, ts.ctypes.data, seeds.ctypes.data, stream),
              "cc_db_add_packed")
 
-    def check_hints(self, qdesc, hints, lb=None, ub=None, max_fine_opt=10, ranked=None):
+    def check_hints(self, qdesc, hints, lb=None, ub=None, max_fine_opt=10, ranked=None, detail=False):
         """CandidateManager driven by explicit hints (checkCandWithHint in the given order, tidyUpCandidates, fineOptimize).
         qdesc: torch uint8 CUDA [DESC_BYTES] of the query scan; hints: array of L.hint_dt (cand_gidx = DB index).
-        Returns (cc_query_result_t record, per-hint L.hint_score_dt array); with ranked=K followed by (cands [1, K], counts [1])."""
+        Returns (cc_query_result_t record, per-hint L.hint_score_dt array); with ranked=K followed by (cands [1, K], counts [1]),
+        and with detail=True by the [1, K] detail array (see query())."""
         import torch
+        det = self._detail_args(1, ranked, detail)
         if lb is None:
             lb, ub = L.default_thresholds()
         hints = np.ascontiguousarray(hints, L.hint_dt)
@@ -497,6 +531,11 @@ class Database:
         stream = torch.cuda.current_stream(qdesc.device).cuda_stream
         if ranked is not None:
             rc_, rn_, ro = L.rank_buffers(1, ranked)
+            if det is not None:
+                _chk(lib().cc_db_check_hints_ranked_detail(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
+                                                           int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream, C.addressof(ro), det.ctypes.data),
+                     "cc_db_check_hints_ranked_detail")
+                return res[0], sc, (rc_, rn_), det
             _chk(lib().cc_db_check_hints_ranked(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
                                                 int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream, C.addressof(ro)),
                  "cc_db_check_hints_ranked")
@@ -537,7 +576,7 @@ class Database:
         return tab, qidx, cfg, lb, ub
 
     def verify(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
-               want_hints=False, allow_flagged=False, ranked=None):
+               want_hints=False, allow_flagged=False, ranked=None, detail=False):
         """Score candidates the caller proposes, in one batch (cc_db_verify_batch).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES];
         cands: int array [n, <= 8] padded with -1, or a list of lists of DB indices; item i is descriptor qidx[i] (None: i)
         against cands[i].  The hint list of an item is generated on the device: every (candidate, level, candidate anchor,
@@ -546,9 +585,11 @@ class Database:
         of hints), plus a list of L.hint_dt arrays, one per item, when want_hints is set.  allow_flagged: as for query().
         ranked=K: followed by (cands [n, K] of L.ranked_cand_dt, counts [n]) -- every refined candidate of an item, best first
         (cc_db_verify_submit_ranked), instead of one item per (query, candidate) pair.  Like query(ranked=K) it is the submit
-        followed by the wait, so a large batch is chunked by the streamed rule (whole chunks), not one chunk per lane."""
+        followed by the wait, so a large batch is chunked by the streamed rule (whole chunks), not one chunk per lane.
+        detail=True (with ranked=K): followed by the [n, K] detail array as well (see query())."""
         import torch
         tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
+        det = self._detail_args(len(tab), ranked, detail)
         n = len(tab)
         res = np.zeros(n, L.query_result_dt)
         d_h = d_n = None
@@ -566,10 +607,11 @@ class Database:
         else:
             rc_, rn_, ro = L.rank_buffers(n, ranked)
             rk = (rc_, rn_)
-            self._ranked_call(lib().cc_db_verify_submit_ranked, "cc_db_verify_submit_ranked", tol, self.h, qdesc.data_ptr(), qdesc.shape[0],
+            fn = "cc_db_verify_submit_ranked" + ("_detail" if det is not None else "")
+            self._ranked_call(getattr(lib(), fn), fn, tol, self.h, qdesc.data_ptr(), qdesc.shape[0],
                               qidx.ctypes.data if qidx is not None else None, tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub),
                               res.ctypes.data, d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream,
-                              C.addressof(ro))
+                              C.addressof(ro), *(() if det is None else (det.ctypes.data,)))
         out = (res,)
         if want_hints:
             cnt = d_n.cpu().numpy()
@@ -577,15 +619,18 @@ class Database:
             out += ([allh[i, :cnt[i]].copy() for i in range(n)],)
         if rk is not None:
             out += (rk,)
+        if det is not None:
+            out += (det,)
         return out if len(out) > 1 else res
 
     def verify_submit(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
-                      ranked=None):
+                      ranked=None, detail=False):
         """Asynchronous form of verify(): queues the batch and returns the result array, which is only valid after query_wait()
         (cc_db_verify_submit; verify and query chunks share the lanes and are collected together).  ranked=K: returns
-        (results, (cands [n, K], counts [n]))."""
+        (results, (cands [n, K], counts [n])), with detail=True followed by the [n, K] detail array."""
         import torch
         tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
+        det = self._detail_args(len(tab), ranked, detail)
         res = np.zeros(len(tab), L.query_result_dt)
         self._pending = getattr(self, "_pending", [])
         self._pending.append(res)  # the library writes into it until query_wait
@@ -593,6 +638,13 @@ class Database:
         if ranked is not None:
             rc_, rn_, ro = L.rank_buffers(len(tab), ranked)
             self._pending.append((rc_, rn_))
+            if det is not None:
+                self._pending.append(det)
+                _chk(lib().cc_db_verify_submit_ranked_detail(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
+                                                             tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub),
+                                                             res.ctypes.data, None, None, stream, C.addressof(ro), det.ctypes.data),
+                     "cc_db_verify_submit_ranked_detail")
+                return res, (rc_, rn_), det
             _chk(lib().cc_db_verify_submit_ranked(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
                                                   tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
                                                   None, None, stream, C.addressof(ro)), "cc_db_verify_submit_ranked")

@@ -129,6 +129,11 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   cc_ranked_cand_t *h_rank = nullptr; // the same, pinned: copied out beside h_results (small chunks: written by the kernel)
   cc_rank_out_t rank_dst = {nullptr, nullptr, 0, 0};  // where the chunk's lists go when it is collected (h_cands NULL: not a ranked chunk)
   int rank_mfo = 0;                   // the chunk's max_fine_opt (the counts are min(max_ret, max_fine_opt, n_cand_tidy))
+  // detail chunks (the *_ranked_detail entry points), allocated with the first one
+  cc_gmm_hess *d_hess = nullptr;            // [prob_cap] cc_k_gmm_hess's record per refined problem
+  cc_ranked_detail_t *d_detail = nullptr;   // [QB * CC_RANK_MAX] cc_k_final_rd's rows, beside d_rank
+  cc_ranked_detail_t *h_detail = nullptr;   // the same, pinned (small chunks: written by the kernel)
+  cc_ranked_detail_t *detail_dst = nullptr; // where the chunk's detail rows go when it is collected (nullptr: not a detail chunk)
 };
 
 struct cc_db {
@@ -291,6 +296,9 @@ static void db_free(cc_db *db) {
     if (ln.h_vin) hipHostFree(ln.h_vin);
     hipFree(ln.d_rank);
     if (ln.h_rank) hipHostFree(ln.h_rank);
+    hipFree(ln.d_hess);
+    hipFree(ln.d_detail);
+    if (ln.h_detail) hipHostFree(ln.h_detail);
     if (ln.done) hipEventDestroy(ln.done);
     if (ln.prep) hipEventDestroy(ln.prep);
     if (ln.fin) hipEventDestroy(ln.fin);
@@ -379,6 +387,39 @@ static int lane_alloc_rank(cc_qlane &ln) {
 }
 static int rank_validate(const cc_rank_out_t *rank, const char *what) {
   if (!rank || !rank->h_cands || !rank->h_n || rank->max_ret < 1 || rank->max_ret > CC_RANK_MAX) return set_err(CC_EINVAL, what);
+  return CC_OK;
+}
+// the buffers of a lane's detail chunks (2 x 1.9 MB and the Hessian records, 72 B per problem slot), allocated with the lane's
+// first one (after lane_alloc: prob_cap is known)
+static int lane_alloc_detail(cc_qlane &ln) {
+  if (ln.d_detail && ln.d_hess) return CC_OK;
+  if (ln.prob_cap <= 0) return set_err(CC_EHIP, "lane_alloc_detail: the lane has no problem buffers");
+  const size_t bytes = sizeof(cc_ranked_detail_t) * (size_t)cc_db::QB * CC_RANK_MAX;
+  if (!ln.h_detail) {
+    const hipError_t e = hipHostMalloc((void **)&ln.h_detail, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      ln.h_detail = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_detail: hipHostMalloc", e);
+    }
+  }
+  if (!ln.d_hess) {
+    const hipError_t e = hipMalloc(&ln.d_hess, sizeof(cc_gmm_hess) * (size_t)ln.prob_cap);
+    if (e != hipSuccess) {
+      ln.d_hess = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_detail: hipMalloc", e);
+    }
+  }
+  if (!ln.d_detail) {
+    const hipError_t e = hipMalloc(&ln.d_detail, bytes);
+    if (e != hipSuccess) {
+      ln.d_detail = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_detail: hipMalloc", e);
+    }
+  }
+  return CC_OK;
+}
+static int detail_validate(const cc_ranked_detail_t *h_detail, const char *what) {
+  if (!h_detail) return set_err(CC_EINVAL, what);
   return CC_OK;
 }
 // a collected chunk's lists: rows [b0, b0 + nb) of the caller's arrays
@@ -1062,7 +1103,8 @@ static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q,
 // km: hits per search in ln.d_hits (db->kmax for queries; CC_KNN_MAX for the hint flow): picks the kernel instances.
 static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_params &CP, const cc_score_t *lb, const cc_score_t *ub,
                                 int max_fine_opt, hipEvent_t *ev, int *d_scores, bool zc /*results and counters straight into the lane's pinned host buffers*/,
-                                int km, int max_ret = 0 /*> 0: a ranked chunk (cc_k_final_r writes the lists to the lane's rank buffer)*/) {
+                                int km, int max_ret = 0 /*> 0: a ranked chunk (cc_k_final_r writes the lists to the lane's rank buffer)*/,
+                                bool detail = false /*with max_ret > 0: cc_k_gmm_hess behind the refinement, cc_k_final_rd writes the detail rows as well*/) {
   hipStream_t ls = ln.stream;
   const bool lg = km != CC_KNN_MAX;
   // dynamic thresholds (the mode at submission): the stages leave their scores in the pass records, cc_k_check_dyn replays the
@@ -1110,8 +1152,19 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
                      (const int *)(ln.d_nprob + 1), (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, lb->correlation,
                      ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
                      (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
+  if (detail)  // the curvature at the refined poses, over the three lists cc_k_select filled (only in chains that asked for it)
+    hipLaunchKernelGGL(cc_k_gmm_hess, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1), (const int *)ln.d_sel,
+                       (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap), (const int *)(ln.d_nprob + 2),
+                       (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap, (const cc_gmm_feat *)ln.d_qfeat,
+                       (const cc_gmm_feat *)db->d_feat, (const cc_gmm_result *)ln.d_gres, (const unsigned *)ln.d_codes, ln.d_hess);
   if (ev) HIPCHK(hipEventRecord(ev[4], ls));
-  if (max_ret > 0) {  // the ranked instance replaces the plain one; a chain without `rank` launches what it always launched
+  if (max_ret > 0 && detail) {
+    hipLaunchKernelGGL(lg ? (dyn ? cc_k_final_rdl<true> : cc_k_final_rdl<false>) : (dyn ? cc_k_final_rd<true> : cc_k_final_rd<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
+                       (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
+                       (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
+                       zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy, zc ? ln.h_rank : ln.d_rank, max_ret, (const cc_gmm_hess *)ln.d_hess,
+                       (const cc_gmm_problem *)ln.d_prob, zc ? ln.h_detail : ln.d_detail);
+  } else if (max_ret > 0) {  // the ranked instance replaces the plain one; a chain without `rank` launches what it always launched
     hipLaunchKernelGGL(lg ? (dyn ? cc_k_final_rl<true> : cc_k_final_rl<false>) : (dyn ? cc_k_final_r<true> : cc_k_final_r<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
                        (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, (const int *)ln.d_pass_cnt,
                        (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
@@ -1144,6 +1197,8 @@ static int lane_finish(cc_db *db, cc_qlane &ln) {
   HIPCHK(hipStreamSynchronize(ln.stream));
   memcpy(ln.h_dst + ln.b0, ln.h_results, sizeof(cc_query_result_t) * ln.nb);
   if (ln.rank_dst.h_cands) rank_deliver(ln, ln.rank_dst, ln.b0, ln.nb, ln.rank_mfo);
+  if (ln.detail_dst)
+    memcpy(ln.detail_dst + (size_t)ln.b0 * ln.rank_dst.max_ret, ln.h_detail, sizeof(cc_ranked_detail_t) * (size_t)ln.nb * ln.rank_dst.max_ret);
   if (ln.profiled) {
     float t[5];
     for (int k = 0; k < 5; k++) hipEventElapsedTime(&t[k], ln.pev[k], ln.pev[k + 1]);
@@ -1199,7 +1254,8 @@ int cc_db_query_collect(cc_db *db, const cc_query_result_t *h_res, int n) {
 // rank: where the chunks' ranked lists go (the *_ranked entry points, validated there), or nullptr: the plain call
 static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                              const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
-                             const cc_rank_out_t *rank) {
+                             const cc_rank_out_t *rank,
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
   if (!db || !d_qdesc || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch");
   if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch: thresholds must satisfy lb.strictSmaller(ub)");
@@ -1275,6 +1331,10 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
       rc = lane_alloc_rank(ln);
       if (rc != CC_OK) break;
     }
+    if (detail) {
+      rc = lane_alloc_detail(ln);
+      if (rc != CC_OK) break;
+    }
     hipStream_t ls = ln.stream;
     bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
     for (int i = 0; i < nb; i++) {
@@ -1335,7 +1395,7 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
                          ln.d_hits, ln.d_hit_cnt);
     }
     if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc, db->kmax, rank ? rank->max_ret : 0);
+    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc, db->kmax, rank ? rank->max_ret : 0, detail != nullptr);
     if (rc != CC_OK) {
       lane_abort(db, ln);
       break;
@@ -1346,6 +1406,7 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
       LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
       LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
       if (rank) LANE_CHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
+      if (detail) LANE_CHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
     }
     LANE_CHK(hipEventRecord(ln.fin, ls));
     for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];
@@ -1354,6 +1415,7 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
     ln.nb = nb;
     ln.h_dst = h_res;
     ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
+    ln.detail_dst = detail;
     ln.rank_mfo = db->cfg.max_fine_opt;
   }
 #undef LANE_CHK
@@ -1362,14 +1424,22 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
 
 int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                        const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_) {
-  return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, nullptr);
+  return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, nullptr, nullptr);
 }
 int cc_db_query_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                               const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
                               const cc_rank_out_t *rank) {
   const int vrc = rank_validate(rank, "cc_db_query_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
   if (vrc != CC_OK) return vrc;
-  return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank);
+  return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, nullptr);
+}
+int cc_db_query_submit_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                     const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  const int vrc = rank_validate(rank, "cc_db_query_submit_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  const int drc = detail_validate(h_detail, "cc_db_query_submit_ranked_detail: h_detail must be given");
+  if (drc != CC_OK) return drc;
+  return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail);
 }
 
 int cc_db_query_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
@@ -1404,7 +1474,8 @@ int cc_db_add_scans_host(cc_db *db, const cc_scan_desc_t *h_desc, int n, const d
 
 // rank: as for query_submit_impl.  The ranked form refuses what the chain would refuse before the descriptors are staged.
 static int query_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
-                                 const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
+                                 const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank,
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
   if (!db || !h_qdesc || nq < 0 || !h_epoch || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch_host: bad argument");
   if (rank) {
     if (!lb || !ub) return set_err(CC_EINVAL, "cc_db_query_batch_host_ranked: bad argument");
@@ -1419,20 +1490,28 @@ static int query_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int n
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)nq, hipMemcpyHostToDevice));
   if (!rank) return cc_db_query_batch(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr);
   db->sync_call = true;  // cc_db_query_batch's body with the lists
-  rc = query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank);
+  rc = query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail);
   db->sync_call = false;
   const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
   return rc != CC_OK ? rc : r2;
 }
 int cc_db_query_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                            const cc_score_t *ub, cc_query_result_t *h_res) {
-  return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, nullptr);
+  return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, nullptr, nullptr);
 }
 int cc_db_query_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                                   const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
   const int vrc = rank_validate(rank, "cc_db_query_batch_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
   if (vrc != CC_OK) return vrc;
-  return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank);
+  return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank, nullptr);
+}
+int cc_db_query_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                         const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  const int vrc = rank_validate(rank, "cc_db_query_batch_host_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  const int drc = detail_validate(h_detail, "cc_db_query_batch_host_ranked_detail: h_detail must be given");
+  if (drc != CC_OK) return drc;
+  return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank, h_detail);
 }
 
 // The per-scan loop on a scan that is still on the device (cc_scan_ingest): the launches follow the scan's ingest on the
@@ -1533,7 +1612,8 @@ int cc_db_add_scan_batch(cc_db *db, cc_scan *const *scans, int n, const double *
 }
 
 static int query_scan_batch_submit_impl(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
-                                        const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
+                                        const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank,
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
   if (!db || !scans || n < 1 || n > CC_SCAN_BATCH_MAX || !h_epoch || !lb || !ub || !h_res)
     return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit: bad argument (1..CC_SCAN_BATCH_MAX scans)");
   DB_POISON_CHK(db, "cc_db_query_scan_batch_submit");
@@ -1542,11 +1622,11 @@ static int query_scan_batch_submit_impl(cc_db *db, cc_scan *const *scans, int n,
   const cc_scan_desc_t *d = nullptr;
   const int rc = gather_handles(db, scans, n, 1, "cc_db_query_scan_batch_submit: null scan handle", &d);
   if (rc != CC_OK) return rc;
-  return query_submit_impl(db, d, n, h_epoch, lb, ub, h_res, nullptr, nullptr, db->ctx->s_loop, rank);
+  return query_submit_impl(db, d, n, h_epoch, lb, ub, h_res, nullptr, nullptr, db->ctx->s_loop, rank, detail);
 }
 int cc_db_query_scan_batch_submit(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
                                   const cc_score_t *ub, cc_query_result_t *h_res) {
-  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, nullptr);
+  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, nullptr, nullptr);
 }
 int cc_db_query_scan_batch_submit_ranked(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
                                          const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
@@ -1554,7 +1634,17 @@ int cc_db_query_scan_batch_submit_ranked(cc_db *db, cc_scan *const *scans, int n
   if (vrc != CC_OK) return vrc;
   if (lb && ub && !thres_strict_smaller(lb, ub))  // (before the handles are gathered: a refused call queues nothing)
     return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit_ranked: thresholds must satisfy lb.strictSmaller(ub)");
-  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, rank);
+  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, rank, nullptr);
+}
+int cc_db_query_scan_batch_submit_ranked_detail(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
+                                                const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  const int vrc = rank_validate(rank, "cc_db_query_scan_batch_submit_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  const int drc = detail_validate(h_detail, "cc_db_query_scan_batch_submit_ranked_detail: h_detail must be given");
+  if (drc != CC_OK) return drc;
+  if (lb && ub && !thres_strict_smaller(lb, ub))  // (before the handles are gathered: a refused call queues nothing)
+    return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit_ranked_detail: thresholds must satisfy lb.strictSmaller(ub)");
+  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, rank, h_detail);
 }
 
 int cc_db_add_scan_host(cc_db *db, const cc_scan_desc_t *h_desc, double ts, int32_t seed) {
@@ -1571,7 +1661,8 @@ int cc_db_query_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_score_t 
 // query whose check table is the caller's hint list, in the caller's order, instead of the KNN result.
 static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                             const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_,
-                            const cc_rank_out_t *rank) {
+                            const cc_rank_out_t *rank,
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
   if (!db || !d_qdesc || n_hints < 0 || (n_hints > 0 && !h_hints) || !lb || !ub || !h_res || max_fine_opt < 1)
     return set_err(CC_EINVAL, "cc_db_check_hints: bad argument");
   DB_POISON_CHK(db, "cc_db_check_hints");
@@ -1609,6 +1700,10 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
     const int arc = lane_alloc_rank(ln);
     if (arc != CC_OK) return arc;
   }
+  if (detail) {
+    const int arc = lane_alloc_detail(ln);
+    if (arc != CC_OK) return arc;
+  }
   HIPCHK(hipEventRecord(ln.done, stream));  // start after what the caller queued
   HIPCHK(hipStreamWaitEvent(ln.stream, ln.done, 0));
   if (db->add_done) HIPCHK(hipStreamWaitEvent(ln.stream, db->add_done, 0));  // ... and after the last append, whatever stream it used
@@ -1632,19 +1727,21 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
       if (h_hints[i].seq_tgt >= ql.n_cont[h_hints[i].level - 1])
         return set_err(CC_EINVAL, "cc_db_check_hints: hint names a contour of the query scan that does not exist");
   }
-  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false, CC_KNN_MAX, rank ? rank->max_ret : 0);  // any database: 64-stride
+  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr);  // any database: 64-stride
   if (rc != CC_OK) return rc;
   std::vector<int> sc((size_t)CC_CHK_STRIDE * CC_NSCORE);
   std::vector<unsigned char> ok(CC_CHK_STRIDE);
   HIPCHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ln.stream));
   if (rank) HIPCHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)rank->max_ret, hipMemcpyDeviceToHost, ln.stream));
+  if (detail) HIPCHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)rank->max_ret, hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(sc.data(), db->d_hint_scores, sizeof(int) * sc.size(), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(ok.data(), ln.d_pass_ok, ok.size(), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipStreamSynchronize(ln.stream));
   rc = chunk_status(ln, 1);  // CC_ECAPACITY: the result and the scores are delivered all the same (flags says what was hit)
   *h_res = ln.h_results[0];
   if (rank) rank_deliver(ln, *rank, 0, 1, max_fine_opt);
+  if (detail) memcpy(detail, ln.h_detail, sizeof(cc_ranked_detail_t) * (size_t)rank->max_ret);
   if (h_scores)
     for (int i = 0; i < n_hints; i++) {
       const int *p = &sc[(size_t)i * CC_NSCORE];
@@ -1660,14 +1757,22 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
 
 int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                       const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_) {
-  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, nullptr);
+  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, nullptr, nullptr);
 }
 int cc_db_check_hints_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                              const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_,
                              const cc_rank_out_t *rank) {
   const int vrc = rank_validate(rank, "cc_db_check_hints_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
   if (vrc != CC_OK) return vrc;
-  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, rank);
+  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, rank, nullptr);
+}
+int cc_db_check_hints_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                                    const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  const int vrc = rank_validate(rank, "cc_db_check_hints_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  const int drc = detail_validate(h_detail, "cc_db_check_hints_ranked_detail: h_detail must be given");
+  if (drc != CC_OK) return drc;
+  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, rank, h_detail);
 }
 
 int cc_db_debug_passes(cc_db *db, cc_pass_dbg_t *h_out, int cap, int *n_out) {
@@ -1695,24 +1800,33 @@ int cc_db_debug_passes(cc_db *db, cc_pass_dbg_t *h_out, int cap, int *n_out) {
 
 static int check_hints_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                  const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
-                                 const cc_rank_out_t *rank) {
+                                 const cc_rank_out_t *rank,
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
   if (!db || !h_qdesc) return set_err(CC_EINVAL, "cc_db_check_hints_host: bad argument");
   HIPCHK(hipSetDevice(db->device));
   int rc = stage_reserve(db, 1);
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t), hipMemcpyHostToDevice));
-  return check_hints_impl(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr, rank);
+  return check_hints_impl(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr, rank, detail);
 }
 int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                            const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores) {
-  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr);
+  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr, nullptr);
 }
 int cc_db_check_hints_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                   const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
                                   const cc_rank_out_t *rank) {
   const int vrc = rank_validate(rank, "cc_db_check_hints_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
   if (vrc != CC_OK) return vrc;
-  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank);
+  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank, nullptr);
+}
+int cc_db_check_hints_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                                         const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  const int vrc = rank_validate(rank, "cc_db_check_hints_host_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  const int drc = detail_validate(h_detail, "cc_db_check_hints_host_ranked_detail: h_detail must be given");
+  if (drc != CC_OK) return drc;
+  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank, h_detail);
 }
 
 // ---- verification of caller-proposed candidates (k_verify.h) ----
@@ -1748,7 +1862,8 @@ static int verify_validate(const cc_db *db, const cc_scan_desc_t *d_qdesc, int n
 
 static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                               const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
-                              cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank) {
+                              cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank,
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
   {  // everything that can be refused is refused before anything is queued or collected
     const int vrc = verify_validate(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
     if (vrc != CC_OK) return vrc;
@@ -1798,6 +1913,10 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
       rc = lane_alloc_rank(ln);
       if (rc != CC_OK) break;
     }
+    if (detail) {
+      rc = lane_alloc_detail(ln);
+      if (rc != CC_OK) break;
+    }
     if (db->dyn_thres) {
       rc = lane_alloc_dyn(ln);
       if (rc != CC_OK) break;
@@ -1823,7 +1942,7 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
                        (const int *)(ln.d_vin + nb), nb, ln.d_hits, ln.d_hit_cnt, d_hints ? d_hints + (size_t)b0 * CC_HINT_MAX : (cc_hint_t *)nullptr,
                        d_n_hints ? d_n_hints + b0 : (int32_t *)nullptr);
     if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, cfg->max_fine_opt, ev, nullptr, zc, CC_KNN_MAX, rank ? rank->max_ret : 0);
+    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, cfg->max_fine_opt, ev, nullptr, zc, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr);
     if (rc != CC_OK) {
       lane_abort(db, ln);
       break;
@@ -1832,6 +1951,7 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
       LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
       LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
       if (rank) LANE_CHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
+      if (detail) LANE_CHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
     }
     LANE_CHK(hipEventRecord(ln.fin, ls));
     for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];  // (a verify chunk reads no sorted view: nothing for an append to wait for beyond this)
@@ -1840,6 +1960,7 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
     ln.nb = nb;
     ln.h_dst = h_res;
     ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
+    ln.detail_dst = detail;
     ln.rank_mfo = cfg->max_fine_opt;
   }
 #undef LANE_CHK
@@ -1848,14 +1969,23 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
 int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                         const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                         cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_) {
-  return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, nullptr);
+  return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, nullptr, nullptr);
 }
 int cc_db_verify_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                                cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank) {
   const int vrc = rank_validate(rank, "cc_db_verify_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
   if (vrc != CC_OK) return vrc;
-  return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank);
+  return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank, nullptr);
+}
+int cc_db_verify_submit_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                                      const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                                      cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  const int vrc = rank_validate(rank, "cc_db_verify_submit_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  const int drc = detail_validate(h_detail, "cc_db_verify_submit_ranked_detail: h_detail must be given");
+  if (drc != CC_OK) return drc;
+  return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank, h_detail);
 }
 
 int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
@@ -1874,7 +2004,8 @@ int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, con
 
 static int verify_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                   const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
-                                  const cc_rank_out_t *rank) {
+                                  const cc_rank_out_t *rank,
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
   {
     const int vrc = verify_validate(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
     if (vrc != CC_OK) return vrc;
@@ -1886,19 +2017,27 @@ static int verify_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int 
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)n_desc, hipMemcpyHostToDevice));
   if (!rank) return cc_db_verify_batch(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr);
   db->sync_call = true;
-  rc = verify_submit_impl(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr, rank);
+  rc = verify_submit_impl(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail);
   db->sync_call = false;
   const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
   return rc != CC_OK ? rc : r2;
 }
 int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                             const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res) {
-  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr);
+  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr);
 }
 int cc_db_verify_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                    const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                                    const cc_rank_out_t *rank) {
   const int vrc = rank_validate(rank, "cc_db_verify_batch_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
   if (vrc != CC_OK) return vrc;
-  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank);
+  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank, nullptr);
+}
+int cc_db_verify_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                                          const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  const int vrc = rank_validate(rank, "cc_db_verify_batch_host_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  if (vrc != CC_OK) return vrc;
+  const int drc = detail_validate(h_detail, "cc_db_verify_batch_host_ranked_detail: h_detail must be given");
+  if (drc != CC_OK) return drc;
+  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank, h_detail);
 }

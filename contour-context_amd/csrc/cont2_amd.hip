@@ -27,6 +27,7 @@
 #include "k_check.h"
 #include "k_merge.h"
 #include "k_gmm.h"
+#include "k_gmm_hess.h"
 #include "k_verify.h"
 #include "cc_hostdb.h"
 
@@ -822,6 +823,22 @@ void cc_est_sens_tf(const double tf_bev[3], int n_row, int n_col, double tf_sens
   tf_sens[0] = c * ox - s * oy + tf_bev[0] - ox;
   tf_sens[1] = s * ox + c * oy + tf_bev[1] - oy;
   tf_sens[2] = tf_bev[2];
+}
+
+void cc_est_sens_info(const double hess_bev[6], const double tf_bev[3], int n_row, int n_col, double hess_sens[6]) {
+  // J = [1 0 a; 0 1 b; 0 0 1] with (a, b) = dR/dtheta * (ox, oy), so J^-1 = [1 0 -a; 0 1 -b; 0 0 1] and J^-T H J^-1 keeps the
+  // translation block, shifts the theta column by -(H_xx a + H_xy b, H_xy a + H_yy b) and the corner accordingly
+  const double ox = n_row / 2 - 0.5, oy = n_col / 2 - 0.5;
+  const double c = cos(tf_bev[2]), s = sin(tf_bev[2]);
+  const double a = -s * ox - c * oy, b = c * ox - s * oy;
+  const double xx = hess_bev[0], xy = hess_bev[1], xt = hess_bev[2], yy = hess_bev[3], yt = hess_bev[4], tt = hess_bev[5];
+  const double nxt = xt - (xx * a + xy * b), nyt = yt - (xy * a + yy * b);
+  hess_sens[0] = xx;
+  hess_sens[1] = xy;
+  hess_sens[2] = nxt;
+  hess_sens[3] = yy;
+  hess_sens[4] = nyt;
+  hess_sens[5] = tt - a * xt - b * yt - a * nxt - b * nyt;
 }
 
 // ------------------------------------------------------------------------------------------ per-scan loop

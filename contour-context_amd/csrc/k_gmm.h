@@ -10,7 +10,8 @@
 //                    reads the problem's codes and files a 56-byte record per pair (the first CC_GMM_NL in LDS, the rest in
 //                    the pair pool, unit by unit), every further evaluation streams those records.
 //                    Two instances: 16 lanes per problem (4 problems per wave) and 64 lanes for the long pair lists.
-//   cc_k_final       tidyUp compaction, fineOptimize ordering, result record (cc_k_final_r: and the ranked list of the refined ones)
+//   cc_k_final       tidyUp compaction, fineOptimize ordering, result record (cc_k_final_r: and the ranked list of the refined ones;
+//                    cc_k_final_rd: and their curvature / refinement detail, from cc_k_gmm_hess in k_gmm_hess.h)
 // The ellipse tables are read where they lie; the two pools are sized per query lane (cc_db_api.inc) and running out of
 // either is reported (CC_ECAPACITY), never a shorter pair list.
 #pragma once
@@ -68,6 +69,13 @@ struct cc_gmm_result {
                    // bit2: contour table truncated (CC_MAXC)
   int n_pairs;     // selected (src, tgt) ellipse pairs
   int code_seg;    // first segment of the problem's pair-code list in the chunk's code pool (cc_k_gmm_init), -1: none
+};
+
+// What cc_k_gmm_hess (k_gmm_hess.h) leaves per refined problem for the detail instances of cc_k_final: gradient and Hessian
+// (xx, xy, xt, yy, yt, tt) of f = -correlation at tf_opt.
+struct cc_gmm_hess {
+  double grad[3];
+  double hess[6];
 };
 
 struct cc_ell {  // values are f32 in the reference too (getManualCov, pos_mean_, cell_cnt_), widened to f64 at use
@@ -1718,13 +1726,16 @@ cc_k_select_l(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__rest
 // RANK (the _r instances): the first min(max_ret, pre) entries of the re-sorted list go to rank_out[q][max_ret] as well -- what
 // fineOptimize would return with ret_size = max_ret (contour_db.h:630-648); the rest of the row is zeroed.
 // ------------------------------------------------------------------------------------------------
-template <bool DYN, int KM, bool RANK = false>
+// DETAIL (the _rd instances, with RANK): lane k of the list also writes entry k's cc_ranked_detail_t -- the Hessian record of its
+// problem (cc_k_gmm_hess), the problem's cc_gmm_result and its initial pose; the rest of that row is zeroed as well.
+template <bool DYN, int KM, bool RANK = false, bool DETAIL = false>
 __device__ __forceinline__ void cc_final_body(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *cands_all, const cc_qstate *qstate,
                                               const cc_gmm_result *gres, const int *pass_cnt, const int *hit_cnt,
                                               const cc_hot_desc_t *qhot, cc_query_result_t *out, const unsigned short *perm_tab,
                                               const int *nprob /*the chunk's problem counters and pool head*/, int *nprob_host /*or nullptr: copy them there*/,
                                               const unsigned char *tidy /*DYN only*/, cc_ranked_cand_t *rank_out = nullptr /*RANK only: [nq][max_ret]*/,
-                                              int max_ret = 0 /*RANK only: 1..CC_RANK_MAX*/) {
+                                              int max_ret = 0 /*RANK only: 1..CC_RANK_MAX*/, const cc_gmm_hess *hess = nullptr /*DETAIL only: [problem slot]*/,
+                                              const cc_gmm_problem *probs = nullptr /*DETAIL only*/, cc_ranked_detail_t *det_out = nullptr /*DETAIL only: [nq][max_ret]*/) {
   // one wave per query: lanes fetch the per-candidate inputs and order the candidates in parallel (cc_tidy_order), lane 0
   // replays the short order-dependent rest on LDS
   __shared__ unsigned short idx[CC_CHK_STRIDE_K(KM)];
@@ -1828,6 +1839,30 @@ __device__ __forceinline__ void cc_final_body(int nq, float corr_lb, int max_fin
         e.tf[2] = atan2(sin(t2), cos(t2));
       }
       rank_out[(size_t)q * max_ret + lane] = e;
+      if constexpr (DETAIL) {
+        cc_ranked_detail_t d;
+        for (int j = 0; j < 6; j++) d.hess[j] = 0;
+        for (int j = 0; j < 3; j++) d.grad[j] = d.tf_init[j] = 0;
+        d.corr_init = 0;
+        d.iterations = d.termination = d.n_pairs = d.flags = 0;
+        if (lane < ret) {
+          const int g = gm[idx[lane]];
+          const cc_gmm_hess h = hess[g];
+          const cc_gmm_result *r = &gres[g];
+          const cc_gmm_problem *pb = &probs[g];
+          for (int j = 0; j < 6; j++) d.hess[j] = h.hess[j];
+          for (int j = 0; j < 3; j++) {
+            d.grad[j] = h.grad[j];
+            d.tf_init[j] = pb->tf[j];
+          }
+          d.corr_init = r->corr_init;
+          d.iterations = r->iterations;
+          d.termination = r->termination;
+          d.n_pairs = r->n_pairs;
+          d.flags = e.flags;
+        }
+        det_out[(size_t)q * max_ret + lane] = d;
+      }
     }
     return;
   }
@@ -1871,4 +1906,27 @@ cc_k_final_rl(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__rest
               const int *__restrict__ nprob, int *__restrict__ nprob_host, const unsigned char *__restrict__ tidy /*DYN only*/,
               cc_ranked_cand_t *__restrict__ rank_out /*[nq][max_ret]*/, int max_ret) {
   cc_final_body<DYN, CC_KNN_MAX_LARGE, true>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy, rank_out, max_ret);
+}
+// the detail instances (the *_ranked_detail entry points): the ranked body, plus one cc_ranked_detail_t per entry
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_final_rd(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+              const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
+              const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
+              const int *__restrict__ nprob, int *__restrict__ nprob_host, const unsigned char *__restrict__ tidy /*DYN only*/,
+              cc_ranked_cand_t *__restrict__ rank_out /*[nq][max_ret]*/, int max_ret, const cc_gmm_hess *__restrict__ hess,
+              const cc_gmm_problem *__restrict__ probs, cc_ranked_detail_t *__restrict__ det_out /*[nq][max_ret]*/) {
+  cc_final_body<DYN, CC_KNN_MAX, true, true>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy, rank_out, max_ret,
+                                             hess, probs, det_out);
+}
+template <bool DYN>
+__global__ void __launch_bounds__(64)
+cc_k_final_rdl(int nq, float corr_lb, int max_fine_opt, const cc_cand_out *__restrict__ cands_all, const cc_qstate *__restrict__ qstate,
+               const cc_gmm_result *__restrict__ gres, const int *__restrict__ pass_cnt, const int *__restrict__ hit_cnt,
+               const cc_hot_desc_t *__restrict__ qhot, cc_query_result_t *__restrict__ out, const unsigned short *__restrict__ perm_tab,
+               const int *__restrict__ nprob, int *__restrict__ nprob_host, const unsigned char *__restrict__ tidy /*DYN only*/,
+               cc_ranked_cand_t *__restrict__ rank_out /*[nq][max_ret]*/, int max_ret, const cc_gmm_hess *__restrict__ hess,
+               const cc_gmm_problem *__restrict__ probs, cc_ranked_detail_t *__restrict__ det_out /*[nq][max_ret]*/) {
+  cc_final_body<DYN, CC_KNN_MAX_LARGE, true, true>(nq, corr_lb, max_fine_opt, cands_all, qstate, gres, pass_cnt, hit_cnt, qhot, out, perm_tab, nprob, nprob_host, tidy, rank_out, max_ret,
+                                                   hess, probs, det_out);
 }

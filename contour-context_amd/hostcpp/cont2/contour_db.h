@@ -70,8 +70,13 @@ class ContourDB {
     int max_ret = 1;                                         // setMaxReturn when the scan was queued; > 1: the batch's ranked lists
     std::shared_ptr<std::vector<cc_ranked_cand_t>> rblock;  // [batch][max_ret]
     std::shared_ptr<std::vector<int32_t>> nblock;           // [batch]
+    bool detail = false;                                    // setWantDetail when the scan was queued: the batch's detail rows
+    std::shared_ptr<std::vector<cc_ranked_detail_t>> dblock; // [batch][max_ret], travels with rblock
     cc_query_result_t *result() const { return block->data() + idx; }
   };
+  bool want_detail_ = false;  // setWantDetail: the answers go through the ranked calls' _detail forms (also with max_ret_ == 1)
+  mutable std::vector<cc_ranked_detail_t> last_details_;  // lastDetails()
+  bool rankedPath() const { return max_ret_ > 1 || want_detail_; }
   int max_ret_ = 1;  // setMaxReturn: entries queryRangedKNN / verifyCandidates hand out (fineOptimize's ret_size, contour_db.h:630)
   static constexpr int SPEC_LOW = 2;  // fewer answers than this queued ahead of the driver: a step goes out with whatever has been published
   mutable std::deque<Spec> spec_;   // scans appended ahead of the driver, oldest first (spec_[j] sits at DB index n_official + j)
@@ -218,11 +223,18 @@ class ContourDB {
       TicToc t1;
       std::shared_ptr<std::vector<cc_ranked_cand_t>> rblock;
       std::shared_ptr<std::vector<int32_t>> nblock;
-      if (max_ret_ > 1) {  // the answers carry their ranked lists
+      std::shared_ptr<std::vector<cc_ranked_detail_t>> dblock;
+      if (rankedPath()) {  // the answers carry their ranked lists (and, if wanted, the detail rows)
         rblock = std::make_shared<std::vector<cc_ranked_cand_t>>((size_t)n * max_ret_);
         nblock = std::make_shared<std::vector<int32_t>>((size_t)n);
         const cc_rank_out_t ro = {rblock->data(), nblock->data(), max_ret_, 0};
-        if (cc_db_query_scan_batch_submit_ranked(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data(), &ro) != CC_OK) die_cc();
+        if (want_detail_) {
+          dblock = std::make_shared<std::vector<cc_ranked_detail_t>>((size_t)n * max_ret_);
+          if (cc_db_query_scan_batch_submit_ranked_detail(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data(), &ro, dblock->data()) != CC_OK)
+            die_cc();
+        } else if (cc_db_query_scan_batch_submit_ranked(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data(), &ro) != CC_OK) {
+          die_cc();
+        }
       } else if (cc_db_query_scan_batch_submit(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data()) != CC_OK) {
         die_cc();
       }
@@ -241,6 +253,8 @@ class ContourDB {
         sp.max_ret = max_ret_;
         sp.rblock = rblock;
         sp.nblock = nblock;
+        sp.detail = want_detail_;
+        sp.dblock = dblock;
         spec_.push_back(std::move(sp));
       }
       pos += (size_t)n;
@@ -333,6 +347,12 @@ class ContourDB {
     max_ret_ = n;  // (answers queued with another setting are not handed out: queryRangedKNN asks again, at the official epoch)
   }
   int maxReturn() const { return max_ret_; }
+  // Mirror-only: collect, next to every candidate queryRangedKNN / verifyCandidates hands out, its cc_ranked_detail_t (curvature of
+  // -correlation at the pose, the refinement's start, initial correlation, iterations, termination, pair count): lastDetails()
+  // after the call, one row per returned candidate, in their order.  Off (the default): the calls the mirror always made.
+  void setWantDetail(bool on) { want_detail_ = on; }  // (answers queued with another setting are asked again, as for setMaxReturn)
+  bool wantDetail() const { return want_detail_; }
+  const std::vector<cc_ranked_detail_t> &lastDetails() const { return last_details_; }
 
   // contour_db.h:698-703
   void queryRangedKNN(const std::shared_ptr<const ContourManager> &q_ptr, const CandidateScoreEnsemble &thres_lb,
@@ -344,9 +364,12 @@ class ContourDB {
     ensure(*q_ptr);
     const cc_score_t lb = to_c(thres_lb), ub = to_c(thres_ub);
     cc_query_result_t r;
-    cc_ranked_cand_t rl[CC_RANK_MAX];  // the ranked list (max_ret_ > 1)
+    cc_ranked_cand_t rl[CC_RANK_MAX];  // the ranked list (rankedPath())
+    cc_ranked_detail_t dl[CC_RANK_MAX];  // ... and its detail rows (want_detail_)
     int32_t rn = 0;
     const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
+    const bool rk = rankedPath();
+    last_details_.clear();
     TicToc wall;
     if (need_rebuild_) rebuild();
     last_lb_ = lb;
@@ -354,15 +377,16 @@ class ContourDB {
     have_thres_ = true;
     cc_scan *qh = q_ptr->scanHandle();
     if (!spec_.empty() && qh && spec_.front().scan == qh && same(spec_.front().lb, lb) && same(spec_.front().ub, ub) &&
-        spec_.front().max_ret == max_ret_) {
+        spec_.front().max_ret == max_ret_ && spec_.front().detail == want_detail_) {
       // the answer was queued when the scan was published (at the epoch the database is officially in now); only ITS chain is
       // waited for, the queries queued behind it stay in flight
       collectOne(0);
       const Spec &sp = spec_.front();
       r = *sp.result();
-      if (max_ret_ > 1) {
+      if (rk) {
         rn = (*sp.nblock)[sp.idx];
         std::copy(sp.rblock->begin() + (size_t)sp.idx * max_ret_, sp.rblock->begin() + (size_t)(sp.idx + 1) * max_ret_, rl);
+        if (want_detail_) std::copy(sp.dblock->begin() + (size_t)sp.idx * max_ret_, sp.dblock->begin() + (size_t)(sp.idx + 1) * max_ret_, dl);
       }
       n_spec_hit_++;
     } else {
@@ -370,14 +394,16 @@ class ContourDB {
       const int32_t epoch = (int32_t)all_bevs_.size();  // the scans appended ahead of the driver are hidden by the epoch
       int rc;
       if (qh && cc_scan_on_device(qh)) {
-        rc = max_ret_ > 1 ? cc_db_query_scan_batch_submit_ranked(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro)
+        rc = want_detail_ ? cc_db_query_scan_batch_submit_ranked_detail(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro, dl)
+             : rk         ? cc_db_query_scan_batch_submit_ranked(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro)
                           : cc_db_query_scan_submit(db_, qh, epoch, &lb, &ub, &r);
         const int r2 = cc_db_query_wait(db_);
         for (auto &sp : spec_) sp.collected = true;
         if (rc == CC_OK) rc = r2;
       } else {  // a scan that was offloaded goes by its host copy
         collectSpec();
-        rc = max_ret_ > 1 ? cc_db_query_batch_host_ranked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro)
+        rc = want_detail_ ? cc_db_query_batch_host_ranked_detail(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro, dl)
+             : rk         ? cc_db_query_batch_host_ranked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro)
                           : cc_db_query_batch_host(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r);
       }
       if (rc != CC_OK) die_cc();  // CHECK(sim_lb.strictSmaller(sim_ub)) etc.; also CC_ECAPACITY (the reference has no capacities)
@@ -393,8 +419,9 @@ class ContourDB {
         stp.addSample("L2 opt", (ms[3] + ms[4]) * 1e-3);
       }
     }
-    if (max_ret_ > 1) {
+    if (rk) {
       for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], cand_ptrs, cand_corr, cand_tf);
+      if (want_detail_) last_details_.assign(dl, dl + rn);
     } else if (r.n_res > 0) {
       cand_ptrs.push_back(all_bevs_[r.cand_gidx]);
       cand_corr.push_back(r.correlation);
@@ -453,13 +480,17 @@ class ContourDB {
     cc_query_result_t r;
     cc_ranked_cand_t rl[CC_RANK_MAX];
     int32_t rn = 0;
+    cc_ranked_detail_t dl[CC_RANK_MAX];
     const cc_rank_out_t ro = {rl, &rn, max_ret, 0};
-    const int rc = max_ret > 1 ? cc_db_verify_batch_host_ranked(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro)
-                               : cc_db_verify_batch_host(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
+    last_details_.clear();
+    const int rc = want_detail_ ? cc_db_verify_batch_host_ranked_detail(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro, dl)
+                   : max_ret > 1 ? cc_db_verify_batch_host_ranked(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro)
+                                 : cc_db_verify_batch_host(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
     for (auto &sp : spec_) sp.collected = true;  // the synchronous call collected every chain in flight
     if (rc != CC_OK) die_cc();
-    if (max_ret > 1) {
+    if (max_ret > 1 || want_detail_) {
       for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], res_cand, res_corr, res_T);
+      if (want_detail_) last_details_.assign(dl, dl + rn);
       return rn;
     }
     if (r.n_res > 0) {
@@ -618,6 +649,8 @@ class CandidateManager {
   CandidateScoreEnsemble sim_var_;                 // the bars as they stand after the hints so far (DYNAMIC_THRES=1)
   Store *st_ = nullptr;
   std::vector<cc_hint_t> hints_;                                // cand_gidx = index into my_cands_ until the call is made
+  bool want_detail_ = false;                      // setWantDetail
+  std::vector<cc_ranked_detail_t> last_details_;  // lastDetails()
   std::vector<std::shared_ptr<const ContourManager>> my_cands_;  // this manager's candidate scans, first-appearance order
   std::map<int, int> id2local_;                                 // the reference keys candidates_ by getIntID() (contour_db.h:468-476)
   int flow_valve = 0;
@@ -702,6 +735,11 @@ class CandidateManager {
     flow_valve++;
   }
 
+  // Mirror-only: fineOptimize collects the detail rows of the candidates it returns (ContourDB::setWantDetail's counterpart for the
+  // hint flow); lastDetails() after fineOptimize, one row per returned candidate.  Off (the default): the calls made before.
+  void setWantDetail(bool on) { want_detail_ = on; }
+  const std::vector<cc_ranked_detail_t> &lastDetails() const { return last_details_; }
+
   // contour_db.h:604-648: returns the number of results (0 or 1; with max_ret > 1 -- mirror-only, the reference's ret_size is
   // hard-wired to 1 -- up to min(max_ret, max_fine_opt) refined candidates, best first)
   int fineOptimize(int max_fine_opt, std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
@@ -718,13 +756,19 @@ class CandidateManager {
     ensureMine();
     std::vector<cc_hint_t> hs(hints_);
     for (auto &h : hs) h.cand_gidx = st_->pos[my_cands_[h.cand_gidx].get()];
-    if (max_ret > 1) {
+    last_details_.clear();
+    if (max_ret > 1 || want_detail_) {
       cc_ranked_cand_t rl[CC_RANK_MAX];
+      cc_ranked_detail_t dl[CC_RANK_MAX];
       int32_t rn = 0;
       const cc_rank_out_t ro = {rl, &rn, max_ret, 0};
-      if (cc_db_check_hints_host_ranked(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r, nullptr, &ro) != CC_OK)
-        die();
+      const int rc = want_detail_ ? cc_db_check_hints_host_ranked_detail(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt,
+                                                                         &r, nullptr, &ro, dl)
+                                  : cc_db_check_hints_host_ranked(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r,
+                                                                  nullptr, &ro);
+      if (rc != CC_OK) die();
       for (int k = 0; k < rn; k++) ContourDB::pushRanked(st_->keep, rl[k], res_cand, res_corr, res_T);
+      if (want_detail_) last_details_.assign(dl, dl + rn);
       return rn;
     }
     if (cc_db_check_hints_host(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r, nullptr) != CC_OK)

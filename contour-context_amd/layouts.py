@@ -73,6 +73,24 @@ def rank_buffers(n, max_ret):
     return cands, cnt, RankOut(cands.ctypes.data, cnt.ctypes.data, int(max_ret), 0)
 
 
+# cc_ranked_detail_t (the *_ranked_detail entry points): curvature of f = -correlation at the entry's pose and what the device
+# knows about its refinement; hess = (xx, xy, xt, yy, yt, tt)
+ranked_detail_dt = np.dtype([("hess", "<f8", (6,)), ("grad", "<f8", (3,)), ("tf_init", "<f8", (3,)), ("corr_init", "<f8"),
+                             ("iterations", "<i4"), ("termination", "<i4"), ("n_pairs", "<i4"), ("flags", "<i4")], align=True)
+assert ranked_detail_dt.itemsize == 120
+
+
+def rank_detail_buffer(n, max_ret):
+    """[n, max_ret] of ranked_detail_dt: the h_detail argument of a *_ranked_detail call of n queries"""
+    return np.zeros((n, max(int(max_ret), 0)), ranked_detail_dt)
+
+
+def hess_matrix(h6):
+    """the symmetric 3 x 3 matrix of a cc_ranked_detail_t.hess (xx, xy, xt, yy, yt, tt)"""
+    h = np.asarray(h6, np.float64)
+    return np.array([[h[0], h[1], h[2]], [h[1], h[3], h[4]], [h[2], h[4], h[5]]])
+
+
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
 

@@ -653,6 +653,56 @@ int cc_db_check_hints_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, cons
                                   const cc_score_t *thres_lb, const cc_score_t *thres_ub, int max_fine_opt, cc_query_result_t *h_res,
                                   cc_hint_score_t *h_scores, const cc_rank_out_t *rank);
 
+/* ---- pose curvature and refinement detail per ranked candidate ----
+ * A ranked entry is a scan, a correlation and a pose; a pose-graph edge also needs to know in which directions that pose is
+ * pinned down (a revisit along a straight corridor scores high and is free to slide along it).  The _ranked_detail forms
+ * return, next to every ranked entry, the curvature of the objective the refinement minimised, at the pose it stopped at,
+ * and what the device knows about the refinement itself.  h_detail is [n][rank->max_ret] on the host, row i / entry k
+ * belonging to h_cands[i][k]; its rows arrive with the h_cands rows and the entries beyond h_n[i] are zeroed, exactly as
+ * there.  h_res and the ranked lists are the bytes the _ranked call returns.  Everything else is the _ranked call's;
+ * h_detail NULL is CC_EINVAL, refused before anything is queued, together with whatever the _ranked call refuses.
+ *
+ * hess is a CURVATURE, not a calibrated covariance: the second derivative of f(p) = -correlation(p), p = (x, y, theta) in
+ * BEV pixels / radians, positive definite at a proper optimum.  A back end scales it (for instance by a variance fitted on
+ * its own data) before using it as an information matrix.  The sum runs over the ellipse pairs selected at tf_init -- the
+ * set the refinement optimised over; where a capacity cut that list (flags), over the pairs the refinement summed. */
+typedef struct {
+  double hess[6];    /* xx, xy, xt, yy, yt, tt of f at the entry's tf: (d2 cost / dp2) / sqrt(auto_corr_src * auto_corr_tgt) */
+  double grad[3];    /* gradient of f at tf (what the refinement left over)                                                */
+  double tf_init[3]; /* T_init the refinement started from (anch_props_[0].T_delta_ after tidyUpCandidates)                */
+  double corr_init;  /* the correlation at tf_init                                                                         */
+  int32_t iterations, termination; /* of the L-BFGS run: ceres::Solver::Summary's iteration count and termination type     */
+  int32_t n_pairs;   /* selected (src, tgt) ellipse pairs                                                                  */
+  int32_t flags;     /* == cc_ranked_cand_t.flags of the entry                                                             */
+} cc_ranked_detail_t; /* 120 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cc_ranked_detail_t) == 120, "cc_ranked_detail_t is 120 bytes");
+#else
+_Static_assert(sizeof(cc_ranked_detail_t) == 120, "cc_ranked_detail_t is 120 bytes");
+#endif
+int cc_db_query_submit_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *thres_lb,
+                                     const cc_score_t *thres_ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt,
+                                     void *stream, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+int cc_db_query_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch,
+                                         const cc_score_t *thres_lb, const cc_score_t *thres_ub, cc_query_result_t *h_res,
+                                         const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+int cc_db_query_scan_batch_submit_ranked_detail(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *thres_lb,
+                                                const cc_score_t *thres_ub, cc_query_result_t *h_res, const cc_rank_out_t *rank,
+                                                cc_ranked_detail_t *h_detail);
+int cc_db_verify_submit_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands,
+                                      int n, const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                                      cc_query_result_t *h_res, cc_hint_t *d_hints, int32_t *d_n_hints, void *stream,
+                                      const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+int cc_db_verify_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands,
+                                          int n, const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                                          cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+int cc_db_check_hints_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints,
+                                    const cc_score_t *thres_lb, const cc_score_t *thres_ub, int max_fine_opt, cc_query_result_t *h_res,
+                                    cc_hint_score_t *h_scores, void *stream, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+int cc_db_check_hints_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints,
+                                         const cc_score_t *thres_lb, const cc_score_t *thres_ub, int max_fine_opt, cc_query_result_t *h_res,
+                                         cc_hint_score_t *h_scores, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+
 /* Parity / debug: the constellations of the LAST cc_db_check_hints[_host] call that passed all four gates, in hint
  * order: the pose getTFFromConstell returned for each (contour_mng.h:1246-1277, before any proposal merging) and the
  * constellation it was computed from, so that a test can redo the rigid fit independently (e.g. with an SVD). */
@@ -729,6 +779,10 @@ int cc_comm_destroy(cc_comm *comm);
 /* ConstellCorrelation::getEstSensTF (correlation.h:287-296): BEV-frame T_delta -> sensor
  * frame. in/out = (x, y, theta). */
 void cc_est_sens_tf(const double tf_bev[3], int n_row, int n_col, double tf_sens[3]);
+/* cc_ranked_detail_t.hess (xx, xy, xt, yy, yt, tt; BEV frame, at the pose tf_bev) for the parameters cc_est_sens_tf returns:
+ * J^-T H J^-1 with J = d tf_sens / d tf_bev (identity on the translation, theta column = dR/dtheta * (n_row/2 - 0.5, n_col/2 - 0.5)).
+ * The first-order change of variables: exact where the gradient vanishes, so use it where cc_ranked_detail_t.grad ~ 0. */
+void cc_est_sens_info(const double hess_bev[6], const double tf_bev[3], int n_row, int n_col, double hess_sens[6]);
 
 #ifdef __cplusplus
 }
