@@ -44,7 +44,8 @@ _lib = None
 # every symbol include/cont2_amd.h declares
 EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_db_cfg", "cc_default_thresholds",
            "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_ingest_points", "cc_ingest_points_host", "cc_scan_ingest_points", "cc_scan_ingest_points_batch",
-           "cc_ingest_segments", "cc_ingest_segments_host", "cc_scan_ingest_segments", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
+           "cc_ingest_segments", "cc_ingest_segments_host", "cc_scan_ingest_segments",
+           "cc_ingest_points_motion", "cc_ingest_points_motion_host", "cc_scan_ingest_points_motion", "cc_motion_knots", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
            "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_hot_ptr", "cc_db_feat_ptr", "cc_pack_scans", "cc_db_add_packed",
            "cc_packed_sizes", "cc_db_bucket_state", "cc_est_sens_tf",
            "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
@@ -80,6 +81,13 @@ def lib():
         _lib.cc_ingest_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.cc_ingest_segments_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.cc_scan_ingest_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.cc_ingest_points_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+        _lib.cc_ingest_points_motion_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]
+        _lib.cc_scan_ingest_points_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.cc_motion_knots.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]
+        _lib.cc_motion_knots.restype = None
         _lib.cc_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_destroy.argtypes = [C.c_void_p]
         _lib.cc_db_size.argtypes = [C.c_void_p]
@@ -170,6 +178,41 @@ def _scan_tf(tf, n):
     return tf
 
 
+TIME_TYPES = {"f32": L.TIME_F32, "u32": L.TIME_U32}   # names Context.ingest takes for cc_point_motion_t.time_type
+
+
+def _scan_motion(motion, t_begin, scale, knots, tf, n):
+    """The motion arguments of ingest() / ingest_host() -> (L.PointMotion, [n, 2] f32 times, [n, K * 12] f32 knots), all host.
+    t_begin: [n] f32 -- for "u32" times either a uint32 array (its bits are passed on) or the f32 that carry those bits."""
+    if tf is not None:
+        raise ValueError("motion and tf exclude each other (compose the per-scan matrix into the knots)")
+    if knots is None or t_begin is None or scale is None:
+        raise ValueError("motion needs t_begin, scale and knots")
+    time_offset, time_type = motion
+    if time_type not in TIME_TYPES:
+        raise ValueError("unknown time type %r (known: %s)" % (time_type, sorted(TIME_TYPES)))
+    knots = np.ascontiguousarray(np.asarray(knots, np.float32).reshape(len(knots), -1))
+    if knots.shape[0] != n or knots.shape[1] == 0 or knots.shape[1] % 12 != 0:
+        raise ValueError("knots must hold K 3 x 4 matrices per scan: [%d, K, 3, 4] or [%d, K, 12], got %s" % (n, n, knots.shape))
+    t_begin = np.asarray(t_begin)
+    tb = t_begin.astype(np.uint32).view(np.float32) if t_begin.dtype.kind in "ui" else t_begin.astype(np.float32)
+    tm = np.ascontiguousarray(np.stack([tb.reshape(n), np.asarray(scale, np.float32).reshape(n)], 1))
+    return L.PointMotion(int(time_offset), TIME_TYPES[time_type], knots.shape[1] // 12, 0), tm, knots
+
+
+def motion_knots(pose_begin, pose_end, ref=1.0, K=32):
+    """Knot matrices of a sweep from the poses (3 x 4 [R | p], sensor to world) at its begin and end (cc_motion_knots): knot k =
+    T(ref)^-1 T((k + 0.5) / K) with the rotation interpolated on SO(3) and the position linearly; ref in [0, 1] is the instant the
+    scan is referred to (1: the sweep's end).  Returns [K, 3, 4] f32."""
+    if K < 1:
+        raise ValueError("K must be at least 1")
+    pb = np.ascontiguousarray(np.asarray(pose_begin, np.float64).reshape(12))
+    pe = np.ascontiguousarray(np.asarray(pose_end, np.float64).reshape(12))
+    out = np.zeros((int(K), 3, 4), np.float32)
+    lib().cc_motion_knots(pb.ctypes.data, pe.ctypes.data, float(ref), int(K), out.ctypes.data)
+    return out
+
+
 def _segment_table(scans, device):
     """[[(points, layout, tf), ...], ...] -> (array of L.PointSegment, int32 [n + 1] first-segment indices).  points: contiguous CUDA
     tensors (device=True) or numpy arrays holding the records as they are; None or an empty one for a segment without points."""
@@ -256,13 +299,18 @@ class Context:
         except Exception:
             pass
 
-    def ingest(self, xyzi, offsets, out=None, debug=False, layout=None, tf=None):
+    def ingest(self, xyzi, offsets, out=None, debug=False, layout=None, tf=None, motion=None, t_begin=None, scale=None, knots=None):
         """xyzi: torch float32 CUDA tensor [total_points, 4]; offsets: int64 host array [n+1] (in points).
         layout: where x, y, z sit in a record -- None / "xyzi" (16-byte KITTI records), "xyz" (packed, 12 bytes) or a
         (stride_bytes, xyz_offset) pair; with a layout `xyzi` is any contiguous CUDA tensor holding the records (cc_ingest_points).
         tf: one row-major 3 x 4 f32 matrix per scan ([n, 3, 4] or [n, 12], host), applied to every point while it is loaded.
+        motion: (time_offset, "f32" | "u32") -- every record carries a 4-byte time word at that byte offset and every point is
+        moved by the knot matrix of its time bin (cc_ingest_points_motion): knots [n, K, 3, 4] or [n, K, 12], t_begin [n] and
+        scale [n] (bins per time unit), all host; bin = trunc(clamp((t - t_begin) * scale, 0, K - 1)).  Not together with tf.
         Returns a torch uint8 CUDA tensor [n, DESC_BYTES] (array of cc_scan_desc_t) (+ debug dict)."""
         import torch
+        if motion is None and (knots is not None or t_begin is not None or scale is not None):
+            raise ValueError("knots, t_begin and scale come with motion=(time_offset, type)")
         assert xyzi.is_cuda and xyzi.is_contiguous() and (layout is not None or xyzi.dtype == torch.float32)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(offsets) - 1
@@ -276,7 +324,13 @@ class Context:
             st = IngestDebug(dbg["bev"].data_ptr(), dbg["pix_rc"].data_ptr(), dbg["labels"].data_ptr())
             dbg_p = C.addressof(st)
         stream = torch.cuda.current_stream(xyzi.device).cuda_stream
-        if layout is None and tf is None:
+        if motion is not None:
+            lay = _point_layout(layout)
+            mo, tm, kn = _scan_motion(motion, t_begin, scale, knots, tf, n)
+            _chk(lib().cc_ingest_points_motion(self.h, xyzi.data_ptr(), C.addressof(lay) if lay is not None else None, C.addressof(mo),
+                                               offsets.ctypes.data, n, tm.ctypes.data, kn.ctypes.data, out.data_ptr(), dbg_p, stream),
+                 "cc_ingest_points_motion")
+        elif layout is None and tf is None:
             _chk(lib().cc_ingest_batch(self.h, xyzi.data_ptr(), offsets.ctypes.data, n, out.data_ptr(), dbg_p, stream),
                  "cc_ingest_batch")
         else:
@@ -328,12 +382,22 @@ class Context:
         _chk(lib().cc_pack_scans(self.h, desc.data_ptr(), n, hot.data_ptr(), feat.data_ptr(), stream), "cc_pack_scans")
         return hot, feat
 
-    def ingest_host(self, xyzi, offsets, layout=None, tf=None):
-        """Host records in, host descriptors out.  layout / tf: as for ingest(); with a layout `xyzi` is a contiguous numpy
-        array of any dtype holding the records as they are."""
+    def ingest_host(self, xyzi, offsets, layout=None, tf=None, motion=None, t_begin=None, scale=None, knots=None):
+        """Host records in, host descriptors out.  layout / tf / motion, t_begin, scale, knots: as for ingest(); with a layout
+        `xyzi` is a contiguous numpy array of any dtype holding the records as they are."""
         offsets = np.ascontiguousarray(offsets, np.int64)
         n = len(offsets) - 1
         out = np.zeros(n, L.scan_desc_dt)
+        if motion is None and (knots is not None or t_begin is not None or scale is not None):
+            raise ValueError("knots, t_begin and scale come with motion=(time_offset, type)")
+        if motion is not None:
+            lay = _point_layout(layout)
+            mo, tm, kn = _scan_motion(motion, t_begin, scale, knots, tf, n)
+            xyzi = np.ascontiguousarray(xyzi)
+            _chk(lib().cc_ingest_points_motion_host(self.h, xyzi.ctypes.data, C.addressof(lay) if lay is not None else None, C.addressof(mo),
+                                                    offsets.ctypes.data, n, tm.ctypes.data, kn.ctypes.data, out.ctypes.data, None),
+                 "cc_ingest_points_motion_host")
+            return out
         if layout is None and tf is None:
             xyzi = np.ascontiguousarray(xyzi, np.float32)
             _chk(lib().cc_ingest_host(self.h, xyzi.ctypes.data, offsets.ctypes.data, n, out.ctypes.data), "cc_ingest_host")

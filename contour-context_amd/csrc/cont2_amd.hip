@@ -69,6 +69,7 @@ struct cc_ctx {
     cc_k2_scratch *d_scr = nullptr;
     long long *d_offsets = nullptr;
     float *d_tf = nullptr;  // [cap][12]: the per-scan transforms of a call that brings some (cc_ingest_points)
+    float *d_mot = nullptr;  // a chunk's [nb][2] times, then its [nb][K][12] knots (cc_ingest_points_motion); allocated at first use
     char *d_seg = nullptr;  // a chunk's segment table (cc_ingest_segments): int scan_seg[cap + 1], then up to cap * CC_SEG_MAX cc_k1_seg; allocated at first use
     // the slow path of K2 (scans with more than CC_MAXC components on a level): queue filled by the fast launch, a few
     // workgroups with CC_NC_BIG-sized tables in global memory
@@ -192,6 +193,7 @@ static void scratch_free(cc_ctx::Scratch &S) {
   hipFree(S.d_offsets);
   hipFree(S.d_tf);
   hipFree(S.d_seg);
+  hipFree(S.d_mot);
   hipFree(S.d_bigq);
   hipFree(S.d_midq);
   if (S.h_mid_seen) hipHostFree(S.h_mid_seen);
@@ -356,6 +358,16 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
+  const int lds1_mot = (int)(((c->lds1 + 15) & ~(size_t)15) + CC_K1_MOT_LDS_BYTES);  // (the knot table sits behind the layout too)
+#define CC_K1_MOT_ATTR(STRIDE)                                                                                                                                  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot)); \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot));  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot));  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot));
+  CC_K1_MOT_ATTR(16)
+  CC_K1_MOT_ATTR(32)
+  CC_K1_MOT_ATTR(0)
+#undef CC_K1_MOT_ATTR
   if (nc > (size_t)CC_MAX_CELLS) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: grid larger than 150 x 150 cells");
@@ -451,14 +463,37 @@ struct seg_call {
   const cc_k1_seg *segs;
   const int32_t *scan_segs;  // [n_scans + 1]
 };
+// A checked cc_*_motion call (motion_check below) as ingest_on takes it.
+struct mot_call {
+  cc_point_motion_t m;
+  const float *h_time;   // [n_scans][2]
+  const float *h_knots;  // [n_scans][K][12]
+};
+static_assert(CC_K1_MOT_KNOTS_MAX == CC_MOTION_KNOTS_MAX, "k_rasterize.h's knot table holds CC_MOTION_KNOTS_MAX matrices");
+// Everything the header promises to check about the motion arguments (`lay` has passed point_layout), before anything is queued or read.
+static int motion_check(const cc_point_layout_t &lay, const cc_point_motion_t *motion, const float *h_time, const float *h_knots, int n_scans, const char *who) {
+  const char *why = nullptr;
+  if (!motion || !h_time || !h_knots) why = "motion, h_time and h_knots must not be NULL";
+  else if (motion->time_offset < 0 || motion->time_offset % 4 != 0 || motion->time_offset > lay.stride_bytes - 4) why = "time_offset must be a multiple of 4 with time_offset + 4 <= stride_bytes";
+  else if (motion->time_offset + 4 > lay.xyz_offset && motion->time_offset < lay.xyz_offset + 12) why = "the time word overlaps x, y, z";
+  else if (motion->time_type != CC_TIME_F32 && motion->time_type != CC_TIME_U32) why = "time_type must be CC_TIME_F32 or CC_TIME_U32";
+  else if (motion->n_knots < 1 || motion->n_knots > CC_MOTION_KNOTS_MAX) why = "n_knots must be 1 .. CC_MOTION_KNOTS_MAX";
+  else
+    for (int i = 0; i < n_scans; i++)
+      if (!std::isfinite(h_time[(size_t)i * 2 + 1])) why = "every scale must be finite";
+  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
+  return CC_OK;
+}
 // cc_ingest_points on the scratch set S (c->ing_mu held by the caller; `lay` has passed point_layout).  h_tf: [n_scans][12] or nullptr.
 // sg: nullptr, or the call's segments -- d_points, lay and h_tf are not looked at then (cc_ingest_segments).
+// mc: nullptr, or the call's per-point time and knots (cc_ingest_points_motion; without h_tf and sg).
 static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_point_layout_t lay, const float *h_tf, const int64_t *h_offsets, int n_scans,
-                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, hipStream_t stream, const char *who, const seg_call *sg = nullptr) {
+                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, hipStream_t stream, const char *who, const seg_call *sg = nullptr,
+                     const mot_call *mc = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   // KITTI records without a transform take the float4 kernels (16-byte loads: the base must be aligned for them); everything
   // else one of the record loaders' instances
-  const bool kitti = lay.stride_bytes == 16 && lay.xyz_offset == 0 && !h_tf && ((uintptr_t)d_points & 15u) == 0;
+  const bool kitti = lay.stride_bytes == 16 && lay.xyz_offset == 0 && !h_tf && !mc && ((uintptr_t)d_points & 15u) == 0;
   for (int i = 0; i < n_scans; i++) {
     const int64_t n = h_offsets[i + 1] - h_offsets[i];
     if (!(n > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
@@ -499,6 +534,28 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
       d_segs.scan_seg = (const int *)S.d_seg;
       d_segs.seg = (const cc_k1_seg *)(S.d_seg + ent_off);
     }
+    cc_k1_motion d_mot = {nullptr, nullptr, 0, 0, 0};
+    if (mc) {  // the chunk's times and knots ride in the same slot of the ring (the segment tables' buffer: a call has one or the other)
+      const size_t kf = (size_t)mc->m.n_knots * 12, bytes = sizeof(float) * (2 + kf) * (size_t)nb;
+      if (!S.d_mot) HIPCHK(hipMalloc(&S.d_mot, sizeof(float) * (2 + (size_t)CC_MOTION_KNOTS_MAX * 12) * (size_t)S.cap));
+      if (c->h_seg_cap[slot] < bytes) {
+        if (c->h_seg[slot]) hipHostFree(c->h_seg[slot]);
+        c->h_seg[slot] = nullptr;
+        c->h_seg_cap[slot] = 0;
+        HIPCHK(hipHostMalloc((void **)&c->h_seg[slot], bytes * 2, hipHostMallocDefault));
+        c->h_seg_cap[slot] = bytes * 2;
+      }
+      float *hm = (float *)c->h_seg[slot];
+      memcpy(hm, mc->h_time + (size_t)b0 * 2, sizeof(float) * 2 * (size_t)nb);
+      memcpy(hm + 2 * (size_t)nb, mc->h_knots + (size_t)b0 * kf, sizeof(float) * kf * (size_t)nb);
+      HIPCHK(hipMemcpyAsync(S.d_mot, hm, bytes, hipMemcpyHostToDevice, stream));
+      d_mot.time = S.d_mot;
+      d_mot.knots = S.d_mot + 2 * (size_t)nb;
+      d_mot.t_off = mc->m.time_offset - lay.xyz_offset;
+      d_mot.time_u32 = mc->m.time_type == CC_TIME_U32 ? 1 : 0;
+      d_mot.n_knots = mc->m.n_knots;
+    }
+    const int mot_tab = (int)((c->lds1 + 15) & ~(size_t)15);  // where the knot table goes in LDS
     HIPCHK(hipEventRecord(c->off_ev[slot], stream));
     c->off_busy[slot] = true;
     const float4 *pts = sg ? nullptr : (const float4 *)d_points + h_offsets[b0];  // (the float4 kernels')
@@ -535,6 +592,22 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
                              c->dcfg, d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
         hipLaunchKernelGGL(cc_k_rasterize_merge_seg, dim3(nb), dim3(1024), 0, stream, c->dcfg, d_segs, (const long long *)S.d_offsets, S.k1_part, S.d_bev,
                            S.d_pix, S.d_k1, S.list, want_dense);
+      } else if (mc) {
+#define CC_K1_MOT_SPLIT(STRIDE)                                                                                                                                  \
+  {                                                                                                                                                              \
+    if (c->dcfg.reso_pow2)                                                                                                                                       \
+      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, \
+                         stream, c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense); \
+    else                                                                                                                                                         \
+      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, \
+                         stream, c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense); \
+    hipLaunchKernelGGL((cc_k_rasterize_merge_mot<STRIDE>), dim3(nb), dim3(1024), 0, stream, c->dcfg, rpts, rstride, d_mot, (const long long *)S.d_offsets,       \
+                       S.k1_part, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);                                                                                 \
+  }
+        if (rstride == 16) CC_K1_MOT_SPLIT(16)
+        else if (rstride == 32) CC_K1_MOT_SPLIT(32)
+        else CC_K1_MOT_SPLIT(0)
+#undef CC_K1_MOT_SPLIT
       } else if (kitti) {
         if (c->dcfg.reso_pow2)
           hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
@@ -568,6 +641,20 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
       else
         hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, false>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream, c->dcfg,
                            d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
+    } else if (mc) {
+#define CC_K1_MOT_WHOLE(STRIDE)                                                                                                                              \
+  {                                                                                                                                                          \
+    if (c->dcfg.reso_pow2)                                                                                                                                   \
+      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, stream,  \
+                         c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense); \
+    else                                                                                                                                                     \
+      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, stream, \
+                         c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense); \
+  }
+      if (rstride == 16) CC_K1_MOT_WHOLE(16)
+      else if (rstride == 32) CC_K1_MOT_WHOLE(32)
+      else CC_K1_MOT_WHOLE(0)
+#undef CC_K1_MOT_WHOLE
     } else if (!kitti) {
 #define CC_K1_REC_WHOLE(STRIDE)                                                                                                                \
   {                                                                                                                                            \
@@ -628,7 +715,7 @@ int cc_ingest_batch(cc_ctx *c, const float *d_xyzi, const int64_t *h_offsets, in
 }
 
 static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                              cc_scan_desc_t *h_out, float *h_bev, const char *who);
+                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const mot_call *mc = nullptr);
 
 int cc_ingest_host(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out) {
   return cc_ingest_host_bev(c, h_xyzi, h_offsets, n_scans, h_out, nullptr);
@@ -666,11 +753,15 @@ static int host_results(const cc_scan_desc_t *d_o, const float *d_b, size_t bev_
 }
 
 static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                              cc_scan_desc_t *h_out, float *h_bev, const char *who) {
+                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const mot_call *mc) {
   if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
   cc_point_layout_t lay;
   const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records are copied to aligned device memory)
   if (rcl != CC_OK) return rcl;
+  if (mc) {
+    const int rcm = motion_check(lay, &mc->m, mc->h_time, mc->h_knots, n_scans, who);
+    if (rcm != CC_OK) return rcm;
+  }
   HIPCHK(hipSetDevice(c->device));
   const int64_t base = h_offsets[0], total = h_offsets[n_scans] - base;
   const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
@@ -697,13 +788,107 @@ static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_la
   if (e != hipSuccess) rc = set_err(CC_EHIP, CC_WHO(": H2D"), e);
   if (rc == CC_OK) {
     std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-    rc = ingest_on(c, c->main, d_x, lay, h_tf, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
+    rc = ingest_on(c, c->main, d_x, lay, h_tf, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who, nullptr, mc);
   }
   if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
   hipFree(d_x);
   hipFree(d_o);
   hipFree(d_b);
   return rc;
+}
+
+// ---- a sweep de-skewed by per-point time (cc_ingest_points_motion and its siblings) ----
+int cc_ingest_points_motion(cc_ctx *c, const void *d_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, const int64_t *h_offsets,
+                            int n_scans, const float *h_time, const float *h_knots, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
+  const char *who = "cc_ingest_points_motion";
+  if (!c || !d_points || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, d_points, who, &lay);
+  if (rcl != CC_OK) return rcl;
+  const int rcm = motion_check(lay, motion, h_time, h_knots, n_scans, who);
+  if (rcm != CC_OK) return rcm;
+  const mot_call mc = {*motion, h_time, h_knots};
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+  return ingest_on(c, c->main, d_points, lay, nullptr, h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who, nullptr, &mc);
+}
+
+int cc_ingest_points_motion_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, const int64_t *h_offsets,
+                                 int n_scans, const float *h_time, const float *h_knots, cc_scan_desc_t *h_out, float *h_bev) {
+  const char *who = "cc_ingest_points_motion_host";
+  if (!motion) return set_err(CC_EINVAL, CC_WHO(": motion, h_time and h_knots must not be NULL"));
+  const mot_call mc = {*motion, h_time, h_knots};
+  return ingest_points_host(c, h_points, layout, h_offsets, n_scans, nullptr, h_out, h_bev, who, &mc);
+}
+
+// SO(3) in f64 for cc_motion_knots: R row-major 3 x 3.
+static void so3_log(const double R[9], double w[3]) {
+  const double v[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};  // sin(theta) * axis
+  const double sn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), cs = 0.5 * (R[0] + R[4] + R[8] - 1.0);
+  const double th = atan2(sn, cs);
+  if (sn > 1e-9) {
+    for (int i = 0; i < 3; i++) w[i] = v[i] * (th / sn);
+  } else if (cs > 0) {  // theta ~ 0: Log(R) ~ vee(R - R^T) / 2
+    for (int i = 0; i < 3; i++) w[i] = v[i];
+  } else {  // theta ~ pi: the axis from the diagonal of (R + I) / 2 = a a^T, signs from its largest column
+    const double d[3] = {0.5 * (R[0] + 1.0), 0.5 * (R[4] + 1.0), 0.5 * (R[8] + 1.0)};
+    const int k = d[0] >= d[1] && d[0] >= d[2] ? 0 : (d[1] >= d[2] ? 1 : 2);
+    double a[3];
+    for (int i = 0; i < 3; i++) a[i] = 0.25 * (R[3 * i + k] + R[3 * k + i]) + (i == k ? 0.5 : 0.0);
+    const double n = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    for (int i = 0; i < 3; i++) w[i] = a[i] / n * th;
+  }
+}
+static void so3_exp(const double w[3], double R[9]) {
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
+  const double A = th > 1e-8 ? sin(th) / th : 1.0 - th2 / 6.0, B = th > 1e-8 ? (1.0 - cos(th)) / th2 : 0.5 - th2 / 24.0;
+  const double W[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double ww = 0;
+      for (int k = 0; k < 3; k++) ww += W[3 * i + k] * W[3 * k + j];
+      R[3 * i + j] = (i == j ? 1.0 : 0.0) + A * W[3 * i + j] + B * ww;
+    }
+}
+
+void cc_motion_knots(const double pb[12], const double pe[12], double ref, int K, float *knots) {
+  if (!pb || !pe || !knots || K < 1) return;
+  double D[9], w[3];  // R_b^T R_e and its logarithm
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double a = 0;
+      for (int k = 0; k < 3; k++) a += pb[4 * k + i] * pe[4 * k + j];
+      D[3 * i + j] = a;
+    }
+  so3_log(D, w);
+  auto pose = [&](double s, double T[12]) {  // T(s)
+    const double ws[3] = {s * w[0], s * w[1], s * w[2]};
+    double E[9];
+    so3_exp(ws, E);
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) {
+        double a = 0;
+        for (int k = 0; k < 3; k++) a += pb[4 * i + k] * E[3 * k + j];
+        T[4 * i + j] = a;
+      }
+      T[4 * i + 3] = (1.0 - s) * pb[4 * i + 3] + s * pe[4 * i + 3];
+    }
+  };
+  double Tr[12];
+  pose(ref, Tr);
+  for (int q = 0; q < K; q++) {
+    double Tk[12];
+    pose((q + 0.5) / K, Tk);
+    for (int i = 0; i < 3; i++) {  // T(ref)^-1 T_k = [Rr^T Rk | Rr^T (pk - pr)]
+      for (int j = 0; j < 3; j++) {
+        double a = 0;
+        for (int k = 0; k < 3; k++) a += Tr[4 * k + i] * Tk[4 * k + j];
+        knots[(size_t)q * 12 + 4 * i + j] = (float)a;
+      }
+      double a = 0;
+      for (int k = 0; k < 3; k++) a += Tr[4 * k + i] * (Tk[4 * k + 3] - Tr[4 * k + 3]);
+      knots[(size_t)q * 12 + 4 * i + 3] = (float)a;
+    }
+  }
 }
 
 // ---- scans made of segments (cc_ingest_segments and its siblings) ----
@@ -940,7 +1125,7 @@ int cc_stage_points_cancel(cc_ctx *c, const float *staged) {
 }
 
 static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who, const cc_point_segment_t *h_segs = nullptr, int n_segs = 0);
+                              const char *who, const cc_point_segment_t *h_segs = nullptr, int n_segs = 0, const mot_call *mc = nullptr);
 
 int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_bev, cc_scan **out) {
   return scan_ingest_points(c, h_xyzi, nullptr, n_points, nullptr, want_bev, out, "cc_scan_ingest");
@@ -955,10 +1140,17 @@ int cc_scan_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, int n_s
   return scan_ingest_points(c, nullptr, nullptr, 0, nullptr, want_bev, out, "cc_scan_ingest_segments", h_segs, n_segs);
 }
 
+int cc_scan_ingest_points_motion(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, int64_t n_points,
+                                 const float *h_time, const float *h_knots, int want_bev, cc_scan **out) {
+  if (!motion) return set_err(CC_EINVAL, "cc_scan_ingest_points_motion: motion, h_time and h_knots must not be NULL");
+  const mot_call mc = {*motion, h_time, h_knots};
+  return scan_ingest_points(c, h_points, layout, n_points, nullptr, want_bev, out, "cc_scan_ingest_points_motion", nullptr, 0, &mc);
+}
+
 // h_segs: nullptr, or the scan's n_segs host segments (cc_scan_ingest_segments; h_xyzi, layout, n_points and h_tf are not looked at then):
 // their records go to the staging buffer one segment after the other, each at a 16-byte boundary.
 static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who, const cc_point_segment_t *h_segs, int n_segs) {
+                              const char *who, const cc_point_segment_t *h_segs, int n_segs, const mot_call *mc) {
   if (!c || (!h_xyzi && !h_segs) || !out || (!h_segs && n_points < 1)) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
   cc_point_layout_t lay = CC_LAYOUT_KITTI;
   std::vector<cc_k1_seg> seg_tab;
@@ -973,6 +1165,10 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
   } else {
     const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records go through a staging buffer to aligned device memory)
     if (rcl != CC_OK) return rcl;
+    if (mc) {
+      const int rcm = motion_check(lay, &mc->m, mc->h_time, mc->h_knots, 1, who);
+      if (rcm != CC_OK) return rcm;
+    }
   }
   const size_t n_bytes = h_segs ? seg_bytes : (size_t)n_points * (size_t)lay.stride_bytes;   // the records travel as they are
   const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
@@ -1062,7 +1258,7 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
   for (int k = 0; k < n_segs; k++) seg_tab[k].base = (const char *)ch.d_pts + seg_place[k] + (seg_tab[k].base - (const char *)h_segs[k].points);
   const seg_call sg = {seg_tab.data(), seg_scan};
   const int rc = h_segs ? ingest_on(c, ch.scr, nullptr, lay, nullptr, seg_qoff.data(), 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, &sg)
-                        : ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
+                        : ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, nullptr, mc);
   if (rc != CC_OK) {
     give_back();
     return rc;

@@ -987,3 +987,101 @@ cc_k_rasterize_merge_seg(cc_dev_cfg cfg, cc_k1_segs segs, const long long *__res
   __syncthreads();
   cc_k1_merge(cfg, cc_ld_segs{T, n_seg}, offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
 }
+
+// ---- a sweep DE-SKEWED by per-point time (cc_ingest_points_motion): every record carries a 4-byte time word, every scan brings
+// K <= CC_MOTION_KNOTS_MAX matrices ("knots", piecewise constant over the sweep), and a point is moved by the knot of ITS time bin
+//     u = (t - t_begin) * scale   (CC_TIME_U32: (float)(uint32)(w - tb) * scale, the subtraction modulo 2^32)
+//     b = trunc(min(max(u, 0), K - 1))     -- NaN counts as 0; clamped BEFORE the conversion, so no out-of-range float -> int
+// with cc_ld_rec::xyz's operations in its order.  The scan's knots sit in LDS behind cc_k1_sweep's layout (at most 3 072 B: 161 408 B
+// at 150 x 150, still one 1 024-thread workgroup per CU); a point's matrix is three 16-byte LDS reads at a per-lane address.  The
+// records of one wave are neighbouring firings: mostly one bin, and equal addresses are a broadcast, not a conflict.
+// No interpolation between knots: it would double the LDS reads and add 12 multiply-adds per point to an issue-bound sweep.
+#define CC_K1_MOT_KNOTS_MAX 64  // = CC_MOTION_KNOTS_MAX (include/cont2_amd.h; checked where both are seen)
+#define CC_K1_MOT_LDS_BYTES (CC_K1_MOT_KNOTS_MAX * 12 * 4)
+struct cc_k1_motion {
+  const float *time;   // [n_scans][2]: t_begin (CC_TIME_U32: the u32's bits), scale
+  const float *knots;  // [n_scans][n_knots][12]
+  int t_off;           // byte offset of the time word from the record's x (negative: the time sits in front of xyz)
+  int time_u32;        // the time word is a u32 (CC_TIME_U32), not an f32
+  int n_knots;
+};
+
+// The scan's knots to LDS (a barrier has to follow before xyz() is called: cc_k1_sweep's after it has cleared the grid, the merge kernel's own).
+__device__ __forceinline__ void cc_k1_knot_table(float *T, const cc_k1_motion &M, int scan) {
+  const float *__restrict__ src = M.knots + (size_t)scan * (size_t)M.n_knots * 12;
+  for (int i = threadIdx.x; i < M.n_knots * 12; i += blockDim.x) T[i] = src[i];
+}
+
+struct cc_xyzt {
+  float x, y, z;
+  unsigned w;  // the time word as it lies in the record
+};
+template <int STRIDE>
+struct cc_ld_rec_motion {
+  typedef cc_xyzt rec;
+  const char *__restrict__ B;  // x of the first point
+  unsigned stride;             // bytes (cc_ld_rec's bounds)
+  int t_off;
+  bool time_u32;               // workgroup-uniform
+  float t_begin, scale;        // workgroup-uniform: scalars
+  unsigned tb_bits;
+  float kmax;                  // n_knots - 1
+  const float4 *T;             // LDS: [n_knots][3] rows of the scan's matrices
+  __device__ __forceinline__ cc_ld_rec_motion(const char *base, int stride_bytes, const cc_k1_motion &M, int scan, const float *lds_tab)
+      : B(base), stride(STRIDE ? (unsigned)STRIDE : (unsigned)stride_bytes), t_off(M.t_off), time_u32(M.time_u32 != 0), T((const float4 *)lds_tab) {
+    tb_bits = (unsigned)cc_uniform_i(__float_as_int(M.time[(size_t)scan * 2]));
+    t_begin = __int_as_float((int)tb_bits);
+    scale = __int_as_float(cc_uniform_i(__float_as_int(M.time[(size_t)scan * 2 + 1])));
+    kmax = (float)(M.n_knots - 1);
+  }
+  __device__ __forceinline__ void advance(long long n) { B += n * (long long)stride; }
+  // the coordinates and the time word are requested together, neither under a branch
+  __device__ __forceinline__ rec load(int j) const {
+    cc_xyzt q;
+    const char *p = B + (unsigned)j * stride;
+    cc_load3f(p, q.x, q.y, q.z);
+    q.w = *(const unsigned *)(p + t_off);
+    return q;
+  }
+  __device__ __forceinline__ static rec zero() { return cc_xyzt{0.f, 0.f, 0.f, 0u}; }
+  __device__ __forceinline__ int bin(unsigned w) const {
+    float u = time_u32 ? (float)(w - tb_bits) * scale : (__int_as_float((int)w) - t_begin) * scale;
+    u = u > 0.f ? u : 0.f;  // (a NaN fails the compare: bin 0)
+    u = u < kmax ? u : kmax;
+    return (int)u;
+  }
+  __device__ __forceinline__ void xyz(const rec &q, float &x, float &y, float &z) const {
+    const int b = bin(q.w);
+    const float4 r0 = T[b * 3], r1 = T[b * 3 + 1], r2 = T[b * 3 + 2];
+    x = ((r0.x * q.x + r0.y * q.y) + r0.z * q.z) + r0.w;
+    y = ((r1.x * q.x + r1.y * q.y) + r1.z * q.z) + r1.w;
+    z = ((r2.x * q.x + r2.y * q.y) + r2.z * q.z) + r2.w;
+  }
+  __device__ __forceinline__ float2 owner_xy(int j) const {
+    float x, y, z;
+    xyz(load(j), x, y, z);
+    return make_float2(x, y);
+  }
+};
+
+// grid, block as cc_k_rasterize_rec; dynamic LDS: tab_off (cc_k_rasterize's bytes) + CC_K1_MOT_LDS_BYTES.  STRIDE: 16, 32, 0 (run-time stride).
+template <int CC_K1_U, bool CC_K1_POW2, bool PART, int STRIDE>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_mot(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, cc_k1_motion mot, int tab_off, const long long *__restrict__ offsets,
+                   float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
+                   int want_dense) {
+  HIP_DYNAMIC_SHARED(char, smem)
+  const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;
+  float *T = (float *)(smem + tab_off);
+  cc_k1_knot_table(T, mot, scan);  // (read after cc_k1_sweep's first barrier)
+  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_rec_motion<STRIDE>(pts, stride, mot, scan, T), offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+}
+template <int STRIDE>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_merge_mot(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, cc_k1_motion mot, const long long *__restrict__ offsets, cc_k1_part part,
+                         float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
+  __shared__ __attribute__((aligned(16))) float T[CC_K1_MOT_LDS_BYTES / 4];  // the owners' re-reads need the scan's knots too
+  cc_k1_knot_table(T, mot, (int)blockIdx.x);
+  __syncthreads();
+  cc_k1_merge(cfg, cc_ld_rec_motion<STRIDE>(pts, stride, mot, (int)blockIdx.x, T), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
+}

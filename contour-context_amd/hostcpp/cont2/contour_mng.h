@@ -373,6 +373,47 @@ class ContourManager {
     str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(segments[0].cloud->header.stamp);
   }
 
+  // Mirror-only: makeBEV for a sweep that is de-skewed while it is rasterised.  Every record of PointType carries a 4-byte time word
+  // (CC_TIME_F32: Velodyne's `time`; CC_TIME_U32: Ouster's `t` in ns) at byte time_offset, and the point is moved by the knot matrix
+  // of its time bin, b = trunc(clamp((t - t_begin) * scale, 0, K - 1)) -- knots.size() = K <= CC_MOTION_KNOTS_MAX row-major 3 x 4
+  // matrices, e.g. from cc_motion_knots with the odometry's poses at the sweep's begin and end (cc_scan_ingest_points_motion,
+  // include/cont2_amd.h).  For CC_TIME_U32 t_begin_or_bits holds the BITS of the u32 begin.  The cloud's own records go to the device
+  // as they are: no pass that gathers a pose per point and writes a second copy.
+  struct BevMotion {
+    size_t time_offset = 0;
+    int time_type = CC_TIME_F32;
+    float t_begin_or_bits = 0.f;
+    float scale = 0.f;
+    std::vector<std::array<float, 12>> knots;
+  };
+  template <typename PointType>
+  void makeBEV(typename pcl::PointCloud<PointType>::ConstPtr &ptr_gapc, const BevMotion &motion, std::string str_id = "") {
+    CC_CHECK(ptr_gapc);
+    CC_CHECK(ptr_gapc->size() > 10);
+    CC_CHECK(!scan_);
+    CC_CHECK(!motion.knots.empty() && motion.knots.size() <= (size_t)CC_MOTION_KNOTS_MAX);
+    static_assert(sizeof(PointType) % 4 == 0 && sizeof(PointType) <= CC_POINT_STRIDE_MAX, "makeBEV: a record the rasteriser's loaders do not take");
+    static_assert(sizeof(std::array<float, 12>) == 12 * sizeof(float), "makeBEV: the knots are passed as [K][12] floats");
+    const PointType &p0 = ptr_gapc->points[0];
+    const char *base = reinterpret_cast<const char *>(&p0);
+    CC_CHECK(reinterpret_cast<const char *>(&p0.y) == reinterpret_cast<const char *>(&p0.x) + 4);
+    CC_CHECK(reinterpret_cast<const char *>(&p0.z) == reinterpret_cast<const char *>(&p0.x) + 8);
+    cc_point_layout_t lay;
+    lay.stride_bytes = (int32_t)sizeof(PointType);
+    lay.xyz_offset = (int32_t)(reinterpret_cast<const char *>(&p0.x) - base);
+    cc_point_motion_t mo;
+    mo.time_offset = (int32_t)motion.time_offset;
+    mo.time_type = (int32_t)motion.time_type;
+    mo.n_knots = (int32_t)motion.knots.size();
+    mo.pad_ = 0;
+    const float h_time[2] = {motion.t_begin_or_bits, motion.scale};
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_points_motion(ctx, base, &lay, &mo, (int64_t)ptr_gapc->size(), h_time, motion.knots[0].data(), want_images_ ? 1 : 0, &scan_) != CC_OK)
+      die();
+    str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
+  }
+
   // Mirror-only: the evaluator's .bin reader (tools/pointcloud_util.h:9-47: at most 1 000 000 floats, x y z i records,
   // intensity dropped) without the intermediate cloud.  A KITTI record IS a staging record (the kernels never read the
   // fourth float), so the file is read straight into the context's pinned buffer.  Returns the number of points.

@@ -120,6 +120,18 @@ class PointSegment(C.Structure):
 assert C.sizeof(PointSegment) == 80 and PointSegment.tf.offset == 32
 
 
+MOTION_KNOTS_MAX = 64          # CC_MOTION_KNOTS_MAX: knot matrices per scan of cc_ingest_points_motion
+TIME_F32, TIME_U32 = 0, 1      # CC_TIME_F32 / CC_TIME_U32
+
+
+class PointMotion(C.Structure):
+    """cc_point_motion_t: where a record's 4-byte time word sits, its type, and the number of knot matrices per scan."""
+    _fields_ = [("time_offset", C.c_int32), ("time_type", C.c_int32), ("n_knots", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(PointMotion) == 16
+
+
 class SimCfg(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ta_cell_cnt", "tp_cell_cnt", "tp_eigval", "ta_h_bar", "ta_rcom", "tp_rcom")]
 

@@ -357,6 +357,60 @@ int cc_ingest_segments(cc_ctx *ctx, const cc_point_segment_t *h_segs, const int3
 int cc_ingest_segments_host(cc_ctx *ctx, const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, cc_scan_desc_t *h_out,
                             float *h_bev);
 
+/* ---- a sweep de-skewed by per-point time while it is rasterised ----
+ * A spinning LiDAR's sweep is recorded over ~0.1 s while the vehicle moves: at 15 m/s and 0.5 rad/s a point at 60 m lands 1.5 - 3 m
+ * (several 1 m cells) from where a rigid scan would put it.  Every driver delivers a per-point time (Velodyne `time`: f32 in the
+ * PointCloud2 record; Ouster `t`: u32 ns) and the odometry has the poses: these calls move every point by the pose of ITS time bin
+ * while the rasteriser loads it -- no pass that gathers a pose per point and writes a second copy of the cloud.  No reference
+ * counterpart.  Per scan i the call brings K "knot" matrices (the same K for every scan of the call, 1 <= K <=
+ * CC_MOTION_KNOTS_MAX; each row-major 3 x 4 f32 like h_tf) and two numbers t_begin_i, scale_i (bins per time unit, f32).  A point
+ * whose time word -- the 4 bytes at time_offset inside its record -- is w:
+ *   1. CC_TIME_F32: u = (t - t_begin_i) * scale_i, one f32 subtraction and one f32 multiplication, each rounded once.
+ *      CC_TIME_U32: u = (float)(uint32)(w - tb_i) * scale_i; tb_i is the u32 whose BITS are passed in the t_begin slot, the
+ *      subtraction wraps modulo 2^32, the conversion rounds to nearest even.
+ *   2. b = trunc(min(max(u, 0), K - 1)); NaN counts as 0 (the value is clamped before it is converted).
+ *   3. the point is moved by knot b of its scan: the operation cc_ingest_points documents for h_tf, in its order.
+ * The scan's result -- descriptor, bev, pix_rc, labels, every byte -- is what cc_ingest_batch gives for the moved points in their
+ * original order: among equal heights in one cell the first point in file order wins, whatever its time; the blind zone, the
+ * border, max / min height and the continuous position see the moved point only.  The matrices are piecewise constant on purpose
+ * (K = 32 on a 0.1 s sweep: 3 ms bins, under 10 cm at 30 m/s); a call with K = 1 gives the bytes of cc_ingest_points with that
+ * matrix as h_tf (by its own kernels).
+ * Checked before anything is queued or read (CC_EINVAL, the context stays as it was): the layout passes cc_ingest_points'
+ * rules; time_offset is a multiple of 4 with time_offset + 4 <= stride_bytes; the time word does not overlap the 12 bytes of
+ * x, y, z; time_type is CC_TIME_F32 or CC_TIME_U32; 1 <= n_knots <= CC_MOTION_KNOTS_MAX; motion, h_time and h_knots are
+ * non-NULL; every scale is finite.  h_time and h_knots are copied before the call returns.
+ * Out of scope: f64 or 64-bit integer time stamps; a time per segment in cc_ingest_segments (its kernels leave no LDS for the
+ * knots); interpolation between knots; a batch form of the per-scan call; 12-byte records, which have no room for a time.
+ * What the kernels cost next to cc_ingest_points': DESIGN.md 3.0. */
+#define CC_MOTION_KNOTS_MAX 64
+enum { CC_TIME_F32 = 0, CC_TIME_U32 = 1 };
+typedef struct {
+  int32_t time_offset; /* byte offset of the time word inside a record */
+  int32_t time_type;   /* CC_TIME_F32 / CC_TIME_U32 */
+  int32_t n_knots;     /* K */
+  int32_t pad_;
+} cc_point_motion_t;   /* 16 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cc_point_motion_t) == 16, "cc_point_motion_t: 16 bytes");
+#else
+_Static_assert(sizeof(cc_point_motion_t) == 16, "cc_point_motion_t: 16 bytes");
+#endif
+/*   h_time  : [n_scans][2] f32: t_begin (CC_TIME_U32: the u32's bits), scale
+ *   h_knots : [n_scans][K][12] f32
+ * Everything else as cc_ingest_points (device records read in place, work queued on `stream`, chunks of max_batch_scans). */
+int cc_ingest_points_motion(cc_ctx *ctx, const void *d_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion,
+                            const int64_t *h_offsets, int n_scans, const float *h_time, const float *h_knots, cc_scan_desc_t *d_out,
+                            const cc_ingest_debug_t *dbg, void *stream);
+/* The same from host records (cc_ingest_points_host's shape; h_bev may be NULL). */
+int cc_ingest_points_motion_host(cc_ctx *ctx, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion,
+                                 const int64_t *h_offsets, int n_scans, const float *h_time, const float *h_knots, cc_scan_desc_t *h_out,
+                                 float *h_bev);
+/* Knots from the poses at the sweep's begin and end (host only, f64; row-major 3 x 4 [R | p], sensor to world):
+ *   T(s) = [R_b Exp(s Log(R_b^T R_e)) | (1 - s) p_b + s p_e],   knot k = T(ref)^-1 T((k + 0.5) / K), rounded to f32.
+ * ref in [0, 1] is the instant the scan is referred to (1: the sweep's end).  Composing an extrinsic matrix is the caller's
+ * multiplication. */
+void cc_motion_knots(const double pose_begin[12], const double pose_end[12], double ref, int K, float *knots /*[K][12]*/);
+
 /* ---- the per-scan loop (test/batch_bin_test.cpp:131-237 at sensor rate) ----
  * A cc_scan is ONE scan's descriptor kept on the device between ContourManager::makeContoursRecurs (contour_mng.h:588),
  * ContourDB::queryRangedKNN (contour_db.h:698) and ContourDB::addScan (:814): the class mirror's ContourManager holds one.
@@ -412,6 +466,10 @@ int cc_scan_ingest_points_batch(cc_ctx *ctx, const void *const *h_points, const 
 /* cc_scan_ingest_points for ONE scan made of n_segs host segments (cc_point_segment_t above; the records go through the context's
  * own staging buffer): an ordinary scan handle comes out. */
 int cc_scan_ingest_segments(cc_ctx *ctx, const cc_point_segment_t *h_segs, int n_segs, int want_bev, cc_scan **out);
+/* cc_scan_ingest_points for ONE scan de-skewed by per-point time (cc_ingest_points_motion above; h_time: 2 values, h_knots:
+ * [K][12]): an ordinary scan handle comes out. */
+int cc_scan_ingest_points_motion(cc_ctx *ctx, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion,
+                                 int64_t n_points, const float *h_time, const float *h_knots, int want_bev, cc_scan **out);
 int cc_scan_ready(const cc_scan *scan);
 int cc_scan_desc(cc_scan *scan, const cc_scan_desc_t **h_desc);
 int cc_scan_bev(cc_scan *scan, const float **h_bev);
