@@ -23,7 +23,7 @@ import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
 _SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_contours.h", "k_contours_list.h",
-         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
+         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "k_pose.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 
 def build(force=False, verbose=False):
@@ -56,7 +56,7 @@ EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_
            "cc_db_check_hints_ranked", "cc_db_verify_batch_host_ranked", "cc_db_check_hints_host_ranked",
            "cc_db_query_submit_ranked_detail", "cc_db_query_batch_host_ranked_detail", "cc_db_query_scan_batch_submit_ranked_detail",
            "cc_db_verify_submit_ranked_detail", "cc_db_verify_batch_host_ranked_detail", "cc_db_check_hints_ranked_detail",
-           "cc_db_check_hints_host_ranked_detail", "cc_est_sens_info",
+           "cc_db_check_hints_host_ranked_detail", "cc_est_sens_info", "cc_db_pose_submit", "cc_db_pose_batch", "cc_db_pose_batch_host",
            "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
            "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
            "cc_comm_unique_id", "cc_comm_create", "cc_comm_create_from_env", "cc_comm_rank", "cc_comm_world", "cc_comm_allgather_packed", "cc_comm_destroy"]
@@ -127,6 +127,9 @@ def lib():
                   "cc_db_check_hints_ranked"):  # the _detail siblings: one more trailing pointer
             getattr(_lib, f + "_detail").argtypes = getattr(_lib, f).argtypes + [C.c_void_p]
         _lib.cc_est_sens_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        for f in ("cc_db_pose_submit", "cc_db_pose_batch"):
+            getattr(_lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        _lib.cc_db_pose_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.cc_est_sens_info.restype = None
         _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
         _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
@@ -717,6 +720,54 @@ class Database:
                                        tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
                                        None, None, stream), "cc_db_verify_submit")
         return res
+
+    def _pose_args(self, qdesc, q, gidx, tf, refine, min_corr, tries, curvature):
+        import torch
+        assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
+        q = np.asarray(q).reshape(-1)
+        n = len(q)
+        if len(np.asarray(gidx).reshape(-1)) != n or np.asarray(tf).size != 3 * n:
+            raise ValueError("q, gidx and tf must name one item each: [n], [n] and [n, 3]")
+        items = L.pose_items(q, gidx, tf)
+        tr = tc = None
+        nt = 0
+        if tries is not None:
+            tr = np.ascontiguousarray(tries, np.float64)
+            if tr.ndim != 3 or tr.shape[0] != n or tr.shape[2] != 3:
+                raise ValueError("tries must have shape [n, T, 3]")
+            nt = tr.shape[1]
+            tc = np.zeros((n, nt), np.float64)
+        if min_corr is None:
+            min_corr = L.default_thresholds()[0].correlation
+        cfg = L.PoseCfg(int(refine), float(min_corr), nt, 0)
+        res = np.zeros(n, L.pose_result_dt)
+        cv = np.zeros(n, L.pose_curv_dt) if curvature else None
+        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+        args = (self.h, qdesc.data_ptr(), qdesc.shape[0], items.ctypes.data, n, C.addressof(cfg), tr.ctypes.data if nt else None, res.ctypes.data,
+                tc.ctypes.data if nt else None, cv.ctypes.data if curvature else None, stream)
+        return args, (items, tr, cfg), res, (tc if tries is not None else None), cv
+
+    def score_poses(self, qdesc, q, gidx, tf, refine=True, min_corr=None, tries=None, curvature=False, allow_flagged=False):
+        """Score, probe and refine relative poses the caller believes in, in one batch (cc_db_pose_batch: the reference's
+        ConstellCorrelation::initProblem / tryProblem / calcCorrelation).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES]; item i
+        is descriptor q[i] (tgt) against database scan gidx[i] (src) at T_init = tf[i] = (x, y, theta) in BEV pixels / radians.
+        refine: run the L-BFGS refinement on the items with pairs whose initial correlation is not below min_corr (None: the
+        shipped lb.correlation, 0.3; -inf: every item that has pairs).  tries [n, T, 3], T <= L.POSE_TRY_MAX: further poses per
+        item, evaluated over the pair set of T_init.  curvature: Hessian and gradient of -correlation at the returned pose.
+        Returns (res [n] of L.pose_result_dt, try_corr [n, T] or None, curv [n] of L.pose_curv_dt or None); a refined row
+        carries L.PF_REFINED in flags.  allow_flagged: as for query()."""
+        args, keep, res, tc, cv = self._pose_args(qdesc, q, gidx, tf, refine, min_corr, tries, curvature)
+        _chk(lib().cc_db_pose_batch(*args), "cc_db_pose_batch", tolerate=(CC_ECAPACITY,) if allow_flagged else ())
+        return res, tc, cv
+
+    def score_poses_submit(self, qdesc, q, gidx, tf, refine=True, min_corr=None, tries=None, curvature=False):
+        """Asynchronous form of score_poses(): queues the batch and returns the same tuple, whose arrays are only valid after
+        query_wait() (cc_db_pose_submit; pose chunks share the lanes with query and verify chunks and are collected together)."""
+        args, keep, res, tc, cv = self._pose_args(qdesc, q, gidx, tf, refine, min_corr, tries, curvature)
+        self._pending = getattr(self, "_pending", [])
+        self._pending.append((keep, res, tc, cv))  # the library reads and writes them until query_wait
+        _chk(lib().cc_db_pose_submit(*args), "cc_db_pose_submit")
+        return res, tc, cv
 
     def debug_passes(self, cap=1152):
         """Constellations of the last check_hints call that passed all gates: numpy array of L.pass_dbg_dt."""

@@ -134,6 +134,15 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   cc_ranked_detail_t *d_detail = nullptr;   // [QB * CC_RANK_MAX] cc_k_final_rd's rows, beside d_rank
   cc_ranked_detail_t *h_detail = nullptr;   // the same, pinned (small chunks: written by the kernel)
   cc_ranked_detail_t *detail_dst = nullptr; // where the chunk's detail rows go when it is collected (nullptr: not a detail chunk)
+  // pose chunks (cc_db_pose_submit), allocated with the first one.  In: item table | try poses | descriptor selector, filled by
+  // the submit, one copy per chunk.  Out: result rows | try results | curvature rows, one copy back (small chunks: written by the kernels)
+  char *d_pin = nullptr, *h_pin = nullptr;
+  char *d_pout = nullptr, *h_pout = nullptr;
+  bool pose = false;                        // the chunk in flight is a pose chunk: its rows are cc_pose_result_t, delivered below
+  cc_pose_result_t *pose_res = nullptr;     // where the chunk's rows go when it is collected: row b0 + i of each array
+  double *pose_try = nullptr;               // [n][pose_ntry] or nullptr
+  cc_pose_curv_t *pose_curv = nullptr;      // [n] or nullptr
+  int pose_ntry = 0;
 };
 
 struct cc_db {
@@ -296,6 +305,10 @@ static void db_free(cc_db *db) {
     if (ln.h_vin) hipHostFree(ln.h_vin);
     hipFree(ln.d_rank);
     if (ln.h_rank) hipHostFree(ln.h_rank);
+    hipFree(ln.d_pin);
+    if (ln.h_pin) hipHostFree(ln.h_pin);
+    hipFree(ln.d_pout);
+    if (ln.h_pout) hipHostFree(ln.h_pout);
     hipFree(ln.d_hess);
     hipFree(ln.d_detail);
     if (ln.h_detail) hipHostFree(ln.h_detail);
@@ -364,6 +377,42 @@ static int lane_alloc_verify(cc_qlane &ln) {
   if (e != hipSuccess) {
     ln.d_vin = nullptr;
     return set_err(CC_EHIP, "lane_alloc_verify: hipMalloc", e);
+  }
+  return CC_OK;
+}
+// the tables of a lane's pose chunks (2 x 228 KB in, 2 x 200 KB out), allocated with the lane's first one
+#define CC_POSE_IN_BYTES(nb, n_try) ((size_t)(nb) * (sizeof(cc_pose_item_t) + (size_t)(n_try) * 3 * sizeof(double) + sizeof(int)))
+#define CC_POSE_OUT_BYTES(nb, n_try, curv) ((size_t)(nb) * (sizeof(cc_pose_result_t) + (size_t)(n_try) * sizeof(double) + ((curv) ? sizeof(cc_pose_curv_t) : 0)))
+static int lane_alloc_pose(cc_qlane &ln) {
+  if (ln.d_pin && ln.d_pout) return CC_OK;
+  const size_t bin = CC_POSE_IN_BYTES(cc_db::QB, CC_POSE_TRY_MAX), bout = CC_POSE_OUT_BYTES(cc_db::QB, CC_POSE_TRY_MAX, true);
+  if (!ln.h_pin) {
+    const hipError_t e = hipHostMalloc((void **)&ln.h_pin, bin, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      ln.h_pin = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_pose: hipHostMalloc", e);
+    }
+  }
+  if (!ln.h_pout) {
+    const hipError_t e = hipHostMalloc((void **)&ln.h_pout, bout, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      ln.h_pout = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_pose: hipHostMalloc", e);
+    }
+  }
+  if (!ln.d_pin) {
+    const hipError_t e = hipMalloc(&ln.d_pin, bin);
+    if (e != hipSuccess) {
+      ln.d_pin = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_pose: hipMalloc", e);
+    }
+  }
+  if (!ln.d_pout) {
+    const hipError_t e = hipMalloc(&ln.d_pout, bout);
+    if (e != hipSuccess) {
+      ln.d_pout = nullptr;
+      return set_err(CC_EHIP, "lane_alloc_pose: hipMalloc", e);
+    }
   }
   return CC_OK;
 }
@@ -1190,11 +1239,37 @@ static int chunk_status(const cc_qlane &ln, int nb) {
   return CC_OK;
 }
 
+// a finished pose chunk: its rows to rows [b0, b0 + nb) of the caller's arrays, its stage times, its capacity flags
+static int pose_finish(cc_db *db, cc_qlane &ln) {
+  ln.pose = false;
+  const int nb = ln.nb, nt = ln.pose_ntry;
+  const cc_pose_result_t *rows = (const cc_pose_result_t *)ln.h_pout;
+  const double *tr = (const double *)(rows + nb);
+  memcpy(ln.pose_res + ln.b0, rows, sizeof(cc_pose_result_t) * (size_t)nb);
+  if (nt > 0) memcpy(ln.pose_try + (size_t)ln.b0 * nt, tr, sizeof(double) * (size_t)nb * nt);
+  if (ln.pose_curv) memcpy(ln.pose_curv + ln.b0, tr + (size_t)nb * nt, sizeof(cc_pose_curv_t) * (size_t)nb);
+  if (ln.profiled) {  // problems | - | - | correlation (with the try poses and the curvature) | rows
+    float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    hipEventElapsedTime(&t[0], ln.pev[0], ln.pev[1]);
+    hipEventElapsedTime(&t[3], ln.pev[3], ln.pev[4]);
+    hipEventElapsedTime(&t[4], ln.pev[4], ln.pev[5]);
+    for (int k = 0; k < 5; k++) db->ms_acc[k] += t[k];
+    db->launch_w += (double)nb;
+  }
+  if (ln.h_nprob[3] > ln.pool_cap) return set_err(CC_ECAPACITY, "the pair pool (or the pair-code pool) of the correlation refinement overflowed");
+  for (int i = 0; i < nb; i++)
+    if (rows[i].flags & ~CC_PF_REFINED)
+      return set_err(CC_ECAPACITY, "a pose item met an internal capacity of the correlation (cc_pose_result_t.flags, CC_QF_*): "
+                                   "its result may differ from the reference's");
+  return CC_OK;
+}
+
 // collect a lane's chunk: wait for its chain, copy its results to where its submitter wanted them, check its capacity flags
 static int lane_finish(cc_db *db, cc_qlane &ln) {
   if (!ln.busy) return CC_OK;
   ln.busy = false;
   HIPCHK(hipStreamSynchronize(ln.stream));
+  if (ln.pose) return pose_finish(db, ln);
   memcpy(ln.h_dst + ln.b0, ln.h_results, sizeof(cc_query_result_t) * ln.nb);
   if (ln.rank_dst.h_cands) rank_deliver(ln, ln.rank_dst, ln.b0, ln.nb, ln.rank_mfo);
   if (ln.detail_dst)
@@ -1220,6 +1295,7 @@ static void lane_abort(cc_db *db, cc_qlane &ln) {
   }
   if (ln.stream) hipStreamSynchronize(ln.stream);
   ln.busy = false;
+  ln.pose = false;
   db->poisoned = true;
 }
 
@@ -1242,7 +1318,7 @@ int cc_db_query_collect(cc_db *db, const cc_query_result_t *h_res, int n) {
   HIPCHK(hipSetDevice(db->device));
   int rc = CC_OK;
   for (auto &ln : db->lane) {
-    if (!ln.busy) continue;
+    if (!ln.busy || ln.pose) continue;  // (a pose chunk has no cc_query_result_t rows: cc_db_query_wait collects it)
     const cc_query_result_t *lo = ln.h_dst + ln.b0, *hi = lo + ln.nb;
     if (hi <= h_res || lo >= h_res + n) continue;
     const int r2 = lane_finish(db, ln);
@@ -2040,4 +2116,171 @@ int cc_db_verify_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qde
   const int drc = detail_validate(h_detail, "cc_db_verify_batch_host_ranked_detail: h_detail must be given");
   if (drc != CC_OK) return drc;
   return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank, h_detail);
+}
+
+// ---- caller-given relative poses (k_pose.h) ----
+// Item i is correlation problem i of its chunk and reads query record i, which launch_query_prep builds from descriptor q_i (the
+// verify flow's selector).  The chain is prep | cc_k_pose_problems | cc_k_gmm_init | cc_k_pose_select | cc_k_gmm_refine x 2 |
+// cc_k_pose_eval | cc_k_pose_final: no retrieval, no checks, no merge, no cc_k_select / cc_k_final.
+static int pose_validate(const cc_db *db, const cc_scan_desc_t *qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+                         const double *h_try, const cc_pose_result_t *h_res, const double *h_try_corr) {
+  if (!db || !qdesc || !h_items || !cfg || !h_res || n < 0) return set_err(CC_EINVAL, "cc_db_pose: bad argument");
+  if (cfg->refine != 0 && cfg->refine != 1) return set_err(CC_EINVAL, "cc_db_pose: refine must be 0 or 1");
+  if (cfg->min_corr != cfg->min_corr) return set_err(CC_EINVAL, "cc_db_pose: min_corr is NaN (-INFINITY: no bar)");
+  if (cfg->n_try < 0 || cfg->n_try > CC_POSE_TRY_MAX) return set_err(CC_EINVAL, "cc_db_pose: n_try must be within 0..CC_POSE_TRY_MAX");
+  if (cfg->n_try > 0 && (!h_try || !h_try_corr)) return set_err(CC_EINVAL, "cc_db_pose: n_try > 0 needs h_try and h_try_corr");
+  for (int i = 0; i < n; i++) {
+    if (h_items[i].q < 0 || h_items[i].q >= n_desc) return set_err(CC_EINVAL, "cc_db_pose: query descriptor index out of range");
+    if (h_items[i].gidx < 0 || h_items[i].gidx >= db->n_scans) return set_err(CC_EINVAL, "cc_db_pose: database scan not in the DB");
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(h_items[i].tf[k])) return set_err(CC_EINVAL, "cc_db_pose: a start pose has a non-finite component");
+  }
+  for (size_t k = 0; k < (size_t)n * cfg->n_try * 3; k++)
+    if (!std::isfinite(h_try[k])) return set_err(CC_EINVAL, "cc_db_pose: a try pose has a non-finite component");
+  return CC_OK;
+}
+
+int cc_db_pose_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+                      const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream_) {
+  {  // everything that can be refused is refused before anything is queued or collected
+    const int vrc = pose_validate(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr);
+    if (vrc != CC_OK) return vrc;
+  }
+  DB_POISON_CHK(db, "cc_db_pose_submit");
+  if (n == 0) return CC_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(db->device));
+  const int nt = cfg->n_try;
+  const bool refine = cfg->refine != 0, curv = h_curv != nullptr;
+  // chunks over the lanes exactly as cc_db_verify_submit cuts its batch (the comments at cc_db_query_submit)
+  hipEvent_t e_start = db->lane[0].done;
+  HIPCHK(hipEventRecord(e_start, stream));
+  for (int i = 0; i < db->n_lanes; i++) {
+    HIPCHK(hipStreamWaitEvent(db->lane[i].stream, e_start, 0));
+    if (db->add_done) HIPCHK(hipStreamWaitEvent(db->lane[i].stream, db->add_done, 0));  // an append queued on another stream
+  }
+  int rc = CC_OK;
+  int qb = (((n + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
+  if (!db->sync_call && n >= db->qb_max) qb = db->qb_max;
+  qb = qb > db->tune.chunk ? db->tune.chunk : qb;
+#define LANE_CHK(call)                        \
+  do {                                        \
+    hipError_t e_ = (call);                   \
+    if (e_ != hipSuccess) {                   \
+      lane_abort(db, ln);                     \
+      return set_err(CC_EHIP, #call, e_);     \
+    }                                         \
+  } while (0)
+  for (int b0 = 0; b0 < n && rc == CC_OK; b0 += qb) {
+    const int nb = n - b0 < qb ? n - b0 : qb;
+    cc_qlane &ln = db->lane[db->next_lane];
+    db->next_lane = (db->next_lane + 1) % db->n_lanes;
+    rc = lane_finish(db, ln);
+    if (rc != CC_OK) break;
+    rc = lane_alloc_pose(ln);
+    if (rc != CC_OK) break;
+    hipStream_t ls = ln.stream;
+    // the chunk's tables, packed: items [nb] | try poses [nb][nt][3] | selector [nb]
+    cc_pose_item_t *h_it = (cc_pose_item_t *)ln.h_pin;
+    double *h_tp = (double *)(h_it + nb);
+    int *h_sel = (int *)(h_tp + (size_t)nb * nt * 3);
+    memcpy(h_it, h_items + b0, sizeof(cc_pose_item_t) * (size_t)nb);
+    if (nt > 0) memcpy(h_tp, h_try + (size_t)b0 * nt * 3, sizeof(double) * (size_t)nb * nt * 3);
+    for (int i = 0; i < nb; i++) h_sel[i] = h_items[b0 + i].q;
+    const cc_pose_item_t *d_it = (const cc_pose_item_t *)ln.d_pin;
+    const double *d_tp = (const double *)(d_it + nb);
+    const int *d_sel = (const int *)(d_tp + (size_t)nb * nt * 3);
+    ln.profiled = db->prof && (db->prof_tick++ % db->prof_every) == 0;
+    hipEvent_t *ev = ln.profiled ? ln.pev : nullptr;
+    const bool zc = nb <= CC_ZC_MAX;  // the kernels write the rows of a small chunk straight into the lane's pinned buffer
+    cc_pose_result_t *o_res = (cc_pose_result_t *)(zc ? ln.h_pout : ln.d_pout);
+    double *o_try = (double *)(o_res + nb);
+    cc_pose_curv_t *o_curv = (cc_pose_curv_t *)(o_try + (size_t)nb * nt);
+    LANE_CHK(hipMemcpyAsync(ln.d_pin, ln.h_pin, CC_POSE_IN_BYTES(nb, nt), hipMemcpyHostToDevice, ls));
+    rc = launch_query_prep(db, ln, d_qdesc, nb, false, d_sel);
+    if (rc != CC_OK) {
+      lane_abort(db, ln);
+      break;
+    }
+    // the caller's stream goes on once the descriptors have been read
+    LANE_CHK(hipEventRecord(ln.prep, ls));
+    LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
+    if (ev) LANE_CHK(hipEventRecord(ev[0], ls));
+    hipLaunchKernelGGL(cc_k_pose_problems, dim3((nb + 255) / 256), dim3(256), 0, ls, d_it, nb, ln.d_prob, ln.d_prob_list, ln.d_nprob);
+    if (ev) {
+      LANE_CHK(hipEventRecord(ev[1], ls));
+      LANE_CHK(hipEventRecord(ev[2], ls));
+      LANE_CHK(hipEventRecord(ev[3], ls));
+    }
+    hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
+                       (const int *)ln.d_nprob, (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, ln.d_gres,
+                       cc_gmm_code_pool{ln.d_codes, ln.code_cap, ln.d_heads + 9, ln.d_nprob + 3, ln.pool_cap});
+    if (refine) {  // (else the list counters stay zero: nothing reads them)
+      hipLaunchKernelGGL(cc_k_pose_select, dim3((nb + 63) / 64), dim3(64), 0, ls, nb, cfg->min_corr, (const cc_gmm_result *)ln.d_gres, ln.d_sel, ln.prob_cap,
+                         ln.d_nprob + 1, ln.d_heads + 8, ln.d_sel + 3 * (size_t)ln.prob_cap, ln.d_heads + 12, ln.d_nprob + 3, ln.d_pool_off);
+      hipLaunchKernelGGL(cc_k_gmm_refine<16>, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1),
+                         (const int *)ln.d_sel, (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap), (const int *)(ln.d_nprob + 2),
+                         (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, cfg->min_corr, ln.d_pool,
+                         ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes, (const int *)nullptr, (const int *)nullptr, 0);
+      hipLaunchKernelGGL(cc_k_gmm_refine<64>, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 2),
+                         (const int *)(ln.d_sel + ln.prob_cap), (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap),
+                         (const int *)(ln.d_nprob + 1), (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, cfg->min_corr,
+                         ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
+                         (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
+    }
+    if (nt > 0 || curv) {
+      const int grid = nb < db->tune.gmm64 ? nb : db->tune.gmm64;
+      hipLaunchKernelGGL(cc_k_pose_eval, dim3(grid), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list, (const int *)ln.d_nprob,
+                         (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, (const cc_gmm_result *)ln.d_gres, (const unsigned *)ln.d_codes, nt,
+                         d_tp, o_try, curv ? o_curv : (cc_pose_curv_t *)nullptr);
+    }
+    if (ev) LANE_CHK(hipEventRecord(ev[4], ls));
+    hipLaunchKernelGGL(cc_k_pose_final, dim3((nb + 255) / 256), dim3(256), 0, ls, d_it, nb, (const cc_gmm_result *)ln.d_gres, o_res, (const int *)ln.d_nprob,
+                       zc ? ln.h_nprob : (int *)nullptr);
+    if (ev) LANE_CHK(hipEventRecord(ev[5], ls));
+    LANE_CHK(hipGetLastError());
+    if (!zc) {
+      LANE_CHK(hipMemcpyAsync(ln.h_pout, ln.d_pout, CC_POSE_OUT_BYTES(nb, nt, curv), hipMemcpyDeviceToHost, ls));
+      LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
+    }
+    LANE_CHK(hipEventRecord(ln.fin, ls));
+    for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];  // (a pose chunk reads no sorted view)
+    ln.busy = true;
+    ln.pose = true;
+    ln.b0 = b0;
+    ln.nb = nb;
+    ln.pose_res = h_res;
+    ln.pose_try = nt > 0 ? h_try_corr : nullptr;
+    ln.pose_curv = h_curv;
+    ln.pose_ntry = nt;
+  }
+#undef LANE_CHK
+  return rc;
+}
+
+int cc_db_pose_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+                     const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream_) {
+  {  // a refused call leaves the chunks in flight where they are
+    const int vrc = pose_validate(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr);
+    if (vrc != CC_OK) return vrc;
+  }
+  db->sync_call = true;
+  const int rc = cc_db_pose_submit(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, stream_);
+  db->sync_call = false;
+  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
+  return rc != CC_OK ? rc : r2;
+}
+
+int cc_db_pose_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+                          const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv) {
+  {
+    const int vrc = pose_validate(db, h_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr);
+    if (vrc != CC_OK) return vrc;
+  }
+  if (n == 0) return CC_OK;
+  HIPCHK(hipSetDevice(db->device));
+  const int rc = stage_reserve(db, n_desc);
+  if (rc != CC_OK) return rc;
+  HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)n_desc, hipMemcpyHostToDevice));
+  return cc_db_pose_batch(db, db->d_stage, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, nullptr);
 }

@@ -29,6 +29,7 @@
 #include "k_gmm.h"
 #include "k_gmm_hess.h"
 #include "k_verify.h"
+#include "k_pose.h"
 #include "cc_hostdb.h"
 
 #ifndef CC_INGEST_BLOCK

@@ -503,6 +503,78 @@ class ContourDB {
     }
     return r.n_res;
   }
+  // Mirror-only as a database call: ConstellCorrelation's public interface (correlation.h:175-238) on scans of this database,
+  // in one device pass (cc_db_pose_batch_host).  Per query: the candidate by its index in adding order (as verifyCandidates
+  // takes it), the relative pose the caller believes in, and further poses to probe over the pair set of T_init.
+  //   corr_init = initProblem(cand, cm_tgt, T_init);  try_corr[t] = tryProblem(T_try[t]);  correlation, T_best = calcCorrelation()
+  // on the queries with pairs whose corr_init is not below min_corr (refine; else corr_init and T_init, flags without CC_PF_REFINED);
+  // hess / grad: the curvature of -correlation at T_best (cc_pose_curv_t).  Every query carries as many T_try as the longest
+  // list of the call needs the device to evaluate (at most CC_POSE_TRY_MAX); shorter lists are padded with T_init.
+  struct PoseQuery {
+    int cand = 0;
+    Eigen::Isometry2d T_init = Eigen::Isometry2d::Identity();
+    std::vector<Eigen::Isometry2d> T_try;
+  };
+  struct PoseScore {
+    double corr_init = 0, correlation = 0;
+    Eigen::Isometry2d T_best = Eigen::Isometry2d::Identity();
+    int n_pairs = 0, iterations = 0, termination = 0, flags = 0;
+    std::vector<double> try_corr;
+    double hess[6] = {0, 0, 0, 0, 0, 0}, grad[3] = {0, 0, 0};
+  };
+  std::vector<PoseScore> scorePoses(const std::shared_ptr<const ContourManager> &cm_tgt, const std::vector<PoseQuery> &queries,
+                                    bool refine = true, float min_corr = 0.3f) const {
+    std::vector<PoseScore> out(queries.size());
+    if (queries.empty()) return out;
+    size_t nt = 0;
+    for (const auto &pq : queries) {
+      CC_CHECK(pq.cand >= 0 && pq.cand < (int)all_bevs_.size());  // (scans appended ahead of the driver are not the caller's yet)
+      CC_CHECK(pq.T_try.size() <= (size_t)CC_POSE_TRY_MAX);
+      nt = std::max(nt, pq.T_try.size());
+    }
+    ensure(*cm_tgt);
+    if (need_rebuild_) rebuild();
+    const auto tf_of = [](const Eigen::Isometry2d &T, double *o) {
+      o[0] = T(0, 2);
+      o[1] = T(1, 2);
+      o[2] = std::atan2(T(1, 0), T(0, 0));
+    };
+    const int n = (int)queries.size();
+    std::vector<cc_pose_item_t> items(n);
+    std::vector<double> tries((size_t)n * nt * 3), tc((size_t)n * nt);
+    for (int i = 0; i < n; i++) {
+      items[i].q = 0;
+      items[i].gidx = queries[i].cand;
+      tf_of(queries[i].T_init, items[i].tf);
+      for (size_t t = 0; t < nt; t++) tf_of(t < queries[i].T_try.size() ? queries[i].T_try[t] : queries[i].T_init, &tries[((size_t)i * nt + t) * 3]);
+    }
+    cc_pose_cfg_t pc;
+    pc.refine = refine ? 1 : 0;
+    pc.min_corr = min_corr;
+    pc.n_try = (int)nt;
+    pc.pad_ = 0;
+    std::vector<cc_pose_result_t> res(n);
+    std::vector<cc_pose_curv_t> cv(n);
+    const int rc = cc_db_pose_batch_host(db_, &cm_tgt->desc(), 1, items.data(), n, &pc, nt ? tries.data() : nullptr, res.data(),
+                                         nt ? tc.data() : nullptr, cv.data());
+    for (auto &sp : spec_) sp.collected = true;  // the synchronous call collected every chain in flight
+    if (rc != CC_OK) die_cc();
+    for (int i = 0; i < n; i++) {
+      PoseScore &o = out[i];
+      o.corr_init = res[i].corr_init;
+      o.correlation = res[i].correlation;
+      o.T_best.rotate(res[i].tf[2]);
+      o.T_best.pretranslate(res[i].tf[0], res[i].tf[1]);
+      o.n_pairs = res[i].n_pairs;
+      o.iterations = res[i].iterations;
+      o.termination = res[i].termination;
+      o.flags = res[i].flags;
+      o.try_corr.assign(tc.begin() + (size_t)i * nt, tc.begin() + (size_t)i * nt + queries[i].T_try.size());
+      std::copy(cv[i].hess, cv[i].hess + 6, o.hess);
+      std::copy(cv[i].grad, cv[i].grad + 3, o.grad);
+    }
+    return out;
+  }
   // contour_db.h:814 and :827
   void addScan(const std::shared_ptr<ContourManager> &added, double curr_timestamp) {
     ensure(*added);

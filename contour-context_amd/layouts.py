@@ -91,6 +91,32 @@ def hess_matrix(h6):
     return np.array([[h[0], h[1], h[2]], [h[1], h[3], h[4]], [h[2], h[4], h[5]]])
 
 
+# caller-given relative poses (cc_db_pose_*): cc_pose_item_t, cc_pose_result_t, cc_pose_curv_t, cc_pose_cfg_t
+POSE_TRY_MAX = 8      # CC_POSE_TRY_MAX
+PF_REFINED = 0x100    # CC_PF_REFINED
+pose_item_dt = np.dtype([("q", "<i4"), ("gidx", "<i4"), ("tf", "<f8", (3,))], align=True)
+pose_result_dt = np.dtype([("corr_init", "<f8"), ("correlation", "<f8"), ("tf", "<f8", (3,)), ("n_pairs", "<i4"), ("iterations", "<i4"),
+                           ("termination", "<i4"), ("flags", "<i4"), ("pad_", "<i4", (2,))], align=True)
+pose_curv_dt = np.dtype([("hess", "<f8", (6,)), ("grad", "<f8", (3,))], align=True)
+assert pose_item_dt.itemsize == 32 and pose_result_dt.itemsize == 64 and pose_curv_dt.itemsize == 72
+
+
+class PoseCfg(C.Structure):  # cc_pose_cfg_t
+    _fields_ = [("refine", C.c_int32), ("min_corr", C.c_float), ("n_try", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(PoseCfg) == 16
+
+
+def pose_items(q, gidx, tf):
+    """[n] of pose_item_dt from the descriptor indices, the database scans and the start poses [n, 3]"""
+    q = np.asarray(q, np.int32).reshape(-1)
+    it = np.zeros(len(q), pose_item_dt)
+    it["q"], it["gidx"] = q, np.asarray(gidx, np.int32).reshape(-1)
+    it["tf"] = np.asarray(tf, np.float64).reshape(len(q), 3)
+    return it
+
+
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
 

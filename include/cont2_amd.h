@@ -761,6 +761,76 @@ int cc_db_check_hints_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdes
                                          const cc_score_t *thres_lb, const cc_score_t *thres_ub, int max_fine_opt, cc_query_result_t *h_res,
                                          cc_hint_score_t *h_scores, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
 
+/* ---- caller-given relative poses: score, probe and refine (ConstellCorrelation's public interface, correlation.h:175-238) ----
+ * Every entry point above takes the start pose of a correlation problem from a constellation that passed the four gates.  These
+ * take it from the caller: item i = (q, gidx, tf) is the query scan d_qdesc[q] (tgt) against the database scan gidx (src, any
+ * index below cc_db_size, searchable or not) at T_init = tf = (x, y, theta), BEV pixels / radians as cc_query_result_t.tf.
+ * Several items may name the same descriptor or the same database scan.  Nothing is gated, merged or sorted: item i in, row i
+ * out.  Per item:
+ *   corr_init    initProblem(src, tgt, T_init): the ellipse pairs are selected at T_init (correlation.h:85-96) and summed there
+ *   n_pairs      the selected pairs; flags carries the problem's CC_QF_GMM_CAP / CC_QF_DESC_CAP bits, as a ranked entry does
+ *   correlation, tf, iterations, termination
+ *                calcCorrelation() from T_init (theta reported as atan2(sin, cos)) and the CC_PF_REFINED bit, when cfg->refine
+ *                is 1, n_pairs > 0 and !((float)corr_init < cfg->min_corr) -- the test of contour_db.h:552-556 with the bar
+ *                given by the caller (-INFINITY: every item that has pairs).  Otherwise correlation is corr_init bit for bit,
+ *                tf is T_init with the angle wrapped, iterations and termination are 0 and the bit is clear.
+ *   try_corr     h_try_corr[i][t] = tryProblem(h_try[i][t]) for cfg->n_try poses per item: -cost(T_try) / sqrt(ac_src ac_tgt)
+ *                over THE PAIR SET OF T_init (the refinement does not change that set; a T_try far from T_init "will cause
+ *                problems", as the reference warns: the caller's business).  A problem without pairs gives 0.
+ *   curvature    h_curv[i] (optional): Hessian and gradient of f = -correlation at the returned tf (at T_init for an item that
+ *                was not refined): function, order and normalisation of cc_ranked_detail_t.hess / grad.  Zeros without pairs.
+ * No threshold other than min_corr plays a role; cc_db_set_dynamic_thres does not apply.
+ *
+ * Refused with CC_EINVAL before anything is queued or collected (the handle and the chunks in flight stay untouched): NULL db,
+ * d_qdesc, h_items, cfg or h_res; n < 0 (n == 0 is CC_OK); q outside [0, n_desc); gidx outside [0, cc_db_size); a non-finite
+ * component of a tf or a try pose; refine other than 0 / 1; a NaN min_corr; n_try outside 0..CC_POSE_TRY_MAX; n_try > 0 with
+ * h_try or h_try_corr NULL.
+ *
+ * Streaming: as cc_db_verify_submit -- chunks over the lanes (at most 1024 items each, 256 on a database with nnk > CC_KNN_MAX),
+ * which wait for the last append on the device; the caller's stream continues once the descriptors are read; cc_db_query_wait
+ * collects pose chunks too, and every output buffer must stay valid until then.  cc_db_query_collect is keyed by
+ * cc_query_result_t ranges and does NOT see pose chunks.  CC_ECAPACITY as for queries (a flagged row, a pool that overflowed:
+ * all rows are still delivered).  With cc_db_profile_enable the problem-building kernel lands in ms_out[0], slots 1 and 2 stay
+ * zero, the correlation kernels (with the evaluation of the try poses and the curvature) in ms_out[3], the output kernel in
+ * ms_out[4]. */
+#define CC_POSE_TRY_MAX 8
+#define CC_PF_REFINED 0x100 /* cc_pose_result_t.flags: the item was refined (beside the CC_QF_GMM_CAP / CC_QF_DESC_CAP bits) */
+typedef struct {
+  int32_t q, gidx; /* descriptor index (tgt), database scan (src) */
+  double tf[3];    /* T_init = (x, y, theta)                      */
+} cc_pose_item_t; /* 32 bytes */
+typedef struct {
+  int32_t refine; /* 1: run calcCorrelation() on the items that pass min_corr, 0: initProblem / tryProblem only */
+  float min_corr; /* items with (float)corr_init below it are not refined; -INFINITY: no bar                   */
+  int32_t n_try;  /* try poses per item, 0..CC_POSE_TRY_MAX (one count per call)                                */
+  int32_t pad_;
+} cc_pose_cfg_t;
+typedef struct {
+  double corr_init, correlation, tf[3];
+  int32_t n_pairs, iterations, termination, flags;
+  int32_t pad_[2];
+} cc_pose_result_t; /* 64 bytes */
+typedef struct {
+  double hess[6], grad[3]; /* as cc_ranked_detail_t.hess / grad */
+} cc_pose_curv_t; /* 72 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cc_pose_item_t) == 32 && sizeof(cc_pose_result_t) == 64 && sizeof(cc_pose_curv_t) == 72, "pose records");
+#else
+_Static_assert(sizeof(cc_pose_item_t) == 32 && sizeof(cc_pose_result_t) == 64 && sizeof(cc_pose_curv_t) == 72, "pose records");
+#endif
+/* h_try: [n][n_try][3] or NULL; h_try_corr: [n][n_try] or NULL; h_curv: [n] or NULL (curvature not wanted) */
+int cc_db_pose_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n,
+                      const cc_pose_cfg_t *cfg, const double *h_try, cc_pose_result_t *h_res, double *h_try_corr,
+                      cc_pose_curv_t *h_curv, void *stream);
+/* submit + cc_db_query_wait */
+int cc_db_pose_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n,
+                     const cc_pose_cfg_t *cfg, const double *h_try, cc_pose_result_t *h_res, double *h_try_corr,
+                     cc_pose_curv_t *h_curv, void *stream);
+/* ... with host descriptors: one H2D copy of them, like cc_db_verify_batch_host */
+int cc_db_pose_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const cc_pose_item_t *h_items, int n,
+                          const cc_pose_cfg_t *cfg, const double *h_try, cc_pose_result_t *h_res, double *h_try_corr,
+                          cc_pose_curv_t *h_curv);
+
 /* Parity / debug: the constellations of the LAST cc_db_check_hints[_host] call that passed all four gates, in hint
  * order: the pose getTFFromConstell returned for each (contour_mng.h:1246-1277, before any proposal merging) and the
  * constellation it was computed from, so that a test can redo the rigid fit independently (e.g. with an SVD). */
