@@ -27,7 +27,24 @@ struct ScanLite {
 
 }  // namespace
 
-#define CC_N_HEADS 24  // a query lane's list heads (cc_qlane::d_heads)
+#define CC_N_HEADS 24  // a query lane's list heads (cc_qlane::d_heads): one allocation, so that one kernel (cc_k_pack_hot) clears all
+enum cc_head_slot {    // what the chain's kernels count in them (cc_qlane::head)
+  CC_HD_NPROB = 0,     // correlation problems of the chunk
+  CC_HD_NSEL16 = 1,    // ... of which the 16-lane refinement instance takes this many
+  CC_HD_NSEL64 = 2,    // ... and the 64-lane instance this many
+  CC_HD_POOL = 3,      // head of the pair pool (d_pool)
+  CC_HD_CNT = 4,       // [4] list heads of the checks (CC_CNT_*)
+  CC_HD_NMID = 8,      // length of the in-between refinement list
+  CC_HD_CODES = 9,     // head of the pair-code pool (d_codes)
+  CC_HD_CLS = 12,      // [CC_GMM_NCLS] the long refinement problems by length class
+};
+static_assert(CC_HD_CLS + CC_GMM_NCLS <= CC_N_HEADS, "the class counts are the last slots of a lane's list heads");
+enum cc_sel_list {  // the sub-lists of cc_qlane::d_sel, prob_cap entries each (cc_qlane::sel)
+  CC_SEL_16 = 0,    // problems of the 16-lane refinement instance
+  CC_SEL_64 = 1,    // (unused: the long problems are listed by class)
+  CC_SEL_MID = 2,   // the in-between list, shared by both instances
+  CC_SEL_CLS = 3,   // [CC_GMM_NCLS] problems of the 64-lane instance by length class
+};
 // full descriptor -> hot record.  grid = n scans, block = 256
 __global__ void __launch_bounds__(256)
 cc_k_pack_hot(const cc_scan_desc_t *__restrict__ desc, int n, cc_hot_desc_t *__restrict__ hot,
@@ -98,8 +115,9 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   int *d_redo = nullptr;              // [QB * CC_CHK_STRIDE] indices of the checks left to the large B1 instance
   cc_cstl_item *d_cstl = nullptr;     // [QB * CC_CHK_STRIDE] constellation record of check i (n_in = 0: did not pass the window test)
   int *d_cstl_idx = nullptr;          // [QB * CC_CHK_STRIDE] dense list of the records that did
-  int *d_heads = nullptr;             // [CC_N_HEADS]: d_nprob[4] | d_cnt[4] | n_sel of the in-between refinement list | head of the pair-code pool | - | - | counts of the long refinement problems by length class [CC_GMM_NCLS] | -; one allocation so that one kernel clears all
-  int *d_cnt = nullptr;               // [4] list heads (CC_CNT_*)
+  int *d_heads = nullptr;             // [CC_N_HEADS] the chunk's list heads, by cc_head_slot
+  int *head(int slot) const { return d_heads + slot; }
+  int *d_cnt = nullptr;               // [4] list heads (CC_CNT_*) = head(CC_HD_CNT)
   cc_pass_rec *d_pass = nullptr;      // [QB][CC_CHK_STRIDE] dense, index = candidate iteration order
   unsigned char *d_pass_ok = nullptr; // [QB][CC_CHK_STRIDE]
   cc_cand_post *d_cpost = nullptr;    // [QB][CC_MAXCAND] dynamic thresholds only (cc_db_set_dynamic_thres): post-bar inputs per problem
@@ -107,12 +125,13 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   int *d_pass_cnt = nullptr;
   cc_cand_out *d_cands = nullptr;     // [QB][CC_MAXCAND]
   cc_qstate *d_qstate = nullptr;
-  int *d_nprob = nullptr;             // [4]: problems | refined by the 16-lane instance | by the 64-lane instance | pool head
+  int *d_nprob = nullptr;             // = head(CC_HD_NPROB); its first four slots (problems | 16-lane | 64-lane | pool head) go back to h_nprob
   cc_query_result_t *d_results = nullptr;
   cc_gmm_problem *d_prob = nullptr;   // [QB][CC_MAXCAND] problem of candidate k of query q
   int *d_prob_list = nullptr;         // [QB * CC_MAXCAND] dense list of the problems that exist
   cc_gmm_result *d_gres = nullptr;
-  int *d_sel = nullptr;               // [3][prob_cap] GMM problems that get the L-BFGS refinement, by instance
+  int *d_sel = nullptr;               // [3 + CC_GMM_NCLS][prob_cap] GMM problems that get the L-BFGS refinement, by cc_sel_list
+  int *sel(int list) const { return d_sel + (size_t)list * prob_cap; }
   char *d_pool = nullptr;             // [pool_cap] records of CC_GRAW_BYTES: pair lists of the refined problems (what does not stay in LDS)
   int *d_pool_off = nullptr;          // [prob_cap] where a selected problem's records go in d_pool (cc_k_select)
   unsigned *d_codes = nullptr;        // [code_cap] pair-code segments of every correlation problem of the chunk (cc_k_gmm_init -> cc_k_gmm_refine)
@@ -345,97 +364,51 @@ static int lane_env_int(const char *name, int lo, int hi, int dflt) {
   const int v = atoi(e);
   return v >= lo && v <= hi ? v : dflt;
 }
-// the dynamic-threshold buffers of a lane (19 MB at QB = 1 024): allocated once the mode is first switched on
-// (both or neither: a failed call leaves the lane without them, and the next call tries again)
-static int lane_alloc_dyn(cc_qlane &ln) {
-  if (ln.d_tidy) return CC_OK;
-  const size_t n = (size_t)cc_db::QB * CC_MAXCAND;
-  hipError_t e = hipMalloc(&ln.d_cpost, sizeof(cc_cand_post) * n);
-  if (e == hipSuccess) {
-    e = hipMalloc(&ln.d_tidy, n);
-    if (e != hipSuccess) {
-      hipFree(ln.d_cpost);
-      ln.d_cpost = nullptr;
-    }
-  } else {
-    ln.d_cpost = nullptr;
+// One buffer of the sets a lane gets on demand (below): allocated when it is not there yet.  A failed pointer stays null, so the
+// next call tries again.  `who`: the set's function, for the message.
+static int lane_buf(void **p, size_t bytes, bool pinned, const char *who) {
+  if (*p) return CC_OK;
+  const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+  if (e == hipSuccess) return CC_OK;
+  *p = nullptr;
+  return set_err(CC_EHIP, (std::string(who) + (pinned ? ": hipHostMalloc" : ": hipMalloc")).c_str(), e);
+}
+#define LANE_BUF(ptr, bytes, pinned)                                         \
+  {                                                                          \
+    const int brc_ = lane_buf((void **)&(ptr), bytes, pinned, __func__);     \
+    if (brc_ != CC_OK) return brc_;                                          \
   }
-  return e == hipSuccess ? CC_OK : set_err(CC_EHIP, "lane_alloc_dyn: hipMalloc", e);
+// the dynamic-threshold buffers of a lane (19 MB at QB = 1 024): allocated once the mode is first switched on
+// (d_tidy last: where it exists, both do; a failed call leaves the lane without it, and the next call tries again)
+static int lane_alloc_dyn(cc_qlane &ln) {
+  const size_t n = (size_t)cc_db::QB * CC_MAXCAND;
+  LANE_BUF(ln.d_cpost, sizeof(cc_cand_post) * n, false);
+  LANE_BUF(ln.d_tidy, n, false);
+  return CC_OK;
 }
 // the item table of a lane's verify chunks (36 KB), allocated with the lane's first one
 static int lane_alloc_verify(cc_qlane &ln) {
-  if (ln.d_vin) return CC_OK;
   const size_t bytes = sizeof(int) * (size_t)cc_db::QB * (1 + CC_VERIFY_CANDS_MAX);
-  if (!ln.h_vin) {
-    const hipError_t e = hipHostMalloc((void **)&ln.h_vin, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      ln.h_vin = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_verify: hipHostMalloc", e);
-    }
-  }
-  const hipError_t e = hipMalloc(&ln.d_vin, bytes);
-  if (e != hipSuccess) {
-    ln.d_vin = nullptr;
-    return set_err(CC_EHIP, "lane_alloc_verify: hipMalloc", e);
-  }
+  LANE_BUF(ln.h_vin, bytes, true);
+  LANE_BUF(ln.d_vin, bytes, false);
   return CC_OK;
 }
 // the tables of a lane's pose chunks (2 x 228 KB in, 2 x 200 KB out), allocated with the lane's first one
 #define CC_POSE_IN_BYTES(nb, n_try) ((size_t)(nb) * (sizeof(cc_pose_item_t) + (size_t)(n_try) * 3 * sizeof(double) + sizeof(int)))
 #define CC_POSE_OUT_BYTES(nb, n_try, curv) ((size_t)(nb) * (sizeof(cc_pose_result_t) + (size_t)(n_try) * sizeof(double) + ((curv) ? sizeof(cc_pose_curv_t) : 0)))
 static int lane_alloc_pose(cc_qlane &ln) {
-  if (ln.d_pin && ln.d_pout) return CC_OK;
   const size_t bin = CC_POSE_IN_BYTES(cc_db::QB, CC_POSE_TRY_MAX), bout = CC_POSE_OUT_BYTES(cc_db::QB, CC_POSE_TRY_MAX, true);
-  if (!ln.h_pin) {
-    const hipError_t e = hipHostMalloc((void **)&ln.h_pin, bin, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      ln.h_pin = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_pose: hipHostMalloc", e);
-    }
-  }
-  if (!ln.h_pout) {
-    const hipError_t e = hipHostMalloc((void **)&ln.h_pout, bout, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      ln.h_pout = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_pose: hipHostMalloc", e);
-    }
-  }
-  if (!ln.d_pin) {
-    const hipError_t e = hipMalloc(&ln.d_pin, bin);
-    if (e != hipSuccess) {
-      ln.d_pin = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_pose: hipMalloc", e);
-    }
-  }
-  if (!ln.d_pout) {
-    const hipError_t e = hipMalloc(&ln.d_pout, bout);
-    if (e != hipSuccess) {
-      ln.d_pout = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_pose: hipMalloc", e);
-    }
-  }
+  LANE_BUF(ln.h_pin, bin, true);
+  LANE_BUF(ln.h_pout, bout, true);
+  LANE_BUF(ln.d_pin, bin, false);
+  LANE_BUF(ln.d_pout, bout, false);
   return CC_OK;
 }
 // the list buffers of a lane's ranked chunks (2 x 640 KB), allocated with the lane's first one
 static int lane_alloc_rank(cc_qlane &ln) {
-  if (ln.d_rank) return CC_OK;
   const size_t bytes = sizeof(cc_ranked_cand_t) * (size_t)cc_db::QB * CC_RANK_MAX;
-  if (!ln.h_rank) {
-    const hipError_t e = hipHostMalloc((void **)&ln.h_rank, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      ln.h_rank = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_rank: hipHostMalloc", e);
-    }
-  }
-  const hipError_t e = hipMalloc(&ln.d_rank, bytes);
-  if (e != hipSuccess) {
-    ln.d_rank = nullptr;
-    return set_err(CC_EHIP, "lane_alloc_rank: hipMalloc", e);
-  }
-  return CC_OK;
-}
-static int rank_validate(const cc_rank_out_t *rank, const char *what) {
-  if (!rank || !rank->h_cands || !rank->h_n || rank->max_ret < 1 || rank->max_ret > CC_RANK_MAX) return set_err(CC_EINVAL, what);
+  LANE_BUF(ln.h_rank, bytes, true);
+  LANE_BUF(ln.d_rank, bytes, false);
   return CC_OK;
 }
 // the buffers of a lane's detail chunks (2 x 1.9 MB and the Hessian records, 72 B per problem slot), allocated with the lane's
@@ -444,31 +417,18 @@ static int lane_alloc_detail(cc_qlane &ln) {
   if (ln.d_detail && ln.d_hess) return CC_OK;
   if (ln.prob_cap <= 0) return set_err(CC_EHIP, "lane_alloc_detail: the lane has no problem buffers");
   const size_t bytes = sizeof(cc_ranked_detail_t) * (size_t)cc_db::QB * CC_RANK_MAX;
-  if (!ln.h_detail) {
-    const hipError_t e = hipHostMalloc((void **)&ln.h_detail, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      ln.h_detail = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_detail: hipHostMalloc", e);
-    }
-  }
-  if (!ln.d_hess) {
-    const hipError_t e = hipMalloc(&ln.d_hess, sizeof(cc_gmm_hess) * (size_t)ln.prob_cap);
-    if (e != hipSuccess) {
-      ln.d_hess = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_detail: hipMalloc", e);
-    }
-  }
-  if (!ln.d_detail) {
-    const hipError_t e = hipMalloc(&ln.d_detail, bytes);
-    if (e != hipSuccess) {
-      ln.d_detail = nullptr;
-      return set_err(CC_EHIP, "lane_alloc_detail: hipMalloc", e);
-    }
-  }
+  LANE_BUF(ln.h_detail, bytes, true);
+  LANE_BUF(ln.d_hess, sizeof(cc_gmm_hess) * (size_t)ln.prob_cap, false);
+  LANE_BUF(ln.d_detail, bytes, false);
   return CC_OK;
 }
-static int detail_validate(const cc_ranked_detail_t *h_detail, const char *what) {
-  if (!h_detail) return set_err(CC_EINVAL, what);
+#undef LANE_BUF
+// The refusals of the *_ranked / *_ranked_detail entry points, worded with the entry point's name (`fn`).  need_detail: the
+// call is a *_ranked_detail one.
+static int want_ranked(const char *fn, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail, bool need_detail) {
+  if (!rank || !rank->h_cands || !rank->h_n || rank->max_ret < 1 || rank->max_ret > CC_RANK_MAX)
+    return set_err(CC_EINVAL, (std::string(fn) + ": rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX").c_str());
+  if (need_detail && !detail) return set_err(CC_EINVAL, (std::string(fn) + ": h_detail must be given").c_str());
   return CC_OK;
 }
 // a collected chunk's lists: rows [b0, b0 + nb) of the caller's arrays
@@ -507,8 +467,8 @@ static int lane_alloc(cc_db *db, cc_qlane &ln) {
   LN_CHK(hipMalloc(&ln.d_cstl, sizeof(cc_cstl_item) * (size_t)QB * CC_CHK_STRIDE));
   LN_CHK(hipMalloc(&ln.d_cstl_idx, sizeof(int) * (size_t)QB * CC_CHK_STRIDE));
   LN_CHK(hipMalloc(&ln.d_heads, sizeof(int) * CC_N_HEADS));  // the chunk's list heads, cleared together by the prep kernel
-  ln.d_nprob = ln.d_heads;
-  ln.d_cnt = ln.d_heads + 4;
+  ln.d_nprob = ln.head(CC_HD_NPROB);
+  ln.d_cnt = ln.head(CC_HD_CNT);
   LN_CHK(hipMalloc(&ln.d_pass, sizeof(cc_pass_rec) * (size_t)QB * CC_CHK_STRIDE));
   LN_CHK(hipMalloc(&ln.d_pass_ok, (size_t)QB * CC_CHK_STRIDE));
   LN_CHK(hipMalloc(&ln.d_pass_cnt, sizeof(int) * QB * 4));
@@ -519,7 +479,7 @@ static int lane_alloc(cc_db *db, cc_qlane &ln) {
   LN_CHK(hipMalloc(&ln.d_prob, sizeof(cc_gmm_problem) * (size_t)ln.prob_cap));
   LN_CHK(hipMalloc(&ln.d_prob_list, sizeof(int) * (size_t)ln.prob_cap));
   LN_CHK(hipMalloc(&ln.d_gres, sizeof(cc_gmm_result) * (size_t)ln.prob_cap));
-  LN_CHK(hipMalloc(&ln.d_sel, sizeof(int) * (3 + CC_GMM_NCLS) * (size_t)ln.prob_cap));  // small | (unused: the long problems are listed by class) | in-between | classes
+  LN_CHK(hipMalloc(&ln.d_sel, sizeof(int) * (3 + CC_GMM_NCLS) * (size_t)ln.prob_cap));  // the lists of cc_sel_list
   // pair lists of the refined correlation problems come from one pool per lane (80 B per pair: 640 MiB at 8192 pairs per
   // query of a full chunk; measured use: ~600 per query on the dense world, ~1 700 on the KITTI-shaped one).  Overflow is reported (CC_ECAPACITY), never
   // truncated.  CC_GMM_POOL_PAIRS overrides the size in pairs (a test forces the overflow with it).
@@ -608,19 +568,13 @@ int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db 
     DB_CHK(hipHostMalloc((void **)&db->h_add_small[i], sizeof(int) * (size_t)CC_ZC_MAX * 64, hipHostMallocDefault));
     DB_CHK(hipEventCreateWithFlags(&db->add_small_ev[i], hipEventDisableTiming));
   }
-  auto env_int = [](const char *name, int lo, int hi, int dflt) {
-    const char *e = getenv(name);
-    if (!e) return dflt;
-    const int v = atoi(e);
-    return v >= lo && v <= hi ? v : dflt;
-  };
-  db->tune.b1 = env_int("CC_B1_GRID", 1, 1 << 20, db->tune.b1);
-  db->tune.b2 = env_int("CC_B2_GRID", 1, 1 << 20, db->tune.b2);
-  db->tune.gmm = env_int("CC_GMM_GRID", 1, 1 << 20, db->tune.gmm);
-  db->tune.gmm64 = env_int("CC_GMM_GRID64", 1, 1 << 20, getenv("CC_GMM_GRID") ? (db->tune.gmm + 1) / 2 : db->tune.gmm64);
-  db->tune.knn_mode = env_int("CC_KNN_MODE", 0, 2, db->tune.knn_mode);
+  db->tune.b1 = lane_env_int("CC_B1_GRID", 1, 1 << 20, db->tune.b1);
+  db->tune.b2 = lane_env_int("CC_B2_GRID", 1, 1 << 20, db->tune.b2);
+  db->tune.gmm = lane_env_int("CC_GMM_GRID", 1, 1 << 20, db->tune.gmm);
+  db->tune.gmm64 = lane_env_int("CC_GMM_GRID64", 1, 1 << 20, getenv("CC_GMM_GRID") ? (db->tune.gmm + 1) / 2 : db->tune.gmm64);
+  db->tune.knn_mode = lane_env_int("CC_KNN_MODE", 0, 2, db->tune.knn_mode);
   db->add_timers = getenv("CC_ADD_TIMERS") != nullptr;
-  db->tune.chunk = env_int("CC_CHUNK", 64, cc_db::QB, db->tune.chunk);
+  db->tune.chunk = lane_env_int("CC_CHUNK", 64, cc_db::QB, db->tune.chunk);
   db->tune.chunk = db->tune.chunk < db->qb_max ? db->tune.chunk : db->qb_max;
   auto env_triple = [](const char *name, int (&v)[3]) {
     const char *e = getenv(name);
@@ -1140,11 +1094,41 @@ static bool thres_strict_smaller(const cc_score_t *lb, const cc_score_t *ub) {
 static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q, int nb, bool meta_from_host = false, const int *d_sel = nullptr) {
   (void)db;
   hipStream_t ls = ln.stream;
-  hipLaunchKernelGGL(cc_k_pack_hot, dim3(nb), dim3(256), 0, ls, d_q, nb, ln.d_qhot, ln.d_heads, ln.d_pass_cnt,  // d_heads = d_nprob[4] | d_cnt[4]
+  hipLaunchKernelGGL(cc_k_pack_hot, dim3(nb), dim3(256), 0, ls, d_q, nb, ln.d_qhot, ln.d_heads, ln.d_pass_cnt,
                      meta_from_host ? (const cc_query_meta *)ln.h_meta : (const cc_query_meta *)nullptr, ln.d_qmeta, d_sel);
   hipLaunchKernelGGL(cc_k_gmm_prep, dim3(nb), dim3(CC_GMM_PREP_BLOCK), 0, ls, d_q, nb, ln.d_qfeat, d_sel);
   HIPCHK(hipGetLastError());
   return CC_OK;
+}
+
+static cc_check_params make_check_params(const cc_db *db, const cc_score_t *lb) {
+  cc_check_params CP;
+  CP.sim = db->cfg.cont_sim;
+  CP.lb = *lb;
+  for (int i = 0; i < 3; i++) {
+    CP.size_class[i] = db->tune.a_class[i];
+    CP.cstl_class[i] = db->tune.b2_class[i];
+  }
+  return CP;
+}
+
+// initial correlation of every problem on the lane's list (cc_k_merge / cc_k_pose_problems filled it)
+static void launch_gmm_init(cc_db *db, cc_qlane &ln) {
+  hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), 0, ln.stream, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
+                     (const int *)ln.d_nprob, (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, ln.d_gres,
+                     cc_gmm_code_pool{ln.d_codes, ln.code_cap, ln.head(CC_HD_CODES), ln.head(CC_HD_POOL), ln.pool_cap});
+}
+// L-BFGS on the problems cc_k_select / cc_k_pose_select listed: the 16-lane instance takes its own list and the in-between list
+// from the front, the 64-lane instance its class lists and the in-between list from the back.  corr_bar: the selection's bar.
+static void launch_refine(cc_db *db, cc_qlane &ln, float corr_bar) {
+  hipStream_t ls = ln.stream;
+  const int *n16 = ln.head(CC_HD_NSEL16), *n64 = ln.head(CC_HD_NSEL64), *n_mid = ln.head(CC_HD_NMID), *mid = ln.sel(CC_SEL_MID);
+  hipLaunchKernelGGL(cc_k_gmm_refine<16>, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, n16, (const int *)ln.sel(CC_SEL_16), n_mid, mid, n64,
+                     (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, corr_bar, ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres,
+                     (const unsigned *)ln.d_codes, (const int *)nullptr, (const int *)nullptr, 0);
+  hipLaunchKernelGGL(cc_k_gmm_refine<64>, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, n64, (const int *)ln.sel(CC_SEL_64), n_mid, mid, n16,
+                     (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, corr_bar, ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres,
+                     (const unsigned *)ln.d_codes, (const int *)ln.sel(CC_SEL_CLS), (const int *)ln.head(CC_HD_CLS), ln.prob_cap);
 }
 
 // The launches of one chunk after the retrieval: checks (K4), proposal merge (K4b), correlation (K5), selection (K6).
@@ -1185,26 +1169,16 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
                      ln.d_nprob, dyn ? ln.d_cpost : (cc_cand_post *)nullptr);
   if (ev) HIPCHK(hipEventRecord(ev[3], ls));
   // initial correlation of every candidate; the candidates fineOptimize would refine; L-BFGS on those only
-  hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
-                     (const int *)ln.d_nprob, (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, ln.d_gres,
-                     cc_gmm_code_pool{ln.d_codes, ln.code_cap, ln.d_heads + 9, ln.d_nprob + 3, ln.pool_cap});
+  launch_gmm_init(db, ln);
   hipLaunchKernelGGL(lg ? (dyn ? cc_k_select_l<true> : cc_k_select_l<false>) : (dyn ? cc_k_select<true> : cc_k_select<false>), dim3(nb), dim3(64), 0, ls, nb, lb->correlation, max_fine_opt,
                      (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_gmm_result *)ln.d_gres, ln.d_sel, ln.prob_cap,
-                     ln.d_nprob + 1, ln.d_heads + 8, (const unsigned short *)db->d_perm_tab, ln.d_sel + 3 * (size_t)ln.prob_cap, ln.d_heads + 12,
-                     ln.d_nprob + 3, ln.d_pool_off, (const cc_cand_post *)ln.d_cpost, ln.d_tidy, *lb, *ub);
-  hipLaunchKernelGGL(cc_k_gmm_refine<16>, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1),
-                     (const int *)ln.d_sel, (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap), (const int *)(ln.d_nprob + 2),
-                     (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, lb->correlation, ln.d_pool,
-                     ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes, (const int *)nullptr, (const int *)nullptr, 0);
-  hipLaunchKernelGGL(cc_k_gmm_refine<64>, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 2),
-                     (const int *)(ln.d_sel + ln.prob_cap), (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap),
-                     (const int *)(ln.d_nprob + 1), (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, lb->correlation,
-                     ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
-                     (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
+                     ln.head(CC_HD_NSEL16), ln.head(CC_HD_NMID), (const unsigned short *)db->d_perm_tab, ln.sel(CC_SEL_CLS), ln.head(CC_HD_CLS),
+                     ln.head(CC_HD_POOL), ln.d_pool_off, (const cc_cand_post *)ln.d_cpost, ln.d_tidy, *lb, *ub);
+  launch_refine(db, ln, lb->correlation);
   if (detail)  // the curvature at the refined poses, over the three lists cc_k_select filled (only in chains that asked for it)
-    hipLaunchKernelGGL(cc_k_gmm_hess, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1), (const int *)ln.d_sel,
-                       (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap), (const int *)(ln.d_nprob + 2),
-                       (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap, (const cc_gmm_feat *)ln.d_qfeat,
+    hipLaunchKernelGGL(cc_k_gmm_hess, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.head(CC_HD_NSEL16), (const int *)ln.sel(CC_SEL_16),
+                       (const int *)ln.head(CC_HD_NMID), (const int *)ln.sel(CC_SEL_MID), (const int *)ln.head(CC_HD_NSEL64),
+                       (const int *)ln.sel(CC_SEL_CLS), (const int *)ln.head(CC_HD_CLS), ln.prob_cap, (const cc_gmm_feat *)ln.d_qfeat,
                        (const cc_gmm_feat *)db->d_feat, (const cc_gmm_result *)ln.d_gres, (const unsigned *)ln.d_codes, ln.d_hess);
   if (ev) HIPCHK(hipEventRecord(ev[4], ls));
   if (max_ret > 0 && detail) {
@@ -1229,14 +1203,29 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
   return CC_OK;
 }
 
-// capacity checks on what a finished chunk brought back
+// capacity checks on what a finished chunk brought back: the pools of the correlation (every kind of chunk) ...
+static int pool_status(const cc_qlane &ln) {
+  if (ln.h_nprob[CC_HD_POOL] > ln.pool_cap) return set_err(CC_ECAPACITY, "the pair pool (or the pair-code pool) of the correlation refinement overflowed");
+  return CC_OK;
+}
+// ... and the flags of a query or verify chunk's results
 static int chunk_status(const cc_qlane &ln, int nb) {
-  if (ln.h_nprob[3] > ln.pool_cap) return set_err(CC_ECAPACITY, "the pair pool (or the pair-code pool) of the correlation refinement overflowed");
+  const int prc = pool_status(ln);
+  if (prc != CC_OK) return prc;
   for (int i = 0; i < nb; i++)
     if (ln.h_results[i].flags)
       return set_err(CC_ECAPACITY, "a query met an internal capacity of the scoring kernels (cc_query_result_t.flags, CC_QF_*): "
                                    "its result may differ from the reference's");
   return CC_OK;
+}
+// a profiled chunk's stage times (knn | check | merge | gmm | final), those of `stages` (bit k: pev[k] .. pev[k + 1])
+static void add_stage_times(cc_db *db, const cc_qlane &ln, unsigned stages) {
+  for (int k = 0; k < 5; k++) {
+    float t = 0.f;
+    if (stages >> k & 1) hipEventElapsedTime(&t, ln.pev[k], ln.pev[k + 1]);
+    db->ms_acc[k] += t;
+  }
+  db->launch_w += (double)ln.nb;  // profiled queries
 }
 
 // a finished pose chunk: its rows to rows [b0, b0 + nb) of the caller's arrays, its stage times, its capacity flags
@@ -1248,15 +1237,9 @@ static int pose_finish(cc_db *db, cc_qlane &ln) {
   memcpy(ln.pose_res + ln.b0, rows, sizeof(cc_pose_result_t) * (size_t)nb);
   if (nt > 0) memcpy(ln.pose_try + (size_t)ln.b0 * nt, tr, sizeof(double) * (size_t)nb * nt);
   if (ln.pose_curv) memcpy(ln.pose_curv + ln.b0, tr + (size_t)nb * nt, sizeof(cc_pose_curv_t) * (size_t)nb);
-  if (ln.profiled) {  // problems | - | - | correlation (with the try poses and the curvature) | rows
-    float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    hipEventElapsedTime(&t[0], ln.pev[0], ln.pev[1]);
-    hipEventElapsedTime(&t[3], ln.pev[3], ln.pev[4]);
-    hipEventElapsedTime(&t[4], ln.pev[4], ln.pev[5]);
-    for (int k = 0; k < 5; k++) db->ms_acc[k] += t[k];
-    db->launch_w += (double)nb;
-  }
-  if (ln.h_nprob[3] > ln.pool_cap) return set_err(CC_ECAPACITY, "the pair pool (or the pair-code pool) of the correlation refinement overflowed");
+  if (ln.profiled) add_stage_times(db, ln, 1u << 0 | 1u << 3 | 1u << 4);  // problems | - | - | correlation (with the try poses and the curvature) | rows
+  const int prc = pool_status(ln);
+  if (prc != CC_OK) return prc;
   for (int i = 0; i < nb; i++)
     if (rows[i].flags & ~CC_PF_REFINED)
       return set_err(CC_ECAPACITY, "a pose item met an internal capacity of the correlation (cc_pose_result_t.flags, CC_QF_*): "
@@ -1274,13 +1257,7 @@ static int lane_finish(cc_db *db, cc_qlane &ln) {
   if (ln.rank_dst.h_cands) rank_deliver(ln, ln.rank_dst, ln.b0, ln.nb, ln.rank_mfo);
   if (ln.detail_dst)
     memcpy(ln.detail_dst + (size_t)ln.b0 * ln.rank_dst.max_ret, ln.h_detail, sizeof(cc_ranked_detail_t) * (size_t)ln.nb * ln.rank_dst.max_ret);
-  if (ln.profiled) {
-    float t[5];
-    for (int k = 0; k < 5; k++) hipEventElapsedTime(&t[k], ln.pev[k], ln.pev[k + 1]);
-    const double w = (double)ln.nb;  // profiled queries
-    for (int k = 0; k < 5; k++) db->ms_acc[k] += t[k];  // knn | check | merge | gmm | final
-    db->launch_w += w;
-  }
+  if (ln.profiled) add_stage_times(db, ln, 0x1Fu);
   return chunk_status(ln, ln.nb);
 }
 
@@ -1327,6 +1304,143 @@ int cc_db_query_collect(cc_db *db, const cc_query_result_t *h_res, int n) {
   return rc;
 }
 
+// A synchronous call = the submit + the wait -- also after an error: nothing may stay in flight behind a synchronous call.
+static int run_sync(cc_db *db, const std::function<int()> &submit) {
+  if (db) db->sync_call = true;
+  const int rc = submit();
+  if (db) db->sync_call = false;
+  const int r2 = db ? cc_db_query_wait(db) : CC_OK;
+  return rc != CC_OK ? rc : r2;
+}
+
+// ---- the chunk driver of the query, verify and pose submits ----
+struct cc_chunk {  // one chunk, as the driver hands it to the steps of a plan
+  cc_qlane &ln;
+  int b0, nb;      // items [b0, b0 + nb) of the call
+  // a chunk of a few queries (the per-scan loop brings one): the searches read the epoch records from the lane's pinned
+  // host buffer (cc_k_pack_hot brings them over) and cc_k_final writes the results there -- three copy commands less in a
+  // chain of ~15 short kernels
+  bool zc;
+  hipEvent_t *ev;  // the lane's stage events [0..5] when the chunk is profiled, or nullptr
+};
+struct cc_prep_src {  // what launch_query_prep builds a chunk's query records from
+  const cc_scan_desc_t *d_q;
+  bool meta_from_host;
+  const int *d_sel;
+};
+// What a submit does of its own, in the order the driver calls it.  The steps from `upload` on return a CC_* code with the
+// message set (HIPCHK for their HIP calls).
+struct cc_chunk_plan {
+  std::function<int(cc_qlane &)> alloc;                          // the lane's on-demand buffers the chunk needs
+  std::function<void(const cc_chunk &)> stage;                   // fill the lane's pinned staging from the caller's arrays
+  std::function<int(const cc_chunk &, cc_prep_src &)> upload;    // the copies in front of the prep kernels, and what those read
+  std::function<int(const cc_chunk &)> head;                     // what stands in the place of the retrieval (stage ev[0] .. ev[1])
+  std::function<int(const cc_chunk &)> body;                     // the rest of the chain
+  std::function<int(const cc_chunk &)> copy_back;                // chunks above CC_ZC_MAX: the results to the lane's pinned buffers
+  std::function<void(const cc_chunk &)> note;                    // where lane_finish delivers the chunk
+};
+
+// One chunk's chain, queued on its lane's stream.  Whatever fails in here -- a HIP call (HIPCHK) or a step of the plan
+// (LANE_CHK: its own CC_* code and message) -- fails with part of the chain queued: submit_chunks drains the lane.
+static int queue_chunk(cc_db *db, hipStream_t stream, const cc_chunk_plan &plan, const cc_chunk &c) {
+#define LANE_CHK(step)               \
+  do {                               \
+    const int rc_ = (step);          \
+    if (rc_ != CC_OK) return rc_;    \
+  } while (0)
+  cc_qlane &ln = c.ln;
+  hipStream_t ls = ln.stream;
+  hipEvent_t *ev = c.ev;
+  cc_prep_src src{nullptr, false, nullptr};
+  LANE_CHK(plan.upload(c, src));
+  LANE_CHK(launch_query_prep(db, ln, src.d_q, c.nb, src.meta_from_host, src.d_sel));
+  // the caller's stream goes on once the descriptors have been read
+  HIPCHK(hipEventRecord(ln.prep, ls));
+  HIPCHK(hipStreamWaitEvent(stream, ln.prep, 0));
+  if (ev) HIPCHK(hipEventRecord(ev[0], ls));
+  LANE_CHK(plan.head(c));
+  if (ev) HIPCHK(hipEventRecord(ev[1], ls));
+  LANE_CHK(plan.body(c));
+  if (!c.zc) LANE_CHK(plan.copy_back(c));
+  HIPCHK(hipEventRecord(ln.fin, ls));
+#undef LANE_CHK
+  return CC_OK;
+}
+
+// The batch is cut into chunks of <= QB items; chunk c runs as one chain of launches on the next lane's stream, so
+// n_lanes chunks are in flight at a time -- of this batch or of the one submitted before it: a lane's previous chunk is
+// collected only when the lane is needed again, so the tail of one batch's chains overlaps the head of the next one's.
+// The lanes start after everything queued on the caller's stream so far; the caller's stream continues once the
+// query descriptors have been read (d_qdesc may then be overwritten).
+static int submit_chunks(cc_db *db, int n, hipStream_t stream, const cc_chunk_plan &plan) {
+  hipEvent_t e_start = db->lane[0].done;
+  HIPCHK(hipEventRecord(e_start, stream));
+  for (int i = 0; i < db->n_lanes; i++) {
+    HIPCHK(hipStreamWaitEvent(db->lane[i].stream, e_start, 0));
+    if (db->add_done) HIPCHK(hipStreamWaitEvent(db->lane[i].stream, db->add_done, 0));  // an append queued on another stream
+  }
+  // chunk size: a batch is cut so that every lane gets a chunk -- except a streamed submit of QB queries or more, which
+  // goes out in chunks of QB: the next batch takes the next lane, and a chain of 1 024 queries is cheaper than two of 512
+  // (+2 % on the bench).  Smaller streamed batches stay cut per lane: whole, they would sit one per lane, several
+  // batches deep, and an append in between has to wait for the chunks that still read the view buffer it rewrites
+  // (measured on the online loop with 512-scan sub-batches and four lanes: 188 k against 265 k scans/s).
+  // (a large-k database's lanes take qb_max = 256 items)
+  int qb = (((n + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
+  if (!db->sync_call && n >= db->qb_max) qb = db->qb_max;
+  qb = qb > db->tune.chunk ? db->tune.chunk : qb;  // (tune.chunk <= qb_max)
+  for (int b0 = 0; b0 < n; b0 += qb) {
+    const int nb = n - b0 < qb ? n - b0 : qb;
+    cc_qlane &ln = db->lane[db->next_lane];
+    db->next_lane = (db->next_lane + 1) % db->n_lanes;
+    int rc = lane_finish(db, ln);
+    if (rc == CC_OK) rc = plan.alloc(ln);  // before anything of the chunk is queued (a lane whose earlier allocation failed tries again)
+    if (rc != CC_OK) return rc;
+    cc_chunk c{ln, b0, nb, nb <= CC_ZC_MAX, nullptr};
+    plan.stage(c);
+    ln.profiled = db->prof && (db->prof_tick++ % db->prof_every) == 0;
+    c.ev = ln.profiled ? ln.pev : nullptr;
+    rc = queue_chunk(db, stream, plan, c);
+    if (rc != CC_OK) {
+      // the lane is drained (its pinned staging buffers must not be reused under copies still in flight) and the handle is
+      // marked failed, as the appends do
+      lane_abort(db, ln);
+      return rc;
+    }
+    for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];  // (a verify or pose chunk reads no sorted view: nothing for an append to wait for beyond this)
+    ln.busy = true;
+    ln.b0 = b0;
+    ln.nb = nb;
+    plan.note(c);
+  }
+  return CC_OK;
+}
+
+// query and verify chunks: the lane's on-demand buffers of the chain's modes ...
+static int lane_alloc_modes(cc_db *db, cc_qlane &ln, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail) {
+  int rc = db->dyn_thres ? lane_alloc_dyn(ln) : CC_OK;
+  if (rc == CC_OK && rank) rc = lane_alloc_rank(ln);
+  if (rc == CC_OK && detail) rc = lane_alloc_detail(ln);
+  return rc;
+}
+// ... what launch_scoring_chain left on the device, to the lane's pinned buffers ...
+static int results_copy_back(const cc_chunk &c, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail) {
+  cc_qlane &ln = c.ln;
+  hipStream_t ls = ln.stream;
+  const int nb = c.nb;
+  HIPCHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
+  HIPCHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
+  if (rank) HIPCHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
+  if (detail) HIPCHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
+  return CC_OK;
+}
+// ... and where lane_finish delivers them
+static void results_note(cc_qlane &ln, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *detail, int max_fine_opt) {
+  ln.h_dst = h_res;
+  ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
+  ln.detail_dst = detail;
+  ln.rank_mfo = max_fine_opt;
+}
+
 // rank: where the chunks' ranked lists go (the *_ranked entry points, validated there), or nullptr: the plain call
 static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                              const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
@@ -1335,7 +1449,6 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
   if (!db || !d_qdesc || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch");
   if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch: thresholds must satisfy lb.strictSmaller(ub)");
-  hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(db->device));
   const int NS = CC_NQLEV * CC_NPIV;
   const int nql = db->cfg.n_q_levels;
@@ -1352,98 +1465,41 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
   KP.cap_k = db->cap_k;
   KP.nnk = db->cfg.nnk;
   KP.n_q_levels = nql;
-  cc_check_params CP;
-  CP.sim = db->cfg.cont_sim;
-  CP.lb = *lb;
-  for (int i = 0; i < 3; i++) {
-    CP.size_class[i] = db->tune.a_class[i];
-    CP.cstl_class[i] = db->tune.b2_class[i];
-  }
-
+  const cc_check_params CP = make_check_params(db, lb);
   for (int i = 0; i < nq; i++)
     if (h_epoch[i] < 0 || h_epoch[i] > db->n_scans) return set_err(CC_EINVAL, "cc_db_query_batch: epoch out of range");
-  // The batch is cut into chunks of <= QB queries; chunk c runs as one chain of launches on the next lane's stream, so
-  // n_lanes chunks are in flight at a time -- of this batch or of the one submitted before it: a lane's previous chunk is
-  // collected only when the lane is needed again, so the tail of one batch's chains overlaps the head of the next one's.
-  // The lanes start after everything queued on the caller's stream so far; the caller's stream continues once the
-  // query descriptors have been read (d_qdesc may then be overwritten).
-  hipEvent_t e_start = db->lane[0].done;
-  HIPCHK(hipEventRecord(e_start, stream));
-  for (int i = 0; i < db->n_lanes; i++) {
-    HIPCHK(hipStreamWaitEvent(db->lane[i].stream, e_start, 0));
-    if (db->add_done) HIPCHK(hipStreamWaitEvent(db->lane[i].stream, db->add_done, 0));  // an append queued on another stream
-  }
-  int rc = CC_OK;
-  int chunk = 0;
-  // chunk size: a batch is cut so that every lane gets a chunk -- except a streamed submit of QB queries or more, which
-  // goes out in chunks of QB: the next batch takes the next lane, and a chain of 1 024 queries is cheaper than two of 512
-  // (+2 % on the bench).  Smaller streamed batches stay cut per lane: whole, they would sit one per lane, several
-  // batches deep, and an append in between has to wait for the chunks that still read the view buffer it rewrites
-  // (measured on the online loop with 512-scan sub-batches and four lanes: 188 k against 265 k scans/s).
-  int qb = (((nq + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
-  if (!db->sync_call && nq >= db->qb_max) qb = db->qb_max;
-  qb = qb > db->tune.chunk ? db->tune.chunk : qb;  // (tune.chunk <= qb_max)
-  // A HIP call that fails once part of a chunk's chain is queued: the lane is drained (its pinned staging buffers must not
-  // be reused under copies still in flight) and the handle is marked failed, as the appends do.
-#define LANE_CHK(call)                        \
-  do {                                        \
-    hipError_t e_ = (call);                   \
-    if (e_ != hipSuccess) {                   \
-      lane_abort(db, ln);                     \
-      return set_err(CC_EHIP, #call, e_);     \
-    }                                         \
-  } while (0)
-  for (int b0 = 0; b0 < nq && rc == CC_OK; b0 += qb, chunk++) {
-    const int nb = nq - b0 < qb ? nq - b0 : qb;
-    cc_qlane &ln = db->lane[db->next_lane];
-    db->next_lane = (db->next_lane + 1) % db->n_lanes;
-    rc = lane_finish(db, ln);
-    if (rc != CC_OK) break;
-    if (db->dyn_thres) {  // before anything of the chunk is queued (a lane whose earlier allocation failed tries again)
-      rc = lane_alloc_dyn(ln);
-      if (rc != CC_OK) break;
-    }
-    if (rank) {
-      rc = lane_alloc_rank(ln);
-      if (rc != CC_OK) break;
-    }
-    if (detail) {
-      rc = lane_alloc_detail(ln);
-      if (rc != CC_OK) break;
-    }
-    hipStream_t ls = ln.stream;
-    bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
-    for (int i = 0; i < nb; i++) {
-      const int e = h_epoch[b0 + i];
+  bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
+  cc_chunk_plan plan;
+  plan.alloc = [&](cc_qlane &ln) -> int { return lane_alloc_modes(db, ln, rank, detail); };
+  plan.stage = [&](const cc_chunk &c) {  // the queries' epoch records
+    cc_query_meta *h_meta = c.ln.h_meta;
+    chunk_vis = false;
+    for (int i = 0; i < c.nb; i++) {
+      const int e = h_epoch[c.b0 + i];
       chunk_vis = chunk_vis || db->idx_slot[e] >= 0;
-      ln.h_meta[i].epoch = e;
+      h_meta[i].epoch = e;
       for (int l = 0; l < CC_NQLEV; l++) {
-        ln.h_meta[i].n_keys[l] = db->nkeys_hist[e][l];
-        for (int b = 0; b < 7; b++) ln.h_meta[i].ranges[l][b] = db->ranges_hist[e][l * 7 + b];
+        h_meta[i].n_keys[l] = db->nkeys_hist[e][l];
+        for (int b = 0; b < 7; b++) h_meta[i].ranges[l][b] = db->ranges_hist[e][l * 7 + b];
       }
       const int is_ = db->idx_slot[e];
       for (int l = 0; l < CC_NQLEV; l++) {
-        ln.h_meta[i].idx_full[l] = is_ < 0 ? 1 : db->idx_store[is_].full[l];
-        for (int b = 0; b < 12; b++) ln.h_meta[i].idx[l][b] = is_ < 0 ? 0.f : db->idx_store[is_].iv[l][b];
+        h_meta[i].idx_full[l] = is_ < 0 ? 1 : db->idx_store[is_].full[l];
+        for (int b = 0; b < 12; b++) h_meta[i].idx[l][b] = is_ < 0 ? 0.f : db->idx_store[is_].iv[l][b];
       }
     }
-    ln.profiled = db->prof && (db->prof_tick++ % db->prof_every) == 0;
-    hipEvent_t *ev = ln.profiled ? ln.pev : nullptr;
-    // a chunk of a few queries (the per-scan loop brings one): the searches read the epoch records from the lane's pinned
-    // host buffer (cc_k_pack_hot brings them over) and cc_k_final writes the results there -- three copy commands less in a
-    // chain of ~15 short kernels
-    const bool zc = nb <= CC_ZC_MAX;
-    const cc_query_meta *qmeta_dev = ln.d_qmeta;  // small chunks: filled by cc_k_pack_hot from the pinned buffer
-    if (!zc) LANE_CHK(hipMemcpyAsync(ln.d_qmeta, ln.h_meta, sizeof(cc_query_meta) * nb, hipMemcpyHostToDevice, ls));
-    rc = launch_query_prep(db, ln, d_qdesc + b0, nb, zc);
-    if (rc != CC_OK) {
-      lane_abort(db, ln);
-      break;
-    }
-    // the caller's stream goes on once the descriptors have been read
-    LANE_CHK(hipEventRecord(ln.prep, ls));
-    LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
-    if (ev) LANE_CHK(hipEventRecord(ev[0], ls));
+  };
+  plan.upload = [&](const cc_chunk &c, cc_prep_src &src) -> int {  // (small chunks: cc_k_pack_hot fills d_qmeta from the pinned buffer)
+    cc_qlane &ln = c.ln;
+    if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_qmeta, ln.h_meta, sizeof(cc_query_meta) * c.nb, hipMemcpyHostToDevice, ln.stream));
+    src = cc_prep_src{d_qdesc + c.b0, c.zc, nullptr};
+    return CC_OK;
+  };
+  plan.head = [&](const cc_chunk &c) -> int {  // the retrieval
+    cc_qlane &ln = c.ln;
+    hipStream_t ls = ln.stream;
+    const int nb = c.nb;
+    const cc_query_meta *qmeta_dev = ln.d_qmeta;
     int max_keys = 0;
     for (int l = 0; l < nql; l++) max_keys = db->n_keys[l] > max_keys ? db->n_keys[l] : max_keys;
     // (a large-k database always walks: the tiled search has no large-k instance)
@@ -1463,39 +1519,24 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
       hipLaunchKernelGGL(chunk_vis ? cc_k_knn_l<true> : cc_k_knn_l<false>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot,
                          qmeta_dev, ln.d_hits, ln.d_hit_cnt);
     } else {
-      if (chunk_vis)
-        hipLaunchKernelGGL(cc_k_knn<true>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot, qmeta_dev,
-                         ln.d_hits, ln.d_hit_cnt);
-      else
-        hipLaunchKernelGGL(cc_k_knn<false>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot, qmeta_dev,
+      hipLaunchKernelGGL(chunk_vis ? cc_k_knn<true> : cc_k_knn<false>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot, qmeta_dev,
                          ln.d_hits, ln.d_hit_cnt);
     }
-    if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, ev, nullptr, zc, db->kmax, rank ? rank->max_ret : 0, detail != nullptr);
-    if (rc != CC_OK) {
-      lane_abort(db, ln);
-      break;
-    }
-    if (d_knn) LANE_CHK(hipMemcpyAsync(d_knn + (size_t)b0 * NS * db->kmax, ln.d_hits, sizeof(cc_knn_hit_t) * (size_t)nb * NS * db->kmax, hipMemcpyDeviceToDevice, ls));
-    if (d_knn_cnt) LANE_CHK(hipMemcpyAsync(d_knn_cnt + (size_t)b0 * NS, ln.d_hit_cnt, sizeof(int) * nb * NS, hipMemcpyDeviceToDevice, ls));
-    if (!zc) {
-      LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
-      LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
-      if (rank) LANE_CHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
-      if (detail) LANE_CHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
-    }
-    LANE_CHK(hipEventRecord(ln.fin, ls));
-    for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];
-    ln.busy = true;
-    ln.b0 = b0;
-    ln.nb = nb;
-    ln.h_dst = h_res;
-    ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
-    ln.detail_dst = detail;
-    ln.rank_mfo = db->cfg.max_fine_opt;
-  }
-#undef LANE_CHK
-  return rc;
+    return CC_OK;
+  };
+  plan.body = [&](const cc_chunk &c) -> int {
+    cc_qlane &ln = c.ln;
+    hipStream_t ls = ln.stream;
+    const int nb = c.nb, b0 = c.b0;
+    const int rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, c.ev, nullptr, c.zc, db->kmax, rank ? rank->max_ret : 0, detail != nullptr);
+    if (rc != CC_OK) return rc;
+    if (d_knn) HIPCHK(hipMemcpyAsync(d_knn + (size_t)b0 * NS * db->kmax, ln.d_hits, sizeof(cc_knn_hit_t) * (size_t)nb * NS * db->kmax, hipMemcpyDeviceToDevice, ls));
+    if (d_knn_cnt) HIPCHK(hipMemcpyAsync(d_knn_cnt + (size_t)b0 * NS, ln.d_hit_cnt, sizeof(int) * nb * NS, hipMemcpyDeviceToDevice, ls));
+    return CC_OK;
+  };
+  plan.copy_back = [&](const cc_chunk &c) -> int { return results_copy_back(c, rank, detail); };
+  plan.note = [&](const cc_chunk &c) { results_note(c.ln, h_res, rank, detail, db->cfg.max_fine_opt); };
+  return submit_chunks(db, nq, (hipStream_t)stream_, plan);
 }
 
 int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
@@ -1505,26 +1546,20 @@ int cc_db_query_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const i
 int cc_db_query_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                               const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
                               const cc_rank_out_t *rank) {
-  const int vrc = rank_validate(rank, "cc_db_query_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, nullptr, false);
   if (vrc != CC_OK) return vrc;
   return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, nullptr);
 }
 int cc_db_query_submit_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                                      const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
-  const int vrc = rank_validate(rank, "cc_db_query_submit_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, h_detail, true);
   if (vrc != CC_OK) return vrc;
-  const int drc = detail_validate(h_detail, "cc_db_query_submit_ranked_detail: h_detail must be given");
-  if (drc != CC_OK) return drc;
   return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail);
 }
 
 int cc_db_query_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                       const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_) {
-  if (db) db->sync_call = true;
-  const int rc = cc_db_query_submit(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_);
-  if (db) db->sync_call = false;
-  const int r2 = db ? cc_db_query_wait(db) : CC_OK;  // also after an error: nothing may stay in flight behind a synchronous call
-  return rc != CC_OK ? rc : r2;
+  return run_sync(db, [&] { return cc_db_query_submit(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_); });
 }
 
 static int stage_reserve(cc_db *db, int n) {
@@ -1565,11 +1600,8 @@ static int query_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int n
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)nq, hipMemcpyHostToDevice));
   if (!rank) return cc_db_query_batch(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr);
-  db->sync_call = true;  // cc_db_query_batch's body with the lists
-  rc = query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail);
-  db->sync_call = false;
-  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
-  return rc != CC_OK ? rc : r2;
+  // cc_db_query_batch's body with the lists
+  return run_sync(db, [&] { return query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail); });
 }
 int cc_db_query_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                            const cc_score_t *ub, cc_query_result_t *h_res) {
@@ -1577,16 +1609,14 @@ int cc_db_query_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, con
 }
 int cc_db_query_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                                   const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
-  const int vrc = rank_validate(rank, "cc_db_query_batch_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, nullptr, false);
   if (vrc != CC_OK) return vrc;
   return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank, nullptr);
 }
 int cc_db_query_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                                          const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
-  const int vrc = rank_validate(rank, "cc_db_query_batch_host_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, h_detail, true);
   if (vrc != CC_OK) return vrc;
-  const int drc = detail_validate(h_detail, "cc_db_query_batch_host_ranked_detail: h_detail must be given");
-  if (drc != CC_OK) return drc;
   return query_batch_host_impl(db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank, h_detail);
 }
 
@@ -1706,7 +1736,7 @@ int cc_db_query_scan_batch_submit(cc_db *db, cc_scan *const *scans, int n, const
 }
 int cc_db_query_scan_batch_submit_ranked(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
                                          const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank) {
-  const int vrc = rank_validate(rank, "cc_db_query_scan_batch_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, nullptr, false);
   if (vrc != CC_OK) return vrc;
   if (lb && ub && !thres_strict_smaller(lb, ub))  // (before the handles are gathered: a refused call queues nothing)
     return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit_ranked: thresholds must satisfy lb.strictSmaller(ub)");
@@ -1714,10 +1744,8 @@ int cc_db_query_scan_batch_submit_ranked(cc_db *db, cc_scan *const *scans, int n
 }
 int cc_db_query_scan_batch_submit_ranked_detail(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
                                                 const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
-  const int vrc = rank_validate(rank, "cc_db_query_scan_batch_submit_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, h_detail, true);
   if (vrc != CC_OK) return vrc;
-  const int drc = detail_validate(h_detail, "cc_db_query_scan_batch_submit_ranked_detail: h_detail must be given");
-  if (drc != CC_OK) return drc;
   if (lb && ub && !thres_strict_smaller(lb, ub))  // (before the handles are gathered: a refused call queues nothing)
     return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit_ranked_detail: thresholds must satisfy lb.strictSmaller(ub)");
   return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, rank, h_detail);
@@ -1768,16 +1796,8 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
   HIPCHK(hipSetDevice(db->device));
   if (!db->d_hint_scores) HIPCHK(hipMalloc(&db->d_hint_scores, sizeof(int) * (size_t)CC_CHK_STRIDE * CC_NSCORE));
   cc_qlane &ln = db->lane[0];
-  if (db->dyn_thres) {
-    const int arc = lane_alloc_dyn(ln);
-    if (arc != CC_OK) return arc;
-  }
-  if (rank) {
-    const int arc = lane_alloc_rank(ln);
-    if (arc != CC_OK) return arc;
-  }
-  if (detail) {
-    const int arc = lane_alloc_detail(ln);
+  {
+    const int arc = lane_alloc_modes(db, ln, rank, detail);
     if (arc != CC_OK) return arc;
   }
   HIPCHK(hipEventRecord(ln.done, stream));  // start after what the caller queued
@@ -1785,13 +1805,7 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
   if (db->add_done) HIPCHK(hipStreamWaitEvent(ln.stream, db->add_done, 0));  // ... and after the last append, whatever stream it used
   HIPCHK(hipMemcpyAsync(ln.d_hits, hits.data(), sizeof(cc_knn_hit_t) * hits.size(), hipMemcpyHostToDevice, ln.stream));
   HIPCHK(hipMemcpyAsync(ln.d_hit_cnt, hit_cnt, sizeof(hit_cnt), hipMemcpyHostToDevice, ln.stream));
-  cc_check_params CP;
-  CP.sim = db->cfg.cont_sim;
-  CP.lb = *lb;
-  for (int i = 0; i < 3; i++) {
-    CP.size_class[i] = db->tune.a_class[i];
-    CP.cstl_class[i] = db->tune.b2_class[i];
-  }
+  const cc_check_params CP = make_check_params(db, lb);
   int rc = launch_query_prep(db, ln, d_qdesc, 1);
   if (rc != CC_OK) return rc;
   {  // a hint must name contours that exist on BOTH sides (the reference would CHECK-fail on the missing view): the query
@@ -1807,10 +1821,8 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
   if (rc != CC_OK) return rc;
   std::vector<int> sc((size_t)CC_CHK_STRIDE * CC_NSCORE);
   std::vector<unsigned char> ok(CC_CHK_STRIDE);
-  HIPCHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t), hipMemcpyDeviceToHost, ln.stream));
-  HIPCHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ln.stream));
-  if (rank) HIPCHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)rank->max_ret, hipMemcpyDeviceToHost, ln.stream));
-  if (detail) HIPCHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)rank->max_ret, hipMemcpyDeviceToHost, ln.stream));
+  rc = results_copy_back(cc_chunk{ln, 0, 1, false, nullptr}, rank, detail);
+  if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpyAsync(sc.data(), db->d_hint_scores, sizeof(int) * sc.size(), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(ok.data(), ln.d_pass_ok, ok.size(), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipStreamSynchronize(ln.stream));
@@ -1838,16 +1850,14 @@ int cc_db_check_hints(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t 
 int cc_db_check_hints_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                              const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_,
                              const cc_rank_out_t *rank) {
-  const int vrc = rank_validate(rank, "cc_db_check_hints_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, nullptr, false);
   if (vrc != CC_OK) return vrc;
   return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, rank, nullptr);
 }
 int cc_db_check_hints_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                     const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
-  const int vrc = rank_validate(rank, "cc_db_check_hints_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, h_detail, true);
   if (vrc != CC_OK) return vrc;
-  const int drc = detail_validate(h_detail, "cc_db_check_hints_ranked_detail: h_detail must be given");
-  if (drc != CC_OK) return drc;
   return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, rank, h_detail);
 }
 
@@ -1892,16 +1902,14 @@ int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hi
 int cc_db_check_hints_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                   const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
                                   const cc_rank_out_t *rank) {
-  const int vrc = rank_validate(rank, "cc_db_check_hints_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, nullptr, false);
   if (vrc != CC_OK) return vrc;
   return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank, nullptr);
 }
 int cc_db_check_hints_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                          const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
-  const int vrc = rank_validate(rank, "cc_db_check_hints_host_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, h_detail, true);
   if (vrc != CC_OK) return vrc;
-  const int drc = detail_validate(h_detail, "cc_db_check_hints_host_ranked_detail: h_detail must be given");
-  if (drc != CC_OK) return drc;
   return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank, h_detail);
 }
 
@@ -1945,102 +1953,42 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
     if (vrc != CC_OK) return vrc;
   }
   DB_POISON_CHK(db, "cc_db_verify_submit");
-  hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(db->device));
-  cc_check_params CP;
-  CP.sim = db->cfg.cont_sim;
-  CP.lb = *lb;
-  for (int i = 0; i < 3; i++) {
-    CP.size_class[i] = db->tune.a_class[i];
-    CP.cstl_class[i] = db->tune.b2_class[i];
-  }
+  const cc_check_params CP = make_check_params(db, lb);
   cc_verify_params VP;
   VP.level_mask = cfg->level_mask ? cfg->level_mask : 0xF;
   VP.max_key_dist_sq = cfg->max_key_dist_sq;
-  // chunks over the lanes exactly as cc_db_query_submit cuts a query batch (the comments there); a large-k database's lanes
-  // take qb_max = 256 items, and the chain is the 64-stride one on any database, as in the hint flow
-  hipEvent_t e_start = db->lane[0].done;
-  HIPCHK(hipEventRecord(e_start, stream));
-  for (int i = 0; i < db->n_lanes; i++) {
-    HIPCHK(hipStreamWaitEvent(db->lane[i].stream, e_start, 0));
-    if (db->add_done) HIPCHK(hipStreamWaitEvent(db->lane[i].stream, db->add_done, 0));  // an append queued on another stream
-  }
-  int rc = CC_OK;
-  int qb = (((n + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
-  if (!db->sync_call && n >= db->qb_max) qb = db->qb_max;
-  qb = qb > db->tune.chunk ? db->tune.chunk : qb;
-#define LANE_CHK(call)                        \
-  do {                                        \
-    hipError_t e_ = (call);                   \
-    if (e_ != hipSuccess) {                   \
-      lane_abort(db, ln);                     \
-      return set_err(CC_EHIP, #call, e_);     \
-    }                                         \
-  } while (0)
-  for (int b0 = 0; b0 < n && rc == CC_OK; b0 += qb) {
-    const int nb = n - b0 < qb ? n - b0 : qb;
-    cc_qlane &ln = db->lane[db->next_lane];
-    db->next_lane = (db->next_lane + 1) % db->n_lanes;
-    rc = lane_finish(db, ln);
-    if (rc != CC_OK) break;
-    rc = lane_alloc_verify(ln);
-    if (rc != CC_OK) break;
-    if (rank) {
-      rc = lane_alloc_rank(ln);
-      if (rc != CC_OK) break;
-    }
-    if (detail) {
-      rc = lane_alloc_detail(ln);
-      if (rc != CC_OK) break;
-    }
-    if (db->dyn_thres) {
-      rc = lane_alloc_dyn(ln);
-      if (rc != CC_OK) break;
-    }
-    hipStream_t ls = ln.stream;
-    int *h_sel = ln.h_vin, *h_cl = ln.h_vin + nb;  // the chunk's table, packed: [nb] | [nb][CC_VERIFY_CANDS_MAX]
-    for (int i = 0; i < nb; i++) h_sel[i] = h_qidx ? h_qidx[b0 + i] : b0 + i;
-    memcpy(h_cl, h_cands + (size_t)b0 * CC_VERIFY_CANDS_MAX, sizeof(int) * (size_t)nb * CC_VERIFY_CANDS_MAX);
-    ln.profiled = db->prof && (db->prof_tick++ % db->prof_every) == 0;
-    hipEvent_t *ev = ln.profiled ? ln.pev : nullptr;
-    const bool zc = nb <= CC_ZC_MAX;  // cc_k_final writes the results of a small chunk straight into the lane's pinned buffer
-    LANE_CHK(hipMemcpyAsync(ln.d_vin, ln.h_vin, sizeof(int) * (size_t)nb * (1 + CC_VERIFY_CANDS_MAX), hipMemcpyHostToDevice, ls));
-    rc = launch_query_prep(db, ln, d_qdesc, nb, false, ln.d_vin);
-    if (rc != CC_OK) {
-      lane_abort(db, ln);
-      break;
-    }
-    // the caller's stream goes on once the descriptors have been read
-    LANE_CHK(hipEventRecord(ln.prep, ls));
-    LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
-    if (ev) LANE_CHK(hipEventRecord(ev[0], ls));
-    hipLaunchKernelGGL(cc_k_hints_expand, dim3(nb), dim3(64), 0, ls, VP, (const cc_hot_desc_t *)ln.d_qhot, (const cc_hot_desc_t *)db->d_hot,
+  // the chain is the 64-stride one on any database, as in the hint flow
+  cc_chunk_plan plan;
+  plan.alloc = [&](cc_qlane &ln) -> int {
+    const int rc = lane_alloc_verify(ln);
+    return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail);
+  };
+  plan.stage = [&](const cc_chunk &c) {  // the chunk's table, packed: [nb] | [nb][CC_VERIFY_CANDS_MAX]
+    int *h_sel = c.ln.h_vin, *h_cl = c.ln.h_vin + c.nb;
+    for (int i = 0; i < c.nb; i++) h_sel[i] = h_qidx ? h_qidx[c.b0 + i] : c.b0 + i;
+    memcpy(h_cl, h_cands + (size_t)c.b0 * CC_VERIFY_CANDS_MAX, sizeof(int) * (size_t)c.nb * CC_VERIFY_CANDS_MAX);
+  };
+  plan.upload = [&](const cc_chunk &c, cc_prep_src &src) -> int {
+    cc_qlane &ln = c.ln;
+    HIPCHK(hipMemcpyAsync(ln.d_vin, ln.h_vin, sizeof(int) * (size_t)c.nb * (1 + CC_VERIFY_CANDS_MAX), hipMemcpyHostToDevice, ln.stream));
+    src = cc_prep_src{d_qdesc, false, ln.d_vin};
+    return CC_OK;
+  };
+  plan.head = [&](const cc_chunk &c) -> int {  // the check table from the candidate lists
+    cc_qlane &ln = c.ln;
+    const int nb = c.nb, b0 = c.b0;
+    hipLaunchKernelGGL(cc_k_hints_expand, dim3(nb), dim3(64), 0, ln.stream, VP, (const cc_hot_desc_t *)ln.d_qhot, (const cc_hot_desc_t *)db->d_hot,
                        (const int *)(ln.d_vin + nb), nb, ln.d_hits, ln.d_hit_cnt, d_hints ? d_hints + (size_t)b0 * CC_HINT_MAX : (cc_hint_t *)nullptr,
                        d_n_hints ? d_n_hints + b0 : (int32_t *)nullptr);
-    if (ev) LANE_CHK(hipEventRecord(ev[1], ls));
-    rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, cfg->max_fine_opt, ev, nullptr, zc, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr);
-    if (rc != CC_OK) {
-      lane_abort(db, ln);
-      break;
-    }
-    if (!zc) {
-      LANE_CHK(hipMemcpyAsync(ln.h_results, ln.d_results, sizeof(cc_query_result_t) * nb, hipMemcpyDeviceToHost, ls));
-      LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
-      if (rank) LANE_CHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
-      if (detail) LANE_CHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
-    }
-    LANE_CHK(hipEventRecord(ln.fin, ls));
-    for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];  // (a verify chunk reads no sorted view: nothing for an append to wait for beyond this)
-    ln.busy = true;
-    ln.b0 = b0;
-    ln.nb = nb;
-    ln.h_dst = h_res;
-    ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
-    ln.detail_dst = detail;
-    ln.rank_mfo = cfg->max_fine_opt;
-  }
-#undef LANE_CHK
-  return rc;
+    return CC_OK;
+  };
+  plan.body = [&](const cc_chunk &c) -> int {
+    return launch_scoring_chain(db, c.ln, c.nb, CP, lb, ub, cfg->max_fine_opt, c.ev, nullptr, c.zc, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr);
+  };
+  plan.copy_back = [&](const cc_chunk &c) -> int { return results_copy_back(c, rank, detail); };
+  plan.note = [&](const cc_chunk &c) { results_note(c.ln, h_res, rank, detail, cfg->max_fine_opt); };
+  return submit_chunks(db, n, (hipStream_t)stream_, plan);
 }
 int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                         const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
@@ -2050,17 +1998,15 @@ int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, co
 int cc_db_verify_submit_ranked(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                                cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank) {
-  const int vrc = rank_validate(rank, "cc_db_verify_submit_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, nullptr, false);
   if (vrc != CC_OK) return vrc;
   return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank, nullptr);
 }
 int cc_db_verify_submit_ranked_detail(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                       const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                                       cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
-  const int vrc = rank_validate(rank, "cc_db_verify_submit_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, h_detail, true);
   if (vrc != CC_OK) return vrc;
-  const int drc = detail_validate(h_detail, "cc_db_verify_submit_ranked_detail: h_detail must be given");
-  if (drc != CC_OK) return drc;
   return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank, h_detail);
 }
 
@@ -2071,11 +2017,7 @@ int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, con
     const int vrc = verify_validate(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
     if (vrc != CC_OK) return vrc;
   }
-  db->sync_call = true;
-  const int rc = cc_db_verify_submit(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_);
-  db->sync_call = false;
-  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
-  return rc != CC_OK ? rc : r2;
+  return run_sync(db, [&] { return cc_db_verify_submit(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_); });
 }
 
 static int verify_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
@@ -2092,11 +2034,7 @@ static int verify_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int 
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)n_desc, hipMemcpyHostToDevice));
   if (!rank) return cc_db_verify_batch(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr);
-  db->sync_call = true;
-  rc = verify_submit_impl(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail);
-  db->sync_call = false;
-  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
-  return rc != CC_OK ? rc : r2;
+  return run_sync(db, [&] { return verify_submit_impl(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail); });
 }
 int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                             const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res) {
@@ -2105,16 +2043,14 @@ int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc
 int cc_db_verify_batch_host_ranked(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                    const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                                    const cc_rank_out_t *rank) {
-  const int vrc = rank_validate(rank, "cc_db_verify_batch_host_ranked: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, nullptr, false);
   if (vrc != CC_OK) return vrc;
   return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank, nullptr);
 }
 int cc_db_verify_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                           const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
-  const int vrc = rank_validate(rank, "cc_db_verify_batch_host_ranked_detail: rank, its h_cands and h_n must be given and max_ret lie within 1..CC_RANK_MAX");
+  const int vrc = want_ranked(__func__, rank, h_detail, true);
   if (vrc != CC_OK) return vrc;
-  const int drc = detail_validate(h_detail, "cc_db_verify_batch_host_ranked_detail: h_detail must be given");
-  if (drc != CC_OK) return drc;
   return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank, h_detail);
 }
 
@@ -2148,114 +2084,90 @@ int cc_db_pose_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, cons
   }
   DB_POISON_CHK(db, "cc_db_pose_submit");
   if (n == 0) return CC_OK;
-  hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(db->device));
   const int nt = cfg->n_try;
   const bool refine = cfg->refine != 0, curv = h_curv != nullptr;
-  // chunks over the lanes exactly as cc_db_verify_submit cuts its batch (the comments at cc_db_query_submit)
-  hipEvent_t e_start = db->lane[0].done;
-  HIPCHK(hipEventRecord(e_start, stream));
-  for (int i = 0; i < db->n_lanes; i++) {
-    HIPCHK(hipStreamWaitEvent(db->lane[i].stream, e_start, 0));
-    if (db->add_done) HIPCHK(hipStreamWaitEvent(db->lane[i].stream, db->add_done, 0));  // an append queued on another stream
-  }
-  int rc = CC_OK;
-  int qb = (((n + db->n_lanes - 1) / db->n_lanes) + 63) / 64 * 64;
-  if (!db->sync_call && n >= db->qb_max) qb = db->qb_max;
-  qb = qb > db->tune.chunk ? db->tune.chunk : qb;
-#define LANE_CHK(call)                        \
-  do {                                        \
-    hipError_t e_ = (call);                   \
-    if (e_ != hipSuccess) {                   \
-      lane_abort(db, ln);                     \
-      return set_err(CC_EHIP, #call, e_);     \
-    }                                         \
-  } while (0)
-  for (int b0 = 0; b0 < n && rc == CC_OK; b0 += qb) {
-    const int nb = n - b0 < qb ? n - b0 : qb;
-    cc_qlane &ln = db->lane[db->next_lane];
-    db->next_lane = (db->next_lane + 1) % db->n_lanes;
-    rc = lane_finish(db, ln);
-    if (rc != CC_OK) break;
-    rc = lane_alloc_pose(ln);
-    if (rc != CC_OK) break;
+  // a chunk's tables in the lane's buffers, packed.  In: items [nb] | try poses [nb][nt][3] | selector [nb]; out: rows [nb] | try
+  // results [nb][nt] | curvature rows [nb] (small chunks: the kernels write them straight into the lane's pinned buffer)
+  struct tables {
+    cc_pose_item_t *it;
+    double *tp;
+    int *sel;
+    cc_pose_result_t *res;
+    double *tr;
+    cc_pose_curv_t *cv;
+  };
+  auto tables_at = [nt](char *in, char *out, int nb) {
+    cc_pose_item_t *it = (cc_pose_item_t *)in;
+    double *tp = (double *)(it + nb);
+    cc_pose_result_t *res = (cc_pose_result_t *)out;
+    double *tr = (double *)(res + nb);
+    return tables{it, tp, (int *)(tp + (size_t)nb * nt * 3), res, tr, (cc_pose_curv_t *)(tr + (size_t)nb * nt)};
+  };
+  cc_chunk_plan plan;
+  plan.alloc = [&](cc_qlane &ln) -> int { return lane_alloc_pose(ln); };
+  plan.stage = [&](const cc_chunk &c) {
+    const tables h = tables_at(c.ln.h_pin, c.ln.h_pout, c.nb);
+    memcpy(h.it, h_items + c.b0, sizeof(cc_pose_item_t) * (size_t)c.nb);
+    if (nt > 0) memcpy(h.tp, h_try + (size_t)c.b0 * nt * 3, sizeof(double) * (size_t)c.nb * nt * 3);
+    for (int i = 0; i < c.nb; i++) h.sel[i] = h_items[c.b0 + i].q;
+  };
+  plan.upload = [&](const cc_chunk &c, cc_prep_src &src) -> int {
+    cc_qlane &ln = c.ln;
+    HIPCHK(hipMemcpyAsync(ln.d_pin, ln.h_pin, CC_POSE_IN_BYTES(c.nb, nt), hipMemcpyHostToDevice, ln.stream));
+    src = cc_prep_src{d_qdesc, false, tables_at(ln.d_pin, ln.d_pout, c.nb).sel};
+    return CC_OK;
+  };
+  plan.head = [&](const cc_chunk &c) -> int {  // item i is problem i
+    cc_qlane &ln = c.ln;
+    hipLaunchKernelGGL(cc_k_pose_problems, dim3((c.nb + 255) / 256), dim3(256), 0, ln.stream, (const cc_pose_item_t *)tables_at(ln.d_pin, ln.d_pout, c.nb).it, c.nb,
+                       ln.d_prob, ln.d_prob_list, ln.d_nprob);
+    return CC_OK;
+  };
+  plan.body = [&](const cc_chunk &c) -> int {
+    cc_qlane &ln = c.ln;
     hipStream_t ls = ln.stream;
-    // the chunk's tables, packed: items [nb] | try poses [nb][nt][3] | selector [nb]
-    cc_pose_item_t *h_it = (cc_pose_item_t *)ln.h_pin;
-    double *h_tp = (double *)(h_it + nb);
-    int *h_sel = (int *)(h_tp + (size_t)nb * nt * 3);
-    memcpy(h_it, h_items + b0, sizeof(cc_pose_item_t) * (size_t)nb);
-    if (nt > 0) memcpy(h_tp, h_try + (size_t)b0 * nt * 3, sizeof(double) * (size_t)nb * nt * 3);
-    for (int i = 0; i < nb; i++) h_sel[i] = h_items[b0 + i].q;
-    const cc_pose_item_t *d_it = (const cc_pose_item_t *)ln.d_pin;
-    const double *d_tp = (const double *)(d_it + nb);
-    const int *d_sel = (const int *)(d_tp + (size_t)nb * nt * 3);
-    ln.profiled = db->prof && (db->prof_tick++ % db->prof_every) == 0;
-    hipEvent_t *ev = ln.profiled ? ln.pev : nullptr;
-    const bool zc = nb <= CC_ZC_MAX;  // the kernels write the rows of a small chunk straight into the lane's pinned buffer
-    cc_pose_result_t *o_res = (cc_pose_result_t *)(zc ? ln.h_pout : ln.d_pout);
-    double *o_try = (double *)(o_res + nb);
-    cc_pose_curv_t *o_curv = (cc_pose_curv_t *)(o_try + (size_t)nb * nt);
-    LANE_CHK(hipMemcpyAsync(ln.d_pin, ln.h_pin, CC_POSE_IN_BYTES(nb, nt), hipMemcpyHostToDevice, ls));
-    rc = launch_query_prep(db, ln, d_qdesc, nb, false, d_sel);
-    if (rc != CC_OK) {
-      lane_abort(db, ln);
-      break;
+    hipEvent_t *ev = c.ev;
+    const int nb = c.nb;
+    const tables d = tables_at(ln.d_pin, c.zc ? ln.h_pout : ln.d_pout, nb);
+    if (ev) {  // (no checks, no merge: the stages in between are empty)
+      HIPCHK(hipEventRecord(ev[2], ls));
+      HIPCHK(hipEventRecord(ev[3], ls));
     }
-    // the caller's stream goes on once the descriptors have been read
-    LANE_CHK(hipEventRecord(ln.prep, ls));
-    LANE_CHK(hipStreamWaitEvent(stream, ln.prep, 0));
-    if (ev) LANE_CHK(hipEventRecord(ev[0], ls));
-    hipLaunchKernelGGL(cc_k_pose_problems, dim3((nb + 255) / 256), dim3(256), 0, ls, d_it, nb, ln.d_prob, ln.d_prob_list, ln.d_nprob);
-    if (ev) {
-      LANE_CHK(hipEventRecord(ev[1], ls));
-      LANE_CHK(hipEventRecord(ev[2], ls));
-      LANE_CHK(hipEventRecord(ev[3], ls));
-    }
-    hipLaunchKernelGGL(cc_k_gmm_init, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list,
-                       (const int *)ln.d_nprob, (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, ln.d_gres,
-                       cc_gmm_code_pool{ln.d_codes, ln.code_cap, ln.d_heads + 9, ln.d_nprob + 3, ln.pool_cap});
+    launch_gmm_init(db, ln);
     if (refine) {  // (else the list counters stay zero: nothing reads them)
       hipLaunchKernelGGL(cc_k_pose_select, dim3((nb + 63) / 64), dim3(64), 0, ls, nb, cfg->min_corr, (const cc_gmm_result *)ln.d_gres, ln.d_sel, ln.prob_cap,
-                         ln.d_nprob + 1, ln.d_heads + 8, ln.d_sel + 3 * (size_t)ln.prob_cap, ln.d_heads + 12, ln.d_nprob + 3, ln.d_pool_off);
-      hipLaunchKernelGGL(cc_k_gmm_refine<16>, dim3(db->tune.gmm), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 1),
-                         (const int *)ln.d_sel, (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap), (const int *)(ln.d_nprob + 2),
-                         (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, cfg->min_corr, ln.d_pool,
-                         ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes, (const int *)nullptr, (const int *)nullptr, 0);
-      hipLaunchKernelGGL(cc_k_gmm_refine<64>, dim3(db->tune.gmm64), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)(ln.d_nprob + 2),
-                         (const int *)(ln.d_sel + ln.prob_cap), (const int *)(ln.d_heads + 8), (const int *)(ln.d_sel + 2 * (size_t)ln.prob_cap),
-                         (const int *)(ln.d_nprob + 1), (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, cfg->min_corr,
-                         ln.d_pool, ln.pool_cap, (const int *)ln.d_pool_off, ln.d_gres, (const unsigned *)ln.d_codes,
-                         (const int *)(ln.d_sel + 3 * (size_t)ln.prob_cap), (const int *)(ln.d_heads + 12), ln.prob_cap);
+                         ln.head(CC_HD_NSEL16), ln.head(CC_HD_NMID), ln.sel(CC_SEL_CLS), ln.head(CC_HD_CLS), ln.head(CC_HD_POOL), ln.d_pool_off);
+      launch_refine(db, ln, cfg->min_corr);
     }
     if (nt > 0 || curv) {
       const int grid = nb < db->tune.gmm64 ? nb : db->tune.gmm64;
       hipLaunchKernelGGL(cc_k_pose_eval, dim3(grid), dim3(64), 0, ls, (const cc_gmm_problem *)ln.d_prob, (const int *)ln.d_prob_list, (const int *)ln.d_nprob,
                          (const cc_gmm_feat *)ln.d_qfeat, (const cc_gmm_feat *)db->d_feat, (const cc_gmm_result *)ln.d_gres, (const unsigned *)ln.d_codes, nt,
-                         d_tp, o_try, curv ? o_curv : (cc_pose_curv_t *)nullptr);
+                         (const double *)d.tp, d.tr, curv ? d.cv : (cc_pose_curv_t *)nullptr);
     }
-    if (ev) LANE_CHK(hipEventRecord(ev[4], ls));
-    hipLaunchKernelGGL(cc_k_pose_final, dim3((nb + 255) / 256), dim3(256), 0, ls, d_it, nb, (const cc_gmm_result *)ln.d_gres, o_res, (const int *)ln.d_nprob,
-                       zc ? ln.h_nprob : (int *)nullptr);
-    if (ev) LANE_CHK(hipEventRecord(ev[5], ls));
-    LANE_CHK(hipGetLastError());
-    if (!zc) {
-      LANE_CHK(hipMemcpyAsync(ln.h_pout, ln.d_pout, CC_POSE_OUT_BYTES(nb, nt, curv), hipMemcpyDeviceToHost, ls));
-      LANE_CHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
-    }
-    LANE_CHK(hipEventRecord(ln.fin, ls));
-    for (int l = 0; l < CC_NQLEV; l++) ln.view[l] = db->scur[l];  // (a pose chunk reads no sorted view)
-    ln.busy = true;
+    if (ev) HIPCHK(hipEventRecord(ev[4], ls));
+    hipLaunchKernelGGL(cc_k_pose_final, dim3((nb + 255) / 256), dim3(256), 0, ls, (const cc_pose_item_t *)d.it, nb, (const cc_gmm_result *)ln.d_gres, d.res, (const int *)ln.d_nprob,
+                       c.zc ? ln.h_nprob : (int *)nullptr);
+    if (ev) HIPCHK(hipEventRecord(ev[5], ls));
+    HIPCHK(hipGetLastError());
+    return CC_OK;
+  };
+  plan.copy_back = [&](const cc_chunk &c) -> int {
+    cc_qlane &ln = c.ln;
+    HIPCHK(hipMemcpyAsync(ln.h_pout, ln.d_pout, CC_POSE_OUT_BYTES(c.nb, nt, curv), hipMemcpyDeviceToHost, ln.stream));
+    HIPCHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ln.stream));
+    return CC_OK;
+  };
+  plan.note = [&](const cc_chunk &c) {
+    cc_qlane &ln = c.ln;
     ln.pose = true;
-    ln.b0 = b0;
-    ln.nb = nb;
     ln.pose_res = h_res;
     ln.pose_try = nt > 0 ? h_try_corr : nullptr;
     ln.pose_curv = h_curv;
     ln.pose_ntry = nt;
-  }
-#undef LANE_CHK
-  return rc;
+  };
+  return submit_chunks(db, n, (hipStream_t)stream_, plan);
 }
 
 int cc_db_pose_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
@@ -2264,11 +2176,7 @@ int cc_db_pose_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const
     const int vrc = pose_validate(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr);
     if (vrc != CC_OK) return vrc;
   }
-  db->sync_call = true;
-  const int rc = cc_db_pose_submit(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, stream_);
-  db->sync_call = false;
-  const int r2 = cc_db_query_wait(db);  // also after an error: nothing may stay in flight behind a synchronous call
-  return rc != CC_OK ? rc : r2;
+  return run_sync(db, [&] { return cc_db_pose_submit(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, stream_); });
 }
 
 int cc_db_pose_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
