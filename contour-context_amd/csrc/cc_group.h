@@ -26,7 +26,8 @@ __device__ __forceinline__ void cc_wave_sync() {
 
 
 // bits of a wave-wide mask below the caller's lane: popcount(m & ((1 << lane) - 1)) as the two v_mbcnt instructions it is (the
-// generic expression costs two ANDs and two bit counts; with the mask in scalar registers nothing else)
+// generic expression costs two ANDs and two bit counts; with the mask in scalar registers nothing else).  A function of the
+// mask and the caller's lane number alone: any set of lanes may call it (the call sites sit inside `if (pred)`).
 __device__ __forceinline__ int cc_mbcnt(unsigned long long m) {
 #ifndef CC_EMU
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
@@ -287,7 +288,7 @@ __device__ __forceinline__ float cc_quad_bcast(float v) { return __shfl(v, Q, 4)
 #endif
 
 // this lane's bit of a wave-uniform 64-bit mask, as a condition (the mask stays in scalar registers: a select on it is one
-// v_cndmask with the register pair as its condition)
+// v_cndmask with the register pair as its condition).  m must be the same in every calling lane; any set of lanes may call.
 #ifndef CC_EMU
 __device__ __forceinline__ bool cc_mask_lane(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 #else
@@ -317,7 +318,10 @@ __device__ __forceinline__ int cc_row_shl1(int v) {
 
 // inclusive prefix sum over the wave's 64 lanes: a Hillis-Steele scan inside each 16-lane row on DPP row shifts (register to
 // register), then the three row totals added to the rows behind them -- ~12 instructions where six ds_bpermute round trips
-// (__shfl_up) are six dependent LDS-crossbar latencies
+// (__shfl_up) are six dependent LDS-crossbar latencies.
+// ALL 64 lanes of the wave must be active at the call (every call site is in wave-uniform control flow, lanes without an
+// element pass 0): the row totals are read from lanes 15, 31 and 47 by v_readlane, and an inactive lane's register holds
+// whatever was there.  The same holds for cc_wave_scan_total, which reads lane 63.
 __device__ __forceinline__ int cc_wave_scan_incl(int v) {
   v += cc_row_shr<1>(v);
   v += cc_row_shr<2>(v);

@@ -2,7 +2,8 @@
 // including a restatement of Eigen 3.3 SelfAdjointEigenSolver<Matrix2f>::compute (scale, trivial
 // 2x2 tridiagonalisation, implicit symmetric QR with Wilkinson shift, ascending sort).
 // Compiled with -ffp-contract=off: every operation below is an individually rounded IEEE f32/f64
-// operation in the order the reference performs it.
+// operation in the order the reference performs it.  cc_eigen2f is checked bit for bit against the oracle's
+// restatement on the CPU harness (tests/test_emu_primitives.py) and device against harness in tests/test_gpu_primitives.py.
 #pragma once
 #include "cc_dev.h"
 
@@ -173,7 +174,9 @@ __device__ __forceinline__ void cc_calc_stat_vals(const cc_dev_cfg &cfg, const c
 // e_atan2f.c / s_atanf.c (argument reduction to four intervals, odd/even degree-11 polynomial, hi/lo table), restated
 // operation for operation in f32: the device library's atan2f is as accurate but not the same function, and one ulp of
 // theta can move a check across the pi/16 window of BCI::checkConstellSim.  Checked bit for bit against glibc 2.35's
-// atan2f on 2e8 arguments (1e8 of them differences of BEV coordinates), tests/test_atan2f_replica.py.
+// atan2f on 2e8 arguments (1e8 of them differences of BEV coordinates); tests/test_atan2f_replica.py keeps that check as
+// g++ compiles it for the CPU harness, tests/test_gpu_primitives.py asserts the same bits from the gfx950 code object (the
+// device's f32 division, denormal handling and -ffp-contract=off are what could break it).
 __device__ __forceinline__ float cc_atanf_fdlibm(float x) {
   const float atanhi[4] = {4.6364760399e-01f, 7.8539812565e-01f, 9.8279368877e-01f, 1.5707962513e+00f};
   const float atanlo[4] = {5.0121582440e-09f, 3.7748947079e-08f, 3.4473217170e-08f, 7.5497894159e-08f};
@@ -219,7 +222,8 @@ __device__ __forceinline__ float cc_atanf_fdlibm(float x) {
 // filter of checkConstellCorrespSim compares two such angles with pi / 6 (contour_mng.h:1195-1210), and the device
 // library's acosf differs from glibc's in the last bit now and then -- once in ~10^7 comparisons a pair is kept on one
 // side and dropped on the other (round 6: drive 131409 of tests/fuzz_gpu_query.py, one check of 100 000 queries).  Bit-identical
-// to this libm on every third float of [-1, 1] (profiles/r6/acosf_replica_check.c) and in tests/test_atan2f_replica.py.
+// to this libm on every third float of [-1, 1] (profiles/r6/acosf_replica_check.c), in tests/test_atan2f_replica.py (CPU
+// harness) and, as compiled for gfx950 (its sqrtf and f32 division included), in tests/test_gpu_primitives.py.
 __device__ __forceinline__ float cc_acosf_fdlibm(float x) {
   const float one = 1.0f, pi = 3.1415925026e+00f, pio2_hi = 1.5707962513e+00f, pio2_lo = 7.5497894159e-08f,
               pS0 = 1.6666667163e-01f, pS1 = -3.2556581497e-01f, pS2 = 2.0121252537e-01f, pS3 = -4.0055535734e-02f,
