@@ -48,7 +48,8 @@ _lib = None
 EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_db_cfg", "cc_default_thresholds",
            "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_ingest_points", "cc_ingest_points_host", "cc_scan_ingest_points", "cc_scan_ingest_points_batch",
            "cc_ingest_segments", "cc_ingest_segments_host", "cc_scan_ingest_segments",
-           "cc_ingest_points_motion", "cc_ingest_points_motion_host", "cc_scan_ingest_points_motion", "cc_motion_knots", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
+           "cc_ingest_points_motion", "cc_ingest_points_motion_host", "cc_scan_ingest_points_motion", "cc_motion_knots",
+           "cc_range_sensor_create", "cc_range_sensor_destroy", "cc_ingest_ranges", "cc_ingest_ranges_host", "cc_scan_ingest_ranges", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
            "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_hot_ptr", "cc_db_feat_ptr", "cc_pack_scans", "cc_db_add_packed",
            "cc_packed_sizes", "cc_db_bucket_state", "cc_est_sens_tf",
            "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
@@ -91,6 +92,11 @@ def lib():
         _lib.cc_scan_ingest_points_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_motion_knots.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]
         _lib.cc_motion_knots.restype = None
+        _lib.cc_range_sensor_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.cc_range_sensor_destroy.argtypes = [C.c_void_p]
+        _lib.cc_ingest_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.cc_ingest_ranges_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.cc_scan_ingest_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_destroy.argtypes = [C.c_void_p]
         _lib.cc_db_size.argtypes = [C.c_void_p]
@@ -219,6 +225,71 @@ def motion_knots(pose_begin, pose_end, ref=1.0, K=32):
     return out
 
 
+RANGE_WORDS = {"u16": (L.RANGE_U16, np.uint16), "u32": (L.RANGE_U32, np.uint32), "f32": (L.RANGE_F32, np.float32)}   # names Context.range_sensor takes
+RANGE_ORDERS = {"row": L.RANGE_ROW_MAJOR, "col": L.RANGE_COL_MAJOR}
+
+
+def _range_model(rows, cols, word, order, range_scale, beam_alt, beam_az_off, col_az, origin, col_knot, K):
+    """The arguments of Context.range_sensor -> (L.RangeModel, the arrays it points to).  Shapes and names are checked here, values
+    by the library."""
+    if word not in RANGE_WORDS:
+        raise ValueError("unknown range word %r (known: %s)" % (word, sorted(RANGE_WORDS)))
+    if order not in RANGE_ORDERS:
+        raise ValueError("unknown storage order %r (known: %s)" % (order, sorted(RANGE_ORDERS)))
+    rows, cols, K = int(rows), int(cols), int(K)
+    row_tab, col_cs = L.range_tables(beam_alt, np.zeros(rows) if beam_az_off is None else beam_az_off, col_az)
+    if row_tab.shape != (rows, 4):
+        raise ValueError("beam_alt / beam_az_off must hold %d angles (one per row), got %d" % (rows, len(row_tab)))
+    if col_cs.shape != (cols, 2):
+        raise ValueError("col_az must hold %d angles (one per column), got %d" % (cols, len(col_cs)))
+    knot = None
+    if col_knot is not None:
+        knot = np.asarray(col_knot).reshape(-1)
+        if knot.dtype.kind not in "iu":
+            raise ValueError("col_knot must hold integers, got %s" % knot.dtype)
+        if knot.size and (int(knot.min()) < -2 ** 31 or int(knot.max()) >= 2 ** 31):
+            raise ValueError("col_knot does not fit 32-bit integers")
+        knot = np.ascontiguousarray(knot.astype(np.int32))   # (the library checks the range 0 .. K - 1)
+        if knot.shape != (cols,):
+            raise ValueError("col_knot must hold %d knot indices (one per column), got %d" % (cols, len(knot)))
+    n, z = origin
+    m = L.RangeModel(rows, cols, RANGE_WORDS[word][0], RANGE_ORDERS[order], float(range_scale), float(n), float(z), K, row_tab.ctypes.data,
+                     col_cs.ctypes.data, knot.ctypes.data if knot is not None else None)
+    return m, (row_tab, col_cs, knot)
+
+
+class RangeSensor:
+    """cc_range_sensor: a range sensor's model with its tables on the device (Context.range_sensor makes one)."""
+
+    def __init__(self, ctx, model, word):
+        self.ctx, self.rows, self.cols, self.K, self.word = ctx, model.n_rows, model.n_cols, model.n_knots, word
+        h = C.c_void_p()
+        _chk(lib().cc_range_sensor_create(ctx.h, C.addressof(model), C.byref(h)), "cc_range_sensor_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().cc_range_sensor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _knots(self, knots, n):
+        """[n, K, 3, 4] or [n, K, 12] -> contiguous f32 [n, K * 12] (host); None exactly when the sensor has no knots"""
+        if (knots is None) != (self.K == 0):
+            raise ValueError("knots come with a sensor made with K >= 1, and only with one (K = %d)" % self.K)
+        if knots is None:
+            return None
+        knots = np.ascontiguousarray(np.asarray(knots, np.float32).reshape(n, -1))
+        if knots.shape != (n, self.K * 12):
+            raise ValueError("knots must hold K = %d 3 x 4 matrices per scan: [%d, %d, 3, 4], got %s" % (self.K, n, self.K, knots.shape))
+        return knots
+
+
 def _segment_table(scans, device):
     """[[(points, layout, tf), ...], ...] -> (array of L.PointSegment, int32 [n + 1] first-segment indices).  points: contiguous CUDA
     tensors (device=True) or numpy arrays holding the records as they are; None or an empty one for a segment without points."""
@@ -344,6 +415,63 @@ class Context:
             _chk(lib().cc_ingest_points(self.h, xyzi.data_ptr(), C.addressof(lay) if lay is not None else None, offsets.ctypes.data, n,
                                         tfa.ctypes.data if tfa is not None else None, out.data_ptr(), dbg_p, stream), "cc_ingest_points")
         return (out, dbg) if debug else out
+
+    def range_sensor(self, rows, cols, word="u16", order="row", range_scale=0.001, beam_alt=None, beam_az_off=None, col_az=None, origin=(0.0, 0.0),
+                     col_knot=None, K=0):
+        """A range sensor (cc_range_sensor_create): images of rows x cols words ("u16" | "u32" | "f32") stored "row"-major (pixel j =
+        row * cols + col) or "col"-major (firing after firing), range_scale metres per unit of the word.  beam_alt / beam_az_off: the
+        beams' altitude and azimuth offset, col_az: the firings' encoder azimuth, all in radians -- the tables are made in f64 and
+        rounded to f32.  origin = (distance of the beam origin from the rotation axis, its height).  K knots per scan (0: none) and
+        col_knot [cols]: the knot of every firing (None: all 0)."""
+        if beam_alt is None or col_az is None:
+            raise ValueError("range_sensor needs beam_alt and col_az")
+        m, keep = _range_model(rows, cols, word, order, range_scale, beam_alt, beam_az_off, col_az, origin, col_knot, K)
+        return RangeSensor(self, m, word)   # (the tables are copied before the call returns; `keep` lives until here)
+
+    def ingest_ranges(self, sensor, ranges, knots=None, out=None, debug=False):
+        """Range images rasterised in place (cc_ingest_ranges): `ranges` is a contiguous CUDA tensor of n * rows * cols words of the
+        sensor's type (any shape; int16 / int32 tensors stand for u16 / u32), knots [n, K, 3, 4] or [n, K, 12] host matrices (None
+        exactly for a sensor with K = 0): every pixel is moved by the knot of its column.  Returns ingest()'s outputs."""
+        import torch
+        if sensor.ctx is not self:
+            raise ValueError("the sensor belongs to another context")
+        assert ranges.is_cuda and ranges.is_contiguous()
+        wbytes = np.dtype(RANGE_WORDS[sensor.word][1]).itemsize
+        if ranges.element_size() != wbytes or (sensor.word == "f32") != ranges.dtype.is_floating_point:
+            raise ValueError("the sensor's words are %s, the tensor holds %s" % (sensor.word, ranges.dtype))
+        hw = sensor.rows * sensor.cols
+        if ranges.numel() == 0 or ranges.numel() % hw != 0:
+            raise ValueError("%d words are not whole images of %d x %d" % (ranges.numel(), sensor.rows, sensor.cols))
+        n = ranges.numel() // hw
+        kn = sensor._knots(knots, n)
+        if out is None:
+            out = torch.empty((n, DESC_BYTES), dtype=torch.uint8, device=ranges.device)
+        dbg_p, dbg = None, None
+        if debug:
+            dbg = {"bev": torch.empty((n, self.n_cell), dtype=torch.float32, device=ranges.device),
+                   "pix_rc": torch.empty((n, self.n_cell, 2), dtype=torch.float32, device=ranges.device),
+                   "labels": torch.empty((n, L.NLEV, self.n_cell), dtype=torch.int16, device=ranges.device)}
+            st = IngestDebug(dbg["bev"].data_ptr(), dbg["pix_rc"].data_ptr(), dbg["labels"].data_ptr())
+            dbg_p = C.addressof(st)
+        stream = torch.cuda.current_stream(ranges.device).cuda_stream
+        _chk(lib().cc_ingest_ranges(self.h, sensor.h, ranges.data_ptr(), n, kn.ctypes.data if kn is not None else None, out.data_ptr(), dbg_p, stream),
+             "cc_ingest_ranges")
+        return (out, dbg) if debug else out
+
+    def ingest_ranges_host(self, sensor, ranges, knots=None):
+        """ingest_ranges() from a host array of the sensor's word type: host descriptors out."""
+        if sensor.ctx is not self:
+            raise ValueError("the sensor belongs to another context")
+        ranges = np.ascontiguousarray(ranges, RANGE_WORDS[sensor.word][1])
+        hw = sensor.rows * sensor.cols
+        if ranges.size == 0 or ranges.size % hw != 0:
+            raise ValueError("%d words are not whole images of %d x %d" % (ranges.size, sensor.rows, sensor.cols))
+        n = ranges.size // hw
+        kn = sensor._knots(knots, n)
+        out = np.zeros(n, L.scan_desc_dt)
+        _chk(lib().cc_ingest_ranges_host(self.h, sensor.h, ranges.ctypes.data, n, kn.ctypes.data if kn is not None else None, out.ctypes.data, None),
+             "cc_ingest_ranges_host")
+        return out
 
     def ingest_segments(self, scans, out=None, debug=False):
         """Every scan from an ordered list of point segments, each with its own record shape and transform (cc_ingest_segments):

@@ -370,9 +370,23 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
   CC_K1_MOT_ATTR(32)
   CC_K1_MOT_ATTR(0)
 #undef CC_K1_MOT_ATTR
+  const int lds1_rng = (int)(((c->lds1 + 15) & ~(size_t)15) + CC_K1_RNG_LDS_BYTES);  // (the row table and the knots sit behind the layout)
+#define CC_K1_RNG_ATTR(WORD)                                                                                                                                  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, false, false, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng)); \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, true, false, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng));  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, false, true, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng));  \
+  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, true, true, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng));
+  CC_K1_RNG_ATTR(CC_K1_WORD_U16)
+  CC_K1_RNG_ATTR(CC_K1_WORD_U32)
+  CC_K1_RNG_ATTR(CC_K1_WORD_F32)
+#undef CC_K1_RNG_ATTR
   if (nc > (size_t)CC_MAX_CELLS) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: grid larger than 150 x 150 cells");
+  }
+  if (lds1_rng > 160 * 1024) {
+    cc_destroy(c);
+    return set_err(CC_EINVAL, "cc_create: the range-image kernels' tables do not fit the LDS behind this grid");
   }
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_contours, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CC_K2L_LDS_BYTES));
   CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_contours_mid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds2));
@@ -472,6 +486,33 @@ struct mot_call {
   const float *h_knots;  // [n_scans][K][12]
 };
 static_assert(CC_K1_MOT_KNOTS_MAX == CC_MOTION_KNOTS_MAX, "k_rasterize.h's knot table holds CC_MOTION_KNOTS_MAX matrices");
+// A range sensor: the checked model with its tables on the device (cc_range_sensor_create).
+struct cc_range_sensor {
+  cc_ctx *ctx = nullptr;  // compared, never dereferenced once the sensor exists: a sensor may outlive its context until it is destroyed
+  int device = 0;
+  cc_k1_range kr;   // what the kernels take (words and knots are set per chunk)
+  int word_type = 0, word_bytes = 0;
+  float4 *d_row = nullptr, *d_col = nullptr;
+};
+static_assert(CC_K1_RNG_ROWS_MAX == CC_RANGE_ROWS_MAX && CC_K1_RNG_COLS_MAX == CC_RANGE_COLS_MAX && (int)CC_K1_WORD_U16 == (int)CC_RANGE_U16 &&
+                  (int)CC_K1_WORD_U32 == (int)CC_RANGE_U32 && (int)CC_K1_WORD_F32 == (int)CC_RANGE_F32,
+              "k_rasterize.h's range-image limits and word types are the header's");
+// A checked cc_*_ranges call (ranges_check below) as ingest_on takes it: d_points are the range words, h_offsets the pixels' (i * H * W).
+struct rng_call {
+  const cc_range_sensor *s;
+  const float *h_knots;  // [n_scans][K][12], nullptr iff K == 0
+};
+// Everything the header promises to check about a cc_*_ranges call that the sensor's creation has not, before anything is queued or read.
+// base: the pointer whose alignment counts (device or host words).
+static int ranges_check(cc_ctx *c, const cc_range_sensor *s, const void *base, const float *h_knots, const char *who) {
+  const char *why = nullptr;
+  if (!s || !base) why = "sensor and ranges must not be NULL";
+  else if (s->ctx != c) why = "the sensor was created on another context";
+  else if (((uintptr_t)base & (uintptr_t)(s->word_bytes - 1)) != 0) why = "the range words must be aligned to their size";
+  else if ((h_knots == nullptr) != (s->kr.n_knots == 0)) why = "h_knots must be NULL exactly when the sensor has no knots (n_knots == 0)";
+  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
+  return CC_OK;
+}
 // Everything the header promises to check about the motion arguments (`lay` has passed point_layout), before anything is queued or read.
 static int motion_check(const cc_point_layout_t &lay, const cc_point_motion_t *motion, const float *h_time, const float *h_knots, int n_scans, const char *who) {
   const char *why = nullptr;
@@ -486,16 +527,34 @@ static int motion_check(const cc_point_layout_t &lay, const cc_point_motion_t *m
   if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
   return CC_OK;
 }
+// `bytes` of pinned memory in slot `slot` of the staging ring (the buffer the chunk's segment table, times and knots ride in), grown
+// when it is too small; nullptr with the error set when the allocation fails.
+static char *slot_stage(cc_ctx *c, int slot, size_t bytes) {
+  if (c->h_seg_cap[slot] < bytes) {
+    if (c->h_seg[slot]) hipHostFree(c->h_seg[slot]);
+    c->h_seg[slot] = nullptr;
+    c->h_seg_cap[slot] = 0;
+    const hipError_t e = hipHostMalloc((void **)&c->h_seg[slot], bytes * 2, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      c->h_seg[slot] = nullptr;
+      set_err(CC_EHIP, "hipHostMalloc of a staging slot", e);
+      return nullptr;
+    }
+    c->h_seg_cap[slot] = bytes * 2;
+  }
+  return c->h_seg[slot];
+}
 // cc_ingest_points on the scratch set S (c->ing_mu held by the caller; `lay` has passed point_layout).  h_tf: [n_scans][12] or nullptr.
 // sg: nullptr, or the call's segments -- d_points, lay and h_tf are not looked at then (cc_ingest_segments).
 // mc: nullptr, or the call's per-point time and knots (cc_ingest_points_motion; without h_tf and sg).
+// rg: nullptr, or the call's range sensor and knots (cc_ingest_ranges; without h_tf, sg and mc): d_points are the range words, a "point" is a pixel.
 static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_point_layout_t lay, const float *h_tf, const int64_t *h_offsets, int n_scans,
                      cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, hipStream_t stream, const char *who, const seg_call *sg = nullptr,
-                     const mot_call *mc = nullptr) {
+                     const mot_call *mc = nullptr, const rng_call *rg = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   // KITTI records without a transform take the float4 kernels (16-byte loads: the base must be aligned for them); everything
   // else one of the record loaders' instances
-  const bool kitti = lay.stride_bytes == 16 && lay.xyz_offset == 0 && !h_tf && !mc && ((uintptr_t)d_points & 15u) == 0;
+  const bool kitti = lay.stride_bytes == 16 && lay.xyz_offset == 0 && !h_tf && !mc && !rg && ((uintptr_t)d_points & 15u) == 0;
   for (int i = 0; i < n_scans; i++) {
     const int64_t n = h_offsets[i + 1] - h_offsets[i];
     if (!(n > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
@@ -522,13 +581,7 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
       const int s0 = sg->scan_segs[b0], ns = sg->scan_segs[b0 + nb] - s0;
       const size_t ent_off = (sizeof(int) * (size_t)(nb + 1) + 7) & ~(size_t)7, bytes = ent_off + sizeof(cc_k1_seg) * (size_t)ns;
       if (!S.d_seg) HIPCHK(hipMalloc(&S.d_seg, ((sizeof(int) * (size_t)(S.cap + 1) + 7) & ~(size_t)7) + sizeof(cc_k1_seg) * CC_SEG_MAX * (size_t)S.cap));
-      if (c->h_seg_cap[slot] < bytes) {
-        if (c->h_seg[slot]) hipHostFree(c->h_seg[slot]);
-        c->h_seg[slot] = nullptr;
-        c->h_seg_cap[slot] = 0;
-        HIPCHK(hipHostMalloc((void **)&c->h_seg[slot], bytes * 2, hipHostMallocDefault));
-        c->h_seg_cap[slot] = bytes * 2;
-      }
+      if (!slot_stage(c, slot, bytes)) return CC_EHIP;
       int *ss = (int *)c->h_seg[slot];
       for (int i = 0; i <= nb; i++) ss[i] = sg->scan_segs[b0 + i] - s0;
       memcpy(c->h_seg[slot] + ent_off, sg->segs + s0, sizeof(cc_k1_seg) * (size_t)ns);
@@ -540,13 +593,7 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
     if (mc) {  // the chunk's times and knots ride in the same slot of the ring (the segment tables' buffer: a call has one or the other)
       const size_t kf = (size_t)mc->m.n_knots * 12, bytes = sizeof(float) * (2 + kf) * (size_t)nb;
       if (!S.d_mot) HIPCHK(hipMalloc(&S.d_mot, sizeof(float) * (2 + (size_t)CC_MOTION_KNOTS_MAX * 12) * (size_t)S.cap));
-      if (c->h_seg_cap[slot] < bytes) {
-        if (c->h_seg[slot]) hipHostFree(c->h_seg[slot]);
-        c->h_seg[slot] = nullptr;
-        c->h_seg_cap[slot] = 0;
-        HIPCHK(hipHostMalloc((void **)&c->h_seg[slot], bytes * 2, hipHostMallocDefault));
-        c->h_seg_cap[slot] = bytes * 2;
-      }
+      if (!slot_stage(c, slot, bytes)) return CC_EHIP;
       float *hm = (float *)c->h_seg[slot];
       memcpy(hm, mc->h_time + (size_t)b0 * 2, sizeof(float) * 2 * (size_t)nb);
       memcpy(hm + 2 * (size_t)nb, mc->h_knots + (size_t)b0 * kf, sizeof(float) * kf * (size_t)nb);
@@ -557,7 +604,21 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
       d_mot.time_u32 = mc->m.time_type == CC_TIME_U32 ? 1 : 0;
       d_mot.n_knots = mc->m.n_knots;
     }
-    const int mot_tab = (int)((c->lds1 + 15) & ~(size_t)15);  // where the knot table goes in LDS
+    cc_k1_range d_rng = {};
+    if (rg) {  // the chunk's knots ride in the same slot of the ring, as the motion call's do
+      d_rng = rg->s->kr;
+      d_rng.words = (const char *)d_points + (long long)h_offsets[b0] * rg->s->word_bytes;
+      d_rng.knots = nullptr;
+      if (d_rng.n_knots > 0) {
+        const size_t kf = (size_t)d_rng.n_knots * 12, bytes = sizeof(float) * kf * (size_t)nb;
+        if (!S.d_mot) HIPCHK(hipMalloc(&S.d_mot, sizeof(float) * (2 + (size_t)CC_MOTION_KNOTS_MAX * 12) * (size_t)S.cap));
+        if (!slot_stage(c, slot, bytes)) return CC_EHIP;
+        memcpy(c->h_seg[slot], rg->h_knots + (size_t)b0 * kf, bytes);
+        HIPCHK(hipMemcpyAsync(S.d_mot, c->h_seg[slot], bytes, hipMemcpyHostToDevice, stream));
+        d_rng.knots = S.d_mot;
+      }
+    }
+    const int mot_tab = (int)((c->lds1 + 15) & ~(size_t)15);  // where the knot table (the range kernels': row table and knots) goes in LDS
     HIPCHK(hipEventRecord(c->off_ev[slot], stream));
     c->off_busy[slot] = true;
     const float4 *pts = sg ? nullptr : (const float4 *)d_points + h_offsets[b0];  // (the float4 kernels')
@@ -576,7 +637,34 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
       c->ev_used += 3;
       HIPCHK(hipEventRecord(pe[0], stream));
     }
-    if (nb <= CC_K1_SPLIT_MAX_SCANS) {
+    if (rg) {  // a range image: the split path for a handful of scans, one workgroup per scan otherwise, like the branches below
+      const bool split = nb <= CC_K1_SPLIT_MAX_SCANS;
+      if (split && !S.k1_part.key) {
+        const size_t np = (size_t)CC_K1_SPLIT_MAX_SCANS * CC_K1_SPLIT;
+        HIPCHK(hipMalloc(&S.k1_part.key, sizeof(unsigned) * np * nc));
+        HIPCHK(hipMalloc(&S.k1_part.idx, sizeof(int) * np * nc));
+        HIPCHK(hipMalloc(&S.k1_part.red, sizeof(unsigned) * np * 2));
+      }
+      const size_t lds_rng = (size_t)mot_tab + CC_K1_RNG_LDS_BYTES;
+#define CC_K1_RNG_ONE(POW2, PART, WORD)                                                                                                                   \
+  hipLaunchKernelGGL((cc_k_rasterize_rng<CC_K1_U_DEFAULT, POW2, PART, WORD>), dim3(PART ? nb * CC_K1_SPLIT : nb), dim3(CC_INGEST_BLOCK), lds_rng, stream, \
+                     c->dcfg, d_rng, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, PART ? S.k1_part : cc_k1_part(), S.list, want_dense)
+#define CC_K1_RNG_LAUNCH(WORD)                                                                                                                   \
+  {                                                                                                                                              \
+    if (split) {                                                                                                                                 \
+      if (c->dcfg.reso_pow2) CC_K1_RNG_ONE(true, true, WORD);                                                                                    \
+      else CC_K1_RNG_ONE(false, true, WORD);                                                                                                     \
+      hipLaunchKernelGGL((cc_k_rasterize_merge_rng<WORD>), dim3(nb), dim3(1024), 0, stream, c->dcfg, d_rng, (const long long *)S.d_offsets,      \
+                         S.k1_part, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);                                                               \
+    } else if (c->dcfg.reso_pow2) CC_K1_RNG_ONE(true, false, WORD);                                                                              \
+    else CC_K1_RNG_ONE(false, false, WORD);                                                                                                      \
+  }
+      if (rg->s->word_type == CC_RANGE_U16) CC_K1_RNG_LAUNCH(CC_K1_WORD_U16)
+      else if (rg->s->word_type == CC_RANGE_U32) CC_K1_RNG_LAUNCH(CC_K1_WORD_U32)
+      else CC_K1_RNG_LAUNCH(CC_K1_WORD_F32)
+#undef CC_K1_RNG_LAUNCH
+#undef CC_K1_RNG_ONE
+    } else if (nb <= CC_K1_SPLIT_MAX_SCANS) {
       // a handful of scans (the per-scan loop brings one): CC_K1_SPLIT workgroups per scan sweep a range of its points each,
       // a second small kernel combines the ranges (first range wins ties: file order)
       if (!S.k1_part.key) {
@@ -820,6 +908,146 @@ int cc_ingest_points_motion_host(cc_ctx *c, const void *h_points, const cc_point
   if (!motion) return set_err(CC_EINVAL, CC_WHO(": motion, h_time and h_knots must not be NULL"));
   const mot_call mc = {*motion, h_time, h_knots};
   return ingest_points_host(c, h_points, layout, h_offsets, n_scans, nullptr, h_out, h_bev, who, &mc);
+}
+
+// ---- a sensor's range image rasterised in place (cc_ingest_ranges and its siblings) ----
+int cc_range_sensor_create(cc_ctx *c, const cc_range_model_t *m, cc_range_sensor **out) {
+  const char *who = "cc_range_sensor_create";
+  if (!c || !m || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  const char *why = nullptr;
+  const long long hw = (long long)m->n_rows * (long long)m->n_cols;
+  if (m->n_rows < 1 || m->n_rows > CC_RANGE_ROWS_MAX) why = "n_rows must be 1 .. CC_RANGE_ROWS_MAX";
+  else if (m->n_cols < 1 || m->n_cols > CC_RANGE_COLS_MAX) why = "n_cols must be 1 .. CC_RANGE_COLS_MAX";
+  else if (!(hw > 10)) why = "an image with <= 10 pixels (CHECK_GT(size, 10), contour_mng.h:507)";
+  else if (hw >= (1 << CC_K1_IDX_BITS)) why = "an image with >= 2^21 pixels";
+  else if (m->word_type != CC_RANGE_U16 && m->word_type != CC_RANGE_U32 && m->word_type != CC_RANGE_F32) why = "word_type must be CC_RANGE_U16, _U32 or _F32";
+  else if (m->order != CC_RANGE_ROW_MAJOR && m->order != CC_RANGE_COL_MAJOR) why = "order must be CC_RANGE_ROW_MAJOR or CC_RANGE_COL_MAJOR";
+  else if (!std::isfinite(m->range_scale) || !std::isfinite(m->origin_n) || !std::isfinite(m->origin_z)) why = "range_scale, origin_n and origin_z must be finite";
+  else if (m->n_knots < 0 || m->n_knots > CC_MOTION_KNOTS_MAX) why = "n_knots must be 0 .. CC_MOTION_KNOTS_MAX";
+  else if (!m->row_tab || !m->col_cos_sin) why = "row_tab and col_cos_sin must not be NULL";
+  else if (m->col_knot)
+    for (int i = 0; i < m->n_cols; i++)
+      if (m->col_knot[i] < 0 || m->col_knot[i] > (m->n_knots > 0 ? m->n_knots - 1 : 0)) why = "every col_knot must be in [0, K - 1] (K = 0: 0)";
+  if (why) return set_err(CC_EINVAL, CC_WHO((std::string(": ") + why)));
+  HIPCHK(hipSetDevice(c->device));
+  // device layout: one float4 per row (the model's four values) and ONE float4 per column (cos, sin, the knot's bits, 0): a pixel's
+  // column data is one aligned 16-byte load
+  std::vector<float4> rows(m->n_rows), cols(m->n_cols);
+  for (int i = 0; i < m->n_rows; i++) rows[i] = make_float4(m->row_tab[4 * i], m->row_tab[4 * i + 1], m->row_tab[4 * i + 2], m->row_tab[4 * i + 3]);
+  for (int i = 0; i < m->n_cols; i++) {
+    const int32_t k = m->col_knot ? m->col_knot[i] : 0;
+    float kb;
+    memcpy(&kb, &k, 4);
+    cols[i] = make_float4(m->col_cos_sin[2 * i], m->col_cos_sin[2 * i + 1], kb, 0.f);
+  }
+  cc_range_sensor *s = new cc_range_sensor();
+  s->ctx = c;
+  s->device = c->device;
+  s->word_type = m->word_type;
+  s->word_bytes = m->word_type == CC_RANGE_U16 ? 2 : 4;
+  hipError_t e = hipMalloc(&s->d_row, sizeof(float4) * rows.size());
+  if (e == hipSuccess) e = hipMalloc(&s->d_col, sizeof(float4) * cols.size());
+  if (e == hipSuccess) e = hipMemcpy(s->d_row, rows.data(), sizeof(float4) * rows.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s->d_col, cols.data(), sizeof(float4) * cols.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    hipFree(s->d_row);
+    hipFree(s->d_col);
+    delete s;
+    return set_err(CC_EHIP, CC_WHO(": the sensor's tables"), e);
+  }
+  cc_k1_range &kr = s->kr;
+  kr.words = nullptr;
+  kr.row = s->d_row;
+  kr.col = s->d_col;
+  kr.knots = nullptr;
+  kr.n_rows = m->n_rows;
+  kr.n_cols = m->n_cols;
+  kr.col_major = m->order == CC_RANGE_COL_MAJOR ? 1 : 0;
+  // j / D on the device (k_rasterize.h has the proof): a shift for a power of two, else the product with ceil(2^33 / D) >> 33
+  const unsigned D = (unsigned)(kr.col_major ? m->n_rows : m->n_cols);
+  kr.div_shift = -1;
+  kr.div_magic = 0;
+  if ((D & (D - 1)) == 0) {
+    kr.div_shift = 0;
+    while ((1u << kr.div_shift) < D) kr.div_shift++;
+  } else {
+    kr.div_magic = (unsigned)(((1ull << CC_K1_RNG_MAGIC_SHIFT) + D - 1) / D);  // D >= 3: below 2^32
+  }
+  kr.n_knots = m->n_knots;
+  kr.range_scale = m->range_scale;
+  kr.origin_n = m->origin_n;
+  kr.origin_z = m->origin_z;
+  *out = s;
+  return CC_OK;
+}
+
+int cc_range_sensor_destroy(cc_range_sensor *s) {
+  if (!s) return CC_OK;
+  hipSetDevice(s->device);
+  hipFree(s->d_row);
+  hipFree(s->d_col);
+  delete s;
+  return CC_OK;
+}
+
+// the pixels' offsets of n_scans images: what ingest_on takes as h_offsets
+static std::vector<int64_t> ranges_offsets(const cc_range_sensor *s, int n_scans) {
+  std::vector<int64_t> off((size_t)n_scans + 1);
+  const int64_t hw = (int64_t)s->kr.n_rows * s->kr.n_cols;
+  for (int i = 0; i <= n_scans; i++) off[i] = hw * i;
+  return off;
+}
+
+int cc_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *d_ranges, int n_scans, const float *h_knots, cc_scan_desc_t *d_out,
+                     const cc_ingest_debug_t *dbg, void *stream_) {
+  const char *who = "cc_ingest_ranges";
+  if (!c || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  const int rcr = ranges_check(c, sensor, d_ranges, h_knots, who);
+  if (rcr != CC_OK) return rcr;
+  const std::vector<int64_t> off = ranges_offsets(sensor, n_scans);
+  const rng_call rg = {sensor, h_knots};
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+  return ingest_on(c, c->main, d_ranges, CC_LAYOUT_KITTI, nullptr, off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who, nullptr, nullptr, &rg);
+}
+
+int cc_ingest_ranges_host(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, int n_scans, const float *h_knots, cc_scan_desc_t *h_out,
+                          float *h_bev) {
+  const char *who = "cc_ingest_ranges_host";
+  if (!c || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  const int rcr = ranges_check(c, sensor, h_ranges, h_knots, who);
+  if (rcr != CC_OK) return rcr;
+  HIPCHK(hipSetDevice(c->device));
+  const std::vector<int64_t> off = ranges_offsets(sensor, n_scans);
+  const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
+  const size_t img_bytes = (size_t)off[n_scans] * (size_t)sensor->word_bytes;
+  char *d_x = nullptr;
+  float *d_b = nullptr;
+  cc_scan_desc_t *d_o = nullptr;
+  HIPCHK(hipMalloc(&d_x, img_bytes));
+  hipError_t e = hipMalloc(&d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans);
+  if (e == hipSuccess && h_bev) e = hipMalloc(&d_b, bev_bytes);
+  if (e != hipSuccess) {
+    hipFree(d_x);
+    hipFree(d_o);
+    return set_err(CC_EHIP, CC_WHO(": hipMalloc"), e);
+  }
+  cc_ingest_debug_t dbg;
+  dbg.d_bev = d_b;
+  dbg.d_pix_rc = nullptr;
+  dbg.d_labels = nullptr;
+  int rc = CC_OK;
+  e = hipMemcpy(d_x, h_ranges, img_bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) rc = set_err(CC_EHIP, CC_WHO(": H2D"), e);
+  if (rc == CC_OK) {
+    const rng_call rg = {sensor, h_knots};
+    std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+    rc = ingest_on(c, c->main, d_x, CC_LAYOUT_KITTI, nullptr, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who, nullptr, nullptr, &rg);
+  }
+  if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
+  hipFree(d_x);
+  hipFree(d_o);
+  hipFree(d_b);
+  return rc;
 }
 
 // SO(3) in f64 for cc_motion_knots: R row-major 3 x 3.
@@ -1127,7 +1355,8 @@ int cc_stage_points_cancel(cc_ctx *c, const float *staged) {
 }
 
 static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who, const cc_point_segment_t *h_segs = nullptr, int n_segs = 0, const mot_call *mc = nullptr);
+                              const char *who, const cc_point_segment_t *h_segs = nullptr, int n_segs = 0, const mot_call *mc = nullptr,
+                              const rng_call *rg = nullptr);
 
 int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_bev, cc_scan **out) {
   return scan_ingest_points(c, h_xyzi, nullptr, n_points, nullptr, want_bev, out, "cc_scan_ingest");
@@ -1149,10 +1378,20 @@ int cc_scan_ingest_points_motion(cc_ctx *c, const void *h_points, const cc_point
   return scan_ingest_points(c, h_points, layout, n_points, nullptr, want_bev, out, "cc_scan_ingest_points_motion", nullptr, 0, &mc);
 }
 
+int cc_scan_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, const float *h_knots, int want_bev, cc_scan **out) {
+  const char *who = "cc_scan_ingest_ranges";
+  if (!c || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  const int rcr = ranges_check(c, sensor, h_ranges, h_knots, who);
+  if (rcr != CC_OK) return rcr;
+  const rng_call rg = {sensor, h_knots};
+  return scan_ingest_points(c, h_ranges, nullptr, (int64_t)sensor->kr.n_rows * sensor->kr.n_cols, nullptr, want_bev, out, who, nullptr, 0, nullptr, &rg);
+}
+
+// rg: nullptr, or the scan is a range image (cc_scan_ingest_ranges, checked): h_xyzi are its n_points words, layout and h_tf are not looked at.
 // h_segs: nullptr, or the scan's n_segs host segments (cc_scan_ingest_segments; h_xyzi, layout, n_points and h_tf are not looked at then):
 // their records go to the staging buffer one segment after the other, each at a 16-byte boundary.
 static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who, const cc_point_segment_t *h_segs, int n_segs, const mot_call *mc) {
+                              const char *who, const cc_point_segment_t *h_segs, int n_segs, const mot_call *mc, const rng_call *rg) {
   if (!c || (!h_xyzi && !h_segs) || !out || (!h_segs && n_points < 1)) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
   cc_point_layout_t lay = CC_LAYOUT_KITTI;
   std::vector<cc_k1_seg> seg_tab;
@@ -1172,7 +1411,7 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
       if (rcm != CC_OK) return rcm;
     }
   }
-  const size_t n_bytes = h_segs ? seg_bytes : (size_t)n_points * (size_t)lay.stride_bytes;   // the records travel as they are
+  const size_t n_bytes = h_segs ? seg_bytes : (size_t)n_points * (size_t)(rg ? rg->s->word_bytes : lay.stride_bytes);   // the records travel as they are
   const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);  // d_pts, the slots, the scratch behind cc_ingest_batch
   HIPCHK(hipSetDevice(c->device));
@@ -1260,7 +1499,7 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
   for (int k = 0; k < n_segs; k++) seg_tab[k].base = (const char *)ch.d_pts + seg_place[k] + (seg_tab[k].base - (const char *)h_segs[k].points);
   const seg_call sg = {seg_tab.data(), seg_scan};
   const int rc = h_segs ? ingest_on(c, ch.scr, nullptr, lay, nullptr, seg_qoff.data(), 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, &sg)
-                        : ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, nullptr, mc);
+                        : ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, nullptr, mc, rg);
   if (rc != CC_OK) {
     give_back();
     return rc;

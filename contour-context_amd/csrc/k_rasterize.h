@@ -1085,3 +1085,149 @@ cc_k_rasterize_merge_mot(cc_dev_cfg cfg, const char *__restrict__ pts, int strid
   __syncthreads();
   cc_k1_merge(cfg, cc_ld_rec_motion<STRIDE>(pts, stride, mot, (int)blockIdx.x, T), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
 }
+
+// ---- a sensor's RANGE IMAGE rasterised in place (cc_ingest_ranges): a scan is H x W range words (u16 / u32 / f32), one per
+// (beam, firing) = (row, col); the sensor model -- per-row (cos alt, sin alt, cos az_off, sin az_off), per-column (cos az, sin az,
+// knot) -- is a few KB shared by every scan of every call.  A pixel becomes a point by the header's formula (f32, every product and
+// sum rounded once: the library is built -ffp-contract=off), is moved by the knot of ITS COLUMN when the call brings knots, and a
+// pixel without a return gets x = NaN: cc_point_cell rejects it like any NaN point.  A point's index -- what the 21-bit fields hold
+// and the tie rule is about -- is its pixel's storage index j within the scan.
+//   load(j)  : the range word (2 or 4 bytes) and the pixel's column entry (ONE 16-byte load), both from the clamped index and
+//              neither under a branch; the row goes along in the record (xyz() sees only the record).
+//   j -> (row, col): q = j / D with D = n_cols (row-major) or n_rows (col-major), r = j - q * D.  D a power of two: a shift.
+//              Otherwise q = (j * M) >> 33 with M = ceil(2^33 / D), a 64-bit product.  Exact for every j < 2^21 and D <= 2^12:
+//              M = (2^33 + e) / D with 0 <= e < D, so j * M / 2^33 = j / D + j * e / (D * 2^33), and the second term is below
+//              1 / D because j * e < 2^21 * 2^12 = 2^33 -- it cannot carry j / D (whose fraction is at most (D - 1) / D) to the
+//              next integer.  M < 2^32 for D >= 3 (D = 1, 2 take the shift), and j * M < 2^53.
+// The row table (H x 16 B <= 2 048 B) and the scan's knots (<= 3 072 B) sit in LDS behind cc_k1_sweep's layout: 158 336 + 5 120 =
+// 163 456 of 163 840 B at 150 x 150, still one 1 024-thread workgroup per CU.  A wave's 64 pixels are neighbouring firings of one beam
+// (row-major) or neighbouring beams of one firing (col-major): row entry and knot are mostly one address -- a broadcast.
+#define CC_K1_RNG_ROWS_MAX 128   // = CC_RANGE_ROWS_MAX (include/cont2_amd.h; checked where both are seen)
+#define CC_K1_RNG_COLS_MAX 4096  // = CC_RANGE_COLS_MAX
+#define CC_K1_RNG_ROW_LDS_BYTES (CC_K1_RNG_ROWS_MAX * 16)
+#define CC_K1_RNG_LDS_BYTES (CC_K1_RNG_ROW_LDS_BYTES + CC_K1_MOT_LDS_BYTES)
+#define CC_K1_RNG_MAGIC_SHIFT 33
+static_assert(((CC_MAX_CELLS * 4 + 15) & ~15) + ((CC_MAX_CELLS + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15) + CC_K1_RNG_LDS_BYTES <= 160 * 1024,
+              "cc_k_rasterize_rng: grid, index fields, output tables, row table and knots fit a CU's 160 KB of LDS");
+enum { CC_K1_WORD_U16 = 0, CC_K1_WORD_U32 = 1, CC_K1_WORD_F32 = 2 };  // = CC_RANGE_U16 / _U32 / _F32
+struct cc_k1_range {
+  const void *words;    // the call's (chunk's) first range word
+  const float4 *row;    // [n_rows]: cos(alt), sin(alt), cos(az_off), sin(az_off)
+  const float4 *col;    // [n_cols]: cos(az), sin(az), the knot index's bits, 0
+  const float *knots;   // [n_scans][n_knots][12], nullptr when n_knots == 0
+  int n_rows, n_cols;
+  int col_major;        // j = col * n_rows + row (else row * n_cols + col)
+  int div_shift;        // >= 0: the divisor is 1 << div_shift; -1: div_magic
+  unsigned div_magic;   // ceil(2^33 / divisor)
+  int n_knots;
+  float range_scale, origin_n, origin_z;
+};
+
+// The row table and the scan's knots to LDS (a barrier has to follow before xyz() is called).  T: CC_K1_RNG_LDS_BYTES.
+__device__ __forceinline__ void cc_k1_range_tables(char *T, const cc_k1_range &R, int scan) {
+  float4 *rows = (float4 *)T;
+  for (int i = threadIdx.x; i < R.n_rows; i += blockDim.x) rows[i] = R.row[i];
+  float *kn = (float *)(T + CC_K1_RNG_ROW_LDS_BYTES);
+  const float *__restrict__ src = R.knots + (size_t)scan * (size_t)R.n_knots * 12;
+  for (int i = threadIdx.x; i < R.n_knots * 12; i += blockDim.x) kn[i] = src[i];
+}
+
+struct cc_rng_rec {
+  unsigned w;  // the range word as it lies in the image (u16: zero-extended)
+  int row;
+  float4 c;    // the pixel's column entry
+};
+template <int WORD>
+struct cc_ld_range {
+  typedef cc_rng_rec rec;
+  const char *__restrict__ B;       // the word of pixel j0 of the scan
+  const float4 *__restrict__ C;     // column entries (global: 64 KB at most, L2-resident)
+  const float4 *rows;               // LDS
+  const float4 *T;                  // LDS: [n_knots][3] rows of the scan's matrices
+  long long first;                  // index within the call of the scan's first pixel
+  int j0;                           // scan-relative index of the pixel B points at
+  int divisor, div_shift;           // workgroup-uniform: scalars
+  unsigned div_magic;
+  bool col_major, has_knots;
+  float range_scale, origin_n, origin_z;
+  __device__ __forceinline__ cc_ld_range(const cc_k1_range &R, int scan, const char *lds_tab)
+      : B((const char *)R.words), C(R.col), rows((const float4 *)lds_tab), T((const float4 *)(lds_tab + CC_K1_RNG_ROW_LDS_BYTES)),
+        first((long long)scan * ((long long)R.n_rows * R.n_cols)), j0(0), divisor(R.col_major ? R.n_rows : R.n_cols), div_shift(R.div_shift),
+        div_magic(R.div_magic), col_major(R.col_major != 0), has_knots(R.n_knots > 0), range_scale(R.range_scale), origin_n(R.origin_n),
+        origin_z(R.origin_z) {}
+  // n: index within the call of the first pixel this workgroup reads (the scan's first, or a part's, in the middle of a row)
+  __device__ __forceinline__ void advance(long long n) {
+    B += n * (long long)(WORD == CC_K1_WORD_U16 ? 2 : 4);
+    j0 = (int)(n - first);
+  }
+  __device__ __forceinline__ rec load(int j) const {
+    cc_rng_rec q;
+    if (WORD == CC_K1_WORD_U16) q.w = *(const unsigned short *)(B + (unsigned)j * 2u);
+    else q.w = *(const unsigned *)(B + (unsigned)j * 4u);
+    const unsigned p = (unsigned)(j0 + j);  // < 2^21
+    const unsigned d = div_shift >= 0 ? p >> div_shift : (unsigned)(((unsigned long long)p * (unsigned long long)div_magic) >> CC_K1_RNG_MAGIC_SHIFT);
+    const unsigned r = p - d * (unsigned)divisor;
+    q.row = (int)(col_major ? r : d);
+    q.c = C[col_major ? d : r];
+    return q;
+  }
+  __device__ __forceinline__ static rec zero() { return cc_rng_rec{0u, 0, make_float4(0.f, 0.f, 0.f, 0.f)}; }
+  __device__ __forceinline__ void xyz(const rec &q, float &x, float &y, float &z) const {
+    const float4 rt = rows[q.row];
+    const float ca = rt.x, sa = rt.y, co = rt.z, so = rt.w, ce = q.c.x, se = q.c.y;
+    float r;
+    bool none;
+    if (WORD == CC_K1_WORD_F32) {
+      const float f = __int_as_float((int)q.w);
+      none = !(f > 0.f);  // zero, negative or NaN: no return
+      r = f * range_scale;
+    } else {
+      none = q.w == 0u;
+      r = (float)q.w * range_scale;
+    }
+    const float d = r - origin_n;
+    const float h = d * ca;
+    const float dx = (ce * co) - (se * so), dy = (se * co) + (ce * so);
+    float px = (h * dx) + (origin_n * ce), py = (h * dy) + (origin_n * se), pz = (d * sa) + origin_z;
+    if (has_knots) {  // workgroup-uniform
+      const int b = __float_as_int(q.c.z);
+      const float4 r0 = T[b * 3], r1 = T[b * 3 + 1], r2 = T[b * 3 + 2];
+      const float tx = ((r0.x * px + r0.y * py) + r0.z * pz) + r0.w;
+      const float ty = ((r1.x * px + r1.y * py) + r1.z * pz) + r1.w;
+      const float tz = ((r2.x * px + r2.y * py) + r2.z * pz) + r2.w;
+      px = tx;
+      py = ty;
+      pz = tz;
+    }
+    x = none ? __int_as_float(0x7FC00000) : px;  // cc_point_cell rejects a NaN x: the pixel owns nothing and counts nowhere
+    y = py;
+    z = pz;
+  }
+  __device__ __forceinline__ float2 owner_xy(int j) const {
+    float x, y, z;
+    xyz(load(j), x, y, z);
+    return make_float2(x, y);
+  }
+};
+
+// grid, block as cc_k_rasterize; dynamic LDS: tab_off (cc_k_rasterize's bytes, 16-byte aligned) + CC_K1_RNG_LDS_BYTES.  offsets: scan i's first
+// pixel = i * n_rows * n_cols.
+template <int CC_K1_U, bool CC_K1_POW2, bool PART, int WORD>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_rng(cc_dev_cfg cfg, cc_k1_range rng, int tab_off, const long long *__restrict__ offsets, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
+                   cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out, int want_dense) {
+  HIP_DYNAMIC_SHARED(char, smem)
+  const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;
+  char *T = smem + tab_off;
+  cc_k1_range_tables(T, rng, scan);  // (read after cc_k1_sweep's first barrier)
+  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_range<WORD>(rng, scan, T), offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+}
+template <int WORD>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_merge_rng(cc_dev_cfg cfg, cc_k1_range rng, const long long *__restrict__ offsets, cc_k1_part part, float *__restrict__ bev_out,
+                         float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
+  __shared__ __attribute__((aligned(16))) char T[CC_K1_RNG_LDS_BYTES];  // the owners' re-reads need the row table and the scan's knots too
+  cc_k1_range_tables(T, rng, (int)blockIdx.x);
+  __syncthreads();
+  cc_k1_merge(cfg, cc_ld_range<WORD>(rng, (int)blockIdx.x, T), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
+}

@@ -414,6 +414,61 @@ class ContourManager {
     str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
   }
 
+  // Mirror-only: makeBEV for a scan that is still the sensor's RANGE IMAGE -- H x W range words (u16 / u32 / f32) as the driver has them,
+  // no x, y, z.  The sensor's model (beam altitudes and azimuth offsets, the firings' encoder azimuths, the knot of every firing) is
+  // made once with rangeSensor() and shared by every scan; the points are computed while the rasteriser loads the words, and with
+  // knots.size() = K >= 1 row-major 3 x 4 matrices (K as the sensor was made with; e.g. from cc_motion_knots) every pixel is moved by
+  // the knot of ITS COLUMN: the sweep is de-skewed without a time word (cc_scan_ingest_ranges, include/cont2_amd.h, has the
+  // arithmetic).  A word of 0 (f32: a word that is not > 0) is a pixel without a return.
+  struct RangeImage {
+    const cc_range_sensor *sensor = nullptr;
+    const void *words = nullptr;  // n_rows * n_cols words of the sensor's type, in its storage order, aligned to their size
+    std::vector<std::array<float, 12>> knots;  // empty for a sensor without knots
+  };
+  // the sensor for scans of this configuration (cc_range_sensor_create on its context); given back with releaseRangeSensor().  The
+  // mirror remembers the K a sensor was made with: the C call sees only whether knots are there, not how many.
+  static cc_range_sensor *rangeSensor(const ContourManagerConfig &config, const cc_range_model_t &model) {
+    cc_range_sensor *s = nullptr;
+    if (cc_range_sensor_create(contextOf(config), &model, &s) != CC_OK) die();
+    std::lock_guard<std::mutex> lk(rangeSensorMutex());
+    rangeSensorKnots()[s] = (int)model.n_knots;
+    return s;
+  }
+  static void releaseRangeSensor(cc_range_sensor *sensor) {
+    {
+      std::lock_guard<std::mutex> lk(rangeSensorMutex());
+      rangeSensorKnots().erase(sensor);
+    }
+    cc_range_sensor_destroy(sensor);
+  }
+  void makeBEV(const RangeImage &image, std::string str_id = "") {
+    CC_CHECK(image.sensor && image.words);
+    CC_CHECK(!scan_);
+    {
+      std::lock_guard<std::mutex> lk(rangeSensorMutex());
+      const auto it = rangeSensorKnots().find(image.sensor);
+      CC_CHECK(it != rangeSensorKnots().end());               // a sensor made by rangeSensor()
+      CC_CHECK(image.knots.size() == (size_t)it->second);     // exactly the K matrices it was made with
+    }
+    static_assert(sizeof(std::array<float, 12>) == 12 * sizeof(float), "makeBEV: the knots are passed as [K][12] floats");
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_ranges(ctx, image.sensor, image.words, image.knots.empty() ? nullptr : image.knots[0].data(), want_images_ ? 1 : 0, &scan_) != CC_OK)
+      die();
+    str_id_ = std::move(str_id);
+  }
+
+ private:
+  static std::mutex &rangeSensorMutex() {
+    static std::mutex mu;
+    return mu;
+  }
+  static std::map<const cc_range_sensor *, int> &rangeSensorKnots() {
+    static std::map<const cc_range_sensor *, int> m;
+    return m;
+  }
+
+ public:
   // Mirror-only: the evaluator's .bin reader (tools/pointcloud_util.h:9-47: at most 1 000 000 floats, x y z i records,
   // intensity dropped) without the intermediate cloud.  A KITTI record IS a staging record (the kernels never read the
   // fourth float), so the file is read straight into the context's pinned buffer.  Returns the number of points.

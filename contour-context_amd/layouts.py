@@ -158,6 +158,32 @@ class PointMotion(C.Structure):
 assert C.sizeof(PointMotion) == 16
 
 
+RANGE_ROWS_MAX, RANGE_COLS_MAX = 128, 4096              # CC_RANGE_ROWS_MAX / CC_RANGE_COLS_MAX
+RANGE_U16, RANGE_U32, RANGE_F32 = 0, 1, 2               # CC_RANGE_U16 / _U32 / _F32
+RANGE_ROW_MAJOR, RANGE_COL_MAJOR = 0, 1                 # CC_RANGE_ROW_MAJOR / _COL_MAJOR
+
+
+class RangeModel(C.Structure):
+    """cc_range_model_t: a range sensor -- image shape, word type and storage order, the beam origin, the number of knots per scan
+    and the host tables (row_tab [H][4]: cos(alt), sin(alt), cos(az_off), sin(az_off); col_cos_sin [W][2]; col_knot [W] or NULL)."""
+    _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("word_type", C.c_int32), ("order", C.c_int32), ("range_scale", C.c_float),
+                ("origin_n", C.c_float), ("origin_z", C.c_float), ("n_knots", C.c_int32), ("row_tab", C.c_void_p), ("col_cos_sin", C.c_void_p),
+                ("col_knot", C.c_void_p)]
+
+
+assert C.sizeof(RangeModel) == 56 and RangeModel.range_scale.offset == 16 and RangeModel.n_knots.offset == 28 and RangeModel.row_tab.offset == 32 \
+    and RangeModel.col_knot.offset == 48
+
+
+def range_tables(beam_alt, beam_az_off, col_az):
+    """The sensor's angles (radians) -> (row_tab [H, 4], col_cos_sin [W, 2]) f32: computed in f64 and rounded to f32."""
+    alt, off, az = (np.asarray(a, np.float64).reshape(-1) for a in (beam_alt, beam_az_off, col_az))
+    if alt.shape != off.shape:
+        raise ValueError("beam_alt and beam_az_off hold one angle per row")
+    return (np.ascontiguousarray(np.stack([np.cos(alt), np.sin(alt), np.cos(off), np.sin(off)], 1).astype(np.float32)),
+            np.ascontiguousarray(np.stack([np.cos(az), np.sin(az)], 1).astype(np.float32)))
+
+
 class SimCfg(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ta_cell_cnt", "tp_cell_cnt", "tp_eigval", "ta_h_bar", "ta_rcom", "tp_rcom")]
 

@@ -411,6 +411,74 @@ int cc_ingest_points_motion_host(cc_ctx *ctx, const void *h_points, const cc_poi
  * multiplication. */
 void cc_motion_knots(const double pose_begin[12], const double pose_end[12], double ref, int K, float *knots /*[K][12]*/);
 
+/* ---- a sensor's RANGE IMAGE rasterised in place, de-skewed per column ----
+ * A spinning LiDAR does not measure x, y, z: it measures one range word per (beam, firing) -- 2 or 4 bytes per pixel of an H x W
+ * image -- and its calibration is a few hundred angles.  These calls take the range words as the driver has them and make the
+ * points while the rasteriser loads them: no pass that expands the image into a 16-byte-per-point cloud, and none that de-skews
+ * it -- in a range image a pixel's time is its column, so the knot of a pixel is a per-column table entry.  No reference counterpart.
+ * A pixel is (row, col) = (beam, firing); pixel j of a scan is (j / W, j % W) in CC_RANGE_ROW_MAJOR order (Ouster LidarScan fields)
+ * and (j % H, j / H) in CC_RANGE_COL_MAJOR order (firing after firing: Velodyne / Hesai packets).  The model is fixed per sensor:
+ *   row_tab[row]     = cos(alt), sin(alt), cos(az_off), sin(az_off) of the beam        (ca, sa, co, so)
+ *   col_cos_sin[col] = cos, sin of the encoder azimuth of the firing                   (ce, se)
+ *   col_knot[col]    = the knot that moves the firing's points, in [0, K - 1]
+ * THE ARITHMETIC, all f32, every product and every sum rounded once, in exactly this association (w: the pixel's word):
+ *   r  = (float)w * range_scale      u16 / u32: the conversion is exact or rounds to nearest even; f32: the word itself * range_scale
+ *   d  = r - origin_n
+ *   h  = d * ca
+ *   dx = (ce * co) - (se * so)       dy = (se * co) + (ce * so)
+ *   x  = (h * dx) + (origin_n * ce)  y  = (h * dy) + (origin_n * se)      z = (d * sa) + origin_z
+ * With K >= 1 knots per scan (x, y, z) is then moved by knot col_knot[col] of ITS scan: the operation cc_ingest_points documents
+ * for h_tf, in its order.  K = 1 is a per-scan extrinsic or pose, K = 32 de-skews a sweep (cc_motion_knots makes the matrices);
+ * K = 0: the points stay in the sensor frame.  A pixel with NO RETURN -- an integer word of 0; an f32 word that is not > 0: zero,
+ * negative or NaN -- is rejected as a NaN point is: it owns nothing and counts nowhere.
+ * The scan's result -- descriptor, bev, pix_rc, labels, every byte -- is what cc_ingest_batch gives for these points in pixel
+ * storage order j: among equal heights in one cell the pixel with the smaller j wins; the blind zone, the border, max / min
+ * height and the continuous position see the final point only.
+ * Checked before anything is queued or read (CC_EINVAL, the context stays as it was): 1 <= n_rows <= CC_RANGE_ROWS_MAX, 1 <= n_cols
+ * <= CC_RANGE_COLS_MAX, 10 < n_rows * n_cols < 2^21; a known word_type and order; finite range_scale, origin_n, origin_z; 0 <=
+ * n_knots <= CC_MOTION_KNOTS_MAX; every col_knot in [0, K - 1] (K = 0: all 0); non-NULL row_tab and col_cos_sin (col_knot may be
+ * NULL: all 0); h_knots NULL exactly when K = 0; the base pointer of the range words aligned to the word size; the sensor used
+ * with the context it was created on.
+ * Out of scope: dual returns; a time word per pixel; destaggered images (the staggered image with az_off per beam is what the model
+ * describes); interpolation between knots; range images as segments; intensity channels.  What the kernels cost: DESIGN.md 3.0. */
+#define CC_RANGE_ROWS_MAX 128
+#define CC_RANGE_COLS_MAX 4096
+enum { CC_RANGE_U16 = 0, CC_RANGE_U32 = 1, CC_RANGE_F32 = 2 };
+enum { CC_RANGE_ROW_MAJOR = 0 /* j = row * W + col: Ouster LidarScan fields, the synth's order */,
+       CC_RANGE_COL_MAJOR = 1 /* j = col * H + row: firing after firing, Velodyne / Hesai packets */ };
+typedef struct {
+  int32_t n_rows, n_cols, word_type, order;
+  float   range_scale;        /* metres per unit of the word (0.001 for Ouster mm, 0.002 Velodyne, 0.004 Hesai, 1 for f32 metres) */
+  float   origin_n, origin_z; /* beam origin: distance from the rotation axis, height above the sensor frame's origin (0, 0: Velodyne) */
+  int32_t n_knots;            /* K, 0 .. CC_MOTION_KNOTS_MAX; 0: points stay in the sensor frame */
+  const float   *row_tab;     /* host [H][4]: cos(alt), sin(alt), cos(az_off), sin(az_off) of the beam */
+  const float   *col_cos_sin; /* host [W][2]: cos, sin of the encoder azimuth of the firing */
+  const int32_t *col_knot;    /* host [W]: knot index of the firing, each in [0, K-1]; NULL: all 0 */
+} cc_range_model_t;           /* 56 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cc_range_model_t) == 56 && offsetof(cc_range_model_t, range_scale) == 16 && offsetof(cc_range_model_t, n_knots) == 28 &&
+                  offsetof(cc_range_model_t, row_tab) == 32 && offsetof(cc_range_model_t, col_knot) == 48,
+              "cc_range_model_t: 56 bytes, range_scale at 16, n_knots at 28, row_tab at 32, col_knot at 48");
+#else
+_Static_assert(sizeof(cc_range_model_t) == 56 && offsetof(cc_range_model_t, range_scale) == 16 && offsetof(cc_range_model_t, n_knots) == 28 &&
+                   offsetof(cc_range_model_t, row_tab) == 32 && offsetof(cc_range_model_t, col_knot) == 48,
+               "cc_range_model_t: 56 bytes, range_scale at 16, n_knots at 28, row_tab at 32, col_knot at 48");
+#endif
+typedef struct cc_range_sensor cc_range_sensor;
+/* Checks the model and copies its tables to the device once (the device layout is the library's own; the host tables may go when
+ * the call returns).  A sensor belongs to the context it was created on and must be destroyed before it. */
+int cc_range_sensor_create(cc_ctx *ctx, const cc_range_model_t *model, cc_range_sensor **out);
+int cc_range_sensor_destroy(cc_range_sensor *sensor);
+/*   d_ranges : scan i is the H * W words at d_ranges + i * H * W * wordsize, device memory, read in place
+ *   h_knots  : [n_scans][K][12] f32 host memory (copied before the call returns); NULL iff K == 0
+ * Everything else as cc_ingest_points (work queued on `stream`, chunks of max_batch_scans, cc_profile_enable brackets the kernels). */
+int cc_ingest_ranges(cc_ctx *ctx, const cc_range_sensor *sensor, const void *d_ranges, int n_scans, const float *h_knots, cc_scan_desc_t *d_out,
+                     const cc_ingest_debug_t *dbg, void *stream);
+/* The same from host range words (cc_ingest_host_bev's shape: one H2D copy, results copied back; h_bev may be NULL; the host
+ * pointer is held to the same alignment). */
+int cc_ingest_ranges_host(cc_ctx *ctx, const cc_range_sensor *sensor, const void *h_ranges, int n_scans, const float *h_knots, cc_scan_desc_t *h_out,
+                          float *h_bev);
+
 /* ---- the per-scan loop (test/batch_bin_test.cpp:131-237 at sensor rate) ----
  * A cc_scan is ONE scan's descriptor kept on the device between ContourManager::makeContoursRecurs (contour_mng.h:588),
  * ContourDB::queryRangedKNN (contour_db.h:698) and ContourDB::addScan (:814): the class mirror's ContourManager holds one.
@@ -470,6 +538,9 @@ int cc_scan_ingest_segments(cc_ctx *ctx, const cc_point_segment_t *h_segs, int n
  * [K][12]): an ordinary scan handle comes out. */
 int cc_scan_ingest_points_motion(cc_ctx *ctx, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion,
                                  int64_t n_points, const float *h_time, const float *h_knots, int want_bev, cc_scan **out);
+/* cc_scan_ingest for ONE scan given as a range image (cc_ingest_ranges above; h_ranges: H * W host words, through the context's own
+ * staging buffer; h_knots: [K][12] or NULL iff K == 0): an ordinary scan handle comes out. */
+int cc_scan_ingest_ranges(cc_ctx *ctx, const cc_range_sensor *sensor, const void *h_ranges, const float *h_knots, int want_bev, cc_scan **out);
 int cc_scan_ready(const cc_scan *scan);
 int cc_scan_desc(cc_scan *scan, const cc_scan_desc_t **h_desc);
 int cc_scan_bev(cc_scan *scan, const float **h_bev);
