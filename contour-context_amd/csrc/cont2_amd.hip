@@ -17,6 +17,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cont2_amd.h"
@@ -209,6 +210,73 @@ static void scratch_free(cc_ctx::Scratch &S) {
   S = cc_ctx::Scratch();
 }
 
+// ---- K1's launches.  The sources (k_rasterize.h) the library instantiates the kernels for, ONE list: cc_create sets every instance's
+// dynamic-LDS limit from it, and k1_launch refuses (at compile time) a source that is not on it.
+template <typename... SRC>
+struct k1_list {};
+typedef k1_list<cc_src_kitti, cc_src_rec<12>, cc_src_rec<16>, cc_src_rec<0>, cc_src_mot<16>, cc_src_mot<32>, cc_src_mot<0>, cc_src_seg, cc_src_rng<CC_K1_WORD_U16>,
+                cc_src_rng<CC_K1_WORD_U32>, cc_src_rng<CC_K1_WORD_F32>>
+    k1_sources;
+template <typename S, typename... SRC>
+static constexpr bool k1_listed(k1_list<SRC...>) {
+  return (std::is_same<S, SRC>::value || ...);
+}
+// Where SRC's table goes in the sweep's dynamic LDS (behind the layout of the instances without one), and the bytes of the whole.
+template <typename SRC>
+static size_t k1_tab_off(const cc_ctx *c) {
+  return (c->lds1 + (size_t)(SRC::TAB_ALIGN - 1)) & ~(size_t)(SRC::TAB_ALIGN - 1);
+}
+template <typename SRC>
+static size_t k1_lds(const cc_ctx *c) {
+  return k1_tab_off<SRC>(c) + (size_t)SRC::TAB_BYTES;
+}
+template <typename SRC>
+static int k1_attr(cc_ctx *c) {
+  const int lds = (int)k1_lds<SRC>(c);
+  HIPCHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, false, false, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  HIPCHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true, false, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  HIPCHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, false, true, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  HIPCHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true, true, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  return CC_OK;
+}
+template <typename... SRC>
+static int k1_attr_all(cc_ctx *c, k1_list<SRC...>) {
+  int rc = CC_OK;
+  ((rc = rc == CC_OK ? k1_attr<SRC>(c) : rc), ...);
+  return rc;
+}
+// K1 for the nb scans whose offsets are in S.d_offsets.  A handful of scans (the per-scan loop brings one): CC_K1_SPLIT workgroups per
+// scan sweep a range of its points each, a second small kernel combines the ranges (first range wins ties: file order).  Otherwise
+// one workgroup per scan.
+template <typename SRC>
+static int k1_launch(cc_ctx *c, cc_ctx::Scratch &S, const SRC &src, int nb, int want_dense, hipStream_t stream) {
+  static_assert(k1_listed<SRC>(k1_sources()), "k1_launch: a source cc_create does not prepare (k1_sources)");
+  const size_t lds = k1_lds<SRC>(c);
+  const int tab_off = (int)k1_tab_off<SRC>(c);
+  const long long *off = (const long long *)S.d_offsets;
+  if (nb <= CC_K1_SPLIT_MAX_SCANS) {
+    if (!S.k1_part.key) {
+      const size_t np = (size_t)CC_K1_SPLIT_MAX_SCANS * CC_K1_SPLIT, nc = (size_t)c->dcfg.n_cell;
+      HIPCHK(hipMalloc(&S.k1_part.key, sizeof(unsigned) * np * nc));
+      HIPCHK(hipMalloc(&S.k1_part.idx, sizeof(int) * np * nc));
+      HIPCHK(hipMalloc(&S.k1_part.red, sizeof(unsigned) * np * 2));
+    }
+    if (c->dcfg.reso_pow2)
+      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, true, SRC>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), lds, stream, c->dcfg, src, tab_off, off,
+                         S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
+    else
+      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false, true, SRC>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), lds, stream, c->dcfg, src, tab_off, off,
+                         S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
+    hipLaunchKernelGGL((cc_k_rasterize_merge<SRC>), dim3(nb), dim3(1024), 0, stream, c->dcfg, src, off, S.k1_part, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);
+  } else if (c->dcfg.reso_pow2)
+    hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, false, SRC>), dim3(nb), dim3(CC_INGEST_BLOCK), lds, stream, c->dcfg, src, tab_off, off, S.d_bev,
+                       S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
+  else
+    hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false, false, SRC>), dim3(nb), dim3(CC_INGEST_BLOCK), lds, stream, c->dcfg, src, tab_off, off, S.d_bev,
+                       S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
+  return CC_OK;
+}
+
 extern "C" {
 
 const char *cc_last_error(void) { return g_err.c_str(); }
@@ -342,49 +410,15 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
   }
   c->lds1 = ((nc * 4 + 15) & ~(size_t)15) + ((nc + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15);
   c->lds2 = CC_K2_LDS_BYTES(nc);
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize<CC_K1_U_DEFAULT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
-#define CC_K1_REC_ATTR(STRIDE)                                                                                                                                    \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1)); \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds1));
-  CC_K1_REC_ATTR(12)
-  CC_K1_REC_ATTR(16)
-  CC_K1_REC_ATTR(0)
-#undef CC_K1_REC_ATTR
-  const int lds1_seg = (int)(c->lds1 + CC_K1_SEG_LDS_BYTES);  // (the segment table sits behind the layout of the other instances)
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_seg));
-  const int lds1_mot = (int)(((c->lds1 + 15) & ~(size_t)15) + CC_K1_MOT_LDS_BYTES);  // (the knot table sits behind the layout too)
-#define CC_K1_MOT_ATTR(STRIDE)                                                                                                                                  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot)); \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, false, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot));  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot));  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, true, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_mot));
-  CC_K1_MOT_ATTR(16)
-  CC_K1_MOT_ATTR(32)
-  CC_K1_MOT_ATTR(0)
-#undef CC_K1_MOT_ATTR
-  const int lds1_rng = (int)(((c->lds1 + 15) & ~(size_t)15) + CC_K1_RNG_LDS_BYTES);  // (the row table and the knots sit behind the layout)
-#define CC_K1_RNG_ATTR(WORD)                                                                                                                                  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, false, false, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng)); \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, true, false, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng));  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, false, true, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng));  \
-  CREATE_CHK(hipFuncSetAttribute((const void *)cc_k_rasterize_rng<CC_K1_U_DEFAULT, true, true, WORD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1_rng));
-  CC_K1_RNG_ATTR(CC_K1_WORD_U16)
-  CC_K1_RNG_ATTR(CC_K1_WORD_U32)
-  CC_K1_RNG_ATTR(CC_K1_WORD_F32)
-#undef CC_K1_RNG_ATTR
+  if (k1_attr_all(c, k1_sources()) != CC_OK) {  // every K1 instance may have its dynamic LDS
+    cc_destroy(c);
+    return CC_EHIP;  // (the message is set)
+  }
   if (nc > (size_t)CC_MAX_CELLS) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: grid larger than 150 x 150 cells");
   }
-  if (lds1_rng > 160 * 1024) {
+  if (k1_lds<cc_src_rng<CC_K1_WORD_U16>>(c) > 160 * 1024) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: the range-image kernels' tables do not fit the LDS behind this grid");
   }
@@ -473,18 +507,38 @@ static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
 // an error text that names the entry point the caller called (the old entry points are thin calls of the new ones' bodies)
 #define CC_WHO(text) (std::string(who) + text).c_str()
 
-// A checked cc_*_segments call (segs_check below) as ingest_on takes it: one entry per segment with the DEVICE address of its first
-// x; the scans' point totals are the call's h_offsets.
-struct seg_call {
-  const cc_k1_seg *segs;
-  const int32_t *scan_segs;  // [n_scans + 1]
+// What a call's scans are made of, as ingest_on and scan_ingest_points take it: the checked arguments of one of the four kinds of entry
+// points.  ingest_on reads DEVICE addresses; scan_ingest_points and the *_host calls are handed the caller's host addresses and put the
+// device ones in before they pass it on.
+struct k1_source {
+  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS } kind;
+  const void *points = nullptr;              // POINTS, MOTION: the records; RANGES: the range words (a "point" is a pixel)
+  cc_point_layout_t lay = {16, 0};           // POINTS, MOTION (has passed point_layout)
+  const float *h_tf = nullptr;               // POINTS: [n_scans][12] or nullptr
+  cc_point_motion_t mot = {};                // MOTION (has passed motion_check), with
+  const float *h_time = nullptr;             //   [n_scans][2]
+  const float *h_knots = nullptr;            // MOTION, RANGES: [n_scans][K][12] (RANGES: nullptr iff K == 0)
+  const struct cc_range_sensor *sensor = nullptr;  // RANGES (has passed ranges_check); the scans' offsets are the pixels' (i * H * W)
+  cc_k1_seg *segs = nullptr;                 // SEGMENTS (segs_check's table): one entry per segment, `base` the address of its first x;
+  const int32_t *scan_segs = nullptr;        //   [n_scans + 1], relative to segs[0]; the scans' point totals are the call's offsets
+  const cc_point_segment_t *h_segs = nullptr;  //   the caller's entries of the same segments (what the host calls copy from)
 };
-// A checked cc_*_motion call (motion_check below) as ingest_on takes it.
-struct mot_call {
-  cc_point_motion_t m;
-  const float *h_time;   // [n_scans][2]
-  const float *h_knots;  // [n_scans][K][12]
-};
+static k1_source k1_points(const void *points, const cc_point_layout_t &lay, const float *h_tf) {
+  k1_source s = {k1_source::POINTS, points, lay, h_tf};
+  return s;
+}
+static k1_source k1_motion(const void *points, const cc_point_layout_t &lay, const cc_point_motion_t &mot, const float *h_time, const float *h_knots) {
+  k1_source s = {k1_source::MOTION, points, lay, nullptr, mot, h_time, h_knots};
+  return s;
+}
+static k1_source k1_ranges(const struct cc_range_sensor *sensor, const void *words, const float *h_knots) {
+  k1_source s = {k1_source::RANGES, words, {16, 0}, nullptr, {}, nullptr, h_knots, sensor};
+  return s;
+}
+static k1_source k1_segments(cc_k1_seg *segs, const int32_t *scan_segs, const cc_point_segment_t *h_segs) {
+  k1_source s = {k1_source::SEGMENTS, nullptr, {16, 0}, nullptr, {}, nullptr, nullptr, nullptr, segs, scan_segs, h_segs};
+  return s;
+}
 static_assert(CC_K1_MOT_KNOTS_MAX == CC_MOTION_KNOTS_MAX, "k_rasterize.h's knot table holds CC_MOTION_KNOTS_MAX matrices");
 // A range sensor: the checked model with its tables on the device (cc_range_sensor_create).
 struct cc_range_sensor {
@@ -497,11 +551,6 @@ struct cc_range_sensor {
 static_assert(CC_K1_RNG_ROWS_MAX == CC_RANGE_ROWS_MAX && CC_K1_RNG_COLS_MAX == CC_RANGE_COLS_MAX && (int)CC_K1_WORD_U16 == (int)CC_RANGE_U16 &&
                   (int)CC_K1_WORD_U32 == (int)CC_RANGE_U32 && (int)CC_K1_WORD_F32 == (int)CC_RANGE_F32,
               "k_rasterize.h's range-image limits and word types are the header's");
-// A checked cc_*_ranges call (ranges_check below) as ingest_on takes it: d_points are the range words, h_offsets the pixels' (i * H * W).
-struct rng_call {
-  const cc_range_sensor *s;
-  const float *h_knots;  // [n_scans][K][12], nullptr iff K == 0
-};
 // Everything the header promises to check about a cc_*_ranges call that the sensor's creation has not, before anything is queued or read.
 // base: the pointer whose alignment counts (device or host words).
 static int ranges_check(cc_ctx *c, const cc_range_sensor *s, const void *base, const float *h_knots, const char *who) {
@@ -544,17 +593,108 @@ static char *slot_stage(cc_ctx *c, int slot, size_t bytes) {
   }
   return c->h_seg[slot];
 }
-// cc_ingest_points on the scratch set S (c->ing_mu held by the caller; `lay` has passed point_layout).  h_tf: [n_scans][12] or nullptr.
-// sg: nullptr, or the call's segments -- d_points, lay and h_tf are not looked at then (cc_ingest_segments).
-// mc: nullptr, or the call's per-point time and knots (cc_ingest_points_motion; without h_tf and sg).
-// rg: nullptr, or the call's range sensor and knots (cc_ingest_ranges; without h_tf, sg and mc): d_points are the range words, a "point" is a pixel.
-static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_point_layout_t lay, const float *h_tf, const int64_t *h_offsets, int n_scans,
-                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, hipStream_t stream, const char *who, const seg_call *sg = nullptr,
-                     const mot_call *mc = nullptr, const rng_call *rg = nullptr) {
+// What a chunk's K1 reads on the device besides the points and the offsets: set by the staging functions, read by k1_dispatch.
+struct k1_staged {
+  const float *d_tf = nullptr;  // POINTS
+  cc_k1_motion mot = {};        // MOTION
+  cc_k1_range rng = {};         // RANGES
+  cc_k1_segs segs = {};         // SEGMENTS
+};
+// A chunk's knots (behind its [nb][2] times when h_time is given) to S.d_mot.  They ride in slot `slot` of the staging ring, in the
+// segment tables' buffer: a call has one or the other.
+static int stage_knots(cc_ctx *c, cc_ctx::Scratch &S, int slot, const float *h_time, const float *h_knots, int n_knots, int b0, int nb, hipStream_t stream,
+                       const float *&d_time, const float *&d_knots) {
+  const size_t kf = (size_t)n_knots * 12, nt = h_time ? 2 * (size_t)nb : 0, bytes = sizeof(float) * (nt + kf * (size_t)nb);
+  if (!S.d_mot) HIPCHK(hipMalloc(&S.d_mot, sizeof(float) * (2 + (size_t)CC_MOTION_KNOTS_MAX * 12) * (size_t)S.cap));
+  if (!slot_stage(c, slot, bytes)) return CC_EHIP;
+  float *hm = (float *)c->h_seg[slot];
+  if (h_time) memcpy(hm, h_time + (size_t)b0 * 2, sizeof(float) * nt);
+  memcpy(hm + nt, h_knots + (size_t)b0 * kf, sizeof(float) * kf * (size_t)nb);
+  HIPCHK(hipMemcpyAsync(S.d_mot, hm, bytes, hipMemcpyHostToDevice, stream));
+  d_time = S.d_mot;
+  d_knots = S.d_mot + nt;
+  return CC_OK;
+}
+// A chunk's segment table to S.d_seg, in the same slot of the ring: scan_seg[nb + 1] relative to the chunk's first segment, then the entries.
+static int stage_segments(cc_ctx *c, cc_ctx::Scratch &S, int slot, const k1_source &src, int b0, int nb, hipStream_t stream, cc_k1_segs &d_segs) {
+  const int s0 = src.scan_segs[b0], ns = src.scan_segs[b0 + nb] - s0;
+  const size_t ent_off = (sizeof(int) * (size_t)(nb + 1) + 7) & ~(size_t)7, bytes = ent_off + sizeof(cc_k1_seg) * (size_t)ns;
+  if (!S.d_seg) HIPCHK(hipMalloc(&S.d_seg, ((sizeof(int) * (size_t)(S.cap + 1) + 7) & ~(size_t)7) + sizeof(cc_k1_seg) * CC_SEG_MAX * (size_t)S.cap));
+  if (!slot_stage(c, slot, bytes)) return CC_EHIP;
+  int *ss = (int *)c->h_seg[slot];
+  for (int i = 0; i <= nb; i++) ss[i] = src.scan_segs[b0 + i] - s0;
+  memcpy(c->h_seg[slot] + ent_off, src.segs + s0, sizeof(cc_k1_seg) * (size_t)ns);
+  HIPCHK(hipMemcpyAsync(S.d_seg, c->h_seg[slot], bytes, hipMemcpyHostToDevice, stream));
+  d_segs.scan_seg = (const int *)S.d_seg;
+  d_segs.seg = (const cc_k1_seg *)(S.d_seg + ent_off);
+  return CC_OK;
+}
+// The copies of a chunk's tables (scans b0 .. b0 + nb - 1), queued behind its offsets; off: the ring slot's pinned offsets.
+static int k1_stage(cc_ctx *c, cc_ctx::Scratch &S, int slot, long long *off, const k1_source &src, const int64_t *h_offsets, int b0, int nb, hipStream_t stream,
+                    k1_staged &st) {
+  switch (src.kind) {
+    case k1_source::POINTS:
+      if (src.h_tf) {  // the chunk's transforms ride in the same slot, behind the offsets
+        float *tfs = (float *)(off + c->off_cap + 1);
+        memcpy(tfs, src.h_tf + (size_t)b0 * 12, sizeof(float) * 12 * (size_t)nb);
+        HIPCHK(hipMemcpyAsync(S.d_tf, tfs, sizeof(float) * 12 * (size_t)nb, hipMemcpyHostToDevice, stream));
+        st.d_tf = S.d_tf;
+      }
+      return CC_OK;
+    case k1_source::SEGMENTS:
+      return stage_segments(c, S, slot, src, b0, nb, stream, st.segs);
+    case k1_source::MOTION:
+      st.mot.t_off = src.mot.time_offset - src.lay.xyz_offset;
+      st.mot.time_u32 = src.mot.time_type == CC_TIME_U32 ? 1 : 0;
+      st.mot.n_knots = src.mot.n_knots;
+      return stage_knots(c, S, slot, src.h_time, src.h_knots, src.mot.n_knots, b0, nb, stream, st.mot.time, st.mot.knots);
+    case k1_source::RANGES: {
+      st.rng = src.sensor->kr;
+      st.rng.words = (const char *)src.points + (long long)h_offsets[b0] * src.sensor->word_bytes;
+      st.rng.knots = nullptr;
+      const float *none = nullptr;
+      return st.rng.n_knots > 0 ? stage_knots(c, S, slot, nullptr, src.h_knots, st.rng.n_knots, b0, nb, stream, none, st.rng.knots) : CC_OK;
+    }
+  }
+  return CC_OK;
+}
+// The chunk's K1: the instance its source asks for.  KITTI records without a transform take the float4 loader (16-byte loads: the base
+// must be aligned for them); everything else one of the record loaders' instances.
+static int k1_dispatch(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, const k1_staged &st, int64_t first, int nb, int want_dense, hipStream_t stream) {
+  const int stride = src.lay.stride_bytes;
+  const char *rpts = nullptr;  // POINTS, MOTION: x of the chunk's first point
+  if (src.kind == k1_source::POINTS || src.kind == k1_source::MOTION) rpts = (const char *)src.points + (long long)first * stride + src.lay.xyz_offset;
+  switch (src.kind) {
+    case k1_source::POINTS:
+      if (stride == 16 && src.lay.xyz_offset == 0 && !src.h_tf && ((uintptr_t)src.points & 15u) == 0)
+        return k1_launch(c, S, cc_src_kitti{(const float4 *)src.points + first}, nb, want_dense, stream);
+      switch (stride) {
+        case 12: return k1_launch(c, S, cc_src_rec<12>{rpts, stride, st.d_tf}, nb, want_dense, stream);
+        case 16: return k1_launch(c, S, cc_src_rec<16>{rpts, stride, st.d_tf}, nb, want_dense, stream);
+        default: return k1_launch(c, S, cc_src_rec<0>{rpts, stride, st.d_tf}, nb, want_dense, stream);
+      }
+    case k1_source::MOTION:
+      switch (stride) {
+        case 16: return k1_launch(c, S, cc_src_mot<16>{rpts, stride, st.mot}, nb, want_dense, stream);
+        case 32: return k1_launch(c, S, cc_src_mot<32>{rpts, stride, st.mot}, nb, want_dense, stream);
+        default: return k1_launch(c, S, cc_src_mot<0>{rpts, stride, st.mot}, nb, want_dense, stream);
+      }
+    case k1_source::RANGES:
+      switch (src.sensor->word_type) {
+        case CC_RANGE_U16: return k1_launch(c, S, cc_src_rng<CC_K1_WORD_U16>{st.rng}, nb, want_dense, stream);
+        case CC_RANGE_U32: return k1_launch(c, S, cc_src_rng<CC_K1_WORD_U32>{st.rng}, nb, want_dense, stream);
+        default: return k1_launch(c, S, cc_src_rng<CC_K1_WORD_F32>{st.rng}, nb, want_dense, stream);
+      }
+    case k1_source::SEGMENTS:
+      return k1_launch(c, S, cc_src_seg{st.segs}, nb, want_dense, stream);
+  }
+  return CC_OK;
+}
+
+// An ingest call on the scratch set S (c->ing_mu held by the caller; src holds device addresses).
+static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg,
+                     hipStream_t stream, const char *who) {
   HIPCHK(hipSetDevice(c->device));
-  // KITTI records without a transform take the float4 kernels (16-byte loads: the base must be aligned for them); everything
-  // else one of the record loaders' instances
-  const bool kitti = lay.stride_bytes == 16 && lay.xyz_offset == 0 && !h_tf && !mc && !rg && ((uintptr_t)d_points & 15u) == 0;
   for (int i = 0; i < n_scans; i++) {
     const int64_t n = h_offsets[i + 1] - h_offsets[i];
     if (!(n > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
@@ -571,60 +711,11 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
     long long *off = c->h_off[slot];
     for (int i = 0; i <= nb; i++) off[i] = (long long)(h_offsets[b0 + i] - h_offsets[b0]);
     HIPCHK(hipMemcpyAsync(S.d_offsets, off, sizeof(long long) * (nb + 1), hipMemcpyHostToDevice, stream));
-    if (h_tf) {  // the chunk's transforms ride in the same slot, behind the offsets
-      float *tfs = (float *)(off + c->off_cap + 1);
-      memcpy(tfs, h_tf + (size_t)b0 * 12, sizeof(float) * 12 * (size_t)nb);
-      HIPCHK(hipMemcpyAsync(S.d_tf, tfs, sizeof(float) * 12 * (size_t)nb, hipMemcpyHostToDevice, stream));
-    }
-    cc_k1_segs d_segs = {nullptr, nullptr};
-    if (sg) {  // the chunk's segment table rides in the same slot of the ring: scan_seg[nb + 1] relative to the chunk's first segment, then the entries
-      const int s0 = sg->scan_segs[b0], ns = sg->scan_segs[b0 + nb] - s0;
-      const size_t ent_off = (sizeof(int) * (size_t)(nb + 1) + 7) & ~(size_t)7, bytes = ent_off + sizeof(cc_k1_seg) * (size_t)ns;
-      if (!S.d_seg) HIPCHK(hipMalloc(&S.d_seg, ((sizeof(int) * (size_t)(S.cap + 1) + 7) & ~(size_t)7) + sizeof(cc_k1_seg) * CC_SEG_MAX * (size_t)S.cap));
-      if (!slot_stage(c, slot, bytes)) return CC_EHIP;
-      int *ss = (int *)c->h_seg[slot];
-      for (int i = 0; i <= nb; i++) ss[i] = sg->scan_segs[b0 + i] - s0;
-      memcpy(c->h_seg[slot] + ent_off, sg->segs + s0, sizeof(cc_k1_seg) * (size_t)ns);
-      HIPCHK(hipMemcpyAsync(S.d_seg, c->h_seg[slot], bytes, hipMemcpyHostToDevice, stream));
-      d_segs.scan_seg = (const int *)S.d_seg;
-      d_segs.seg = (const cc_k1_seg *)(S.d_seg + ent_off);
-    }
-    cc_k1_motion d_mot = {nullptr, nullptr, 0, 0, 0};
-    if (mc) {  // the chunk's times and knots ride in the same slot of the ring (the segment tables' buffer: a call has one or the other)
-      const size_t kf = (size_t)mc->m.n_knots * 12, bytes = sizeof(float) * (2 + kf) * (size_t)nb;
-      if (!S.d_mot) HIPCHK(hipMalloc(&S.d_mot, sizeof(float) * (2 + (size_t)CC_MOTION_KNOTS_MAX * 12) * (size_t)S.cap));
-      if (!slot_stage(c, slot, bytes)) return CC_EHIP;
-      float *hm = (float *)c->h_seg[slot];
-      memcpy(hm, mc->h_time + (size_t)b0 * 2, sizeof(float) * 2 * (size_t)nb);
-      memcpy(hm + 2 * (size_t)nb, mc->h_knots + (size_t)b0 * kf, sizeof(float) * kf * (size_t)nb);
-      HIPCHK(hipMemcpyAsync(S.d_mot, hm, bytes, hipMemcpyHostToDevice, stream));
-      d_mot.time = S.d_mot;
-      d_mot.knots = S.d_mot + 2 * (size_t)nb;
-      d_mot.t_off = mc->m.time_offset - lay.xyz_offset;
-      d_mot.time_u32 = mc->m.time_type == CC_TIME_U32 ? 1 : 0;
-      d_mot.n_knots = mc->m.n_knots;
-    }
-    cc_k1_range d_rng = {};
-    if (rg) {  // the chunk's knots ride in the same slot of the ring, as the motion call's do
-      d_rng = rg->s->kr;
-      d_rng.words = (const char *)d_points + (long long)h_offsets[b0] * rg->s->word_bytes;
-      d_rng.knots = nullptr;
-      if (d_rng.n_knots > 0) {
-        const size_t kf = (size_t)d_rng.n_knots * 12, bytes = sizeof(float) * kf * (size_t)nb;
-        if (!S.d_mot) HIPCHK(hipMalloc(&S.d_mot, sizeof(float) * (2 + (size_t)CC_MOTION_KNOTS_MAX * 12) * (size_t)S.cap));
-        if (!slot_stage(c, slot, bytes)) return CC_EHIP;
-        memcpy(c->h_seg[slot], rg->h_knots + (size_t)b0 * kf, bytes);
-        HIPCHK(hipMemcpyAsync(S.d_mot, c->h_seg[slot], bytes, hipMemcpyHostToDevice, stream));
-        d_rng.knots = S.d_mot;
-      }
-    }
-    const int mot_tab = (int)((c->lds1 + 15) & ~(size_t)15);  // where the knot table (the range kernels': row table and knots) goes in LDS
+    k1_staged st;
+    const int rcs = k1_stage(c, S, slot, off, src, h_offsets, b0, nb, stream, st);
+    if (rcs != CC_OK) return rcs;
     HIPCHK(hipEventRecord(c->off_ev[slot], stream));
     c->off_busy[slot] = true;
-    const float4 *pts = sg ? nullptr : (const float4 *)d_points + h_offsets[b0];  // (the float4 kernels')
-    const char *rpts = sg ? nullptr : (const char *)d_points + (long long)h_offsets[b0] * lay.stride_bytes + lay.xyz_offset;
-    const float *d_tf = h_tf ? S.d_tf : nullptr;
-    const int rstride = lay.stride_bytes;
     // K1's dense image / positions: for the debug outputs, for a configuration K2's list kernel hands on as a whole
     // (min_cont_cell_cnt_ > 3); otherwise only for scans whose active cells overflow the list
     const int want_dense = ((dbg && (dbg->d_bev || dbg->d_pix_rc)) || c->dcfg.min_cont_cell_cnt > 3) ? 1 : 0;
@@ -637,134 +728,8 @@ static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const void *d_points, cc_poi
       c->ev_used += 3;
       HIPCHK(hipEventRecord(pe[0], stream));
     }
-    if (rg) {  // a range image: the split path for a handful of scans, one workgroup per scan otherwise, like the branches below
-      const bool split = nb <= CC_K1_SPLIT_MAX_SCANS;
-      if (split && !S.k1_part.key) {
-        const size_t np = (size_t)CC_K1_SPLIT_MAX_SCANS * CC_K1_SPLIT;
-        HIPCHK(hipMalloc(&S.k1_part.key, sizeof(unsigned) * np * nc));
-        HIPCHK(hipMalloc(&S.k1_part.idx, sizeof(int) * np * nc));
-        HIPCHK(hipMalloc(&S.k1_part.red, sizeof(unsigned) * np * 2));
-      }
-      const size_t lds_rng = (size_t)mot_tab + CC_K1_RNG_LDS_BYTES;
-#define CC_K1_RNG_ONE(POW2, PART, WORD)                                                                                                                   \
-  hipLaunchKernelGGL((cc_k_rasterize_rng<CC_K1_U_DEFAULT, POW2, PART, WORD>), dim3(PART ? nb * CC_K1_SPLIT : nb), dim3(CC_INGEST_BLOCK), lds_rng, stream, \
-                     c->dcfg, d_rng, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, PART ? S.k1_part : cc_k1_part(), S.list, want_dense)
-#define CC_K1_RNG_LAUNCH(WORD)                                                                                                                   \
-  {                                                                                                                                              \
-    if (split) {                                                                                                                                 \
-      if (c->dcfg.reso_pow2) CC_K1_RNG_ONE(true, true, WORD);                                                                                    \
-      else CC_K1_RNG_ONE(false, true, WORD);                                                                                                     \
-      hipLaunchKernelGGL((cc_k_rasterize_merge_rng<WORD>), dim3(nb), dim3(1024), 0, stream, c->dcfg, d_rng, (const long long *)S.d_offsets,      \
-                         S.k1_part, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);                                                               \
-    } else if (c->dcfg.reso_pow2) CC_K1_RNG_ONE(true, false, WORD);                                                                              \
-    else CC_K1_RNG_ONE(false, false, WORD);                                                                                                      \
-  }
-      if (rg->s->word_type == CC_RANGE_U16) CC_K1_RNG_LAUNCH(CC_K1_WORD_U16)
-      else if (rg->s->word_type == CC_RANGE_U32) CC_K1_RNG_LAUNCH(CC_K1_WORD_U32)
-      else CC_K1_RNG_LAUNCH(CC_K1_WORD_F32)
-#undef CC_K1_RNG_LAUNCH
-#undef CC_K1_RNG_ONE
-    } else if (nb <= CC_K1_SPLIT_MAX_SCANS) {
-      // a handful of scans (the per-scan loop brings one): CC_K1_SPLIT workgroups per scan sweep a range of its points each,
-      // a second small kernel combines the ranges (first range wins ties: file order)
-      if (!S.k1_part.key) {
-        const size_t np = (size_t)CC_K1_SPLIT_MAX_SCANS * CC_K1_SPLIT;
-        HIPCHK(hipMalloc(&S.k1_part.key, sizeof(unsigned) * np * nc));
-        HIPCHK(hipMalloc(&S.k1_part.idx, sizeof(int) * np * nc));
-        HIPCHK(hipMalloc(&S.k1_part.red, sizeof(unsigned) * np * 2));
-      }
-      if (sg) {
-        if (c->dcfg.reso_pow2)
-          hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream,
-                             c->dcfg, d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
-        else
-          hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream,
-                             c->dcfg, d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
-        hipLaunchKernelGGL(cc_k_rasterize_merge_seg, dim3(nb), dim3(1024), 0, stream, c->dcfg, d_segs, (const long long *)S.d_offsets, S.k1_part, S.d_bev,
-                           S.d_pix, S.d_k1, S.list, want_dense);
-      } else if (mc) {
-#define CC_K1_MOT_SPLIT(STRIDE)                                                                                                                                  \
-  {                                                                                                                                                              \
-    if (c->dcfg.reso_pow2)                                                                                                                                       \
-      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, \
-                         stream, c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense); \
-    else                                                                                                                                                         \
-      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, \
-                         stream, c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense); \
-    hipLaunchKernelGGL((cc_k_rasterize_merge_mot<STRIDE>), dim3(nb), dim3(1024), 0, stream, c->dcfg, rpts, rstride, d_mot, (const long long *)S.d_offsets,       \
-                       S.k1_part, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);                                                                                 \
-  }
-        if (rstride == 16) CC_K1_MOT_SPLIT(16)
-        else if (rstride == 32) CC_K1_MOT_SPLIT(32)
-        else CC_K1_MOT_SPLIT(0)
-#undef CC_K1_MOT_SPLIT
-      } else if (kitti) {
-        if (c->dcfg.reso_pow2)
-          hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
-                             (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
-        else
-          hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false, true>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts,
-                             (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);
-        hipLaunchKernelGGL(cc_k_rasterize_merge, dim3(nb), dim3(1024), 0, stream, c->dcfg, pts, (const long long *)S.d_offsets, S.k1_part, S.d_bev,
-                           S.d_pix, S.d_k1, S.list, want_dense);
-      } else {
-#define CC_K1_REC_SPLIT(STRIDE)                                                                                                                              \
-  {                                                                                                                                                          \
-    if (c->dcfg.reso_pow2)                                                                                                                                   \
-      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
-                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);                      \
-    else                                                                                                                                                     \
-      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, true, STRIDE>), dim3(nb * CC_K1_SPLIT), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
-                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, S.k1_part, S.list, want_dense);                      \
-    hipLaunchKernelGGL((cc_k_rasterize_merge_rec<STRIDE>), dim3(nb), dim3(1024), 0, stream, c->dcfg, rpts, rstride, d_tf, (const long long *)S.d_offsets,    \
-                       S.k1_part, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);                                                                             \
-  }
-        if (rstride == 12) CC_K1_REC_SPLIT(12)
-        else if (rstride == 16) CC_K1_REC_SPLIT(16)
-        else CC_K1_REC_SPLIT(0)
-#undef CC_K1_REC_SPLIT
-      }
-    } else if (sg) {
-      if (c->dcfg.reso_pow2)
-        hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, true, false>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream, c->dcfg,
-                           d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
-      else
-        hipLaunchKernelGGL((cc_k_rasterize_seg<CC_K1_U_DEFAULT, false, false>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1 + CC_K1_SEG_LDS_BYTES, stream, c->dcfg,
-                           d_segs, (int)c->lds1, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
-    } else if (mc) {
-#define CC_K1_MOT_WHOLE(STRIDE)                                                                                                                              \
-  {                                                                                                                                                          \
-    if (c->dcfg.reso_pow2)                                                                                                                                   \
-      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, true, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, stream,  \
-                         c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense); \
-    else                                                                                                                                                     \
-      hipLaunchKernelGGL((cc_k_rasterize_mot<CC_K1_U_DEFAULT, false, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), mot_tab + CC_K1_MOT_LDS_BYTES, stream, \
-                         c->dcfg, rpts, rstride, d_mot, mot_tab, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense); \
-  }
-      if (rstride == 16) CC_K1_MOT_WHOLE(16)
-      else if (rstride == 32) CC_K1_MOT_WHOLE(32)
-      else CC_K1_MOT_WHOLE(0)
-#undef CC_K1_MOT_WHOLE
-    } else if (!kitti) {
-#define CC_K1_REC_WHOLE(STRIDE)                                                                                                                \
-  {                                                                                                                                            \
-    if (c->dcfg.reso_pow2)                                                                                                                     \
-      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, true, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
-                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);     \
-    else                                                                                                                                       \
-      hipLaunchKernelGGL((cc_k_rasterize_rec<CC_K1_U_DEFAULT, false, false, STRIDE>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, \
-                         rpts, rstride, d_tf, (const long long *)S.d_offsets, S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);     \
-  }
-      if (rstride == 12) CC_K1_REC_WHOLE(12)
-      else if (rstride == 16) CC_K1_REC_WHOLE(16)
-      else CC_K1_REC_WHOLE(0)
-#undef CC_K1_REC_WHOLE
-    } else if (c->dcfg.reso_pow2)
-      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, true>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts, (const long long *)S.d_offsets,
-                         S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
-    else
-      hipLaunchKernelGGL((cc_k_rasterize<CC_K1_U_DEFAULT, false>), dim3(nb), dim3(CC_INGEST_BLOCK), c->lds1, stream, c->dcfg, pts, (const long long *)S.d_offsets,
-                         S.d_bev, S.d_pix, S.d_k1, cc_k1_part(), S.list, want_dense);
+    const int rck = k1_dispatch(c, S, src, st, h_offsets[b0], nb, want_dense, stream);
+    if (rck != CC_OK) return rck;
     if (pe) HIPCHK(hipEventRecord(pe[1], stream));
     int16_t *lab = (dbg && dbg->d_labels) ? dbg->d_labels + (size_t)b0 * CC_NLEV * nc : nullptr;
     hipLaunchKernelGGL(cc_k_contours, dim3(nb), dim3(CC_K2_BLOCK), (size_t)CC_K2L_LDS_BYTES, stream, c->dcfg, (const float *)S.d_bev,
@@ -801,11 +766,12 @@ int cc_ingest_batch(cc_ctx *c, const float *d_xyzi, const int64_t *h_offsets, in
                     const cc_ingest_debug_t *dbg, void *stream_) {
   if (!c || !d_xyzi || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, "cc_ingest_batch: bad argument");
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);  // offsets ring, K1/K2 scratch, ev_last: one call at a time
-  return ingest_on(c, c->main, d_xyzi, CC_LAYOUT_KITTI, nullptr, h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_batch");
+  return ingest_on(c, c->main, k1_points(d_xyzi, CC_LAYOUT_KITTI, nullptr), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_batch");
 }
 
 static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const mot_call *mc = nullptr);
+                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const cc_point_motion_t *motion = nullptr, const float *h_time = nullptr,
+                              const float *h_knots = nullptr);
 
 int cc_ingest_host(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out) {
   return cc_ingest_host_bev(c, h_xyzi, h_offsets, n_scans, h_out, nullptr);
@@ -818,7 +784,7 @@ int cc_ingest_points(cc_ctx *c, const void *d_points, const cc_point_layout_t *l
   const int rcl = point_layout(layout, d_points, "cc_ingest_points", &lay);
   if (rcl != CC_OK) return rcl;
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, d_points, lay, h_tf, h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_points");
+  return ingest_on(c, c->main, k1_points(d_points, lay, h_tf), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_points");
 }
 
 int cc_ingest_host_bev(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out, float *h_bev) {
@@ -842,20 +808,11 @@ static int host_results(const cc_scan_desc_t *d_o, const float *d_b, size_t bev_
   return CC_OK;
 }
 
-static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const mot_call *mc) {
-  if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  cc_point_layout_t lay;
-  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records are copied to aligned device memory)
-  if (rcl != CC_OK) return rcl;
-  if (mc) {
-    const int rcm = motion_check(lay, &mc->m, mc->h_time, mc->h_knots, n_scans, who);
-    if (rcm != CC_OK) return rcm;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t base = h_offsets[0], total = h_offsets[n_scans] - base;
+// The body of the *_host calls, behind their checks: device memory for the call's pts_bytes of records, its descriptors and (h_bev) its
+// images; copy_in(d_x, d_o) brings the records over; then the call itself (src reads its records at d_x), and the results back.
+static int ingest_host(cc_ctx *c, k1_source src, size_t pts_bytes, const int64_t *offsets, int n_scans, cc_scan_desc_t *h_out, float *h_bev, const char *who,
+                       const std::function<hipError_t(char *, cc_scan_desc_t *)> &copy_in) {
   const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
-  const size_t pts_bytes = (size_t)lay.stride_bytes * (size_t)total;
   char *d_x = nullptr;
   float *d_b = nullptr;
   cc_scan_desc_t *d_o = nullptr;
@@ -871,20 +828,38 @@ static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_la
   dbg.d_bev = d_b;
   dbg.d_pix_rc = nullptr;
   dbg.d_labels = nullptr;
-  int rc = CC_OK;
-  std::vector<int64_t> off(n_scans + 1);
-  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
-  e = hipMemcpy(d_x, (const char *)h_points + (size_t)lay.stride_bytes * (size_t)base, pts_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) rc = set_err(CC_EHIP, CC_WHO(": H2D"), e);
+  e = copy_in(d_x, d_o);
+  int rc = e == hipSuccess ? CC_OK : set_err(CC_EHIP, CC_WHO(": H2D"), e);
   if (rc == CC_OK) {
+    src.points = d_x;
     std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-    rc = ingest_on(c, c->main, d_x, lay, h_tf, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who, nullptr, mc);
+    rc = ingest_on(c, c->main, src, offsets, n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
   }
   if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
   hipFree(d_x);
   hipFree(d_o);
   hipFree(d_b);
   return rc;
+}
+
+static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
+                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const cc_point_motion_t *motion, const float *h_time, const float *h_knots) {
+  if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records are copied to aligned device memory)
+  if (rcl != CC_OK) return rcl;
+  if (motion) {
+    const int rcm = motion_check(lay, motion, h_time, h_knots, n_scans, who);
+    if (rcm != CC_OK) return rcm;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t base = h_offsets[0];
+  const size_t pts_bytes = (size_t)lay.stride_bytes * (size_t)(h_offsets[n_scans] - base);
+  std::vector<int64_t> off(n_scans + 1);
+  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
+  const char *h_first = (const char *)h_points + (size_t)lay.stride_bytes * (size_t)base;
+  return ingest_host(c, motion ? k1_motion(nullptr, lay, *motion, h_time, h_knots) : k1_points(nullptr, lay, h_tf), pts_bytes, off.data(), n_scans, h_out, h_bev,
+                     who, [&](char *d_x, cc_scan_desc_t *) { return hipMemcpy(d_x, h_first, pts_bytes, hipMemcpyHostToDevice); });
 }
 
 // ---- a sweep de-skewed by per-point time (cc_ingest_points_motion and its siblings) ----
@@ -897,17 +872,15 @@ int cc_ingest_points_motion(cc_ctx *c, const void *d_points, const cc_point_layo
   if (rcl != CC_OK) return rcl;
   const int rcm = motion_check(lay, motion, h_time, h_knots, n_scans, who);
   if (rcm != CC_OK) return rcm;
-  const mot_call mc = {*motion, h_time, h_knots};
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, d_points, lay, nullptr, h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who, nullptr, &mc);
+  return ingest_on(c, c->main, k1_motion(d_points, lay, *motion, h_time, h_knots), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who);
 }
 
 int cc_ingest_points_motion_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, const int64_t *h_offsets,
                                  int n_scans, const float *h_time, const float *h_knots, cc_scan_desc_t *h_out, float *h_bev) {
   const char *who = "cc_ingest_points_motion_host";
   if (!motion) return set_err(CC_EINVAL, CC_WHO(": motion, h_time and h_knots must not be NULL"));
-  const mot_call mc = {*motion, h_time, h_knots};
-  return ingest_points_host(c, h_points, layout, h_offsets, n_scans, nullptr, h_out, h_bev, who, &mc);
+  return ingest_points_host(c, h_points, layout, h_offsets, n_scans, nullptr, h_out, h_bev, who, motion, h_time, h_knots);
 }
 
 // ---- a sensor's range image rasterised in place (cc_ingest_ranges and its siblings) ----
@@ -1005,9 +978,8 @@ int cc_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *d_ran
   const int rcr = ranges_check(c, sensor, d_ranges, h_knots, who);
   if (rcr != CC_OK) return rcr;
   const std::vector<int64_t> off = ranges_offsets(sensor, n_scans);
-  const rng_call rg = {sensor, h_knots};
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, d_ranges, CC_LAYOUT_KITTI, nullptr, off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who, nullptr, nullptr, &rg);
+  return ingest_on(c, c->main, k1_ranges(sensor, d_ranges, h_knots), off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who);
 }
 
 int cc_ingest_ranges_host(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, int n_scans, const float *h_knots, cc_scan_desc_t *h_out,
@@ -1018,36 +990,9 @@ int cc_ingest_ranges_host(cc_ctx *c, const cc_range_sensor *sensor, const void *
   if (rcr != CC_OK) return rcr;
   HIPCHK(hipSetDevice(c->device));
   const std::vector<int64_t> off = ranges_offsets(sensor, n_scans);
-  const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
   const size_t img_bytes = (size_t)off[n_scans] * (size_t)sensor->word_bytes;
-  char *d_x = nullptr;
-  float *d_b = nullptr;
-  cc_scan_desc_t *d_o = nullptr;
-  HIPCHK(hipMalloc(&d_x, img_bytes));
-  hipError_t e = hipMalloc(&d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans);
-  if (e == hipSuccess && h_bev) e = hipMalloc(&d_b, bev_bytes);
-  if (e != hipSuccess) {
-    hipFree(d_x);
-    hipFree(d_o);
-    return set_err(CC_EHIP, CC_WHO(": hipMalloc"), e);
-  }
-  cc_ingest_debug_t dbg;
-  dbg.d_bev = d_b;
-  dbg.d_pix_rc = nullptr;
-  dbg.d_labels = nullptr;
-  int rc = CC_OK;
-  e = hipMemcpy(d_x, h_ranges, img_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) rc = set_err(CC_EHIP, CC_WHO(": H2D"), e);
-  if (rc == CC_OK) {
-    const rng_call rg = {sensor, h_knots};
-    std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-    rc = ingest_on(c, c->main, d_x, CC_LAYOUT_KITTI, nullptr, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who, nullptr, nullptr, &rg);
-  }
-  if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
-  hipFree(d_x);
-  hipFree(d_o);
-  hipFree(d_b);
-  return rc;
+  return ingest_host(c, k1_ranges(sensor, nullptr, h_knots), img_bytes, off.data(), n_scans, h_out, h_bev, who,
+                     [&](char *d_x, cc_scan_desc_t *) { return hipMemcpy(d_x, h_ranges, img_bytes, hipMemcpyHostToDevice); });
 }
 
 // SO(3) in f64 for cc_motion_knots: R row-major 3 x 3.
@@ -1166,9 +1111,8 @@ int cc_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, const int32_
   if (rcs != CC_OK) return rcs;
   std::vector<int32_t> ss(n_scans + 1);
   for (int i = 0; i <= n_scans; i++) ss[i] = h_scan_segs[i] - h_scan_segs[0];  // (tab begins with the call's first segment)
-  const seg_call sg = {tab.data(), ss.data()};
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, nullptr, CC_LAYOUT_KITTI, nullptr, q_off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who, &sg);
+  return ingest_on(c, c->main, k1_segments(tab.data(), ss.data(), h_segs + h_scan_segs[0]), q_off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who);
 }
 
 // Where the records of the checked segments `tab` (host pointers) go in ONE buffer: every segment at a 16-byte boundary, whole records.
@@ -1193,42 +1137,19 @@ int cc_ingest_segments_host(cc_ctx *c, const cc_point_segment_t *h_segs, const i
   HIPCHK(hipSetDevice(c->device));
   std::vector<size_t> off;
   const size_t pts_bytes = segs_place(h_segs, tab, off);
-  const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
-  char *d_x = nullptr;
-  float *d_b = nullptr;
-  cc_scan_desc_t *d_o = nullptr;
-  HIPCHK(hipMalloc(&d_x, pts_bytes));
-  hipError_t e = hipMalloc(&d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans);
-  if (e == hipSuccess && h_bev) e = hipMalloc(&d_b, bev_bytes);
-  if (e != hipSuccess) {
-    hipFree(d_x);
-    hipFree(d_o);
-    return set_err(CC_EHIP, CC_WHO(": hipMalloc"), e);
-  }
-  for (size_t k = 0; k < tab.size() && e == hipSuccess; k++) {
-    if (tab[k].n > 0) e = hipMemcpy(d_x + off[k], h_segs[k].points, (size_t)tab[k].n * tab[k].stride, hipMemcpyHostToDevice);
-    tab[k].base = d_x + off[k] + (tab[k].base - (const char *)h_segs[k].points);
-  }
-  // (the rows of a descriptor that its counts do not cover are not written by the kernels: zero here, so that the call's bytes are
-  // those of cc_ingest_segments into zeroed memory)
-  if (e == hipSuccess) e = hipMemset(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans);
-  int rc = e == hipSuccess ? CC_OK : set_err(CC_EHIP, CC_WHO(": H2D"), e);
-  cc_ingest_debug_t dbg;
-  dbg.d_bev = d_b;
-  dbg.d_pix_rc = nullptr;
-  dbg.d_labels = nullptr;
-  if (rc == CC_OK) {
-    std::vector<int32_t> ss(n_scans + 1);
-    for (int i = 0; i <= n_scans; i++) ss[i] = h_scan_segs[i] - h_scan_segs[0];
-    const seg_call sg = {tab.data(), ss.data()};
-    std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-    rc = ingest_on(c, c->main, nullptr, CC_LAYOUT_KITTI, nullptr, q_off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who, &sg);
-  }
-  if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
-  hipFree(d_x);
-  hipFree(d_o);
-  hipFree(d_b);
-  return rc;
+  std::vector<int32_t> ss(n_scans + 1);
+  for (int i = 0; i <= n_scans; i++) ss[i] = h_scan_segs[i] - h_scan_segs[0];
+  return ingest_host(c, k1_segments(tab.data(), ss.data(), h_segs), pts_bytes, q_off.data(), n_scans, h_out, h_bev, who, [&](char *d_x, cc_scan_desc_t *d_o) {
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < tab.size() && e == hipSuccess; k++) {
+      if (tab[k].n > 0) e = hipMemcpy(d_x + off[k], h_segs[k].points, (size_t)tab[k].n * tab[k].stride, hipMemcpyHostToDevice);
+      tab[k].base = d_x + off[k] + (tab[k].base - (const char *)h_segs[k].points);
+    }
+    // (the rows of a descriptor that its counts do not cover are not written by the kernels: zero here, so that the call's bytes are
+    // those of cc_ingest_segments into zeroed memory)
+    if (e == hipSuccess) e = hipMemset(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans);
+    return e;
+  });
 }
 
 void cc_est_sens_tf(const double tf_bev[3], int n_row, int n_col, double tf_sens[3]) {
@@ -1265,6 +1186,32 @@ struct cc_scan {
   float *h_bev = nullptr;            // host copy of the max-height image, if it was asked for
   bool bev_pending = false;
 };
+
+// n descriptor slots of the pool to out[]; all or none: when the pool cannot grow, the slots taken so far go back.
+// The pool grows geometrically (64, 64, 128, 256, ... up to 1 024 slots = 169 MB per block): a hipMalloc synchronises the
+// device, and a driver that keeps thousands of scans resident should not pay that every 64 scans of its loop.
+static hipError_t slot_take(cc_ctx *c, int n, cc_scan_desc_t **out) {
+  std::lock_guard<std::mutex> lk(c->slot_mu);
+  for (int i = 0; i < n; i++) {
+    if (c->slot_free.empty()) {
+      size_t have = 0;
+      for (size_t b = 0; b < c->slot_blocks.size(); b++) have += c->slot_block_n[b];
+      const int nblk = (int)(have < 64 ? 64 : (have > 1024 ? 1024 : have));
+      cc_scan_desc_t *blk = nullptr;
+      const hipError_t e_ = hipMalloc(&blk, sizeof(cc_scan_desc_t) * nblk);
+      if (e_ != hipSuccess) {
+        for (int k = 0; k < i; k++) c->slot_free.push_back(out[k]);
+        return e_;
+      }
+      c->slot_blocks.push_back(blk);
+      c->slot_block_n.push_back(nblk);
+      for (int k = nblk - 1; k >= 0; k--) c->slot_free.push_back(blk + k);
+    }
+    out[i] = c->slot_free.back();
+    c->slot_free.pop_back();
+  }
+  return hipSuccess;
+}
 
 static int loop_reserve_points(cc_ctx *c, int64_t n_points) {  // ing_mu held
   if (!c->s_loop) HIPCHK(stream_take(c->device, &c->s_loop));
@@ -1354,28 +1301,25 @@ int cc_stage_points_cancel(cc_ctx *c, const float *staged) {
   return set_err(CC_EINVAL, "cc_stage_points_cancel: not a staging buffer of this context");
 }
 
-static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who, const cc_point_segment_t *h_segs = nullptr, int n_segs = 0, const mot_call *mc = nullptr,
-                              const rng_call *rg = nullptr);
+static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t *layout, int64_t n_points, int n_segs, int want_bev, cc_scan **out, const char *who);
 
 int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_bev, cc_scan **out) {
-  return scan_ingest_points(c, h_xyzi, nullptr, n_points, nullptr, want_bev, out, "cc_scan_ingest");
+  return scan_ingest_points(c, k1_points(h_xyzi, CC_LAYOUT_KITTI, nullptr), nullptr, n_points, 0, want_bev, out, "cc_scan_ingest");
 }
 
 int cc_scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out) {
-  return scan_ingest_points(c, h_xyzi, layout, n_points, h_tf, want_bev, out, "cc_scan_ingest_points");
+  return scan_ingest_points(c, k1_points(h_xyzi, CC_LAYOUT_KITTI, h_tf), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points");
 }
 
 int cc_scan_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, int n_segs, int want_bev, cc_scan **out) {
   if (!h_segs) return set_err(CC_EINVAL, "cc_scan_ingest_segments: bad argument");
-  return scan_ingest_points(c, nullptr, nullptr, 0, nullptr, want_bev, out, "cc_scan_ingest_segments", h_segs, n_segs);
+  return scan_ingest_points(c, k1_segments(nullptr, nullptr, h_segs), nullptr, 0, n_segs, want_bev, out, "cc_scan_ingest_segments");
 }
 
 int cc_scan_ingest_points_motion(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, int64_t n_points,
                                  const float *h_time, const float *h_knots, int want_bev, cc_scan **out) {
   if (!motion) return set_err(CC_EINVAL, "cc_scan_ingest_points_motion: motion, h_time and h_knots must not be NULL");
-  const mot_call mc = {*motion, h_time, h_knots};
-  return scan_ingest_points(c, h_points, layout, n_points, nullptr, want_bev, out, "cc_scan_ingest_points_motion", nullptr, 0, &mc);
+  return scan_ingest_points(c, k1_motion(h_points, CC_LAYOUT_KITTI, *motion, h_time, h_knots), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points_motion");
 }
 
 int cc_scan_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, const float *h_knots, int want_bev, cc_scan **out) {
@@ -1383,17 +1327,16 @@ int cc_scan_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *
   if (!c || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
   const int rcr = ranges_check(c, sensor, h_ranges, h_knots, who);
   if (rcr != CC_OK) return rcr;
-  const rng_call rg = {sensor, h_knots};
-  return scan_ingest_points(c, h_ranges, nullptr, (int64_t)sensor->kr.n_rows * sensor->kr.n_cols, nullptr, want_bev, out, who, nullptr, 0, nullptr, &rg);
+  return scan_ingest_points(c, k1_ranges(sensor, h_ranges, h_knots), nullptr, (int64_t)sensor->kr.n_rows * sensor->kr.n_cols, 0, want_bev, out, who);
 }
 
-// rg: nullptr, or the scan is a range image (cc_scan_ingest_ranges, checked): h_xyzi are its n_points words, layout and h_tf are not looked at.
-// h_segs: nullptr, or the scan's n_segs host segments (cc_scan_ingest_segments; h_xyzi, layout, n_points and h_tf are not looked at then):
-// their records go to the staging buffer one segment after the other, each at a 16-byte boundary.
-static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out,
-                              const char *who, const cc_point_segment_t *h_segs, int n_segs, const mot_call *mc, const rng_call *rg) {
+// One scan of the per-scan loop.  src: the caller's arguments with HOST addresses, checked here but for a range image's (cc_scan_ingest_ranges
+// has): POINTS, MOTION: src.points are n_points records of `layout` (src.lay is set here); RANGES: n_points words; SEGMENTS: src.h_segs are
+// the scan's n_segs segments -- their records go to the staging buffer one segment after the other, each at a 16-byte boundary.
+static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t *layout, int64_t n_points, int n_segs, int want_bev, cc_scan **out, const char *who) {
+  const void *h_xyzi = src.points;
+  const cc_point_segment_t *h_segs = src.h_segs;
   if (!c || (!h_xyzi && !h_segs) || !out || (!h_segs && n_points < 1)) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  cc_point_layout_t lay = CC_LAYOUT_KITTI;
   std::vector<cc_k1_seg> seg_tab;
   std::vector<int64_t> seg_qoff;
   std::vector<size_t> seg_place;
@@ -1403,15 +1346,18 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
     const int rcs = segs_check(h_segs, seg_scan, 1, who, seg_tab, seg_qoff);
     if (rcs != CC_OK) return rcs;
     seg_bytes = segs_place(h_segs, seg_tab, seg_place);
-  } else {
-    const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records go through a staging buffer to aligned device memory)
+    src.segs = seg_tab.data();
+    src.scan_segs = seg_scan;
+    n_points = seg_qoff[1];
+  } else if (src.kind != k1_source::RANGES) {
+    const int rcl = point_layout(layout, nullptr, who, &src.lay);  // (the records go through a staging buffer to aligned device memory)
     if (rcl != CC_OK) return rcl;
-    if (mc) {
-      const int rcm = motion_check(lay, &mc->m, mc->h_time, mc->h_knots, 1, who);
+    if (src.kind == k1_source::MOTION) {
+      const int rcm = motion_check(src.lay, &src.mot, src.h_time, src.h_knots, 1, who);
       if (rcm != CC_OK) return rcm;
     }
   }
-  const size_t n_bytes = h_segs ? seg_bytes : (size_t)n_points * (size_t)(rg ? rg->s->word_bytes : lay.stride_bytes);   // the records travel as they are
+  const size_t n_bytes = h_segs ? seg_bytes : (size_t)n_points * (size_t)(src.kind == k1_source::RANGES ? src.sensor->word_bytes : src.lay.stride_bytes);   // the records travel as they are
   const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);  // d_pts, the slots, the scratch behind cc_ingest_batch
   HIPCHK(hipSetDevice(c->device));
@@ -1454,26 +1400,10 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
   c->pts_busy[slot] = true;
   cc_scan *sc = new cc_scan();  // from here on every failure path gives the handle (and, once taken, the descriptor slot) back
   sc->ctx = c;
-  {
-    std::lock_guard<std::mutex> lk(c->slot_mu);
-    if (c->slot_free.empty()) {
-      // the pool grows geometrically (64, 64, 128, 256, ... up to 1 024 slots = 169 MB per block): a hipMalloc synchronises the
-      // device, and a driver that keeps thousands of scans resident should not pay that every 64 scans of its loop
-      size_t have = 0;
-      for (size_t b = 0; b < c->slot_blocks.size(); b++) have += c->slot_block_n[b];
-      const int nblk = (int)(have < 64 ? 64 : (have > 1024 ? 1024 : have));
-      cc_scan_desc_t *blk = nullptr;
-      const hipError_t e_ = hipMalloc(&blk, sizeof(cc_scan_desc_t) * nblk);
-      if (e_ != hipSuccess) {
-        delete sc;
-        return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_);
-      }
-      c->slot_blocks.push_back(blk);
-      c->slot_block_n.push_back(nblk);
-      for (int i = nblk - 1; i >= 0; i--) c->slot_free.push_back(blk + i);
-    }
-    sc->d_desc = c->slot_free.back();
-    c->slot_free.pop_back();
+  const hipError_t e_slot = slot_take(c, 1, &sc->d_desc);
+  if (e_slot != hipSuccess) {
+    delete sc;
+    return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_slot);
   }
   auto give_back = [&](void) {
     {
@@ -1497,9 +1427,8 @@ static int scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layo
     }
   }
   for (int k = 0; k < n_segs; k++) seg_tab[k].base = (const char *)ch.d_pts + seg_place[k] + (seg_tab[k].base - (const char *)h_segs[k].points);
-  const seg_call sg = {seg_tab.data(), seg_scan};
-  const int rc = h_segs ? ingest_on(c, ch.scr, nullptr, lay, nullptr, seg_qoff.data(), 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, &sg)
-                        : ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who, nullptr, mc, rg);
+  src.points = ch.d_pts;
+  const int rc = ingest_on(c, ch.scr, src, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
   if (rc != CC_OK) {
     give_back();
     return rc;
@@ -1636,35 +1565,15 @@ static int scan_ingest_points_batch(cc_ctx *c, const void *const *h_xyzi, const 
       delete sc[i];
     }
   };
-  {
-    std::lock_guard<std::mutex> slk(c->slot_mu);
-    for (int i = 0; i < n; i++) {
-      if (c->slot_free.empty()) {
-        size_t have = 0;
-        for (size_t b = 0; b < c->slot_blocks.size(); b++) have += c->slot_block_n[b];
-        const int nblk = (int)(have < 64 ? 64 : (have > 1024 ? 1024 : have));
-        cc_scan_desc_t *blk = nullptr;
-        const hipError_t e_ = hipMalloc(&blk, sizeof(cc_scan_desc_t) * nblk);
-        if (e_ != hipSuccess) {
-          for (int k = 0; k < n_have; k++) {
-            c->slot_free.push_back(sc[k]->d_desc);
-            delete sc[k];
-          }
-          return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_);
-        }
-        c->slot_blocks.push_back(blk);
-        c->slot_block_n.push_back(nblk);
-        for (int k = nblk - 1; k >= 0; k--) c->slot_free.push_back(blk + k);
-      }
-      sc[i] = new cc_scan();
-      sc[i]->ctx = c;
-      sc[i]->d_desc = c->slot_free.back();
-      c->slot_free.pop_back();
-      tab.p[i] = sc[i]->d_desc;
-      n_have = i + 1;
-    }
+  const hipError_t e_slot = slot_take(c, n, tab.p);
+  if (e_slot != hipSuccess) return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_slot);
+  for (int i = 0; i < n; i++) {
+    sc[i] = new cc_scan();
+    sc[i]->ctx = c;
+    sc[i]->d_desc = tab.p[i];
   }
-  const int rc = ingest_on(c, ch.scr, ch.d_pts, lay, h_tf, off, n, ch.d_desc_tmp, nullptr, ch.s, who);
+  n_have = n;
+  const int rc = ingest_on(c, ch.scr, k1_points(ch.d_pts, lay, h_tf), off, n, ch.d_desc_tmp, nullptr, ch.s, who);
   if (rc != CC_OK) {
     give_back();
     return rc;

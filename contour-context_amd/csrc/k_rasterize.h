@@ -541,28 +541,6 @@ __device__ __forceinline__ void cc_k1_sweep(char *smem, const cc_dev_cfg &cfg, L
   }
 }
 
-// KITTI float4 records, no transform (cc_ingest_batch; the other entry points with the default layout and no transform)
-template <int CC_K1_U, bool CC_K1_POW2, bool PART = false>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *__restrict__ offsets,
-               float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
-               int want_dense) {
-  HIP_DYNAMIC_SHARED(char, smem)
-  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_kitti{pts}, offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
-}
-
-// Records of another shape and / or a per-scan transform (cc_ingest_points and its siblings).  STRIDE: 12 (packed xyz), 16 (KITTI
-// records with a transform, or not 16-byte aligned), 0 (run-time stride).  pts: x of the call's first point; tf: [n_scans][12] or nullptr.
-template <int CC_K1_U, bool CC_K1_POW2, bool PART, int STRIDE>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_rec(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, const float *__restrict__ tf, const long long *__restrict__ offsets,
-                   float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
-                   int want_dense) {
-  HIP_DYNAMIC_SHARED(char, smem)
-  const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;
-  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_rec<STRIDE>(pts, stride, tf, scan), offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
-}
-
 // The ranges of a scan combined: a cell's height is the largest of the ranges' keys and its point the one of the FIRST
 // range that reaches it -- ranges are in file order and each holds the first of its own points, so this is the first point
 // of the scan at that height: the reference's strict `bev < height` update (contour_mng.h:517) as in the one-sweep kernel.
@@ -627,19 +605,6 @@ __device__ __forceinline__ void cc_k1_merge(const cc_dev_cfg &cfg, LD P, const l
     scan_out[scan] = o;
   }
 }
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_merge(cc_dev_cfg cfg, const float4 *__restrict__ pts, const long long *__restrict__ offsets, cc_k1_part part,
-                     float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
-  cc_k1_merge(cfg, cc_ld_kitti{pts}, offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
-}
-template <int STRIDE>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_merge_rec(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, const float *__restrict__ tf, const long long *__restrict__ offsets,
-                         cc_k1_part part, float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out,
-                         cc_k1_list_out list_out, int want_dense) {
-  cc_k1_merge(cfg, cc_ld_rec<STRIDE>(pts, stride, tf, (int)blockIdx.x), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
-}
-
 // ---- a scan made of several SEGMENTS (cc_ingest_segments): records in up to CC_SEG_MAX places, each with its own stride and its own
 // optional transform; the scan is their points one after the other, and a point's index -- what the 21-bit fields hold, what step B
 // min-reduces and what "the first range wins" in the merge kernel is about -- is its index in THAT sequence.  So the tie rule holds
@@ -971,23 +936,6 @@ __device__ __forceinline__ void cc_k1_sweep_seg(char *smem, int tab_off, const c
   cc_k1_finish<PART>(cfg, cc_ld_segs{T, n_seg}, hmax, idx3, red, emit_tab, n_w3, kmin, unit, scan, n_pts, bev_out, pix_out, scan_out, part, list_out, want_dense, tid, nt);
 }
 
-// grid, block as cc_k_rasterize; dynamic LDS: tab_off (cc_k_rasterize's bytes) + CC_K1_SEG_LDS_BYTES
-template <int CC_K1_U, bool CC_K1_POW2, bool PART>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_seg(cc_dev_cfg cfg, cc_k1_segs segs, int tab_off, const long long *__restrict__ offsets, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
-                   cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out, int want_dense) {
-  HIP_DYNAMIC_SHARED(char, smem)
-  cc_k1_sweep_seg<CC_K1_U, CC_K1_POW2, PART>(smem, tab_off, cfg, segs, offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
-}
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_merge_seg(cc_dev_cfg cfg, cc_k1_segs segs, const long long *__restrict__ offsets, cc_k1_part part, float *__restrict__ bev_out,
-                         float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
-  __shared__ cc_k1_seg T[CC_SEG_MAX];
-  const int n_seg = cc_k1_seg_table(T, segs, (int)blockIdx.x);
-  __syncthreads();
-  cc_k1_merge(cfg, cc_ld_segs{T, n_seg}, offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
-}
-
 // ---- a sweep DE-SKEWED by per-point time (cc_ingest_points_motion): every record carries a 4-byte time word, every scan brings
 // K <= CC_MOTION_KNOTS_MAX matrices ("knots", piecewise constant over the sweep), and a point is moved by the knot of ITS time bin
 //     u = (t - t_begin) * scale   (CC_TIME_U32: (float)(uint32)(w - tb) * scale, the subtraction modulo 2^32)
@@ -1064,28 +1012,6 @@ struct cc_ld_rec_motion {
   }
 };
 
-// grid, block as cc_k_rasterize_rec; dynamic LDS: tab_off (cc_k_rasterize's bytes) + CC_K1_MOT_LDS_BYTES.  STRIDE: 16, 32, 0 (run-time stride).
-template <int CC_K1_U, bool CC_K1_POW2, bool PART, int STRIDE>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_mot(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, cc_k1_motion mot, int tab_off, const long long *__restrict__ offsets,
-                   float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out,
-                   int want_dense) {
-  HIP_DYNAMIC_SHARED(char, smem)
-  const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;
-  float *T = (float *)(smem + tab_off);
-  cc_k1_knot_table(T, mot, scan);  // (read after cc_k1_sweep's first barrier)
-  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_rec_motion<STRIDE>(pts, stride, mot, scan, T), offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
-}
-template <int STRIDE>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_merge_mot(cc_dev_cfg cfg, const char *__restrict__ pts, int stride, cc_k1_motion mot, const long long *__restrict__ offsets, cc_k1_part part,
-                         float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
-  __shared__ __attribute__((aligned(16))) float T[CC_K1_MOT_LDS_BYTES / 4];  // the owners' re-reads need the scan's knots too
-  cc_k1_knot_table(T, mot, (int)blockIdx.x);
-  __syncthreads();
-  cc_k1_merge(cfg, cc_ld_rec_motion<STRIDE>(pts, stride, mot, (int)blockIdx.x, T), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
-}
-
 // ---- a sensor's RANGE IMAGE rasterised in place (cc_ingest_ranges): a scan is H x W range words (u16 / u32 / f32), one per
 // (beam, firing) = (row, col); the sensor model -- per-row (cos alt, sin alt, cos az_off, sin az_off), per-column (cos az, sin az,
 // knot) -- is a few KB shared by every scan of every call.  A pixel becomes a point by the header's formula (f32, every product and
@@ -1108,7 +1034,7 @@ cc_k_rasterize_merge_mot(cc_dev_cfg cfg, const char *__restrict__ pts, int strid
 #define CC_K1_RNG_LDS_BYTES (CC_K1_RNG_ROW_LDS_BYTES + CC_K1_MOT_LDS_BYTES)
 #define CC_K1_RNG_MAGIC_SHIFT 33
 static_assert(((CC_MAX_CELLS * 4 + 15) & ~15) + ((CC_MAX_CELLS + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15) + CC_K1_RNG_LDS_BYTES <= 160 * 1024,
-              "cc_k_rasterize_rng: grid, index fields, output tables, row table and knots fit a CU's 160 KB of LDS");
+              "cc_src_rng: grid, index fields, output tables, row table and knots fit a CU's 160 KB of LDS");
 enum { CC_K1_WORD_U16 = 0, CC_K1_WORD_U32 = 1, CC_K1_WORD_F32 = 2 };  // = CC_RANGE_U16 / _U32 / _F32
 struct cc_k1_range {
   const void *words;    // the call's (chunk's) first range word
@@ -1210,24 +1136,99 @@ struct cc_ld_range {
   }
 };
 
-// grid, block as cc_k_rasterize; dynamic LDS: tab_off (cc_k_rasterize's bytes, 16-byte aligned) + CC_K1_RNG_LDS_BYTES.  offsets: scan i's first
-// pixel = i * n_rows * n_cols.
-template <int CC_K1_U, bool CC_K1_POW2, bool PART, int WORD>
-__global__ void __launch_bounds__(1024)
-cc_k_rasterize_rng(cc_dev_cfg cfg, cc_k1_range rng, int tab_off, const long long *__restrict__ offsets, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
-                   cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out, int want_dense) {
-  HIP_DYNAMIC_SHARED(char, smem)
-  const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;
-  char *T = smem + tab_off;
-  cc_k1_range_tables(T, rng, scan);  // (read after cc_k1_sweep's first barrier)
-  cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, cc_ld_range<WORD>(rng, scan, T), offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
-}
+
+// ---- point SOURCES: what a call hands the kernels, one by-value struct per family.  A source is the kernel argument and knows how
+// to make its family's loader:
+//   TAB_BYTES / TAB_ALIGN : the per-scan table the loader reads from LDS (0: none).  The sweep kernel has it in its dynamic LDS
+//                           behind cc_k1_sweep's layout, at tab_off = that layout's bytes rounded up to TAB_ALIGN; the merge kernel
+//                           in static LDS
+//   tables(tab, scan)     : the scan's table to LDS (a barrier has to follow before the loader's xyz() / owner_xy() is called:
+//                           cc_k1_sweep's first one, after it has cleared the grid; the merge kernel's own)
+//   loader(scan, tab)     : the loader, positioned at the first point of the call's first scan
+//   SEGMENTED             : the sweep is cc_k1_sweep_seg (which stages the table itself and re-seats a record loader per piece);
+//                           loader() is the output pass' only
+// KITTI float4 records, no transform (cc_ingest_batch; the other entry points with the default layout and no transform)
+struct cc_src_kitti {
+  static constexpr int TAB_BYTES = 0, TAB_ALIGN = 1;
+  static constexpr bool SEGMENTED = false;
+  const float4 *pts;
+  __device__ __forceinline__ void tables(char *, int) const {}
+  __device__ __forceinline__ cc_ld_kitti loader(int, const char *) const { return cc_ld_kitti{pts}; }
+};
+// Records of another shape and / or a per-scan transform (cc_ingest_points and its siblings).  STRIDE: 12 (packed xyz), 16 (KITTI
+// records with a transform, or not 16-byte aligned), 0 (run-time stride).  pts: x of the call's first point; tf: [n_scans][12] or nullptr.
+template <int STRIDE>
+struct cc_src_rec {
+  static constexpr int TAB_BYTES = 0, TAB_ALIGN = 1;
+  static constexpr bool SEGMENTED = false;
+  const char *pts;
+  int stride;
+  const float *tf;
+  __device__ __forceinline__ void tables(char *, int) const {}
+  __device__ __forceinline__ cc_ld_rec<STRIDE> loader(int scan, const char *) const { return cc_ld_rec<STRIDE>(pts, stride, tf, scan); }
+};
+// Records with a time word, de-skewed by the scan's knots (cc_ingest_points_motion).  STRIDE: 16, 32, 0 (run-time stride).
+template <int STRIDE>
+struct cc_src_mot {
+  static constexpr int TAB_BYTES = CC_K1_MOT_LDS_BYTES, TAB_ALIGN = 16;
+  static constexpr bool SEGMENTED = false;
+  const char *pts;
+  int stride;
+  cc_k1_motion mot;
+  __device__ __forceinline__ void tables(char *tab, int scan) const { cc_k1_knot_table((float *)tab, mot, scan); }
+  __device__ __forceinline__ cc_ld_rec_motion<STRIDE> loader(int scan, const char *tab) const {
+    return cc_ld_rec_motion<STRIDE>(pts, stride, mot, scan, (const float *)tab);
+  }
+};
+// Range images (cc_ingest_ranges).  WORD: CC_K1_WORD_U16 / _U32 / _F32.  offsets: scan i's first pixel = i * n_rows * n_cols.
 template <int WORD>
+struct cc_src_rng {
+  static constexpr int TAB_BYTES = CC_K1_RNG_LDS_BYTES, TAB_ALIGN = 16;
+  static constexpr bool SEGMENTED = false;
+  cc_k1_range rng;
+  __device__ __forceinline__ void tables(char *tab, int scan) const { cc_k1_range_tables(tab, rng, scan); }
+  __device__ __forceinline__ cc_ld_range<WORD> loader(int scan, const char *tab) const { return cc_ld_range<WORD>(rng, scan, tab); }
+};
+// Scans made of segments (cc_ingest_segments)
+struct cc_src_seg {
+  static constexpr int TAB_BYTES = CC_K1_SEG_LDS_BYTES, TAB_ALIGN = 8;
+  static constexpr bool SEGMENTED = true;
+  cc_k1_segs segs;
+  __device__ __forceinline__ void tables(char *tab, int scan) const { cc_k1_seg_table((cc_k1_seg *)tab, segs, scan); }
+  __device__ __forceinline__ cc_ld_segs loader(int scan, const char *tab) const {
+    return cc_ld_segs{(const cc_k1_seg *)tab, segs.scan_seg[scan + 1] - segs.scan_seg[scan]};
+  }
+};
+
+// The sweep.  grid = n_scans (PART: n_scans * CC_K1_SPLIT), block = multiple of 64; dynamic LDS: tab_off + SRC::TAB_BYTES, tab_off =
+// cc_k1_sweep's bytes (n_cell*4 + ((n_cell+2)/3)*8 + 16 + CC_K1_EMIT_LDS_BYTES, the pieces 16-byte aligned) rounded up to SRC::TAB_ALIGN.
+template <int CC_K1_U, bool CC_K1_POW2, bool PART, typename SRC>
 __global__ void __launch_bounds__(1024)
-cc_k_rasterize_merge_rng(cc_dev_cfg cfg, cc_k1_range rng, const long long *__restrict__ offsets, cc_k1_part part, float *__restrict__ bev_out,
-                         float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
-  __shared__ __attribute__((aligned(16))) char T[CC_K1_RNG_LDS_BYTES];  // the owners' re-reads need the row table and the scan's knots too
-  cc_k1_range_tables(T, rng, (int)blockIdx.x);
-  __syncthreads();
-  cc_k1_merge(cfg, cc_ld_range<WORD>(rng, (int)blockIdx.x, T), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
+cc_k_rasterize(cc_dev_cfg cfg, SRC src, int tab_off, const long long *__restrict__ offsets, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
+               cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out, int want_dense) {
+  HIP_DYNAMIC_SHARED(char, smem)
+  if constexpr (SRC::SEGMENTED) {
+    cc_k1_sweep_seg<CC_K1_U, CC_K1_POW2, PART>(smem, tab_off, cfg, src.segs, offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+  } else {
+    const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;
+    char *tab = smem + tab_off;
+    src.tables(tab, scan);  // (read after cc_k1_sweep's first barrier)
+    cc_k1_sweep<CC_K1_U, CC_K1_POW2, PART>(smem, cfg, src.loader(scan, tab), offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+  }
+}
+
+// The merge of a split sweep's ranges.  grid = n_scans, block = multiple of 64.  The owners' re-reads need the scan's table too.
+template <typename SRC>
+__global__ void __launch_bounds__(1024)
+cc_k_rasterize_merge(cc_dev_cfg cfg, SRC src, const long long *__restrict__ offsets, cc_k1_part part, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
+                     cc_k1_scan_out *__restrict__ scan_out, cc_k1_list_out list_out, int want_dense) {
+  const int scan = (int)blockIdx.x;
+  char *tab = nullptr;
+  if constexpr (SRC::TAB_BYTES > 0) {
+    __shared__ __attribute__((aligned(16))) char T[SRC::TAB_BYTES];
+    tab = T;
+    src.tables(tab, scan);
+    __syncthreads();
+  }
+  cc_k1_merge(cfg, src.loader(scan, tab), offsets, part, bev_out, pix_out, scan_out, list_out, want_dense);
 }
