@@ -861,6 +861,9 @@ cc_k_contours_big(cc_dev_cfg cfg, const float *__restrict__ bev_in, const float2
       }
       return;
     }
+#ifdef CC_EMU
+    if (threadIdx.x == 0 && getenv("CC_EMU_TRACE_K2")) fprintf(stderr, "[k2 big] scan %d\n", queue->scan[k]);
+#endif
     cc_k2_body<CC_NC_BIG, true>(cfg, bev_in, pix_in, k1_out, &slots[blockIdx.x].scr, &slots[blockIdx.x].tab, nullptr, queue->scan[k], desc_out,
                                 labels_dbg, smem);
   }

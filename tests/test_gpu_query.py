@@ -7,6 +7,10 @@ pytestmark = pytest.mark.gpu
 
 INT_FIELDS = ["n_res", "cand_gidx", "cand_aft_check1", "cand_aft_check2", "cand_aft_check3", "n_cand_pose", "n_cand_tidy",
               "n_knn_hits"]
+# The device's f64 exp and glibc's differ by an ulp or two; that reaches an f32 ring component of a retrieval key only through a
+# term within ~1e-8 (relative) of an f32 rounding boundary -- about 1.5e-5 per component of ~1 500 terms (tests/key_reference.py).
+# More than one component in a thousand with other bits than the oracle's is a different sum, not a different exp.
+RING_DIFF_CAP = 1e-3
 
 
 @pytest.fixture(scope="module")
@@ -152,12 +156,16 @@ def _seq_vs_oracle(cc, oracle, xyzi, ts, mcfg=None, dcfg=None, min_hits=10, chec
     ores, _, odesc = oracle.run_sequence(xyzi.cpu().numpy().reshape(-1, 4), offs, ts, seeds, mcfg=mcfg, dcfg=dcfg, want_desc=True)
     assert (ores["n_res"] > 0).sum() >= min_hits, "sequence should contain loop closures (%d)" % (ores["n_res"] > 0).sum()
     bad = []
-    if check_desc:  # every descriptor: integers, contour rows and BCIs bit-exact, keys to the last bits of the f64 exp
-        from parity import compare_desc
+    if check_desc:  # every descriptor: integers, contour rows, BCIs and key components 0..2 bit-exact, the ring components to the
+        from parity import compare_desc  # last bits of the f64 exp -- and at most RING_DIFF_CAP of them different at all
+        n_diff = n_ring = 0
         for i in range(n):
-            b = compare_desc(odesc[i], d[i], float_exact=False)
+            b, nd, nr = compare_desc(odesc[i], d[i], float_exact=False, ring_count=True)
+            n_diff, n_ring = n_diff + nd, n_ring + nr
             if b:
                 bad.append("scan %d: %s" % (i, b[:4]))
+        print("%d of %d non-zero ring components of the keys differ from the oracle's in their bits" % (n_diff, n_ring))
+        assert n_ring > 0 and n_diff <= RING_DIFF_CAP * n_ring, (n_diff, n_ring)
     for i in range(n):
         for f in INT_FIELDS:
             if ores[f][i] != res[f][i]:
@@ -294,11 +302,11 @@ def test_full_sequence_online_replay(cc, oracle, tmp_path, world):
             s = oracle.Scan(xh[i], int_id=gi, keep_cells=False)
             if i % 32 == 0:
                 od_ = s.desc()[0]
-                bad = compare_desc(od_, dh[i // 32], float_exact=False)
+                bad, nd, nr = compare_desc(od_, dh[i // 32], float_exact=False, ring_count=True)
                 assert not bad, "scan %d: %s" % (gi, bad[:5])
                 n_desc_checked += 1
-                n_key_vals += int((od_["keys"] != 0).sum())
-                n_key_diff += int((od_["keys"].view(np.uint32) != dh[i // 32]["keys"].view(np.uint32)).sum())
+                n_key_vals += nr
+                n_key_diff += nd
             s.clear_image()
             ores[gi] = odb.query(s)
             odb.add_scan(s, ts[i])
@@ -340,8 +348,9 @@ def test_full_sequence_online_replay(cc, oracle, tmp_path, world):
         assert abs(pr_g[f] - pr_o[f]) < 1e-4, (f, pr_g[f], pr_o[f])
     assert pr_o["max_f1"] > 0.8, pr_o["max_f1"]   # the synthetic loop closures are found, and found right
     print(world + " online replay: %d scans, %d loop closures, max-F1 %.6f at %.6f, %d TP, %d descriptors compared (contour rows and BCIs "
-          "bit-exact; %d of %d non-zero key components differ in the last bits: device exp vs glibc exp)"
+          "bit-exact; %d of %d non-zero ring components of the keys differ in the last bits: device exp vs glibc exp)"
           % (n, int(hit.sum()), pr_o["max_f1"], pr_o["sim_thres"], pr_o["tp_count"], n_desc_checked, n_key_diff, n_key_vals))
+    assert n_key_vals > 0 and n_key_diff <= RING_DIFF_CAP * n_key_vals, (n_key_diff, n_key_vals)
     db.close()
     ctx.close()
 

@@ -15,6 +15,21 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+RING_DIFF_CAP = 1e-3   # ring components of the keys whose bits may differ from the oracle's (test_gpu_query.py says why)
+
+
+def _keys_to_the_bit(oracle_scan, od, got):
+    """tests/key_reference.py on the oracle's inputs: the oracle's keys pass it, then the device's -- bit for bit except components
+    that are provably ambiguous -> (ambiguous components, ring components whose bits differ from the oracle's, non-zero ones)"""
+    import key_reference as KR
+    from parity import compare_desc
+    keys, amb, _ = KR.scan_reference(oracle_scan, od, oracle_scan.cfg)
+    KR.check_keys(keys, amb, od["keys"])
+    n_amb = KR.check_keys(keys, amb, got["keys"])
+    _, n_diff, n_ring = compare_desc(od, got, float_exact=False, ring_count=True)
+    return n_amb, n_diff, n_ring
+
+
 INT_FIELDS = ["n_res", "cand_gidx", "cand_aft_check1", "cand_aft_check2", "cand_aft_check3", "n_cand_pose", "n_cand_tidy",
               "n_knn_hits"]
 
@@ -66,6 +81,7 @@ def test_real_shaped_scans_bit_exact(cc, oracle):
     got = cc.desc_to_numpy(d)
     lab = dbg["labels"].cpu().numpy()
     most = 0
+    tally = np.zeros(3, np.int64)
     for i, s in enumerate(scans):
         o = oracle.Scan(s)
         od = o.desc()[0]
@@ -76,7 +92,10 @@ def test_real_shaped_scans_bit_exact(cc, oracle):
         bad = compare_desc(od, got[i], float_exact=False)
         assert not bad, "scan %d: %s" % (i, bad[:5])
         assert np.array_equal(o.labels(), lab[i]), "canonical label images differ (scan %d)" % i
+        tally += _keys_to_the_bit(o, od, got[i])        # the mid path (window probing) at real occupancy
     assert most >= 100, most   # 100+ contours on a level somewhere
+    print("real-shaped scans: %d ambiguous, %d of %d non-zero ring components differ from the oracle's in their bits" % tuple(tally))
+    assert tally[2] > 500 and tally[1] <= RING_DIFF_CAP * tally[2] and tally[0] <= RING_DIFF_CAP * tally[2], tally
     ctx.close()
 
 
@@ -104,6 +123,7 @@ def test_component_and_key_capacities_are_flagged(cc, oracle):
     ctx, d, dbg = _ingest(cc, [blobs, real_shaped_scan(3), _blob_field(700, height=3.2)])
     got = cc.desc_to_numpy(d)
     lab = dbg["labels"].cpu().numpy()
+    tally = np.zeros(3, np.int64)
     for i, s in ((0, blobs), (2, _blob_field(700, height=3.2))):
         o = oracle.Scan(s)
         od = o.desc()[0]
@@ -112,6 +132,9 @@ def test_component_and_key_capacities_are_flagged(cc, oracle):
         assert not bad, bad[:5]
         assert got["flags"][i] == 1, got["flags"]
         assert np.array_equal(o.labels(), lab[i])
+        tally += _keys_to_the_bit(o, od, got[i])                        # the slow path's keys
+    print("blob fields: %d ambiguous, %d of %d non-zero ring components differ from the oracle's in their bits" % tuple(tally))
+    assert tally[1] <= RING_DIFF_CAP * tally[2] and tally[0] <= RING_DIFF_CAP * tally[2], tally
     assert got["flags"][1] == 0
     hd = ctx.ingest_host(blobs, np.array([0, len(blobs)], np.int64))
     assert not compare_desc(oracle.Scan(blobs).desc()[0], hd[0], float_exact=False)
