@@ -23,7 +23,7 @@ import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
 _SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_contours.h", "k_contours_list.h",
-         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "k_pose.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
+         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 # how every gfx950 code object of this project that includes csrc/ headers is compiled: the library below and the device
 # probe library of the test suite (tests/dev_probe.py), so that what the probes measure is the code the library runs
@@ -61,6 +61,7 @@ EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_
            "cc_db_query_submit_ranked_detail", "cc_db_query_batch_host_ranked_detail", "cc_db_query_scan_batch_submit_ranked_detail",
            "cc_db_verify_submit_ranked_detail", "cc_db_verify_batch_host_ranked_detail", "cc_db_check_hints_ranked_detail",
            "cc_db_check_hints_host_ranked_detail", "cc_est_sens_info", "cc_db_pose_submit", "cc_db_pose_batch", "cc_db_pose_batch_host",
+           "cc_db_query_submit_packed", "cc_db_verify_submit_packed", "cc_db_pose_submit_packed",
            "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
            "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
            "cc_comm_unique_id", "cc_comm_create", "cc_comm_create_from_env", "cc_comm_rank", "cc_comm_world", "cc_comm_allgather_packed", "cc_comm_destroy"]
@@ -140,6 +141,9 @@ def lib():
             getattr(_lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
         _lib.cc_db_pose_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.cc_est_sens_info.restype = None
+        _lib.cc_db_query_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
+        _lib.cc_db_verify_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
+        _lib.cc_db_pose_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
         _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
         _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
     return _lib
@@ -548,6 +552,38 @@ def desc_to_numpy(desc_tensor):
     return desc_tensor.cpu().numpy().view(L.scan_desc_dt).reshape(-1)
 
 
+class Packed:
+    """Packed records as the query of Database.query / verify / score_poses (and their _submit forms) in the place of `qdesc`:
+    hot / feat are the tensors Context.pack returns (or records gathered from another rank, or a saved map), idx names the
+    record of every query (None: query i is record i).  Where the call has its own selector (verify's qidx, score_poses' q) that
+    one names the records and idx must be None."""
+
+    def __init__(self, hot, feat, idx=None):
+        assert hot.is_cuda and feat.is_cuda and hot.is_contiguous() and feat.is_contiguous() and feat.shape[0] == hot.shape[0]
+        self.hot, self.feat = hot, feat
+        self.idx = None if idx is None else np.ascontiguousarray(idx, np.int32).reshape(-1)
+        self.device = hot.device
+
+    def _src(self):
+        return L.PackedSrc(self.hot.data_ptr(), self.feat.data_ptr(), int(self.hot.shape[0]), 0)
+
+
+class Stored:
+    """Scans of the database itself as the query (Database.stored makes one): idx names them by database index."""
+
+    def __init__(self, db, idx=None):
+        self.db = db
+        self.idx = None if idx is None else np.ascontiguousarray(list(idx) if isinstance(idx, range) else idx, np.int32).reshape(-1)
+        self.device = None
+
+    def _src(self):
+        return L.PackedSrc(None, None, 0, 0)
+
+
+def _is_src(q):
+    return isinstance(q, (Packed, Stored))
+
+
 class Database:
     """cc_db: device-resident ContourDB (contour_db.h:673-845) + batched queryRangedKNN."""
 
@@ -588,6 +624,58 @@ class Database:
         stream = torch.cuda.current_stream(desc.device).cuda_stream
         _chk(lib().cc_db_add_scans(self.h, desc.data_ptr(), n, ts.ctypes.data, seeds.ctypes.data, stream), "cc_db_add_scans")
 
+    def stored(self, idx=None):
+        """The database's own scans as the query of query / verify / score_poses (and their _submit forms): scan idx[i] is query
+        i (an int names one scan; None leaves the naming to the call's own selector -- verify's qidx, score_poses' q).  Nothing is
+        excluded: scan g queried at epoch g is the online loop's query of g, at a later epoch the answer may be g itself."""
+        return Stored(self, None if idx is None else ([idx] if isinstance(idx, (int, np.integer)) else idx))
+
+    def _q_device(self, q):
+        """the device of a query argument: a descriptor tensor, a Packed or a Stored source"""
+        import torch
+        dev = getattr(q, "device", None)
+        return dev if dev is not None else torch.device("cuda", self.ctx.device)
+
+    def _src_args(self, q):
+        """a Packed / Stored query -> (cc_packed_src_t, its record selector or None, the stream the call is queued on)"""
+        import torch
+        if isinstance(q, Stored) and q.db is not self:
+            raise ValueError("the stored scans belong to another database")
+        dev = q.device if q.device is not None else torch.device("cuda", self.ctx.device)
+        return q._src(), q.idx, torch.cuda.current_stream(dev).cuda_stream
+
+    def _packed_query(self, q, epochs, lb, ub, want_knn, ranked, det, tol, wait):
+        """query() / query_submit() from a record source: cc_db_query_submit_packed (+ the wait)"""
+        import torch
+        src, idx, stream = self._src_args(q)
+        if lb is None:
+            lb, ub = L.default_thresholds()
+        epochs = np.ascontiguousarray(epochs, np.int32)
+        nq = len(epochs)
+        if idx is not None and len(idx) != nq:
+            raise ValueError("the source names %d records for %d epochs" % (len(idx), nq))
+        res = np.zeros(nq, L.query_result_dt)
+        knn = cnt = None
+        if want_knn:
+            dev = q.device if q.device is not None else torch.device("cuda", self.ctx.device)
+            knn = torch.zeros((nq, L.NQLEV, L.NPIV, self.knn_stride, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=dev)
+            cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=dev)
+        rk = ro = None
+        if ranked is not None:
+            rc_, rn_, ro = L.rank_buffers(nq, ranked)
+            rk = (rc_, rn_)
+        args = (self.h, C.addressof(src), idx.ctypes.data if idx is not None else None, nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
+                res.ctypes.data, knn.data_ptr() if want_knn else None, cnt.data_ptr() if want_knn else None, stream,
+                C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None)
+        keep = (q, src, idx, epochs, lb, ub, ro)
+        if wait:
+            self._ranked_call(lib().cc_db_query_submit_packed, "cc_db_query_submit_packed", tol, *args)
+        else:
+            self._pending = getattr(self, "_pending", [])
+            self._pending.append((keep, res, rk, det))  # the library reads and writes them until query_wait
+            _chk(lib().cc_db_query_submit_packed(*args), "cc_db_query_submit_packed")
+        return res, knn, cnt, rk
+
     def add_scans_prepare(self, desc):
         """Queue the device half of add_scans(desc, ...) on the current stream without waiting (cc_db_add_scans_prepare)."""
         import torch
@@ -617,6 +705,8 @@ class Database:
 
     def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False):
         """qdesc: torch uint8 CUDA [nq, DESC_BYTES]; epochs int32 [nq] (DB state each query sees).
+        In the place of qdesc: self.stored(idx) -- scans of this database by index -- or Packed(hot, feat, idx): the query comes
+        from the packed records instead of from descriptors (cc_db_query_submit_packed + the wait), with the same answers.
         Returns numpy structured array of cc_query_result_t (+ knn hits / counts as torch tensors).
         allow_flagged: a query that met an internal capacity (cc_query_result_t.flags != 0) makes the library return
         CC_ECAPACITY with every result delivered; True hands the results back (the caller looks at `flags`) instead of raising.
@@ -628,6 +718,18 @@ class Database:
         -correlation at its pose (hess, grad) and the refinement's start, initial correlation, iterations, termination and pair
         count (cc_db_query_submit_ranked_detail).  Without ranked it is a ValueError."""
         import torch
+        if _is_src(qdesc):  # a record source in the place of the descriptors: the submit followed by the wait, like ranked=K
+            nq, ks = len(np.asarray(epochs).reshape(-1)), self.knn_stride
+            det = self._detail_args(nq, ranked, detail)
+            res, knn, cnt, rk = self._packed_query(qdesc, epochs, lb, ub, want_knn, ranked, det, (CC_ECAPACITY,) if allow_flagged else (), True)
+            out = (res,)
+            if want_knn:
+                out += (knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy())
+            if rk is not None:
+                out += (rk,)
+            if det is not None:
+                out += (det,)
+            return out if len(out) > 1 else res
         det = self._detail_args(qdesc.shape[0], ranked, detail)
         if lb is None:
             lb, ub = L.default_thresholds()
@@ -667,8 +769,12 @@ class Database:
         """Asynchronous form of query(): queues the batch and returns the result array, which is only valid after
         query_wait() (cc_db_query_submit / cc_db_query_wait).  qdesc may be overwritten by work queued afterwards on the
         current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait();
-        with detail=True followed by the [nq, K] detail array (see query())."""
+        with detail=True followed by the [nq, K] detail array (see query()).  qdesc may be self.stored(idx) or a Packed."""
         import torch
+        if _is_src(qdesc):
+            det = self._detail_args(len(np.asarray(epochs).reshape(-1)), ranked, detail)
+            res, _k, _c, rk = self._packed_query(qdesc, epochs, lb, ub, False, ranked, det, (), False)
+            return res if rk is None else ((res, rk) if det is None else (res, rk, det))
         det = self._detail_args(qdesc.shape[0], ranked, detail)
         if lb is None:
             lb, ub = L.default_thresholds()
@@ -746,7 +852,12 @@ class Database:
         import torch
         if lb is None:
             lb, ub = L.default_thresholds()
-        assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
+        if _is_src(qdesc):
+            if qdesc.idx is not None and qidx is not None:
+                raise ValueError("name the records by the source's idx or by qidx, not both")
+            qidx = qdesc.idx if qidx is None else qidx
+        else:
+            assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
         if isinstance(cands, np.ndarray):
             rows = np.asarray(cands, np.int64).reshape(len(cands), -1)
         else:
@@ -775,7 +886,9 @@ class Database:
 
     def verify(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
                want_hints=False, allow_flagged=False, ranked=None, detail=False):
-        """Score candidates the caller proposes, in one batch (cc_db_verify_batch).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES];
+        """Score candidates the caller proposes, in one batch (cc_db_verify_batch).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES]
+        -- or self.stored(idx) / Packed(hot, feat, idx): item i is record idx[i] (or qidx[i] of a source without idx), read from
+        the packed records (cc_db_verify_submit_packed + the wait); an item may name a stored scan among its own candidates;
         cands: int array [n, <= 8] padded with -1, or a list of lists of DB indices; item i is descriptor qidx[i] (None: i)
         against cands[i].  The hint list of an item is generated on the device: every (candidate, level, candidate anchor,
         query anchor) whose keys are non-zero and at most max_key_dist_sq apart (float("inf"): no bound), candidate outermost.
@@ -792,12 +905,22 @@ class Database:
         res = np.zeros(n, L.query_result_dt)
         d_h = d_n = None
         if want_hints:
-            d_h = torch.zeros((max(n, 1), L.HINT_MAX, L.hint_dt.itemsize), dtype=torch.uint8, device=qdesc.device)
-            d_n = torch.zeros(max(n, 1), dtype=torch.int32, device=qdesc.device)
-        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+            d_h = torch.zeros((max(n, 1), L.HINT_MAX, L.hint_dt.itemsize), dtype=torch.uint8, device=self._q_device(qdesc))
+            d_n = torch.zeros(max(n, 1), dtype=torch.int32, device=self._q_device(qdesc))
+        stream = torch.cuda.current_stream(self._q_device(qdesc)).cuda_stream
         tol = (CC_ECAPACITY,) if allow_flagged else ()
         rk = None
-        if ranked is None:
+        if _is_src(qdesc):  # a record source: cc_db_verify_submit_packed followed by the wait
+            src = self._src_args(qdesc)[0]
+            ro = None
+            if ranked is not None:
+                rc_, rn_, ro = L.rank_buffers(n, ranked)
+                rk = (rc_, rn_)
+            self._ranked_call(lib().cc_db_verify_submit_packed, "cc_db_verify_submit_packed", tol, self.h, C.addressof(src),
+                              qidx.ctypes.data if qidx is not None else None, tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub),
+                              res.ctypes.data, d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream,
+                              C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None)
+        elif ranked is None:
             _chk(lib().cc_db_verify_batch(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
                                           tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
                                           d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream),
@@ -825,14 +948,27 @@ class Database:
                       ranked=None, detail=False):
         """Asynchronous form of verify(): queues the batch and returns the result array, which is only valid after query_wait()
         (cc_db_verify_submit; verify and query chunks share the lanes and are collected together).  ranked=K: returns
-        (results, (cands [n, K], counts [n])), with detail=True followed by the [n, K] detail array."""
+        (results, (cands [n, K], counts [n])), with detail=True followed by the [n, K] detail array.  qdesc may be self.stored(idx)
+        or a Packed, as for verify()."""
         import torch
         tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
         det = self._detail_args(len(tab), ranked, detail)
         res = np.zeros(len(tab), L.query_result_dt)
         self._pending = getattr(self, "_pending", [])
         self._pending.append(res)  # the library writes into it until query_wait
-        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
+        stream = torch.cuda.current_stream(self._q_device(qdesc)).cuda_stream
+        if _is_src(qdesc):
+            src = self._src_args(qdesc)[0]
+            rk = ro = None
+            if ranked is not None:
+                rc_, rn_, ro = L.rank_buffers(len(tab), ranked)
+                rk = (rc_, rn_)
+            self._pending.append((qdesc, tab, qidx, rk, det))
+            _chk(lib().cc_db_verify_submit_packed(self.h, C.addressof(src), qidx.ctypes.data if qidx is not None else None, tab.ctypes.data, len(tab),
+                                                  C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data, None, None, stream,
+                                                  C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None),
+                 "cc_db_verify_submit_packed")
+            return res if rk is None else ((res, rk) if det is None else (res, rk, det))
         if ranked is not None:
             rc_, rn_, ro = L.rank_buffers(len(tab), ranked)
             self._pending.append((rc_, rn_))
@@ -854,7 +990,11 @@ class Database:
 
     def _pose_args(self, qdesc, q, gidx, tf, refine, min_corr, tries, curvature):
         import torch
-        assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
+        if _is_src(qdesc):
+            if qdesc.idx is not None:
+                raise ValueError("score_poses names the records by q: give the source without idx")
+        else:
+            assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
         q = np.asarray(q).reshape(-1)
         n = len(q)
         if len(np.asarray(gidx).reshape(-1)) != n or np.asarray(tf).size != 3 * n:
@@ -873,14 +1013,19 @@ class Database:
         cfg = L.PoseCfg(int(refine), float(min_corr), nt, 0)
         res = np.zeros(n, L.pose_result_dt)
         cv = np.zeros(n, L.pose_curv_dt) if curvature else None
-        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
-        args = (self.h, qdesc.data_ptr(), qdesc.shape[0], items.ctypes.data, n, C.addressof(cfg), tr.ctypes.data if nt else None, res.ctypes.data,
+        stream = torch.cuda.current_stream(self._q_device(qdesc)).cuda_stream
+        tail = (items.ctypes.data, n, C.addressof(cfg), tr.ctypes.data if nt else None, res.ctypes.data,
                 tc.ctypes.data if nt else None, cv.ctypes.data if curvature else None, stream)
+        if _is_src(qdesc):  # the arguments of cc_db_pose_submit_packed
+            src = self._src_args(qdesc)[0]
+            return (self.h, C.addressof(src)) + tail, (items, tr, cfg, src, qdesc), res, (tc if tries is not None else None), cv
+        args = (self.h, qdesc.data_ptr(), qdesc.shape[0]) + tail
         return args, (items, tr, cfg), res, (tc if tries is not None else None), cv
 
     def score_poses(self, qdesc, q, gidx, tf, refine=True, min_corr=None, tries=None, curvature=False, allow_flagged=False):
         """Score, probe and refine relative poses the caller believes in, in one batch (cc_db_pose_batch: the reference's
-        ConstellCorrelation::initProblem / tryProblem / calcCorrelation).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES]; item i
+        ConstellCorrelation::initProblem / tryProblem / calcCorrelation).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES], or
+        self.stored() / Packed(hot, feat) -- q then names packed records (cc_db_pose_submit_packed + the wait); item i
         is descriptor q[i] (tgt) against database scan gidx[i] (src) at T_init = tf[i] = (x, y, theta) in BEV pixels / radians.
         refine: run the L-BFGS refinement on the items with pairs whose initial correlation is not below min_corr (None: the
         shipped lb.correlation, 0.3; -inf: every item that has pairs).  tries [n, T, 3], T <= L.POSE_TRY_MAX: further poses per
@@ -888,6 +1033,9 @@ class Database:
         Returns (res [n] of L.pose_result_dt, try_corr [n, T] or None, curv [n] of L.pose_curv_dt or None); a refined row
         carries L.PF_REFINED in flags.  allow_flagged: as for query()."""
         args, keep, res, tc, cv = self._pose_args(qdesc, q, gidx, tf, refine, min_corr, tries, curvature)
+        if _is_src(qdesc):  # the submit followed by the wait
+            self._ranked_call(lib().cc_db_pose_submit_packed, "cc_db_pose_submit_packed", (CC_ECAPACITY,) if allow_flagged else (), *args)
+            return res, tc, cv
         _chk(lib().cc_db_pose_batch(*args), "cc_db_pose_batch", tolerate=(CC_ECAPACITY,) if allow_flagged else ())
         return res, tc, cv
 
@@ -897,7 +1045,7 @@ class Database:
         args, keep, res, tc, cv = self._pose_args(qdesc, q, gidx, tf, refine, min_corr, tries, curvature)
         self._pending = getattr(self, "_pending", [])
         self._pending.append((keep, res, tc, cv))  # the library reads and writes them until query_wait
-        _chk(lib().cc_db_pose_submit(*args), "cc_db_pose_submit")
+        _chk((lib().cc_db_pose_submit_packed if _is_src(qdesc) else lib().cc_db_pose_submit)(*args), "cc_db_pose_submit")
         return res, tc, cv
 
     def debug_passes(self, cap=1152):

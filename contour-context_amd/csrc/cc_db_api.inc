@@ -1101,6 +1101,39 @@ static int launch_query_prep(cc_db *db, cc_qlane &ln, const cc_scan_desc_t *d_q,
   return CC_OK;
 }
 
+// The same for a chunk whose query scans exist as packed records (k_prep_packed.h): record i of the chunk is a copy of record
+// d_sel[i] of the source; the heads, the pass counters and a small chunk's epoch records as above.
+struct cc_rec_src {  // a cc_packed_src_t, resolved (packed_resolve)
+  const cc_hot_desc_t *hot;
+  const cc_gmm_feat *feat;
+  int n_rec;
+};
+static int launch_prep_packed(cc_qlane &ln, const cc_rec_src &rs, const int *d_sel, int nb, bool meta_from_host) {
+  hipLaunchKernelGGL(cc_k_prep_packed, dim3(nb * CC_PREPP_SPLIT), dim3(CC_PREPP_BLOCK), 0, ln.stream, rs.hot, rs.feat, d_sel, nb, ln.d_qhot, ln.d_qfeat,
+                     ln.d_heads, CC_N_HEADS, ln.d_pass_cnt, meta_from_host ? (const cc_query_meta *)ln.h_meta : (const cc_query_meta *)nullptr, ln.d_qmeta);
+  HIPCHK(hipGetLastError());
+  return CC_OK;
+}
+// The refusals every *_submit_packed form shares, worded with the entry point's name, and the source it reads.
+static int packed_resolve(const char *fn, const cc_db *db, const cc_packed_src_t *src, cc_rec_src *out) {
+  if (!db) return set_err(CC_EINVAL, (std::string(fn) + ": bad argument").c_str());
+  if (!src) return set_err(CC_EINVAL, (std::string(fn) + ": src must be given").c_str());
+  if ((src->d_hot == nullptr) != (src->d_feat == nullptr)) return set_err(CC_EINVAL, (std::string(fn) + ": d_hot and d_feat are given together, or both NULL (the database's own records)").c_str());
+  if (!src->d_hot) {  // the database's committed rows
+    *out = cc_rec_src{db->d_hot, db->d_feat, db->n_scans};
+    return CC_OK;
+  }
+  if (src->n_rec < 1) return set_err(CC_EINVAL, (std::string(fn) + ": n_rec must be positive").c_str());
+  if (((uintptr_t)src->d_hot | (uintptr_t)src->d_feat) & 15) return set_err(CC_EINVAL, (std::string(fn) + ": the record arrays must be 16-byte aligned").c_str());
+  *out = cc_rec_src{(const cc_hot_desc_t *)src->d_hot, (const cc_gmm_feat *)src->d_feat, src->n_rec};
+  return CC_OK;
+}
+// rank NULL: the plain call; h_detail NULL: the ranked one; both: the ranked-detail one
+static int packed_modes(const char *fn, const cc_rank_out_t *rank, const cc_ranked_detail_t *h_detail) {
+  if (!rank && h_detail) return set_err(CC_EINVAL, (std::string(fn) + ": h_detail comes with rank").c_str());
+  return rank ? want_ranked(fn, rank, h_detail, false) : CC_OK;
+}
+
 static cc_check_params make_check_params(const cc_db *db, const cc_score_t *lb) {
   cc_check_params CP;
   CP.sim = db->cfg.cont_sim;
@@ -1323,10 +1356,11 @@ struct cc_chunk {  // one chunk, as the driver hands it to the steps of a plan
   bool zc;
   hipEvent_t *ev;  // the lane's stage events [0..5] when the chunk is profiled, or nullptr
 };
-struct cc_prep_src {  // what launch_query_prep builds a chunk's query records from
-  const cc_scan_desc_t *d_q;
+struct cc_prep_src {  // what the prep stage makes a chunk's query records from
+  const cc_scan_desc_t *d_q;  // descriptors: launch_query_prep builds the records (nullptr with `rec`)
   bool meta_from_host;
   const int *d_sel;
+  const cc_rec_src *rec = nullptr;  // packed records (the *_submit_packed forms): launch_prep_packed copies record d_sel[i]
 };
 // What a submit does of its own, in the order the driver calls it.  The steps from `upload` on return a CC_* code with the
 // message set (HIPCHK for their HIP calls).
@@ -1353,8 +1387,9 @@ static int queue_chunk(cc_db *db, hipStream_t stream, const cc_chunk_plan &plan,
   hipEvent_t *ev = c.ev;
   cc_prep_src src{nullptr, false, nullptr};
   LANE_CHK(plan.upload(c, src));
-  LANE_CHK(launch_query_prep(db, ln, src.d_q, c.nb, src.meta_from_host, src.d_sel));
-  // the caller's stream goes on once the descriptors have been read
+  if (src.rec) LANE_CHK(launch_prep_packed(ln, *src.rec, src.d_sel, c.nb, src.meta_from_host));
+  else LANE_CHK(launch_query_prep(db, ln, src.d_q, c.nb, src.meta_from_host, src.d_sel));
+  // the caller's stream goes on once the descriptors (the records) have been read
   HIPCHK(hipEventRecord(ln.prep, ls));
   HIPCHK(hipStreamWaitEvent(stream, ln.prep, 0));
   if (ev) HIPCHK(hipEventRecord(ev[0], ls));
@@ -1445,8 +1480,10 @@ static void results_note(cc_qlane &ln, cc_query_result_t *h_res, const cc_rank_o
 static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                              const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
                              const cc_rank_out_t *rank,
-    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
-  if (!db || !d_qdesc || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
+                             const cc_rec_src *rec = nullptr /*the queries are packed records (then d_qdesc is nullptr) ...*/,
+                             const int32_t *h_rec = nullptr /*... query i is record h_rec[i] of them, or nullptr: record i*/) {
+  if (!db || (!d_qdesc && !rec) || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch");
   if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch: thresholds must satisfy lb.strictSmaller(ub)");
   HIPCHK(hipSetDevice(db->device));
@@ -1468,12 +1505,22 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
   const cc_check_params CP = make_check_params(db, lb);
   for (int i = 0; i < nq; i++)
     if (h_epoch[i] < 0 || h_epoch[i] > db->n_scans) return set_err(CC_EINVAL, "cc_db_query_batch: epoch out of range");
+  if (rec)
+    for (int i = 0; i < nq; i++) {
+      const int r = h_rec ? h_rec[i] : i;
+      if (r < 0 || r >= rec->n_rec) return set_err(CC_EINVAL, "cc_db_query_submit_packed: record index outside the source");
+    }
   bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
   cc_chunk_plan plan;
-  plan.alloc = [&](cc_qlane &ln) -> int { return lane_alloc_modes(db, ln, rank, detail); };
+  plan.alloc = [&](cc_qlane &ln) -> int {
+    const int rc = rec ? lane_alloc_verify(ln) : CC_OK;  // (the record selector of a packed chunk goes where a verify chunk's does)
+    return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail);
+  };
   plan.stage = [&](const cc_chunk &c) {  // the queries' epoch records
     cc_query_meta *h_meta = c.ln.h_meta;
     chunk_vis = false;
+    if (rec)
+      for (int i = 0; i < c.nb; i++) c.ln.h_vin[i] = h_rec ? h_rec[c.b0 + i] : c.b0 + i;
     for (int i = 0; i < c.nb; i++) {
       const int e = h_epoch[c.b0 + i];
       chunk_vis = chunk_vis || db->idx_slot[e] >= 0;
@@ -1492,6 +1539,11 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
   plan.upload = [&](const cc_chunk &c, cc_prep_src &src) -> int {  // (small chunks: cc_k_pack_hot fills d_qmeta from the pinned buffer)
     cc_qlane &ln = c.ln;
     if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_qmeta, ln.h_meta, sizeof(cc_query_meta) * c.nb, hipMemcpyHostToDevice, ln.stream));
+    if (rec) {  // (small chunks: cc_k_prep_packed reads the selector from the pinned buffer too)
+      if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_vin, ln.h_vin, sizeof(int) * c.nb, hipMemcpyHostToDevice, ln.stream));
+      src = cc_prep_src{nullptr, c.zc, c.zc ? ln.h_vin : ln.d_vin, rec};
+      return CC_OK;
+    }
     src = cc_prep_src{d_qdesc + c.b0, c.zc, nullptr};
     return CC_OK;
   };
@@ -1917,11 +1969,13 @@ int cc_db_check_hints_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qdes
 // The batched form of the hint flow: item i is query descriptor h_qidx[i] against <= CC_VERIFY_CANDS_MAX database scans.  The
 // check table of a chunk is written by cc_k_hints_expand in the place of the KNN search; everything after it is the query
 // path's chain, chunked over the lanes and collected like cc_db_query_submit's chunks.
-static int verify_validate(const cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands,
-                           int n, const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, const cc_query_result_t *h_res) {
+static int verify_validate(const cc_db *db, const void *d_qdesc /*the descriptors, or the hot records of a packed source*/, int n_desc,
+                           const int32_t *h_qidx, const int32_t *h_cands, int n, const cc_verify_cfg_t *cfg, const cc_score_t *lb,
+                           const cc_score_t *ub, const cc_query_result_t *h_res, bool packed = false) {
   if (!db || !d_qdesc || n_desc < 0 || n < 0 || (n > 0 && !h_cands) || !cfg || !lb || !ub || !h_res)
     return set_err(CC_EINVAL, "cc_db_verify: bad argument");
-  if (!h_qidx && n != n_desc) return set_err(CC_EINVAL, "cc_db_verify: without h_qidx item i reads descriptor i, so n must equal n_desc");
+  if (!h_qidx && packed && n > n_desc) return set_err(CC_EINVAL, "cc_db_verify: without h_qidx item i reads record i, so n must not exceed the source");
+  if (!h_qidx && !packed && n != n_desc) return set_err(CC_EINVAL, "cc_db_verify: without h_qidx item i reads descriptor i, so n must equal n_desc");
   if (cfg->max_fine_opt < 1) return set_err(CC_EINVAL, "cc_db_verify: max_fine_opt must be positive");
   if (cfg->level_mask < 0 || cfg->level_mask > 15) return set_err(CC_EINVAL, "cc_db_verify: level_mask must be within 0..15 (bit level-1 of levels 1..4)");
   if (!(cfg->max_key_dist_sq >= 0.f)) return set_err(CC_EINVAL, "cc_db_verify: max_key_dist_sq must be >= 0 (INFINITY: no bound)");
@@ -1947,9 +2001,10 @@ static int verify_validate(const cc_db *db, const cc_scan_desc_t *d_qdesc, int n
 static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                               const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                               cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank,
-    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
+                              const cc_rec_src *rec = nullptr /*the queries are packed records: d_qdesc is nullptr, n_desc their number*/) {
   {  // everything that can be refused is refused before anything is queued or collected
-    const int vrc = verify_validate(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
+    const int vrc = verify_validate(db, rec ? (const void *)rec->hot : (const void *)d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rec != nullptr);
     if (vrc != CC_OK) return vrc;
   }
   DB_POISON_CHK(db, "cc_db_verify_submit");
@@ -1972,7 +2027,7 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
   plan.upload = [&](const cc_chunk &c, cc_prep_src &src) -> int {
     cc_qlane &ln = c.ln;
     HIPCHK(hipMemcpyAsync(ln.d_vin, ln.h_vin, sizeof(int) * (size_t)c.nb * (1 + CC_VERIFY_CANDS_MAX), hipMemcpyHostToDevice, ln.stream));
-    src = cc_prep_src{d_qdesc, false, ln.d_vin};
+    src = cc_prep_src{d_qdesc, false, ln.d_vin, rec};
     return CC_OK;
   };
   plan.head = [&](const cc_chunk &c) -> int {  // the check table from the candidate lists
@@ -2058,7 +2113,7 @@ int cc_db_verify_batch_host_ranked_detail(cc_db *db, const cc_scan_desc_t *h_qde
 // Item i is correlation problem i of its chunk and reads query record i, which launch_query_prep builds from descriptor q_i (the
 // verify flow's selector).  The chain is prep | cc_k_pose_problems | cc_k_gmm_init | cc_k_pose_select | cc_k_gmm_refine x 2 |
 // cc_k_pose_eval | cc_k_pose_final: no retrieval, no checks, no merge, no cc_k_select / cc_k_final.
-static int pose_validate(const cc_db *db, const cc_scan_desc_t *qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+static int pose_validate(const cc_db *db, const void *qdesc /*the descriptors, or the hot records of a packed source*/, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
                          const double *h_try, const cc_pose_result_t *h_res, const double *h_try_corr) {
   if (!db || !qdesc || !h_items || !cfg || !h_res || n < 0) return set_err(CC_EINVAL, "cc_db_pose: bad argument");
   if (cfg->refine != 0 && cfg->refine != 1) return set_err(CC_EINVAL, "cc_db_pose: refine must be 0 or 1");
@@ -2076,10 +2131,11 @@ static int pose_validate(const cc_db *db, const cc_scan_desc_t *qdesc, int n_des
   return CC_OK;
 }
 
-int cc_db_pose_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
-                      const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream_) {
+// rec: the queries are packed records (then d_qdesc is nullptr and n_desc their number), or nullptr
+static int pose_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+                            const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream_, const cc_rec_src *rec) {
   {  // everything that can be refused is refused before anything is queued or collected
-    const int vrc = pose_validate(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr);
+    const int vrc = pose_validate(db, rec ? (const void *)rec->hot : (const void *)d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr);
     if (vrc != CC_OK) return vrc;
   }
   DB_POISON_CHK(db, "cc_db_pose_submit");
@@ -2115,7 +2171,7 @@ int cc_db_pose_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, cons
   plan.upload = [&](const cc_chunk &c, cc_prep_src &src) -> int {
     cc_qlane &ln = c.ln;
     HIPCHK(hipMemcpyAsync(ln.d_pin, ln.h_pin, CC_POSE_IN_BYTES(c.nb, nt), hipMemcpyHostToDevice, ln.stream));
-    src = cc_prep_src{d_qdesc, false, tables_at(ln.d_pin, ln.d_pout, c.nb).sel};
+    src = cc_prep_src{d_qdesc, false, tables_at(ln.d_pin, ln.d_pout, c.nb).sel, rec};
     return CC_OK;
   };
   plan.head = [&](const cc_chunk &c) -> int {  // item i is problem i
@@ -2169,6 +2225,10 @@ int cc_db_pose_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, cons
   };
   return submit_chunks(db, n, (hipStream_t)stream_, plan);
 }
+int cc_db_pose_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+                      const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream_) {
+  return pose_submit_impl(db, d_qdesc, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, stream_, nullptr);
+}
 
 int cc_db_pose_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
                      const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream_) {
@@ -2191,4 +2251,33 @@ int cc_db_pose_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, 
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)n_desc, hipMemcpyHostToDevice));
   return cc_db_pose_batch(db, db->d_stage, n_desc, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, nullptr);
+}
+
+// ---- packed records and stored scans as the query of the three flows (k_prep_packed.h) ----
+// The submits above with a record source in the place of the descriptors: the chunk driver launches cc_k_prep_packed where it
+// launches cc_k_pack_hot + cc_k_gmm_prep for them; every plan.head / plan.body is the descriptor form's.
+int cc_db_query_submit_packed(cc_db *db, const cc_packed_src_t *src, const int32_t *h_rec, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                              const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
+                              const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  cc_rec_src rs;
+  int vrc = packed_resolve(__func__, db, src, &rs);
+  if (vrc == CC_OK) vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  return query_submit_impl(db, nullptr, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, &rs, h_rec);
+}
+int cc_db_verify_submit_packed(cc_db *db, const cc_packed_src_t *src, const int32_t *h_qidx, const int32_t *h_cands, int n, const cc_verify_cfg_t *cfg,
+                               const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res, cc_hint_t *d_hints, int32_t *d_n_hints,
+                               void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail) {
+  cc_rec_src rs;
+  int vrc = packed_resolve(__func__, db, src, &rs);
+  if (vrc == CC_OK) vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  return verify_submit_impl(db, nullptr, rs.n_rec, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank, h_detail, &rs);
+}
+int cc_db_pose_submit_packed(cc_db *db, const cc_packed_src_t *src, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg, const double *h_try,
+                             cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream_) {
+  cc_rec_src rs;
+  const int vrc = packed_resolve(__func__, db, src, &rs);
+  if (vrc != CC_OK) return vrc;
+  return pose_submit_impl(db, nullptr, rs.n_rec, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, stream_, &rs);
 }

@@ -32,6 +32,7 @@
 #include "k_gmm_hess.h"
 #include "k_verify.h"
 #include "k_pose.h"
+#include "k_prep_packed.h"
 #include "cc_hostdb.h"
 
 #ifndef CC_INGEST_BLOCK

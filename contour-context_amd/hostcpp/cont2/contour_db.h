@@ -419,17 +419,57 @@ class ContourDB {
         stp.addSample("L2 opt", (ms[3] + ms[4]) * 1e-3);
       }
     }
-    if (rk) {
-      for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], cand_ptrs, cand_corr, cand_tf);
+    handOut(rk, r, rl, rn, dl, cand_ptrs, cand_corr, cand_tf);
+  }
+  // an answer as the reference's result vectors hold it: the ranked list (with its detail rows), or the one candidate of the plain
+  // call.  Returns the number of entries.
+  int handOut(bool ranked, const cc_query_result_t &r, const cc_ranked_cand_t *rl, int rn, const cc_ranked_detail_t *dl,
+              std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
+              std::vector<Eigen::Isometry2d> &res_T) const {
+    if (ranked) {
+      for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], res_cand, res_corr, res_T);
       if (want_detail_) last_details_.assign(dl, dl + rn);
-    } else if (r.n_res > 0) {
-      cand_ptrs.push_back(all_bevs_[r.cand_gidx]);
-      cand_corr.push_back(r.correlation);
+      return rn;
+    }
+    if (r.n_res > 0) {
+      res_cand.push_back(all_bevs_[r.cand_gidx]);
+      res_corr.push_back(r.correlation);
       Eigen::Isometry2d T;
       T.rotate(r.tf[2]);
       T.pretranslate(r.tf[0], r.tf[1]);
-      cand_tf.push_back(T);
+      res_T.push_back(T);
     }
+    return r.n_res;
+  }
+  // Mirror-only: queryRangedKNN for a scan this database holds, by its index in adding order, against the database as it was
+  // after `epoch` scans (epoch == idx: what queryRangedKNN answered when the driver queried that scan; a later epoch may return
+  // the scan itself) -- from the records the database keeps (cc_db_query_submit_packed): no descriptor is needed, the scan's
+  // ContourManager may have been offloaded.  Honours setMaxReturn / setWantDetail as queryRangedKNN does.
+  void queryStored(int idx, int epoch, const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
+                   std::vector<std::shared_ptr<const ContourManager>> &cand_ptrs, std::vector<double> &cand_corr,
+                   std::vector<Eigen::Isometry2d> &cand_tf) const {
+    cand_ptrs.clear();
+    cand_corr.clear();
+    cand_tf.clear();
+    CC_CHECK(db_ && idx >= 0 && idx < (int)all_bevs_.size());  // (scans appended ahead of the driver are not the caller's yet)
+    CC_CHECK(epoch >= 0 && epoch <= (int)all_bevs_.size());
+    if (need_rebuild_) rebuild();
+    const cc_score_t lb = to_c(thres_lb), ub = to_c(thres_ub);
+    cc_query_result_t r;
+    cc_ranked_cand_t rl[CC_RANK_MAX];
+    cc_ranked_detail_t dl[CC_RANK_MAX];
+    int32_t rn = 0;
+    const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
+    const bool rk = rankedPath();
+    last_details_.clear();
+    const cc_packed_src_t own = {nullptr, nullptr, 0, 0};
+    const int32_t rec = idx, ep = epoch;
+    int rc = cc_db_query_submit_packed(db_, &own, &rec, 1, &ep, &lb, &ub, &r, nullptr, nullptr, nullptr, rk ? &ro : nullptr, want_detail_ ? dl : nullptr);
+    const int r2 = cc_db_query_wait(db_);
+    for (auto &sp : spec_) sp.collected = true;  // the wait collected every chain in flight
+    if (rc == CC_OK) rc = r2;
+    if (rc != CC_OK) die_cc();
+    handOut(rk, r, rl, rn, dl, cand_ptrs, cand_corr, cand_tf);
   }
   // one entry of a ranked list as the reference's result vectors hold it
   template <class Scans>
@@ -454,12 +494,26 @@ class ContourDB {
                        std::vector<Eigen::Isometry2d> &res_T) const {
     return verifyCandidates(q_ptr, cand_indices, thres_lb, thres_ub, res_cand, res_corr, res_T, 1);
   }
+  // verifyCandidates for a scan this database holds, by its index in adding order, from the records the database keeps
+  // (cc_db_verify_submit_packed); idx may be among its own candidates.
+  int verifyStored(int idx, const std::vector<int> &cand_indices, const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
+                   std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
+                   std::vector<Eigen::Isometry2d> &res_T, int max_ret = 1) const {
+    CC_CHECK(db_ && idx >= 0 && idx < (int)all_bevs_.size());
+    return verifyFrom(nullptr, idx, cand_indices, thres_lb, thres_ub, res_cand, res_corr, res_T, max_ret);
+  }
   // ... and the ranked list of them: up to max_ret (1..CC_RANK_MAX) of the candidates that survive, best first -- one verdict
   // per proposed candidate from one device pass.  Returns the number of entries.
   int verifyCandidates(const std::shared_ptr<const ContourManager> &q_ptr, const std::vector<int> &cand_indices,
                        const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
                        std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
                        std::vector<Eigen::Isometry2d> &res_T, int max_ret) const {
+    return verifyFrom(q_ptr.get(), 0, cand_indices, thres_lb, thres_ub, res_cand, res_corr, res_T, max_ret);
+  }
+  // q: the query scan by its host descriptor, or nullptr: the stored scan `idx`
+  int verifyFrom(const ContourManager *q, int idx, const std::vector<int> &cand_indices, const CandidateScoreEnsemble &thres_lb,
+                 const CandidateScoreEnsemble &thres_ub, std::vector<std::shared_ptr<const ContourManager>> &res_cand,
+                 std::vector<double> &res_corr, std::vector<Eigen::Isometry2d> &res_T, int max_ret) const {
     CC_CHECK(max_ret >= 1 && max_ret <= CC_RANK_MAX);
     res_cand.clear();
     res_corr.clear();
@@ -467,7 +521,7 @@ class ContourDB {
     CC_CHECK((int)cand_indices.size() <= CC_VERIFY_CANDS_MAX);
     for (const int c : cand_indices) CC_CHECK(c >= 0 && c < (int)all_bevs_.size());  // (scans appended ahead of the driver are not the caller's yet)
     if (cand_indices.empty()) return 0;
-    ensure(*q_ptr);
+    if (q) ensure(*q);
     if (need_rebuild_) rebuild();
     const cc_score_t lb = to_c(thres_lb), ub = to_c(thres_ub);
     int32_t cands[CC_VERIFY_CANDS_MAX];
@@ -483,25 +537,22 @@ class ContourDB {
     cc_ranked_detail_t dl[CC_RANK_MAX];
     const cc_rank_out_t ro = {rl, &rn, max_ret, 0};
     last_details_.clear();
-    const int rc = want_detail_ ? cc_db_verify_batch_host_ranked_detail(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro, dl)
-                   : max_ret > 1 ? cc_db_verify_batch_host_ranked(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro)
-                                 : cc_db_verify_batch_host(db_, &q_ptr->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
-    for (auto &sp : spec_) sp.collected = true;  // the synchronous call collected every chain in flight
+    const bool rk = max_ret > 1 || want_detail_;
+    int rc;
+    if (q) {
+      rc = want_detail_ ? cc_db_verify_batch_host_ranked_detail(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro, dl)
+           : max_ret > 1 ? cc_db_verify_batch_host_ranked(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro)
+                         : cc_db_verify_batch_host(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
+    } else {
+      const cc_packed_src_t own = {nullptr, nullptr, 0, 0};
+      const int32_t rec = idx;
+      rc = cc_db_verify_submit_packed(db_, &own, &rec, cands, 1, &vc, &lb, &ub, &r, nullptr, nullptr, nullptr, rk ? &ro : nullptr, want_detail_ ? dl : nullptr);
+      const int r2 = cc_db_query_wait(db_);
+      if (rc == CC_OK) rc = r2;
+    }
+    for (auto &sp : spec_) sp.collected = true;  // the synchronous call (the wait) collected every chain in flight
     if (rc != CC_OK) die_cc();
-    if (max_ret > 1 || want_detail_) {
-      for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], res_cand, res_corr, res_T);
-      if (want_detail_) last_details_.assign(dl, dl + rn);
-      return rn;
-    }
-    if (r.n_res > 0) {
-      res_cand.push_back(all_bevs_[r.cand_gidx]);
-      res_corr.push_back(r.correlation);
-      Eigen::Isometry2d T;
-      T.rotate(r.tf[2]);
-      T.pretranslate(r.tf[0], r.tf[1]);
-      res_T.push_back(T);
-    }
-    return r.n_res;
+    return handOut(rk, r, rl, rn, dl, res_cand, res_corr, res_T);
   }
   // Mirror-only as a database call: ConstellCorrelation's public interface (correlation.h:175-238) on scans of this database,
   // in one device pass (cc_db_pose_batch_host).  Per query: the candidate by its index in adding order (as verifyCandidates
@@ -524,6 +575,16 @@ class ContourDB {
   };
   std::vector<PoseScore> scorePoses(const std::shared_ptr<const ContourManager> &cm_tgt, const std::vector<PoseQuery> &queries,
                                     bool refine = true, float min_corr = 0.3f) const {
+    return scorePosesFrom(cm_tgt.get(), 0, queries, refine, min_corr);
+  }
+  // scorePoses for a scan this database holds (tgt), by its index in adding order, from the records the database keeps
+  // (cc_db_pose_submit_packed); a query's candidate may be that scan itself.
+  std::vector<PoseScore> scorePosesStored(int idx, const std::vector<PoseQuery> &queries, bool refine = true, float min_corr = 0.3f) const {
+    CC_CHECK(db_ && idx >= 0 && idx < (int)all_bevs_.size());
+    return scorePosesFrom(nullptr, idx, queries, refine, min_corr);
+  }
+  // tgt: the query scan by its host descriptor, or nullptr: the stored scan `idx`
+  std::vector<PoseScore> scorePosesFrom(const ContourManager *tgt, int idx, const std::vector<PoseQuery> &queries, bool refine, float min_corr) const {
     std::vector<PoseScore> out(queries.size());
     if (queries.empty()) return out;
     size_t nt = 0;
@@ -532,7 +593,7 @@ class ContourDB {
       CC_CHECK(pq.T_try.size() <= (size_t)CC_POSE_TRY_MAX);
       nt = std::max(nt, pq.T_try.size());
     }
-    ensure(*cm_tgt);
+    if (tgt) ensure(*tgt);
     if (need_rebuild_) rebuild();
     const auto tf_of = [](const Eigen::Isometry2d &T, double *o) {
       o[0] = T(0, 2);
@@ -543,7 +604,7 @@ class ContourDB {
     std::vector<cc_pose_item_t> items(n);
     std::vector<double> tries((size_t)n * nt * 3), tc((size_t)n * nt);
     for (int i = 0; i < n; i++) {
-      items[i].q = 0;
+      items[i].q = tgt ? 0 : idx;
       items[i].gidx = queries[i].cand;
       tf_of(queries[i].T_init, items[i].tf);
       for (size_t t = 0; t < nt; t++) tf_of(t < queries[i].T_try.size() ? queries[i].T_try[t] : queries[i].T_init, &tries[((size_t)i * nt + t) * 3]);
@@ -555,9 +616,16 @@ class ContourDB {
     pc.pad_ = 0;
     std::vector<cc_pose_result_t> res(n);
     std::vector<cc_pose_curv_t> cv(n);
-    const int rc = cc_db_pose_batch_host(db_, &cm_tgt->desc(), 1, items.data(), n, &pc, nt ? tries.data() : nullptr, res.data(),
-                                         nt ? tc.data() : nullptr, cv.data());
-    for (auto &sp : spec_) sp.collected = true;  // the synchronous call collected every chain in flight
+    int rc;
+    if (tgt) {
+      rc = cc_db_pose_batch_host(db_, &tgt->desc(), 1, items.data(), n, &pc, nt ? tries.data() : nullptr, res.data(), nt ? tc.data() : nullptr, cv.data());
+    } else {
+      const cc_packed_src_t own = {nullptr, nullptr, 0, 0};
+      rc = cc_db_pose_submit_packed(db_, &own, items.data(), n, &pc, nt ? tries.data() : nullptr, res.data(), nt ? tc.data() : nullptr, cv.data(), nullptr);
+      const int r2 = cc_db_query_wait(db_);
+      if (rc == CC_OK) rc = r2;
+    }
+    for (auto &sp : spec_) sp.collected = true;  // the synchronous call (the wait) collected every chain in flight
     if (rc != CC_OK) die_cc();
     for (int i = 0; i < n; i++) {
       PoseScore &o = out[i];

@@ -117,6 +117,13 @@ def pose_items(q, gidx, tf):
     return it
 
 
+class PackedSrc(C.Structure):  # cc_packed_src_t (the *_submit_packed entry points): both pointers None = the database's own records
+    _fields_ = [("d_hot", C.c_void_p), ("d_feat", C.c_void_p), ("n_rec", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(PackedSrc) == 24
+
+
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
 

@@ -902,6 +902,44 @@ int cc_db_pose_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, 
                           const cc_pose_cfg_t *cfg, const double *h_try, cc_pose_result_t *h_res, double *h_try_corr,
                           cc_pose_curv_t *h_curv);
 
+/* ---- packed records and stored scans as the query of the three flows ----
+ * The scoring chain reads a query scan only through the two compact records cc_pack_scans makes of its descriptor (below: "the
+ * compact per-scan records") -- the records the database keeps per scan and the ranks exchange.  The _packed forms take the
+ * query from such records instead of from 169 KB descriptors: rows of a caller's arrays (a second session's map, records
+ * gathered from another rank) or the database's own rows (a re-check among scans of the map, the replay of a finished drive).
+ * The chunk's prep stage is then one copy kernel (csrc/k_prep_packed.h) in the place of the two that build the records.
+ *
+ * Source: d_hot / d_feat are device arrays of n_rec records each (cc_packed_sizes), both bases 16-byte aligned; both NULL
+ * names the database's own records, and n_rec is then cc_db_size at the call (a scan that is only prepared is not part of it).
+ *
+ * Each form carries the most general argument list of its flow: rank NULL is the plain call, rank with h_detail NULL the
+ * _ranked call, both given the _ranked_detail call.  h_rec / h_qidx name the record of query / item i (NULL: record i);
+ * cc_pose_item_t.q names a record.  The answers are, byte for byte, those of the descriptor form on the descriptors the records
+ * were packed from: results, ranked lists, detail rows, generated hint lists, d_knn / d_knn_cnt, CC_QF_* flags and CC_ECAPACITY;
+ * chunking, lanes, epochs, dynamic thresholds, large-k databases and collection (cc_db_query_wait / cc_db_query_collect) are
+ * the descriptor form's.  Nothing is excluded on the caller's behalf: stored scan g queried at epoch g is the online loop's
+ * query of scan g, at a later epoch the answer may be g itself; an item may name one stored scan as query and as candidate.
+ * The caller's stream continues once the records are read.
+ *
+ * Refused with CC_EINVAL before anything is queued or collected: src NULL, exactly one of d_hot / d_feat NULL, n_rec < 1 with
+ * caller arrays, a base that is not 16-byte aligned, a record index outside [0, n_rec), h_detail without rank, and whatever the
+ * descriptor form of the call refuses. */
+typedef struct {
+  const void *d_hot;  /* [n_rec] hot records, device; NULL together with d_feat: the database's own records    */
+  const void *d_feat; /* [n_rec] correlation inputs, device                                                    */
+  int32_t n_rec;      /* records in the arrays; ignored for the database's own (then cc_db_size at the call)   */
+  int32_t pad_;
+} cc_packed_src_t;
+int cc_db_query_submit_packed(cc_db *db, const cc_packed_src_t *src, const int32_t *h_rec, int nq, const int32_t *h_epoch,
+                              const cc_score_t *thres_lb, const cc_score_t *thres_ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn,
+                              int32_t *d_knn_cnt, void *stream, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+int cc_db_verify_submit_packed(cc_db *db, const cc_packed_src_t *src, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                               const cc_verify_cfg_t *cfg, const cc_score_t *thres_lb, const cc_score_t *thres_ub,
+                               cc_query_result_t *h_res, cc_hint_t *d_hints, int32_t *d_n_hints, void *stream,
+                               const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail);
+int cc_db_pose_submit_packed(cc_db *db, const cc_packed_src_t *src, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
+                             const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream);
+
 /* Parity / debug: the constellations of the LAST cc_db_check_hints[_host] call that passed all four gates, in hint
  * order: the pose getTFFromConstell returned for each (contour_mng.h:1246-1277, before any proposal merging) and the
  * constellation it was computed from, so that a test can redo the rigid fit independently (e.g. with an SVD). */
