@@ -23,7 +23,7 @@ import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
 _SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_contours.h", "k_contours_list.h",
-         "k_knn.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
+         "k_knn.h", "k_mask.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 # how every gfx950 code object of this project that includes csrc/ headers is compiled: the library below and the device
 # probe library of the test suite (tests/dev_probe.py), so that what the probes measure is the code the library runs
@@ -62,6 +62,7 @@ EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_
            "cc_db_verify_submit_ranked_detail", "cc_db_verify_batch_host_ranked_detail", "cc_db_check_hints_ranked_detail",
            "cc_db_check_hints_host_ranked_detail", "cc_est_sens_info", "cc_db_pose_submit", "cc_db_pose_batch", "cc_db_pose_batch_host",
            "cc_db_query_submit_packed", "cc_db_verify_submit_packed", "cc_db_pose_submit_packed",
+           "cc_db_query_submit_masked", "cc_db_query_batch_host_masked", "cc_mask_gates", "cc_db_debug_knn_chunks",
            "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
            "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
            "cc_comm_unique_id", "cc_comm_create", "cc_comm_create_from_env", "cc_comm_rank", "cc_comm_world", "cc_comm_allgather_packed", "cc_comm_destroy"]
@@ -144,6 +145,10 @@ def lib():
         _lib.cc_db_query_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
         _lib.cc_db_verify_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
         _lib.cc_db_pose_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        _lib.cc_db_query_submit_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10
+        _lib.cc_db_query_batch_host_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        _lib.cc_db_debug_knn_chunks.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.cc_mask_gates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
         _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
     return _lib
@@ -520,6 +525,21 @@ class Context:
         _chk(lib().cc_pack_scans(self.h, desc.data_ptr(), n, hot.data_ptr(), feat.data_ptr(), stream), "cc_pack_scans")
         return hot, feat
 
+    def gate_mask(self, xy, gates, row_words=None):
+        """Rows of a position prior, made on the device (cc_mask_gates): xy float32 CUDA [n_scans, 2], the scans' positions;
+        gates float32 CUDA [n_rows, 3] of (x, y, radius).  Returns the int32 CUDA table [n_rows, row_words] (row_words defaults
+        to ceil(n_scans / 32)) in which bit g of row r is set iff scan g lies within gate r's circle, the f32 sum
+        dx * dx + dy * dy <= radius * radius as written; hand it to ScanMask(bits, rows)."""
+        import torch
+        assert xy.is_cuda and gates.is_cuda and xy.dtype == torch.float32 and gates.dtype == torch.float32
+        xy, gates = xy.contiguous().reshape(-1, 2), gates.contiguous().reshape(-1, 3)
+        n, nr = int(xy.shape[0]), int(gates.shape[0])
+        rw = max((n + 31) // 32, 1) if row_words is None else int(row_words)
+        bits = torch.empty((nr, max(rw, 1)), dtype=torch.int32, device=xy.device)
+        stream = torch.cuda.current_stream(xy.device).cuda_stream
+        _chk(lib().cc_mask_gates(self.h, xy.data_ptr(), n, gates.data_ptr(), nr, bits.data_ptr(), rw, stream), "cc_mask_gates")
+        return bits
+
     def ingest_host(self, xyzi, offsets, layout=None, tf=None, motion=None, t_begin=None, scale=None, knots=None):
         """Host records in, host descriptors out.  layout / tf / motion, t_begin, scale, knots: as for ingest(); with a layout
         `xyzi` is a contiguous numpy array of any dtype holding the records as they are."""
@@ -584,6 +604,34 @@ def _is_src(q):
     return isinstance(q, (Packed, Stored))
 
 
+class ScanMask:
+    """The scans that may answer a query (the mask= of Database.query / query_submit): bits is an int32 or uint32 CUDA tensor
+    [n_rows, row_words] -- bit g & 31 of word g >> 5 of a row set = scan g may answer -- and rows names one row per query
+    (-1: no restriction; many queries may share a row).  A masked query behaves as if the other scans' keys were not in the
+    database's trees.  The table must stay unchanged until the call it is handed to has been waited for."""
+
+    def __init__(self, bits, rows):
+        import torch
+        assert bits.is_cuda and bits.dim() == 2 and bits.is_contiguous() and bits.dtype in (torch.int32, torch.uint32)
+        self.bits = bits
+        self.rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        self.device = bits.device
+
+    @classmethod
+    def from_allowed(cls, allowed, rows=None, device="cuda", n_db=None):
+        """allowed: a bool array [n_rows, n_db] or a list of index arrays (n_db: the number of scans the rows cover, by default
+        the largest index + 1), packed on the host and uploaded.  rows: the row of every query (default: query i names row i)."""
+        import torch
+        tab = L.pack_mask_rows(allowed, n_db=n_db)
+        bits = torch.from_numpy(tab.view(np.int32)).to(device)
+        return cls(bits, np.arange(len(tab), dtype=np.int32) if rows is None else rows)
+
+    def _c(self, nq):
+        if len(self.rows) != nq:
+            raise ValueError("the mask names rows for %d queries, the call has %d" % (len(self.rows), nq))
+        return L.ScanMaskC(self.bits.data_ptr(), int(self.bits.shape[0]), int(self.bits.shape[1]), self.rows.ctypes.data)
+
+
 class Database:
     """cc_db: device-resident ContourDB (contour_db.h:673-845) + batched queryRangedKNN."""
 
@@ -644,6 +692,48 @@ class Database:
         dev = q.device if q.device is not None else torch.device("cuda", self.ctx.device)
         return q._src(), q.idx, torch.cuda.current_stream(dev).cuda_stream
 
+    def _masked_query(self, q, mask, epochs, lb, ub, want_knn, ranked, det, tol, wait):
+        """query() / query_submit() with mask=: cc_db_query_submit_masked (+ the wait), from descriptors or a record source"""
+        import torch
+        if not isinstance(mask, ScanMask):
+            raise TypeError("mask must be a ScanMask")
+        if lb is None:
+            lb, ub = L.default_thresholds()
+        epochs = np.ascontiguousarray(epochs, np.int32)
+        nq = len(epochs)
+        src = idx = None
+        if _is_src(q):
+            src, idx, stream = self._src_args(q)
+            if idx is not None and len(idx) != nq:
+                raise ValueError("the source names %d records for %d epochs" % (len(idx), nq))
+            dev = self._q_device(q)
+        else:
+            assert q.is_cuda and q.is_contiguous() and q.shape[0] == nq
+            dev = q.device
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        cm = mask._c(nq)
+        res = np.zeros(nq, L.query_result_dt)
+        knn = cnt = None
+        if want_knn:
+            knn = torch.zeros((nq, L.NQLEV, L.NPIV, self.knn_stride, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=dev)
+            cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=dev)
+        rk = ro = None
+        if ranked is not None:
+            rc_, rn_, ro = L.rank_buffers(nq, ranked)
+            rk = (rc_, rn_)
+        args = (self.h, q.data_ptr() if src is None else None, C.addressof(src) if src is not None else None,
+                idx.ctypes.data if idx is not None else None, nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
+                res.ctypes.data, knn.data_ptr() if want_knn else None, cnt.data_ptr() if want_knn else None, stream,
+                C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None, C.addressof(cm))
+        keep = (q, src, idx, epochs, lb, ub, ro, mask, cm)  # the lanes read the mask's table until the wait
+        if wait:
+            self._ranked_call(lib().cc_db_query_submit_masked, "cc_db_query_submit_masked", tol, *args)
+        else:
+            self._pending = getattr(self, "_pending", [])
+            self._pending.append((keep, res, rk, det))
+            _chk(lib().cc_db_query_submit_masked(*args), "cc_db_query_submit_masked")
+        return res, knn, cnt, rk
+
     def _packed_query(self, q, epochs, lb, ub, want_knn, ranked, det, tol, wait):
         """query() / query_submit() from a record source: cc_db_query_submit_packed (+ the wait)"""
         import torch
@@ -703,7 +793,7 @@ class Database:
             raise e
         _chk(lib().cc_db_query_wait(self.h), "cc_db_query_wait", tolerate=tol)
 
-    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False):
+    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False, mask=None):
         """qdesc: torch uint8 CUDA [nq, DESC_BYTES]; epochs int32 [nq] (DB state each query sees).
         In the place of qdesc: self.stored(idx) -- scans of this database by index -- or Packed(hot, feat, idx): the query comes
         from the packed records instead of from descriptors (cc_db_query_submit_packed + the wait), with the same answers.
@@ -716,12 +806,18 @@ class Database:
         after lane, where the plain synchronous call cuts one chunk per lane -- the same answers, scheduled differently.
         detail=True (with ranked=K): followed by a [nq, K] array of L.ranked_detail_dt as well -- per entry the curvature of
         -correlation at its pose (hess, grad) and the refinement's start, initial correlation, iterations, termination and pair
-        count (cc_db_query_submit_ranked_detail).  Without ranked it is a ValueError."""
+        count (cc_db_query_submit_ranked_detail).  Without ranked it is a ValueError.
+        mask=ScanMask(...): only the scans of each query's row may answer (cc_db_query_submit_masked + the wait): the retrieval
+        runs as if the other scans' keys were not in the trees.  It combines with every form above."""
         import torch
-        if _is_src(qdesc):  # a record source in the place of the descriptors: the submit followed by the wait, like ranked=K
+        if _is_src(qdesc) or mask is not None:  # the submit followed by the wait, like ranked=K
             nq, ks = len(np.asarray(epochs).reshape(-1)), self.knn_stride
             det = self._detail_args(nq, ranked, detail)
-            res, knn, cnt, rk = self._packed_query(qdesc, epochs, lb, ub, want_knn, ranked, det, (CC_ECAPACITY,) if allow_flagged else (), True)
+            tol = (CC_ECAPACITY,) if allow_flagged else ()
+            if mask is not None:
+                res, knn, cnt, rk = self._masked_query(qdesc, mask, epochs, lb, ub, want_knn, ranked, det, tol, True)
+            else:
+                res, knn, cnt, rk = self._packed_query(qdesc, epochs, lb, ub, want_knn, ranked, det, tol, True)
             out = (res,)
             if want_knn:
                 out += (knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy())
@@ -765,15 +861,19 @@ class Database:
             out += (det,)
         return out if len(out) > 1 else res
 
-    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False):
+    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False, mask=None):
         """Asynchronous form of query(): queues the batch and returns the result array, which is only valid after
         query_wait() (cc_db_query_submit / cc_db_query_wait).  qdesc may be overwritten by work queued afterwards on the
         current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait();
-        with detail=True followed by the [nq, K] detail array (see query()).  qdesc may be self.stored(idx) or a Packed."""
+        with detail=True followed by the [nq, K] detail array (see query()).  qdesc may be self.stored(idx) or a Packed.
+        mask=ScanMask(...): as for query(); the pending list keeps the mask's table alive until query_wait()."""
         import torch
-        if _is_src(qdesc):
+        if _is_src(qdesc) or mask is not None:
             det = self._detail_args(len(np.asarray(epochs).reshape(-1)), ranked, detail)
-            res, _k, _c, rk = self._packed_query(qdesc, epochs, lb, ub, False, ranked, det, (), False)
+            if mask is not None:
+                res, _k, _c, rk = self._masked_query(qdesc, mask, epochs, lb, ub, False, ranked, det, (), False)
+            else:
+                res, _k, _c, rk = self._packed_query(qdesc, epochs, lb, ub, False, ranked, det, (), False)
             return res if rk is None else ((res, rk) if det is None else (res, rk, det))
         det = self._detail_args(qdesc.shape[0], ranked, detail)
         if lb is None:

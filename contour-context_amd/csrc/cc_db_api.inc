@@ -143,6 +143,9 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   // verify chunks (cc_db_verify_submit), allocated with the first one: per item the descriptor it reads and its candidates
   int *d_vin = nullptr;               // [QB] descriptor index | [QB][CC_VERIFY_CANDS_MAX] candidate lists
   int *h_vin = nullptr;               // the same, pinned: filled by the submit, one copy per chunk
+  // masked chunks (cc_db_query_submit_masked), allocated with the first one: the row of the mask each query names, or -1
+  int *d_mrow = nullptr;              // [QB]
+  int *h_mrow = nullptr;              // the same, pinned
   // ranked chunks (the *_ranked entry points), allocated with the first one: cc_k_final_r's lists, [nb][max_ret]
   cc_ranked_cand_t *d_rank = nullptr; // [QB * CC_RANK_MAX]
   cc_ranked_cand_t *h_rank = nullptr; // the same, pinned: copied out beside h_results (small chunks: written by the kernel)
@@ -254,6 +257,9 @@ struct cc_db {
   bool add_pending = false;
   cc_scan_desc_t *d_stage = nullptr;  // staging for the host-descriptor entry points
   int stage_cap = 0;
+  uint32_t *d_mask_stage = nullptr;   // staging for the table of cc_db_query_batch_host_masked, in words
+  size_t mask_stage_cap = 0;
+  long long knn_chunks[3] = {0, 0, 0};  // query chunks by retrieval so far: walk | tiled | masked walk (cc_db_debug_knn_chunks)
   cc_scan_desc_t *d_hstage[2] = {nullptr, nullptr};  // [CC_SCAN_BATCH_MAX] each: the descriptors of a batch of scan handles, gathered (append | query)
   int *d_hint_scores = nullptr;     // [CC_CHK_STRIDE][CC_NSCORE] per-check gate scores (cc_db_check_hints)
   bool prof = false;
@@ -322,6 +328,8 @@ static void db_free(cc_db *db) {
     hipHostFree(ln.h_nprob);
     hipFree(ln.d_vin);
     if (ln.h_vin) hipHostFree(ln.h_vin);
+    hipFree(ln.d_mrow);
+    if (ln.h_mrow) hipHostFree(ln.h_mrow);
     hipFree(ln.d_rank);
     if (ln.h_rank) hipHostFree(ln.h_rank);
     hipFree(ln.d_pin);
@@ -348,6 +356,7 @@ static void db_free(cc_db *db) {
     if (pp.h_lite) hipHostFree(pp.h_lite);
   }
   hipFree(db->d_stage);
+  hipFree(db->d_mask_stage);
   hipFree(db->d_hstage[0]);
   hipFree(db->d_hstage[1]);
   hipFree(db->d_hint_scores);
@@ -391,6 +400,13 @@ static int lane_alloc_verify(cc_qlane &ln) {
   const size_t bytes = sizeof(int) * (size_t)cc_db::QB * (1 + CC_VERIFY_CANDS_MAX);
   LANE_BUF(ln.h_vin, bytes, true);
   LANE_BUF(ln.d_vin, bytes, false);
+  return CC_OK;
+}
+// the row table of a lane's masked chunks (4 KB), allocated with the lane's first one
+static int lane_alloc_mask(cc_qlane &ln) {
+  const size_t bytes = sizeof(int) * (size_t)cc_db::QB;
+  LANE_BUF(ln.h_mrow, bytes, true);
+  LANE_BUF(ln.d_mrow, bytes, false);
   return CC_OK;
 }
 // the tables of a lane's pose chunks (2 x 228 KB in, 2 x 200 KB out), allocated with the lane's first one
@@ -1476,15 +1492,37 @@ static void results_note(cc_qlane &ln, cc_query_result_t *h_res, const cc_rank_o
   ln.rank_mfo = max_fine_opt;
 }
 
+// The refusals of a masked query (cc_db_query_submit_masked / cc_db_query_batch_host_masked), before anything is queued.
+static int mask_validate(const cc_db *db, const cc_scan_mask_t *mask, int nq, const int32_t *h_epoch) {
+  if (!mask->bits || (!mask->h_row && nq > 0)) return set_err(CC_EINVAL, "cc_db_query_submit_masked: the mask's bits and h_row must be given");
+  if (mask->n_rows < 1 || mask->row_words < 1) return set_err(CC_EINVAL, "cc_db_query_submit_masked: the mask needs n_rows >= 1 and row_words >= 1");
+  if (db->dyn_thres)
+    return set_err(CC_EINVAL, "cc_db_query_submit_masked: masked queries are not supported in dynamic-threshold mode (cc_db_set_dynamic_thres)");
+  int max_epoch = 0;
+  for (int i = 0; i < nq; i++) {
+    const int r = mask->h_row[i];
+    if (r < -1 || r >= mask->n_rows) return set_err(CC_EINVAL, "cc_db_query_submit_masked: h_row names a row outside [-1, n_rows)");
+    if (r >= 0 && h_epoch[i] > max_epoch) max_epoch = h_epoch[i];
+  }
+  if ((long long)32 * mask->row_words < (long long)max_epoch)
+    return set_err(CC_EINVAL, "cc_db_query_submit_masked: 32 * row_words is smaller than the largest epoch of a query that names a row");
+  return CC_OK;
+}
+
 // rank: where the chunks' ranked lists go (the *_ranked entry points, validated there), or nullptr: the plain call
 static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                              const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
                              const cc_rank_out_t *rank,
     cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
                              const cc_rec_src *rec = nullptr /*the queries are packed records (then d_qdesc is nullptr) ...*/,
-                             const int32_t *h_rec = nullptr /*... query i is record h_rec[i] of them, or nullptr: record i*/) {
+                             const int32_t *h_rec = nullptr /*... query i is record h_rec[i] of them, or nullptr: record i*/,
+                             const cc_scan_mask_t *mask = nullptr /*the scans that may answer (bits: device), or nullptr: all of them*/) {
   if (!db || (!d_qdesc && !rec) || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch");
+  if (mask) {
+    const int vrc = mask_validate(db, mask, nq, h_epoch);
+    if (vrc != CC_OK) return vrc;
+  }
   if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch: thresholds must satisfy lb.strictSmaller(ub)");
   HIPCHK(hipSetDevice(db->device));
   const int NS = CC_NQLEV * CC_NPIV;
@@ -1511,14 +1549,23 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
       if (r < 0 || r >= rec->n_rec) return set_err(CC_EINVAL, "cc_db_query_submit_packed: record index outside the source");
     }
   bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
+  bool chunk_masked = false;  // some query of the chunk names a row of the mask
   cc_chunk_plan plan;
   plan.alloc = [&](cc_qlane &ln) -> int {
-    const int rc = rec ? lane_alloc_verify(ln) : CC_OK;  // (the record selector of a packed chunk goes where a verify chunk's does)
+    int rc = rec ? lane_alloc_verify(ln) : CC_OK;  // (the record selector of a packed chunk goes where a verify chunk's does)
+    if (rc == CC_OK && mask) rc = lane_alloc_mask(ln);
     return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail);
   };
   plan.stage = [&](const cc_chunk &c) {  // the queries' epoch records
     cc_query_meta *h_meta = c.ln.h_meta;
     chunk_vis = false;
+    chunk_masked = false;
+    if (mask)
+      for (int i = 0; i < c.nb; i++) {
+        const int r = mask->h_row[c.b0 + i];
+        c.ln.h_mrow[i] = r;
+        chunk_masked = chunk_masked || r >= 0;
+      }
     if (rec)
       for (int i = 0; i < c.nb; i++) c.ln.h_vin[i] = h_rec ? h_rec[c.b0 + i] : c.b0 + i;
     for (int i = 0; i < c.nb; i++) {
@@ -1539,6 +1586,8 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
   plan.upload = [&](const cc_chunk &c, cc_prep_src &src) -> int {  // (small chunks: cc_k_pack_hot fills d_qmeta from the pinned buffer)
     cc_qlane &ln = c.ln;
     if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_qmeta, ln.h_meta, sizeof(cc_query_meta) * c.nb, hipMemcpyHostToDevice, ln.stream));
+    // (small chunks: the masked walk reads its rows from the pinned buffer, as cc_k_prep_packed reads the selector below)
+    if (chunk_masked && !c.zc) HIPCHK(hipMemcpyAsync(ln.d_mrow, ln.h_mrow, sizeof(int) * c.nb, hipMemcpyHostToDevice, ln.stream));
     if (rec) {  // (small chunks: cc_k_prep_packed reads the selector from the pinned buffer too)
       if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_vin, ln.h_vin, sizeof(int) * c.nb, hipMemcpyHostToDevice, ln.stream));
       src = cc_prep_src{nullptr, c.zc, c.zc ? ln.h_vin : ln.d_vin, rec};
@@ -1556,7 +1605,16 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
     for (int l = 0; l < nql; l++) max_keys = db->n_keys[l] > max_keys ? db->n_keys[l] : max_keys;
     // (a large-k database always walks: the tiled search has no large-k instance)
     const bool tiled = db->kmax == CC_KNN_MAX && (db->tune.knn_mode == 2 || (db->tune.knn_mode == 1 && max_keys >= CC_KNN_TILE_MIN_KEYS));
-    if (tiled) {
+    db->knn_chunks[chunk_masked ? 2 : tiled ? 1 : 0]++;
+    if (chunk_masked) {  // a masked chunk always walks: the tiled search has no masked instance
+      const int *qrow = c.zc ? ln.h_mrow : ln.d_mrow;
+      if (db->kmax != CC_KNN_MAX)
+        hipLaunchKernelGGL(chunk_vis ? cc_k_knn_lm<true> : cc_k_knn_lm<false>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot,
+                           qmeta_dev, ln.d_hits, ln.d_hit_cnt, (const unsigned *)mask->bits, (int)mask->row_words, qrow);
+      else
+        hipLaunchKernelGGL(chunk_vis ? cc_k_knn_m<true> : cc_k_knn_m<false>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot,
+                           qmeta_dev, ln.d_hits, ln.d_hit_cnt, (const unsigned *)mask->bits, (int)mask->row_words, qrow);
+    } else if (tiled) {
       int *ord = ln.d_knn_order;
       for (int s0 = 0; s0 < nb; s0 += cc_db::KQB) {  // the search order of a sub-chunk is built in LDS (cc_k_knn_order)
         const int ns = nb - s0 < cc_db::KQB ? nb - s0 : cc_db::KQB;
@@ -2280,4 +2338,79 @@ int cc_db_pose_submit_packed(cc_db *db, const cc_packed_src_t *src, const cc_pos
   const int vrc = packed_resolve(__func__, db, src, &rs);
   if (vrc != CC_OK) return vrc;
   return pose_submit_impl(db, nullptr, rs.n_rec, h_items, n, cfg, h_try, h_res, h_try_corr, h_curv, stream_, &rs);
+}
+
+// ---- masked queries: the retrieval restricted to a caller-given set of scans (k_knn.h: the walk's MASK instances) ----
+// The one masked form of cc_db_query_submit[_packed][_ranked[_detail]]: descriptors or a record source, rank / h_detail as in
+// the packed form.  mask NULL is the unmasked call of the same arguments.
+int cc_db_query_submit_masked(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_packed_src_t *src, const int32_t *h_rec, int nq,
+                              const int32_t *h_epoch, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn,
+                              int32_t *d_knn_cnt, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                              const cc_scan_mask_t *mask) {
+  if ((d_qdesc != nullptr) == (src != nullptr)) return set_err(CC_EINVAL, "cc_db_query_submit_masked: exactly one of d_qdesc and src must be given");
+  int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  if (!src) return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, nullptr, nullptr, mask);
+  cc_rec_src rs;
+  vrc = packed_resolve(__func__, db, src, &rs);
+  if (vrc != CC_OK) return vrc;
+  return query_submit_impl(db, nullptr, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, &rs, h_rec, mask);
+}
+
+// ... with host descriptors and a host table: both are staged on the device (the table in a buffer of the handle's that grows
+// on demand; the call is synchronous, so the next one finds it free), then the submit above and the wait.
+int cc_db_query_batch_host_masked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                  const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                                  const cc_scan_mask_t *mask) {
+  if (!db || !h_qdesc || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch_host_masked: bad argument");
+  DB_POISON_CHK(db, "cc_db_query_batch_host_masked");
+  int rc = packed_modes(__func__, rank, h_detail);
+  if (rc != CC_OK) return rc;
+  if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch_host_masked: thresholds must satisfy lb.strictSmaller(ub)");
+  for (int i = 0; i < nq; i++)
+    if (h_epoch[i] < 0 || h_epoch[i] > db->n_scans) return set_err(CC_EINVAL, "cc_db_query_batch_host_masked: epoch out of range");
+  if (mask) {  // (before anything is staged: a refused call copies nothing)
+    rc = mask_validate(db, mask, nq, h_epoch);
+    if (rc != CC_OK) return rc;
+  }
+  if (nq == 0) return CC_OK;
+  HIPCHK(hipSetDevice(db->device));
+  rc = stage_reserve(db, nq);
+  if (rc != CC_OK) return rc;
+  HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)nq, hipMemcpyHostToDevice));
+  cc_scan_mask_t dm;
+  if (mask) {
+    const size_t words = (size_t)mask->n_rows * (size_t)mask->row_words;
+    if (words > db->mask_stage_cap) {
+      hipFree(db->d_mask_stage);
+      db->d_mask_stage = nullptr;
+      db->mask_stage_cap = 0;
+      HIPCHK(hipMalloc(&db->d_mask_stage, sizeof(uint32_t) * words));
+      db->mask_stage_cap = words;
+    }
+    HIPCHK(hipMemcpy(db->d_mask_stage, mask->bits, sizeof(uint32_t) * words, hipMemcpyHostToDevice));
+    dm = *mask;
+    dm.bits = db->d_mask_stage;
+  }
+  return run_sync(db, [&] { return query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank, h_detail, nullptr, nullptr, mask ? &dm : nullptr); });
+}
+
+// Parity / debug: which retrieval the query chunks submitted so far ran
+int cc_db_debug_knn_chunks(const cc_db *db, int64_t out[3]) {
+  if (!db || !out) return set_err(CC_EINVAL, "cc_db_debug_knn_chunks: bad argument");
+  for (int i = 0; i < 3; i++) out[i] = db->knn_chunks[i];
+  return CC_OK;
+}
+
+// Rows of a position prior (k_mask.h): bit g of row r = scan g lies within gate r's circle.  Queued on `stream`.
+int cc_mask_gates(cc_ctx *ctx, const float *d_xy, int n_scans, const float *d_gate, int n_rows, uint32_t *d_bits, int row_words, void *stream_) {
+  if (!ctx || n_scans < 0 || (n_scans > 0 && !d_xy) || !d_gate || n_rows < 1 || !d_bits || row_words < 1)
+    return set_err(CC_EINVAL, "cc_mask_gates: bad argument (n_rows >= 1, row_words >= 1)");
+  if ((long long)32 * row_words < (long long)n_scans) return set_err(CC_EINVAL, "cc_mask_gates: 32 * row_words is smaller than n_scans");
+  HIPCHK(hipSetDevice(ctx->device));
+  const long long blocks = (long long)n_rows * ((row_words + 1) / 2);
+  if (blocks > INT_MAX) return set_err(CC_EINVAL, "cc_mask_gates: the table is too large for one launch");
+  hipLaunchKernelGGL(cc_k_mask_gates, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream_, d_xy, n_scans, d_gate, (unsigned *)d_bits, row_words);
+  HIPCHK(hipGetLastError());
+  return CC_OK;
 }

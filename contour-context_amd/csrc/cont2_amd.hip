@@ -26,6 +26,7 @@
 #include "k_contours.h"
 #include "k_contours_list.h"
 #include "k_knn.h"
+#include "k_mask.h"
 #include "k_check.h"
 #include "k_merge.h"
 #include "k_gmm.h"

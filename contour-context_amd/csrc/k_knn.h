@@ -363,9 +363,15 @@ __device__ __forceinline__ void cc_knn_by_width(int cnt, F &&f) {
 // its bucket's indexed interval; the common instance carries none of it (the test in the shared loop cost the walk 8 %:
 // the kernel sits at its scalar-register limit).
 // KM: the hit capacity per search (CC_KNN_MAX for nnk <= 64: cc_k_knn; CC_KNN_MAX_LARGE: cc_k_knn_l), the stride of `hits`.
-template <bool VIS, int KM>
+// MASK: the chunk has a query that names a row of a scan mask (cc_scan_mask_t: bit g & 31 of word g >> 5 of a row set = scan g may
+// answer): a key that has passed the distance and epoch tests is filed only if its scan's bit is set in the query's row
+// (qrow[q], wave-uniform; -1: no restriction) -- the search then is the unmasked search of a layer without the other scans'
+// keys.  A key that passes the epoch test belongs to a scan below the epoch, and the host has checked 32 * row_words >= epoch.
+// The unmasked instances carry none of it.
+template <bool VIS, int KM, bool MASK>
 __device__ __forceinline__ void cc_knn_walk(cc_knn_params P, const cc_hot_desc_t *qhot, const cc_query_meta *qmeta,
-                                            cc_knn_hit_t *hits, int *hit_cnt) {
+                                            cc_knn_hit_t *hits, int *hit_cnt, const unsigned *mbits = nullptr, int row_words = 0,
+                                            const int *qrow = nullptr) {
   static_assert(KM == CC_KNN_MAX || KM == CC_KNN_MAX_LARGE, "cc_knn_walk: the two instances");
   __shared__ unsigned long long buf[KM == CC_KNN_MAX ? CC_KNN_CAP : CC_KNN_CAP_LARGE];
   const int lane = threadIdx.x;
@@ -407,6 +413,13 @@ __device__ __forceinline__ void cc_knn_walk(cc_knn_params P, const cc_hot_desc_t
   const int epoch = qm->epoch;
   const int nnk = P.nnk;
   const bool idx_full = VIS ? qm->idx_full[ll] != 0 : true;  // wave-uniform
+  const unsigned *mrow = nullptr;  // this query's row of the mask (wave-uniform), or nullptr: every scan may answer
+  const int *kgidx = nullptr;
+  if constexpr (MASK) {
+    const int r = qrow[q];
+    if (r >= 0) mrow = mbits + (size_t)r * (size_t)row_words;
+    kgidx = P.kgidx[ll];
+  }
 
   // ---- index ranges of the visible buckets (src/cont2/contour_db.cpp:322-369: mid = the bucket of the anchor's first
   // dimension, visited are {0..mid} and {mid + i : i > mid, mid + i < 6}) and the anchor's own position.
@@ -516,6 +529,12 @@ __device__ __forceinline__ void cc_knn_walk(cc_knn_params P, const cc_hot_desc_t
         // distance still compete, on the key id
         pass[dir] = inside[dir] && act[dir] <= epoch && (tightened ? (r <= ub) : (r < ub));
         if (VIS && !idx_full && pass[dir]) pass[dir] = cc_knn_key_indexed(qm, ll, c[dir][0]);  // rare: see cc_query_meta
+        if constexpr (MASK) {
+          if (mrow && pass[dir]) {
+            const unsigned g = (unsigned)kgidx[(unsigned)kid[dir]];
+            pass[dir] = ((mrow[g >> 5] >> (g & 31u)) & 1u) != 0u;
+          }
+        }
       }
       kcur[dir] = kid[dir];
       // the step's outermost key decides whether the direction goes on: (key[0] - q[0])^2 is a lower bound of the
@@ -597,7 +616,7 @@ template <bool VIS>
 __global__ void __launch_bounds__(64)
 cc_k_knn(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta,
          cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt) {
-  cc_knn_walk<VIS, CC_KNN_MAX>(P, qhot, qmeta, hits, hit_cnt);
+  cc_knn_walk<VIS, CC_KNN_MAX, false>(P, qhot, qmeta, hits, hit_cnt);
 }
 
 // the large-k instance (64 < nnk <= CC_KNN_MAX_LARGE): hits [.][CC_KNN_MAX_LARGE]
@@ -605,7 +624,23 @@ template <bool VIS>
 __global__ void __launch_bounds__(64)
 cc_k_knn_l(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta,
            cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt) {
-  cc_knn_walk<VIS, CC_KNN_MAX_LARGE>(P, qhot, qmeta, hits, hit_cnt);
+  cc_knn_walk<VIS, CC_KNN_MAX_LARGE, false>(P, qhot, qmeta, hits, hit_cnt);
+}
+
+// the masked instances (a chunk in which some query names a row of a cc_scan_mask_t): mbits [n_rows][row_words], qrow [nq]
+template <bool VIS>
+__global__ void __launch_bounds__(64)
+cc_k_knn_m(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta,
+           cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt, const unsigned *__restrict__ mbits, int row_words,
+           const int *__restrict__ qrow) {
+  cc_knn_walk<VIS, CC_KNN_MAX, true>(P, qhot, qmeta, hits, hit_cnt, mbits, row_words, qrow);
+}
+template <bool VIS>
+__global__ void __launch_bounds__(64)
+cc_k_knn_lm(cc_knn_params P, const cc_hot_desc_t *__restrict__ qhot, const cc_query_meta *__restrict__ qmeta,
+            cc_knn_hit_t *__restrict__ hits, int *__restrict__ hit_cnt, const unsigned *__restrict__ mbits, int row_words,
+            const int *__restrict__ qrow) {
+  cc_knn_walk<VIS, CC_KNN_MAX_LARGE, true>(P, qhot, qmeta, hits, hit_cnt, mbits, row_words, qrow);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -471,6 +471,39 @@ class ContourDB {
     if (rc != CC_OK) die_cc();
     handOut(rk, r, rl, rn, dl, cand_ptrs, cand_corr, cand_tf);
   }
+  // Mirror-only: queryRangedKNN among the scans the caller allows -- scans of this database by their index in adding order
+  // (another session's part of the map, the scans near a position prior, everything but a retired key frame) -- as if the other
+  // scans' keys were not in the trees (cc_db_query_batch_host_masked): the search keeps the nnk_ nearest ALLOWED keys per anchor.
+  // Synchronous, at the official epoch, like verifyCandidates; honours setMaxReturn / setWantDetail; the read-ahead queue is
+  // neither consumed nor extended.
+  void queryAllowed(const std::shared_ptr<const ContourManager> &q_ptr, const std::vector<int> &allowed_indices,
+                    const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
+                    std::vector<std::shared_ptr<const ContourManager>> &cand_ptrs, std::vector<double> &cand_corr,
+                    std::vector<Eigen::Isometry2d> &cand_tf) const {
+    cand_ptrs.clear();
+    cand_corr.clear();
+    cand_tf.clear();
+    const int n_db = (int)all_bevs_.size();
+    for (const int c : allowed_indices) CC_CHECK(c >= 0 && c < n_db);  // (scans appended ahead of the driver are not the caller's yet)
+    ensure(*q_ptr);
+    if (need_rebuild_) rebuild();
+    const cc_score_t lb = to_c(thres_lb), ub = to_c(thres_ub);
+    std::vector<uint32_t> row((size_t)(n_db + 31) / 32 + 1, 0u);
+    for (const int c : allowed_indices) row[(size_t)c >> 5] |= 1u << (c & 31);
+    const int32_t epoch = n_db, r0 = 0;
+    const cc_scan_mask_t mask = {row.data(), 1, (int32_t)row.size(), &r0};
+    cc_query_result_t r;
+    cc_ranked_cand_t rl[CC_RANK_MAX];
+    cc_ranked_detail_t dl[CC_RANK_MAX];
+    int32_t rn = 0;
+    const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
+    const bool rk = rankedPath();
+    last_details_.clear();
+    const int rc = cc_db_query_batch_host_masked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, rk ? &ro : nullptr, want_detail_ ? dl : nullptr, &mask);
+    for (auto &sp : spec_) sp.collected = true;  // the synchronous call (its wait) collected every chain in flight
+    if (rc != CC_OK) die_cc();
+    handOut(rk, r, rl, rn, dl, cand_ptrs, cand_corr, cand_tf);
+  }
   // one entry of a ranked list as the reference's result vectors hold it
   template <class Scans>
   static void pushRanked(const Scans &scans, const cc_ranked_cand_t &e, std::vector<std::shared_ptr<const ContourManager>> &res_cand,

@@ -124,6 +124,35 @@ class PackedSrc(C.Structure):  # cc_packed_src_t (the *_submit_packed entry poin
 assert C.sizeof(PackedSrc) == 24
 
 
+class ScanMaskC(C.Structure):  # cc_scan_mask_t (the masked query forms): bit g & 31 of word g >> 5 of a row = scan g may answer
+    _fields_ = [("bits", C.c_void_p), ("n_rows", C.c_int32), ("row_words", C.c_int32), ("h_row", C.c_void_p)]
+
+
+assert C.sizeof(ScanMaskC) == 24 and ScanMaskC.n_rows.offset == 8 and ScanMaskC.row_words.offset == 12 and ScanMaskC.h_row.offset == 16
+
+
+def pack_mask_rows(allowed, n_db=None, row_words=None):
+    """allowed: a bool array [n_rows, n_db] or a list of index arrays (then n_db bounds the indices) -> uint32 [n_rows, row_words],
+    bit g & 31 of word g >> 5 of row r set iff scan g is in row r's set; row_words defaults to ceil(n_db / 32), at least 1."""
+    if isinstance(allowed, np.ndarray) and allowed.dtype == np.bool_:
+        a = np.atleast_2d(allowed)
+    else:
+        rows = [np.asarray(r, np.int64).reshape(-1) for r in allowed]
+        n = int(n_db) if n_db is not None else max([int(r.max()) + 1 for r in rows if len(r)] + [1])
+        a = np.zeros((len(rows), n), np.bool_)
+        for i, r in enumerate(rows):
+            if len(r) and (r.min() < 0 or r.max() >= n):
+                raise ValueError("row %d names a scan outside [0, %d)" % (i, n))
+            a[i, r] = True
+    n = a.shape[1]
+    rw = max((n + 31) // 32, 1) if row_words is None else int(row_words)
+    if 32 * rw < n:
+        raise ValueError("row_words = %d holds fewer than %d scans" % (rw, n))
+    pad = np.zeros((a.shape[0], 32 * rw), np.bool_)
+    pad[:, :n] = a
+    return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little").view("<u4").reshape(a.shape[0], rw))
+
+
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
 

@@ -940,6 +940,50 @@ int cc_db_verify_submit_packed(cc_db *db, const cc_packed_src_t *src, const int3
 int cc_db_pose_submit_packed(cc_db *db, const cc_packed_src_t *src, const cc_pose_item_t *h_items, int n, const cc_pose_cfg_t *cfg,
                              const double *h_try, cc_pose_result_t *h_res, double *h_try_corr, cc_pose_curv_t *h_curv, void *stream);
 
+/* ---- masked queries: the retrieval restricted to a caller-given set of database scans ----
+ * A query sees the database through its epoch, a prefix of the adding order.  A mask adds a set: the other session's scans but
+ * not one's own last seconds, the scans near a position prior, everything but a retired key frame.  A masked query behaves
+ * exactly as if the keys of every scan outside its set were not in the buckets' trees (in the reference's terms:
+ * TreeBucket::data_tree_ and gkidx_tree_ filtered to the allowed scans, bucket_ranges_ left alone, then queryRangedKNN):
+ * the search keeps the nnk nearest ALLOWED keys per anchor, which filtering an unmasked answer cannot give.  Epoch and mask
+ * are ANDed; bucket ranges, thresholds and everything after the retrieval are unchanged.
+ *
+ * A mask is a table of bit rows: bit g & 31 of word g >> 5 of a row set = scan g may answer.  Query i names row h_row[i]
+ * (many queries may share a row); -1 = no restriction.
+ *
+ * cc_db_query_submit_masked is the one masked form of cc_db_query_submit[_packed][_ranked[_detail]]: exactly one of d_qdesc
+ * and src is given; src, h_rec, rank and h_detail mean what they mean in cc_db_query_submit_packed.  mask NULL is that call,
+ * byte for byte and launch for launch.  A chunk in which some query names a row runs the one-wave-per-search retrieval
+ * (the tiled search has no masked instance); a chunk in which none does runs the unmasked launches.
+ * LIFETIME: `bits` is read by the lanes after the submit returns; it must stay unchanged until cc_db_query_wait or
+ * cc_db_query_collect has delivered the chunk.  h_row is read before the submit returns.
+ * Refused with CC_EINVAL (cc_last_error names the cause) before anything is queued: n_rows < 1 or row_words < 1; an h_row[i]
+ * outside [-1, n_rows); 32 * row_words smaller than the largest epoch of a query that names a row; a database in
+ * cc_db_set_dynamic_thres mode (no masked form of the replay exists); and whatever the unmasked call refuses.
+ * cc_db_query_batch_host_masked: host descriptors and a host table, both staged by the call; synchronous.
+ *
+ * cc_mask_gates makes the rows of a position prior on the device: bit g of row r is set iff, in f32 as written,
+ * dx = x_g - x_r, dy = y_g - y_r, dx * dx + dy * dy <= rad_r * rad_r, and rad_r >= 0.  A NaN anywhere or a negative radius sets
+ * no bit; bits n_scans .. 32 * row_words - 1 are written as 0.  32 * row_words < n_scans is refused with CC_EINVAL.  The launch
+ * is queued on `stream`. */
+typedef struct cc_scan_mask {
+  const uint32_t *bits; /* [n_rows][row_words]; device memory for the _submit form, host memory for the _host form */
+  int32_t n_rows, row_words;
+  const int32_t *h_row; /* [nq] host: the row of query i, or -1: every scan may answer */
+} cc_scan_mask_t;
+int cc_db_query_submit_masked(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_packed_src_t *src, const int32_t *h_rec, int nq,
+                              const int32_t *h_epoch, const cc_score_t *thres_lb, const cc_score_t *thres_ub, cc_query_result_t *h_res,
+                              cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream, const cc_rank_out_t *rank,
+                              cc_ranked_detail_t *h_detail, const cc_scan_mask_t *mask);
+int cc_db_query_batch_host_masked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch,
+                                  const cc_score_t *thres_lb, const cc_score_t *thres_ub, cc_query_result_t *h_res,
+                                  const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail, const cc_scan_mask_t *mask);
+int cc_mask_gates(cc_ctx *ctx, const float *d_xy /*[n_scans][2]*/, int n_scans, const float *d_gate /*[n_rows][3]: x, y, radius*/,
+                  int n_rows, uint32_t *d_bits /*[n_rows][row_words]*/, int row_words, void *stream);
+/* Parity / debug: the query chunks submitted on this handle so far, by the retrieval they ran: out[0] one wave per search,
+ * out[1] the tiled search, out[2] the masked walk. */
+int cc_db_debug_knn_chunks(const cc_db *db, int64_t out[3]);
+
 /* Parity / debug: the constellations of the LAST cc_db_check_hints[_host] call that passed all four gates, in hint
  * order: the pose getTFFromConstell returned for each (contour_mng.h:1246-1277, before any proposal merging) and the
  * constellation it was computed from, so that a test can redo the rigid fit independently (e.g. with an SVD). */
