@@ -490,6 +490,18 @@ void orc_gmm_eval(void *src, void *tgt, const double tf_init[3], const double p[
   autocorr[0] = g.auto_corr_src_;
   autocorr[1] = g.auto_corr_tgt_;
 }
+// what GMMPair's ctor selects at T_init, for tests/gmm_cases.py: the ellipses per level (correlation.h:49-82, the loops that
+// break at cnt_run * 1.0 / cnt_full >= min_area_perc_) and the pairs per level (correlation.h:85-96: delta_mu = T_init * mu_s - mu_t,
+// kept if delta_mu.norm() < 3.0 * (max_majax_src + max_majax_tgt)); orc_gmm.h:144-161 restates both
+void orc_gmm_counts(void *src, void *tgt, const double tf_init[3], int32_t n_ell_src[4], int32_t n_ell_tgt[4], int32_t n_pairs[4]) {
+  Iso2d T = Iso2d::fromAngTrans(tf_init[2], V2D(tf_init[0], tf_init[1]));
+  GMMPair g(*((ScanH *)src)->cm, *((ScanH *)tgt)->cm, GMMOptConfig(), T);
+  for (int li = 0; li < 4; li++) {
+    n_ell_src[li] = (int32_t)g.ellipses_src[li].size();
+    n_ell_tgt[li] = (int32_t)g.ellipses_tgt[li].size();
+    n_pairs[li] = (int32_t)g.selected_pair_idx_[li].size();
+  }
+}
 void orc_umeyama(void *src, void *tgt, const int8_t *pairs, int n, double tf[3]) {
   std::vector<ConstellationPair> c;
   for (int i = 0; i < n; i++) c.emplace_back(pairs[3 * i], pairs[3 * i + 1], pairs[3 * i + 2]);

@@ -68,6 +68,8 @@ def lib():
         _lib.orc_gmm.argtypes = [C.c_void_p] * 7
         _lib.orc_gmm_eval.argtypes = [C.c_void_p] * 7
         _lib.orc_gmm_trace.argtypes = [C.c_void_p] * 5
+        _lib.orc_gmm_counts.argtypes = [C.c_void_p] * 6
+        _lib.orc_gmm_counts.restype = None
         _lib.orc_umeyama.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.orc_knn_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         _lib.orc_eigen2f.argtypes = [C.c_void_p] * 3
@@ -263,6 +265,14 @@ def gmm_eval(src, tgt, tf_init, p):
     ac = np.zeros(2)
     lib().orc_gmm_eval(src.h, tgt.h, _p(tf_init), _p(p), C.byref(cost), _p(grad), _p(ac))
     return cost.value, grad, ac
+
+
+def gmm_counts(src, tgt, tf_init):
+    """what GMMPair's ctor selects at tf_init, per level 1..4: (src ellipses [4], tgt ellipses [4], pairs [4])"""
+    tf_init = np.ascontiguousarray(tf_init, np.float64)
+    ns, nt, npair = (np.zeros(4, np.int32) for _ in range(3))
+    lib().orc_gmm_counts(src.h, tgt.h, _p(tf_init), _p(ns), _p(nt), _p(npair))
+    return ns, nt, npair
 
 
 def umeyama(src, tgt, pairs):

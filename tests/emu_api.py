@@ -10,14 +10,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "emu", "libcc_emu.so")
 
 
-def build():
+def build(variant=None, flags=()):
+    """the harness library; variant: a second library tests/emu/libcc_emu_<variant>.so compiled with the extra `flags`"""
+    so = SO if variant is None else os.path.join(HERE, "emu", "libcc_emu_%s.so" % variant)
     srcs = [os.path.join(HERE, "emu", "emu_main.cpp"), os.path.join(HERE, "emu", "hip", "hip_runtime.h")]
     csrc = os.path.join(HERE, "..", "contour-context_amd", "csrc")
     srcs += [os.path.join(csrc, f) for f in os.listdir(csrc)]
     srcs.append(os.path.join(HERE, "..", "include", "cont2_amd.h"))
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
-        subprocess.check_call(["sh", os.path.join(HERE, "emu", "build.sh")])
-    return SO
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["sh", os.path.join(HERE, "emu", "build.sh")] + ([] if variant is None else [os.path.basename(so)] + list(flags)))
+    return so
 
 
 # one OS thread per HIP thread: keep the grids of the list-driven kernels small on the harness (read at cc_db_create).
@@ -26,9 +28,9 @@ SMALL_GRIDS = {"CC_B1_GRID": "6", "CC_B2_GRID": "6", "CC_GMM_GRID": "6"}
 
 
 class EmuApi:
-    def __init__(self, L):
+    def __init__(self, L, so=None):
         self.L = L
-        self.lib = C.CDLL(build())
+        self.lib = C.CDLL(so or build())
         self.lib.cc_last_error.restype = C.c_char_p
         self.lib.cc_packed_sizes.restype = None
         for f in ("cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_db_create", "cc_db_destroy", "cc_db_size",

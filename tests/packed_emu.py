@@ -29,9 +29,9 @@ def _b(s):
 
 
 class PackedEmu:
-    def __init__(self, L, dcfg, cap=64, lanes=None, dyn=False):
+    def __init__(self, L, dcfg, cap=64, lanes=None, dyn=False, so=None):
         self.L = L
-        self.api = emu_api.EmuApi(L)
+        self.api = emu_api.EmuApi(L, so)
         lib = self.lib = self.api.lib
         for f in ("cc_db_query_submit_packed", "cc_db_verify_submit_packed", "cc_db_pose_submit_packed", "cc_db_query_submit_ranked",
                   "cc_db_query_submit_ranked_detail", "cc_db_verify_submit", "cc_db_verify_submit_ranked", "cc_db_verify_submit_ranked_detail",

@@ -413,6 +413,9 @@ class _EB:
         return self._r(self.v * o.v + c.v, self._pe(o) + c.e)
 
 
+ErrBound = _EB   # (gmm_cases.py follows cc_gmm_self_term with it)
+
+
 def gmm_term_cases(n=2000):
     """raw [n, 14] f32 (src cov, tgt cov, src mean, tgt mean, weights) and pose [n, 6] f64 (px py cos sin cos2 sin2): ellipses
     with axes from the point_sigma floor (1.0) to 50 px at every orientation, built in f32 the way cc_k_gmm_prep builds them;
