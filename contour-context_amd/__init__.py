@@ -17,6 +17,8 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, _HERE)
+import abi  # noqa: E402
+import calls  # noqa: E402
 import layouts as L  # noqa: E402
 import synth  # noqa: E402,F401
 import sharding  # noqa: E402,F401
@@ -44,28 +46,7 @@ def build(force=False, verbose=False):
 
 _lib = None
 
-# every symbol include/cont2_amd.h declares
-EXPORTS = ["cc_last_error", "cc_version", "cc_default_manager_cfg", "cc_default_db_cfg", "cc_default_thresholds",
-           "cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_ingest_host_bev", "cc_ingest_points", "cc_ingest_points_host", "cc_scan_ingest_points", "cc_scan_ingest_points_batch",
-           "cc_ingest_segments", "cc_ingest_segments_host", "cc_scan_ingest_segments",
-           "cc_ingest_points_motion", "cc_ingest_points_motion_host", "cc_scan_ingest_points_motion", "cc_motion_knots",
-           "cc_range_sensor_create", "cc_range_sensor_destroy", "cc_ingest_ranges", "cc_ingest_ranges_host", "cc_scan_ingest_ranges", "cc_db_create", "cc_db_destroy", "cc_db_size", "cc_db_knn_stride",
-           "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_hot_ptr", "cc_db_feat_ptr", "cc_pack_scans", "cc_db_add_packed",
-           "cc_packed_sizes", "cc_db_bucket_state", "cc_est_sens_tf",
-           "cc_profile_enable", "cc_profile_read", "cc_db_profile_enable", "cc_db_profile_read",
-           "cc_db_add_scan_host", "cc_db_query_host", "cc_db_set_lanes", "cc_db_set_dynamic_thres",
-           "cc_db_add_scans_host", "cc_db_query_batch_host", "cc_db_check_hints", "cc_db_check_hints_host", "cc_db_debug_passes",
-           "cc_db_verify_submit", "cc_db_verify_batch", "cc_db_verify_batch_host",
-           "cc_db_query_submit_ranked", "cc_db_query_batch_host_ranked", "cc_db_query_scan_batch_submit_ranked", "cc_db_verify_submit_ranked",
-           "cc_db_check_hints_ranked", "cc_db_verify_batch_host_ranked", "cc_db_check_hints_host_ranked",
-           "cc_db_query_submit_ranked_detail", "cc_db_query_batch_host_ranked_detail", "cc_db_query_scan_batch_submit_ranked_detail",
-           "cc_db_verify_submit_ranked_detail", "cc_db_verify_batch_host_ranked_detail", "cc_db_check_hints_ranked_detail",
-           "cc_db_check_hints_host_ranked_detail", "cc_est_sens_info", "cc_db_pose_submit", "cc_db_pose_batch", "cc_db_pose_batch_host",
-           "cc_db_query_submit_packed", "cc_db_verify_submit_packed", "cc_db_pose_submit_packed",
-           "cc_db_query_submit_masked", "cc_db_query_batch_host_masked", "cc_mask_gates", "cc_db_debug_knn_chunks",
-           "cc_stage_points", "cc_stage_points_slot", "cc_stage_points_cancel", "cc_scan_ingest", "cc_scan_desc", "cc_scan_bev", "cc_scan_offload", "cc_scan_on_device", "cc_scan_release", "cc_db_query_scan",
-           "cc_db_add_scan", "cc_db_query_scan_submit", "cc_db_query_collect", "cc_db_add_scan_prepare", "cc_runtime_init", "cc_scan_ingest_batch", "cc_scan_ready", "cc_db_add_scan_batch", "cc_db_query_scan_batch_submit",
-           "cc_comm_unique_id", "cc_comm_create", "cc_comm_create_from_env", "cc_comm_rank", "cc_comm_world", "cc_comm_allgather_packed", "cc_comm_destroy"]
+EXPORTS = list(abi.SIGNATURES)  # every symbol include/cont2_amd.h declares
 
 
 def lib():
@@ -73,100 +54,21 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("libcont2_amd.so is not built (run __graft_entry__.build()); there is no CPU fallback")
-        _lib = C.CDLL(os.environ.get("CC_AMD_LIB") or LIB_PATH)  # CC_AMD_LIB: tuning aid (another build of the same library)
-        _lib.cc_last_error.restype = C.c_char_p
-        _lib.cc_create.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_destroy.argtypes = [C.c_void_p]
-        _lib.cc_ingest_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_ingest_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_ingest_host_bev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _lib.cc_ingest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_ingest_points_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_scan_ingest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_scan_ingest_points_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _lib.cc_ingest_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_ingest_segments_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _lib.cc_scan_ingest_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _lib.cc_ingest_points_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p]
-        _lib.cc_ingest_points_motion_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                      C.c_void_p, C.c_void_p]
-        _lib.cc_scan_ingest_points_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_motion_knots.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]
-        _lib.cc_motion_knots.restype = None
-        _lib.cc_range_sensor_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_range_sensor_destroy.argtypes = [C.c_void_p]
-        _lib.cc_ingest_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_ingest_ranges_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_scan_ingest_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_db_destroy.argtypes = [C.c_void_p]
-        _lib.cc_db_size.argtypes = [C.c_void_p]
-        _lib.cc_db_knn_stride.argtypes = [C.c_void_p]
-        _lib.cc_db_add_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_db_add_scans_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_db_query_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        _lib.cc_db_query_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        _lib.cc_db_query_wait.argtypes = [C.c_void_p]
-        for f in ("cc_db_hot_ptr", "cc_db_feat_ptr"):
-            getattr(_lib, f).argtypes = [C.c_void_p]
-            getattr(_lib, f).restype = C.c_void_p
-        _lib.cc_packed_sizes.argtypes = [C.c_void_p, C.c_void_p]
-        _lib.cc_packed_sizes.restype = None
-        _lib.cc_pack_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_db_add_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_db_bucket_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_est_sens_tf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _lib.cc_profile_enable.argtypes = [C.c_void_p, C.c_int]
-        _lib.cc_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_db_profile_enable.argtypes = [C.c_void_p, C.c_int]
-        _lib.cc_db_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_db_check_hints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.cc_db_check_hints_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                                C.c_void_p, C.c_void_p]
-        for f in ("cc_db_verify_submit", "cc_db_verify_batch"):
-            getattr(_lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        _lib.cc_db_verify_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-        _lib.cc_db_query_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
-        _lib.cc_db_query_batch_host_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        _lib.cc_db_query_scan_batch_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        _lib.cc_db_verify_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
-        _lib.cc_db_check_hints_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        for f in ("cc_db_query_submit_ranked", "cc_db_query_batch_host_ranked", "cc_db_query_scan_batch_submit_ranked", "cc_db_verify_submit_ranked",
-                  "cc_db_check_hints_ranked"):  # the _detail siblings: one more trailing pointer
-            getattr(_lib, f + "_detail").argtypes = getattr(_lib, f).argtypes + [C.c_void_p]
-        _lib.cc_est_sens_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        for f in ("cc_db_pose_submit", "cc_db_pose_batch"):
-            getattr(_lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
-        _lib.cc_db_pose_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        _lib.cc_est_sens_info.restype = None
-        _lib.cc_db_query_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
-        _lib.cc_db_verify_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
-        _lib.cc_db_pose_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
-        _lib.cc_db_query_submit_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10
-        _lib.cc_db_query_batch_host_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        _lib.cc_db_debug_knn_chunks.argtypes = [C.c_void_p, C.c_void_p]
-        _lib.cc_mask_gates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
-        _lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
+        _lib = abi.bind(C.CDLL(os.environ.get("CC_AMD_LIB") or LIB_PATH))  # CC_AMD_LIB: tuning aid (another build of the same library)
     return _lib
 
 
-class CCError(RuntimeError):
-    rc = 0
-
-
-CC_ECAPACITY = -4
+CCError, CC_ECAPACITY = calls.CCError, calls.CC_ECAPACITY
 
 
 def _chk(rc, what, tolerate=()):
-    if rc != 0 and rc not in tolerate:
-        e = CCError("%s failed (%d): %s" % (what, rc, lib().cc_last_error().decode()))
-        e.rc = rc
-        raise e
-    return rc
+    return calls.chk(lib(), rc, what, tolerate)
+
+
+def _ret(*parts):
+    """the parts a call has, as a tuple; a lone part as itself"""
+    out = tuple(p for p in parts if p is not None)
+    return out if len(out) > 1 else out[0]
 
 
 class IngestDebug(C.Structure):
@@ -338,18 +240,15 @@ def _segment_table(scans, device):
 def comm_from_env():
     """cc_comm_create_from_env: (handle, rank, world) from RANK / WORLD_SIZE / LOCAL_RANK / MASTER_PORT (one node)."""
     h, r, w = C.c_void_p(), C.c_int(), C.c_int()
-    lib().cc_comm_create_from_env.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _chk(lib().cc_comm_create_from_env(C.byref(h), C.byref(r), C.byref(w)), "cc_comm_create_from_env")
     return h, r.value, w.value
 
 
 def comm_allgather(comm, d_send, d_recv, bytes_per_rank, stream):
-    lib().cc_comm_allgather_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     _chk(lib().cc_comm_allgather_packed(comm, d_send, d_recv, bytes_per_rank, stream), "cc_comm_allgather_packed")
 
 
 def comm_destroy(comm):
-    lib().cc_comm_destroy.argtypes = [C.c_void_p]
     lib().cc_comm_destroy(comm)
 
 
@@ -626,10 +525,8 @@ class ScanMask:
         bits = torch.from_numpy(tab.view(np.int32)).to(device)
         return cls(bits, np.arange(len(tab), dtype=np.int32) if rows is None else rows)
 
-    def _c(self, nq):
-        if len(self.rows) != nq:
-            raise ValueError("the mask names rows for %d queries, the call has %d" % (len(self.rows), nq))
-        return L.ScanMaskC(self.bits.data_ptr(), int(self.bits.shape[0]), int(self.bits.shape[1]), self.rows.ctypes.data)
+    def _c(self):
+        return self.bits.data_ptr(), int(self.bits.shape[0]), int(self.bits.shape[1]), self.rows
 
 
 class Database:
@@ -641,6 +538,7 @@ class Database:
         h = C.c_void_p()
         _chk(lib().cc_db_create(ctx.h, C.addressof(self.cfg), capacity, C.byref(h)), "cc_db_create")
         self.h = h
+        self._pending = []  # what the library reads or writes until query_wait
 
     def close(self):
         if getattr(self, "h", None):
@@ -678,93 +576,39 @@ class Database:
         excluded: scan g queried at epoch g is the online loop's query of g, at a later epoch the answer may be g itself."""
         return Stored(self, None if idx is None else ([idx] if isinstance(idx, (int, np.integer)) else idx))
 
-    def _q_device(self, q):
-        """the device of a query argument: a descriptor tensor, a Packed or a Stored source"""
+    def _source(self, q, rows=False):
+        """A query argument -- a descriptor tensor, a Packed or a Stored -- checked -> (the keywords that name it to a flow of
+        `calls`, its device, the stream the call is queued on).  rows: the flow indexes the descriptors (uint8 [n, DESC_BYTES])."""
         import torch
-        dev = getattr(q, "device", None)
-        return dev if dev is not None else torch.device("cuda", self.ctx.device)
-
-    def _src_args(self, q):
-        """a Packed / Stored query -> (cc_packed_src_t, its record selector or None, the stream the call is queued on)"""
-        import torch
-        if isinstance(q, Stored) and q.db is not self:
-            raise ValueError("the stored scans belong to another database")
-        dev = q.device if q.device is not None else torch.device("cuda", self.ctx.device)
-        return q._src(), q.idx, torch.cuda.current_stream(dev).cuda_stream
-
-    def _masked_query(self, q, mask, epochs, lb, ub, want_knn, ranked, det, tol, wait):
-        """query() / query_submit() with mask=: cc_db_query_submit_masked (+ the wait), from descriptors or a record source"""
-        import torch
-        if not isinstance(mask, ScanMask):
-            raise TypeError("mask must be a ScanMask")
-        if lb is None:
-            lb, ub = L.default_thresholds()
-        epochs = np.ascontiguousarray(epochs, np.int32)
-        nq = len(epochs)
-        src = idx = None
         if _is_src(q):
-            src, idx, stream = self._src_args(q)
-            if idx is not None and len(idx) != nq:
-                raise ValueError("the source names %d records for %d epochs" % (len(idx), nq))
-            dev = self._q_device(q)
-        else:
-            assert q.is_cuda and q.is_contiguous() and q.shape[0] == nq
-            dev = q.device
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        cm = mask._c(nq)
-        res = np.zeros(nq, L.query_result_dt)
-        knn = cnt = None
-        if want_knn:
-            knn = torch.zeros((nq, L.NQLEV, L.NPIV, self.knn_stride, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=dev)
-            cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=dev)
-        rk = ro = None
-        if ranked is not None:
-            rc_, rn_, ro = L.rank_buffers(nq, ranked)
-            rk = (rc_, rn_)
-        args = (self.h, q.data_ptr() if src is None else None, C.addressof(src) if src is not None else None,
-                idx.ctypes.data if idx is not None else None, nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
-                res.ctypes.data, knn.data_ptr() if want_knn else None, cnt.data_ptr() if want_knn else None, stream,
-                C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None, C.addressof(cm))
-        keep = (q, src, idx, epochs, lb, ub, ro, mask, cm)  # the lanes read the mask's table until the wait
-        if wait:
-            self._ranked_call(lib().cc_db_query_submit_masked, "cc_db_query_submit_masked", tol, *args)
-        else:
-            self._pending = getattr(self, "_pending", [])
-            self._pending.append((keep, res, rk, det))
-            _chk(lib().cc_db_query_submit_masked(*args), "cc_db_query_submit_masked")
-        return res, knn, cnt, rk
-
-    def _packed_query(self, q, epochs, lb, ub, want_knn, ranked, det, tol, wait):
-        """query() / query_submit() from a record source: cc_db_query_submit_packed (+ the wait)"""
-        import torch
-        src, idx, stream = self._src_args(q)
-        if lb is None:
-            lb, ub = L.default_thresholds()
-        epochs = np.ascontiguousarray(epochs, np.int32)
-        nq = len(epochs)
-        if idx is not None and len(idx) != nq:
-            raise ValueError("the source names %d records for %d epochs" % (len(idx), nq))
-        res = np.zeros(nq, L.query_result_dt)
-        knn = cnt = None
-        if want_knn:
+            if isinstance(q, Stored) and q.db is not self:
+                raise ValueError("the stored scans belong to another database")
+            kw = {"src": q._src(), "idx": q.idx}
             dev = q.device if q.device is not None else torch.device("cuda", self.ctx.device)
-            knn = torch.zeros((nq, L.NQLEV, L.NPIV, self.knn_stride, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=dev)
-            cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=dev)
-        rk = ro = None
-        if ranked is not None:
-            rc_, rn_, ro = L.rank_buffers(nq, ranked)
-            rk = (rc_, rn_)
-        args = (self.h, C.addressof(src), idx.ctypes.data if idx is not None else None, nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
-                res.ctypes.data, knn.data_ptr() if want_knn else None, cnt.data_ptr() if want_knn else None, stream,
-                C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None)
-        keep = (q, src, idx, epochs, lb, ub, ro)
-        if wait:
-            self._ranked_call(lib().cc_db_query_submit_packed, "cc_db_query_submit_packed", tol, *args)
         else:
-            self._pending = getattr(self, "_pending", [])
-            self._pending.append((keep, res, rk, det))  # the library reads and writes them until query_wait
-            _chk(lib().cc_db_query_submit_packed(*args), "cc_db_query_submit_packed")
-        return res, knn, cnt, rk
+            assert q.is_cuda and q.is_contiguous()
+            kw, dev = {"qdesc": q.data_ptr()}, q.device
+            if rows:
+                assert q.dtype == torch.uint8 and q.dim() == 2 and q.shape[1] == DESC_BYTES
+                kw["n_desc"] = q.shape[0]
+        return kw, dev, torch.cuda.current_stream(dev).cuda_stream
+
+    def _held(self, *objs):
+        """A new entry of the pending list that holds `objs` (the query's tensors or source, the mask) -> the list in it to which
+        the submit appends its host buffers before the library is called: a submit that fails may have queued some chunks."""
+        keep = []
+        self._pending.append((objs, keep))
+        return keep
+
+    def _query_kw(self, qdesc, epochs, mask):
+        """what query() and query_submit() hand to calls.query for their query, epochs and mask -> (keywords, device, nq)"""
+        if mask is not None and not isinstance(mask, ScanMask):
+            raise TypeError("mask must be a ScanMask")
+        kw, dev, stream = self._source(qdesc)
+        epochs = np.ascontiguousarray(epochs, np.int32).reshape(-1)
+        assert "src" in kw or qdesc.shape[0] == len(epochs)
+        kw.update(epochs=epochs, stream=stream, mask=None if mask is None else mask._c())
+        return kw, dev, len(epochs)
 
     def add_scans_prepare(self, desc):
         """Queue the device half of add_scans(desc, ...) on the current stream without waiting (cc_db_add_scans_prepare)."""
@@ -773,25 +617,7 @@ class Database:
         stream = torch.cuda.current_stream(desc.device).cuda_stream
         _chk(lib().cc_db_add_scans_prepare(self.h, desc.data_ptr(), desc.shape[0], stream), "cc_db_add_scans_prepare")
 
-    @staticmethod
-    def _detail_args(n, ranked, detail):
-        """detail=True: the h_detail buffer of a *_ranked_detail call ([n, ranked] of L.ranked_detail_dt), else None"""
-        if not detail:
-            return None
-        if ranked is None:
-            raise ValueError("detail=True needs ranked=K: the detail rows belong to the entries of the ranked list")
-        return L.rank_detail_buffer(n, ranked)
-
-    def _ranked_call(self, fn, what, tol, *args):
-        """a *_submit_ranked call followed by the wait: the synchronous ranked forms of query() and verify()"""
-        rc = fn(*args)
-        if rc != 0 and rc not in tol:  # refused or failed: the message is this call's; nothing of it may stay in flight
-            msg = lib().cc_last_error().decode()
-            lib().cc_db_query_wait(self.h)
-            e = CCError("%s failed (%d): %s" % (what, rc, msg))
-            e.rc = rc
-            raise e
-        _chk(lib().cc_db_query_wait(self.h), "cc_db_query_wait", tolerate=tol)
+    _detail_args = staticmethod(calls.detail_buffer)  # (kept under this name for tests/test_emu_ranked_detail.py, which asks it for the refusal)
 
     def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False, mask=None):
         """qdesc: torch uint8 CUDA [nq, DESC_BYTES]; epochs int32 [nq] (DB state each query sees).
@@ -810,56 +636,18 @@ class Database:
         mask=ScanMask(...): only the scans of each query's row may answer (cc_db_query_submit_masked + the wait): the retrieval
         runs as if the other scans' keys were not in the trees.  It combines with every form above."""
         import torch
-        if _is_src(qdesc) or mask is not None:  # the submit followed by the wait, like ranked=K
-            nq, ks = len(np.asarray(epochs).reshape(-1)), self.knn_stride
-            det = self._detail_args(nq, ranked, detail)
-            tol = (CC_ECAPACITY,) if allow_flagged else ()
-            if mask is not None:
-                res, knn, cnt, rk = self._masked_query(qdesc, mask, epochs, lb, ub, want_knn, ranked, det, tol, True)
-            else:
-                res, knn, cnt, rk = self._packed_query(qdesc, epochs, lb, ub, want_knn, ranked, det, tol, True)
-            out = (res,)
-            if want_knn:
-                out += (knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy())
-            if rk is not None:
-                out += (rk,)
-            if det is not None:
-                out += (det,)
-            return out if len(out) > 1 else res
-        det = self._detail_args(qdesc.shape[0], ranked, detail)
-        if lb is None:
-            lb, ub = L.default_thresholds()
-        epochs = np.ascontiguousarray(epochs, np.int32)
-        nq = qdesc.shape[0]
-        assert qdesc.is_cuda and qdesc.is_contiguous() and len(epochs) == nq
-        res = np.zeros(nq, L.query_result_dt)
+        kw, dev, nq = self._query_kw(qdesc, epochs, mask)
         knn = cnt = None
-        ks = self.knn_stride
         if want_knn:
-            knn = torch.zeros((nq, L.NQLEV, L.NPIV, ks, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=qdesc.device)
-            cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=qdesc.device)
-        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
-        tol = (CC_ECAPACITY,) if allow_flagged else ()
-        rk = None
-        if ranked is None:
-            _chk(lib().cc_db_query_batch(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
-                                         res.ctypes.data, knn.data_ptr() if want_knn else None,
-                                         cnt.data_ptr() if want_knn else None, stream), "cc_db_query_batch", tolerate=tol)
-        else:
-            rc_, rn_, ro = L.rank_buffers(nq, ranked)
-            rk = (rc_, rn_)
-            fn = "cc_db_query_submit_ranked" + ("_detail" if det is not None else "")
-            self._ranked_call(getattr(lib(), fn), fn, tol, self.h, qdesc.data_ptr(), nq, epochs.ctypes.data,
-                              C.addressof(lb), C.addressof(ub), res.ctypes.data, knn.data_ptr() if want_knn else None,
-                              cnt.data_ptr() if want_knn else None, stream, C.addressof(ro), *(() if det is None else (det.ctypes.data,)))
-        out = (res,)
+            ks = self.knn_stride
+            knn = torch.zeros((nq, L.NQLEV, L.NPIV, ks, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=dev)
+            cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=dev)
+            kw.update(knn=knn.data_ptr(), knn_cnt=cnt.data_ptr())
+        r = calls.query(lib(), self.h, lb=lb, ub=ub, ranked=ranked, detail=detail,
+                        tolerate=(CC_ECAPACITY,) if allow_flagged else (), **kw)
         if want_knn:
-            out += (knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy())
-        if rk is not None:
-            out += (rk,)
-        if det is not None:
-            out += (det,)
-        return out if len(out) > 1 else res
+            knn, cnt = knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy()
+        return _ret(r.res, knn, cnt, r.rank, r.detail)
 
     def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False, mask=None):
         """Asynchronous form of query(): queues the batch and returns the result array, which is only valid after
@@ -867,39 +655,9 @@ class Database:
         current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait();
         with detail=True followed by the [nq, K] detail array (see query()).  qdesc may be self.stored(idx) or a Packed.
         mask=ScanMask(...): as for query(); the pending list keeps the mask's table alive until query_wait()."""
-        import torch
-        if _is_src(qdesc) or mask is not None:
-            det = self._detail_args(len(np.asarray(epochs).reshape(-1)), ranked, detail)
-            if mask is not None:
-                res, _k, _c, rk = self._masked_query(qdesc, mask, epochs, lb, ub, False, ranked, det, (), False)
-            else:
-                res, _k, _c, rk = self._packed_query(qdesc, epochs, lb, ub, False, ranked, det, (), False)
-            return res if rk is None else ((res, rk) if det is None else (res, rk, det))
-        det = self._detail_args(qdesc.shape[0], ranked, detail)
-        if lb is None:
-            lb, ub = L.default_thresholds()
-        epochs = np.ascontiguousarray(epochs, np.int32)
-        nq = qdesc.shape[0]
-        assert qdesc.is_cuda and qdesc.is_contiguous() and len(epochs) == nq
-        res = np.zeros(nq, L.query_result_dt)
-        self._pending = getattr(self, "_pending", [])
-        self._pending.append(res)  # the library writes into it until query_wait
-        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
-        if ranked is not None:
-            rc_, rn_, ro = L.rank_buffers(nq, ranked)
-            self._pending.append((rc_, rn_))
-            if det is not None:
-                self._pending.append(det)
-                _chk(lib().cc_db_query_submit_ranked_detail(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
-                                                            res.ctypes.data, None, None, stream, C.addressof(ro), det.ctypes.data),
-                     "cc_db_query_submit_ranked_detail")
-                return res, (rc_, rn_), det
-            _chk(lib().cc_db_query_submit_ranked(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
-                                                 res.ctypes.data, None, None, stream, C.addressof(ro)), "cc_db_query_submit_ranked")
-            return res, (rc_, rn_)
-        _chk(lib().cc_db_query_submit(self.h, qdesc.data_ptr(), nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub),
-                                      res.ctypes.data, None, None, stream), "cc_db_query_submit")
-        return res
+        kw, _dev, _nq = self._query_kw(qdesc, epochs, mask)
+        r = calls.query(lib(), self.h, lb=lb, ub=ub, ranked=ranked, detail=detail, wait=False, keep=self._held(qdesc, mask), **kw)
+        return _ret(r.res, r.rank, r.detail)
 
     def query_wait(self):
         _chk(lib().cc_db_query_wait(self.h), "cc_db_query_wait")
@@ -924,65 +682,26 @@ class Database:
         Returns (cc_query_result_t record, per-hint L.hint_score_dt array); with ranked=K followed by (cands [1, K], counts [1]),
         and with detail=True by the [1, K] detail array (see query())."""
         import torch
-        det = self._detail_args(1, ranked, detail)
-        if lb is None:
-            lb, ub = L.default_thresholds()
-        hints = np.ascontiguousarray(hints, L.hint_dt)
         qdesc = qdesc.reshape(-1)
         assert qdesc.is_cuda and qdesc.is_contiguous() and qdesc.numel() == DESC_BYTES
-        res = np.zeros(1, L.query_result_dt)
-        sc = np.zeros(len(hints), L.hint_score_dt)
-        stream = torch.cuda.current_stream(qdesc.device).cuda_stream
-        if ranked is not None:
-            rc_, rn_, ro = L.rank_buffers(1, ranked)
-            if det is not None:
-                _chk(lib().cc_db_check_hints_ranked_detail(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
-                                                           int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream, C.addressof(ro), det.ctypes.data),
-                     "cc_db_check_hints_ranked_detail")
-                return res[0], sc, (rc_, rn_), det
-            _chk(lib().cc_db_check_hints_ranked(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
-                                                int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream, C.addressof(ro)),
-                 "cc_db_check_hints_ranked")
-            return res[0], sc, (rc_, rn_)
-        _chk(lib().cc_db_check_hints(self.h, qdesc.data_ptr(), hints.ctypes.data, len(hints), C.addressof(lb), C.addressof(ub),
-                                     int(max_fine_opt), res.ctypes.data, sc.ctypes.data, stream), "cc_db_check_hints")
-        return res[0], sc
+        r = calls.check_hints(lib(), self.h, qdesc.data_ptr(), hints, lb, ub, max_fine_opt, torch.cuda.current_stream(qdesc.device).cuda_stream,
+                              ranked, detail)
+        return _ret(r.res[0], r.scores, r.rank, r.detail)
 
-    def _verify_args(self, qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt):
+    def _verify(self, qdesc, cands, max_fine_opt, want_hints=False, **kw):
+        """what verify() and verify_submit() share: the tensor checks, the stream, the device's hint lists, the call
+        -> (calls.verify's record, the hint tensors or None)"""
         import torch
-        if lb is None:
-            lb, ub = L.default_thresholds()
-        if _is_src(qdesc):
-            if qdesc.idx is not None and qidx is not None:
-                raise ValueError("name the records by the source's idx or by qidx, not both")
-            qidx = qdesc.idx if qidx is None else qidx
-        else:
-            assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
-        if isinstance(cands, np.ndarray):
-            rows = np.asarray(cands, np.int64).reshape(len(cands), -1)
-        else:
-            rows = [list(c) for c in cands]
-        n = len(rows)
-        tab = np.full((n, L.VERIFY_CANDS_MAX), -1, np.int32)
-        for i, c in enumerate(rows):
-            if len(c) > L.VERIFY_CANDS_MAX:
-                if any(int(v) != -1 for v in c[L.VERIFY_CANDS_MAX:]):
-                    raise ValueError("item %d: more than VERIFY_CANDS_MAX = %d candidates" % (i, L.VERIFY_CANDS_MAX))
-                c = c[:L.VERIFY_CANDS_MAX]
-            tab[i, :len(c)] = c
-        if qidx is not None:
-            qidx = np.ascontiguousarray(qidx, np.int32)
-            if len(qidx) != n:
-                raise ValueError("qidx must name one descriptor per item")
-        mask = 0
-        for lv in levels:
-            if not 1 <= int(lv) <= 4:
-                raise ValueError("hint levels are 1..4")
-            mask |= 1 << (int(lv) - 1)
-        if mask == 0:
-            raise ValueError("no hint level given")
-        cfg = L.VerifyCfg(mask, int(self.cfg.max_fine_opt if max_fine_opt is None else max_fine_opt), float(max_key_dist_sq), 0)
-        return tab, qidx, cfg, lb, ub
+        skw, dev, stream = self._source(qdesc, rows=True)
+        cands = calls.cand_table(cands)
+        d_h = d_n = None
+        if want_hints:
+            d_h = torch.zeros((max(len(cands), 1), L.HINT_MAX, L.hint_dt.itemsize), dtype=torch.uint8, device=dev)
+            d_n = torch.zeros(max(len(cands), 1), dtype=torch.int32, device=dev)
+            kw.update(hints=d_h.data_ptr(), n_hints=d_n.data_ptr())
+        r = calls.verify(lib(), self.h, cands, max_fine_opt=self.cfg.max_fine_opt if max_fine_opt is None else max_fine_opt, stream=stream,
+                         **skw, **kw)
+        return r, d_h, d_n
 
     def verify(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
                want_hints=False, allow_flagged=False, ranked=None, detail=False):
@@ -998,51 +717,14 @@ class Database:
         (cc_db_verify_submit_ranked), instead of one item per (query, candidate) pair.  Like query(ranked=K) it is the submit
         followed by the wait, so a large batch is chunked by the streamed rule (whole chunks), not one chunk per lane.
         detail=True (with ranked=K): followed by the [n, K] detail array as well (see query())."""
-        import torch
-        tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
-        det = self._detail_args(len(tab), ranked, detail)
-        n = len(tab)
-        res = np.zeros(n, L.query_result_dt)
-        d_h = d_n = None
-        if want_hints:
-            d_h = torch.zeros((max(n, 1), L.HINT_MAX, L.hint_dt.itemsize), dtype=torch.uint8, device=self._q_device(qdesc))
-            d_n = torch.zeros(max(n, 1), dtype=torch.int32, device=self._q_device(qdesc))
-        stream = torch.cuda.current_stream(self._q_device(qdesc)).cuda_stream
-        tol = (CC_ECAPACITY,) if allow_flagged else ()
-        rk = None
-        if _is_src(qdesc):  # a record source: cc_db_verify_submit_packed followed by the wait
-            src = self._src_args(qdesc)[0]
-            ro = None
-            if ranked is not None:
-                rc_, rn_, ro = L.rank_buffers(n, ranked)
-                rk = (rc_, rn_)
-            self._ranked_call(lib().cc_db_verify_submit_packed, "cc_db_verify_submit_packed", tol, self.h, C.addressof(src),
-                              qidx.ctypes.data if qidx is not None else None, tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub),
-                              res.ctypes.data, d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream,
-                              C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None)
-        elif ranked is None:
-            _chk(lib().cc_db_verify_batch(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
-                                          tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
-                                          d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream),
-                 "cc_db_verify_batch", tolerate=tol)
-        else:
-            rc_, rn_, ro = L.rank_buffers(n, ranked)
-            rk = (rc_, rn_)
-            fn = "cc_db_verify_submit_ranked" + ("_detail" if det is not None else "")
-            self._ranked_call(getattr(lib(), fn), fn, tol, self.h, qdesc.data_ptr(), qdesc.shape[0],
-                              qidx.ctypes.data if qidx is not None else None, tab.ctypes.data, n, C.addressof(cfg), C.addressof(lb), C.addressof(ub),
-                              res.ctypes.data, d_h.data_ptr() if want_hints else None, d_n.data_ptr() if want_hints else None, stream,
-                              C.addressof(ro), *(() if det is None else (det.ctypes.data,)))
-        out = (res,)
+        r, d_h, d_n = self._verify(qdesc, cands, max_fine_opt, want_hints, qidx=qidx, levels=levels, max_key_dist_sq=max_key_dist_sq, lb=lb, ub=ub,
+                                   ranked=ranked, detail=detail, tolerate=(CC_ECAPACITY,) if allow_flagged else ())
+        hints = None
         if want_hints:
             cnt = d_n.cpu().numpy()
             allh = d_h.cpu().numpy().view(L.hint_dt).reshape(-1, L.HINT_MAX)
-            out += ([allh[i, :cnt[i]].copy() for i in range(n)],)
-        if rk is not None:
-            out += (rk,)
-        if det is not None:
-            out += (det,)
-        return out if len(out) > 1 else res
+            hints = [allh[i, :cnt[i]].copy() for i in range(len(r.res))]
+        return _ret(r.res, hints, r.rank, r.detail)
 
     def verify_submit(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
                       ranked=None, detail=False):
@@ -1050,77 +732,14 @@ class Database:
         (cc_db_verify_submit; verify and query chunks share the lanes and are collected together).  ranked=K: returns
         (results, (cands [n, K], counts [n])), with detail=True followed by the [n, K] detail array.  qdesc may be self.stored(idx)
         or a Packed, as for verify()."""
-        import torch
-        tab, qidx, cfg, lb, ub = self._verify_args(qdesc, cands, qidx, levels, max_key_dist_sq, lb, ub, max_fine_opt)
-        det = self._detail_args(len(tab), ranked, detail)
-        res = np.zeros(len(tab), L.query_result_dt)
-        self._pending = getattr(self, "_pending", [])
-        self._pending.append(res)  # the library writes into it until query_wait
-        stream = torch.cuda.current_stream(self._q_device(qdesc)).cuda_stream
-        if _is_src(qdesc):
-            src = self._src_args(qdesc)[0]
-            rk = ro = None
-            if ranked is not None:
-                rc_, rn_, ro = L.rank_buffers(len(tab), ranked)
-                rk = (rc_, rn_)
-            self._pending.append((qdesc, tab, qidx, rk, det))
-            _chk(lib().cc_db_verify_submit_packed(self.h, C.addressof(src), qidx.ctypes.data if qidx is not None else None, tab.ctypes.data, len(tab),
-                                                  C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data, None, None, stream,
-                                                  C.addressof(ro) if ro is not None else None, det.ctypes.data if det is not None else None),
-                 "cc_db_verify_submit_packed")
-            return res if rk is None else ((res, rk) if det is None else (res, rk, det))
-        if ranked is not None:
-            rc_, rn_, ro = L.rank_buffers(len(tab), ranked)
-            self._pending.append((rc_, rn_))
-            if det is not None:
-                self._pending.append(det)
-                _chk(lib().cc_db_verify_submit_ranked_detail(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
-                                                             tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub),
-                                                             res.ctypes.data, None, None, stream, C.addressof(ro), det.ctypes.data),
-                     "cc_db_verify_submit_ranked_detail")
-                return res, (rc_, rn_), det
-            _chk(lib().cc_db_verify_submit_ranked(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
-                                                  tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
-                                                  None, None, stream, C.addressof(ro)), "cc_db_verify_submit_ranked")
-            return res, (rc_, rn_)
-        _chk(lib().cc_db_verify_submit(self.h, qdesc.data_ptr(), qdesc.shape[0], qidx.ctypes.data if qidx is not None else None,
-                                       tab.ctypes.data, len(tab), C.addressof(cfg), C.addressof(lb), C.addressof(ub), res.ctypes.data,
-                                       None, None, stream), "cc_db_verify_submit")
-        return res
+        r = self._verify(qdesc, cands, max_fine_opt, qidx=qidx, levels=levels, max_key_dist_sq=max_key_dist_sq, lb=lb, ub=ub,
+                         ranked=ranked, detail=detail, wait=False, keep=self._held(qdesc))[0]
+        return _ret(r.res, r.rank, r.detail)
 
-    def _pose_args(self, qdesc, q, gidx, tf, refine, min_corr, tries, curvature):
-        import torch
-        if _is_src(qdesc):
-            if qdesc.idx is not None:
-                raise ValueError("score_poses names the records by q: give the source without idx")
-        else:
-            assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.is_contiguous() and qdesc.dim() == 2 and qdesc.shape[1] == DESC_BYTES
-        q = np.asarray(q).reshape(-1)
-        n = len(q)
-        if len(np.asarray(gidx).reshape(-1)) != n or np.asarray(tf).size != 3 * n:
-            raise ValueError("q, gidx and tf must name one item each: [n], [n] and [n, 3]")
-        items = L.pose_items(q, gidx, tf)
-        tr = tc = None
-        nt = 0
-        if tries is not None:
-            tr = np.ascontiguousarray(tries, np.float64)
-            if tr.ndim != 3 or tr.shape[0] != n or tr.shape[2] != 3:
-                raise ValueError("tries must have shape [n, T, 3]")
-            nt = tr.shape[1]
-            tc = np.zeros((n, nt), np.float64)
-        if min_corr is None:
-            min_corr = L.default_thresholds()[0].correlation
-        cfg = L.PoseCfg(int(refine), float(min_corr), nt, 0)
-        res = np.zeros(n, L.pose_result_dt)
-        cv = np.zeros(n, L.pose_curv_dt) if curvature else None
-        stream = torch.cuda.current_stream(self._q_device(qdesc)).cuda_stream
-        tail = (items.ctypes.data, n, C.addressof(cfg), tr.ctypes.data if nt else None, res.ctypes.data,
-                tc.ctypes.data if nt else None, cv.ctypes.data if curvature else None, stream)
-        if _is_src(qdesc):  # the arguments of cc_db_pose_submit_packed
-            src = self._src_args(qdesc)[0]
-            return (self.h, C.addressof(src)) + tail, (items, tr, cfg, src, qdesc), res, (tc if tries is not None else None), cv
-        args = (self.h, qdesc.data_ptr(), qdesc.shape[0]) + tail
-        return args, (items, tr, cfg), res, (tc if tries is not None else None), cv
+    def _pose(self, qdesc, q, gidx, tf, **kw):
+        """what score_poses() and score_poses_submit() share: the tensor checks, the stream, the call"""
+        skw, _dev, stream = self._source(qdesc, rows=True)
+        return calls.pose(lib(), self.h, q, gidx, tf, stream=stream, **skw, **kw)
 
     def score_poses(self, qdesc, q, gidx, tf, refine=True, min_corr=None, tries=None, curvature=False, allow_flagged=False):
         """Score, probe and refine relative poses the caller believes in, in one batch (cc_db_pose_batch: the reference's
@@ -1132,27 +751,21 @@ class Database:
         item, evaluated over the pair set of T_init.  curvature: Hessian and gradient of -correlation at the returned pose.
         Returns (res [n] of L.pose_result_dt, try_corr [n, T] or None, curv [n] of L.pose_curv_dt or None); a refined row
         carries L.PF_REFINED in flags.  allow_flagged: as for query()."""
-        args, keep, res, tc, cv = self._pose_args(qdesc, q, gidx, tf, refine, min_corr, tries, curvature)
-        if _is_src(qdesc):  # the submit followed by the wait
-            self._ranked_call(lib().cc_db_pose_submit_packed, "cc_db_pose_submit_packed", (CC_ECAPACITY,) if allow_flagged else (), *args)
-            return res, tc, cv
-        _chk(lib().cc_db_pose_batch(*args), "cc_db_pose_batch", tolerate=(CC_ECAPACITY,) if allow_flagged else ())
-        return res, tc, cv
+        r = self._pose(qdesc, q, gidx, tf, refine=refine, min_corr=min_corr, tries=tries, curvature=curvature,
+                       tolerate=(CC_ECAPACITY,) if allow_flagged else ())
+        return r.res, r.try_corr, r.curv
 
     def score_poses_submit(self, qdesc, q, gidx, tf, refine=True, min_corr=None, tries=None, curvature=False):
         """Asynchronous form of score_poses(): queues the batch and returns the same tuple, whose arrays are only valid after
         query_wait() (cc_db_pose_submit; pose chunks share the lanes with query and verify chunks and are collected together)."""
-        args, keep, res, tc, cv = self._pose_args(qdesc, q, gidx, tf, refine, min_corr, tries, curvature)
-        self._pending = getattr(self, "_pending", [])
-        self._pending.append((keep, res, tc, cv))  # the library reads and writes them until query_wait
-        _chk((lib().cc_db_pose_submit_packed if _is_src(qdesc) else lib().cc_db_pose_submit)(*args), "cc_db_pose_submit")
-        return res, tc, cv
+        r = self._pose(qdesc, q, gidx, tf, refine=refine, min_corr=min_corr, tries=tries, curvature=curvature, wait=False,
+                       keep=self._held(qdesc))
+        return r.res, r.try_corr, r.curv
 
     def debug_passes(self, cap=1152):
         """Constellations of the last check_hints call that passed all gates: numpy array of L.pass_dbg_dt."""
         out = np.zeros(cap, L.pass_dbg_dt)
         n = C.c_int()
-        lib().cc_db_debug_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _chk(lib().cc_db_debug_passes(self.h, out.ctypes.data, cap, C.byref(n)), "cc_db_debug_passes")
         return out[:n.value]
 

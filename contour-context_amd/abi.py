@@ -1,0 +1,133 @@
+"""The ctypes signature of every function include/cont2_amd.h declares, in one table, and bind() to apply it to a loaded
+library (the product's, the CPU harness's, another build).  tests/test_abi_layout.py holds the table against the header.
+
+One line per prototype, in the header's order: return code, name, one code per parameter.
+  parameters   P any pointer or array   I int / int32_t   Q int64_t   Z size_t   D double   F float   (- : none)
+  return       I int   V void   S const char *   P any other pointer"""
+import ctypes as C
+
+_SPEC = """
+V cc_default_manager_cfg P
+V cc_default_db_cfg P
+V cc_default_thresholds PP
+S cc_last_error -
+I cc_version -
+I cc_runtime_init II
+I cc_create IPIP
+I cc_destroy P
+I cc_profile_enable PI
+I cc_profile_read PPP
+I cc_ingest_batch PPPIPPP
+I cc_ingest_host PPPIP
+I cc_ingest_host_bev PPPIPP
+I cc_ingest_points PPPPIPPPP
+I cc_ingest_points_host PPPPIPPP
+I cc_ingest_segments PPPIPPP
+I cc_ingest_segments_host PPPIPP
+I cc_ingest_points_motion PPPPPIPPPPP
+I cc_ingest_points_motion_host PPPPPIPPPP
+V cc_motion_knots PPDIP
+I cc_range_sensor_create PPP
+I cc_range_sensor_destroy P
+I cc_ingest_ranges PPPIPPPP
+I cc_ingest_ranges_host PPPIPPP
+P cc_stage_points PQ
+P cc_stage_points_slot PQI
+I cc_stage_points_cancel PP
+I cc_scan_ingest PPQIP
+I cc_scan_ingest_batch PPPIP
+I cc_scan_ingest_points PPPQPIP
+I cc_scan_ingest_points_batch PPPPIPP
+I cc_scan_ingest_segments PPIIP
+I cc_scan_ingest_points_motion PPPPQPPIP
+I cc_scan_ingest_ranges PPPPIP
+I cc_scan_ready P
+I cc_scan_desc PP
+I cc_scan_bev PP
+I cc_scan_offload P
+I cc_scan_on_device P
+I cc_scan_release P
+I cc_db_create PPIP
+I cc_db_destroy P
+I cc_db_size P
+I cc_db_knn_stride P
+I cc_db_add_scans PPIPPP
+I cc_db_add_scans_prepare PPIP
+I cc_db_query_batch PPIPPPPPPP
+I cc_db_query_submit PPIPPPPPPP
+I cc_db_query_wait P
+I cc_db_add_scan_host PPDI
+I cc_db_query_host PPPPP
+I cc_db_query_scan PPPPP
+I cc_db_add_scan PPDI
+I cc_db_query_scan_submit PPIPPP
+I cc_db_query_collect PPI
+I cc_db_add_scan_prepare PP
+I cc_db_add_scan_batch PPIPP
+I cc_db_query_scan_batch_submit PPIPPPP
+I cc_db_add_scans_host PPIPP
+I cc_db_query_batch_host PPIPPPP
+I cc_db_check_hints PPPIPPIPPP
+I cc_db_check_hints_host PPPIPPIPP
+I cc_db_verify_submit PPIPPIPPPPPPP
+I cc_db_verify_batch PPIPPIPPPPPPP
+I cc_db_verify_batch_host PPIPPIPPPP
+I cc_db_query_submit_ranked PPIPPPPPPPP
+I cc_db_query_batch_host_ranked PPIPPPPP
+I cc_db_query_scan_batch_submit_ranked PPIPPPPP
+I cc_db_verify_submit_ranked PPIPPIPPPPPPPP
+I cc_db_check_hints_ranked PPPIPPIPPPP
+I cc_db_verify_batch_host_ranked PPIPPIPPPPP
+I cc_db_check_hints_host_ranked PPPIPPIPPP
+I cc_db_query_submit_ranked_detail PPIPPPPPPPPP
+I cc_db_query_batch_host_ranked_detail PPIPPPPPP
+I cc_db_query_scan_batch_submit_ranked_detail PPIPPPPPP
+I cc_db_verify_submit_ranked_detail PPIPPIPPPPPPPPP
+I cc_db_verify_batch_host_ranked_detail PPIPPIPPPPPP
+I cc_db_check_hints_ranked_detail PPPIPPIPPPPP
+I cc_db_check_hints_host_ranked_detail PPPIPPIPPPP
+I cc_db_pose_submit PPIPIPPPPPP
+I cc_db_pose_batch PPIPIPPPPPP
+I cc_db_pose_batch_host PPIPIPPPPP
+I cc_db_query_submit_packed PPPIPPPPPPPPP
+I cc_db_verify_submit_packed PPPPIPPPPPPPPP
+I cc_db_pose_submit_packed PPPIPPPPPP
+I cc_db_query_submit_masked PPPPIPPPPPPPPPP
+I cc_db_query_batch_host_masked PPIPPPPPPP
+I cc_mask_gates PPIPIPIP
+I cc_db_debug_knn_chunks PP
+I cc_db_debug_passes PPIP
+V cc_packed_sizes PP
+I cc_pack_scans PPIPPP
+I cc_db_add_packed PPPIPPP
+P cc_db_hot_ptr P
+P cc_db_feat_ptr P
+I cc_db_profile_enable PI
+I cc_db_profile_read PPP
+I cc_db_set_lanes PI
+I cc_db_set_dynamic_thres PI
+I cc_db_bucket_state PPP
+I cc_comm_unique_id P
+I cc_comm_create IIIPP
+I cc_comm_create_from_env PPP
+I cc_comm_rank P
+I cc_comm_world P
+I cc_comm_allgather_packed PPPZP
+I cc_comm_destroy P
+V cc_est_sens_tf PIIP
+V cc_est_sens_info PPIIP
+"""
+
+_ARG = {"P": C.c_void_p, "I": C.c_int, "Q": C.c_int64, "Z": C.c_size_t, "D": C.c_double, "F": C.c_float}
+_RET = {"I": C.c_int, "V": None, "S": C.c_char_p, "P": C.c_void_p}
+
+# symbol -> (restype, argtypes)
+SIGNATURES = {name: (_RET[ret], [_ARG[a] for a in args.strip("-")]) for ret, name, args in (ln.split() for ln in _SPEC.split("\n") if ln)}
+
+
+def bind(cdll):
+    """Give every function of the table its restype and argtypes on `cdll` (a library that lacks one is an AttributeError)."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(cdll, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return cdll

@@ -1,0 +1,237 @@
+"""The marshalling of the scoring flows of include/cont2_amd.h -- query, verify, check-hints, pose -- free of torch: one function
+per flow prepares the host buffers, chooses the entry point, builds its argument tuple, calls it and (in the synchronous forms)
+waits.  Every function takes the bound library (abi.bind) and the database handle; device memory arrives as integer addresses
+or None, host arrays as numpy arrays, the stream as an integer or None.  Database (the package) and the CPU-harness drivers of
+the test suite both sit on top of it; no caller needs the C argument order of an entry point.
+
+wait=True is the synchronous form of the flow, wait=False leaves the batch in flight until cc_db_query_wait.  A submit may fail
+with some of its chunks queued, and the library goes on writing into their buffers until the wait: a caller of a wait=False form
+hands in `keep`, a list it holds until its wait, and the flow appends its buffers to it before the entry point is called.  Which
+entry point runs is behaviour (a synchronous *_batch cuts one chunk per lane, a submit + wait whole chunks):
+  query    descriptors: cc_db_query_batch (wait) / cc_db_query_submit; ranked: cc_db_query_submit_ranked[_detail];
+           a record source: cc_db_query_submit_packed; a mask, either kind of query: cc_db_query_submit_masked
+  verify   descriptors: cc_db_verify_batch (wait) / cc_db_verify_submit; ranked: cc_db_verify_submit_ranked[_detail];
+           a record source: cc_db_verify_submit_packed
+  hints    cc_db_check_hints[_ranked[_detail]] (synchronous by itself)
+  pose     descriptors: cc_db_pose_batch (wait) / cc_db_pose_submit; a record source: cc_db_pose_submit_packed"""
+import ctypes as C
+
+import numpy as np
+
+import layouts as L
+
+CC_ECAPACITY = -4
+
+
+class CCError(RuntimeError):
+    rc = 0
+
+
+def _error(what, rc, msg):
+    e = CCError("%s failed (%d): %s" % (what, rc, msg))
+    e.rc = rc
+    return e
+
+
+def chk(lib, rc, what, tolerate=()):
+    if rc != 0 and rc not in tolerate:
+        raise _error(what, rc, lib.cc_last_error().decode())
+    return rc
+
+
+class Out:
+    """What a flow hands back: its host outputs by name (None where the form has none) and `keep`, every object the library
+    reads or writes until the wait."""
+
+    def __init__(self, keep, **outs):
+        self.keep = keep
+        self.__dict__.update(outs)
+
+
+def _a(x):
+    """the address of a numpy array or a ctypes structure; None stays NULL"""
+    if x is None:
+        return None
+    return x.ctypes.data if isinstance(x, np.ndarray) else C.addressof(x)
+
+
+def _call(lib, db, fn, args, wait, tolerate, keep, held):
+    """Call entry point `fn`, with `held` (what it reads and writes) registered in the caller's `keep` list first.  A submit with
+    wait set is followed by the wait; a refused submit keeps its own message, and nothing of it may stay in flight."""
+    if keep is not None:
+        keep.append(held)
+    rc = getattr(lib, fn)(*args)
+    if not wait or fn.endswith("_batch"):  # left in flight, or synchronous by itself
+        return chk(lib, rc, fn, tolerate)
+    if rc != 0 and rc not in tolerate:
+        msg = lib.cc_last_error().decode()
+        lib.cc_db_query_wait(db)
+        raise _error(fn, rc, msg)
+    return chk(lib, lib.cc_db_query_wait(db), "cc_db_query_wait", tolerate)
+
+
+def detail_buffer(n, ranked, detail):
+    """detail=True: the h_detail buffer of a *_ranked_detail call ([n, ranked] of L.ranked_detail_dt), else None"""
+    if not detail:
+        return None
+    if ranked is None:
+        raise ValueError("detail=True needs ranked=K: the detail rows belong to the entries of the ranked list")
+    return L.rank_detail_buffer(n, ranked)
+
+
+def _rank(n, ranked, detail):
+    """-> ((cands, counts) or None, cc_rank_out_t or None, detail array or None)"""
+    det = detail_buffer(n, ranked, detail)
+    if ranked is None:
+        return None, None, None
+    cands, cnt, ro = L.rank_buffers(n, ranked)
+    return (cands, cnt), ro, det
+
+
+def _ranked_fn(stem, ro, det):
+    """the descriptor form's entry point with a ranked list (and detail), and the arguments it takes after the stream"""
+    return stem + "_ranked" + ("_detail" if det is not None else ""), (_a(ro),) + (() if det is None else (_a(det),))
+
+
+def query(lib, db, epochs, qdesc=None, src=None, idx=None, mask=None, lb=None, ub=None, knn=None, knn_cnt=None, stream=None,
+          ranked=None, detail=False, wait=True, tolerate=(), keep=None):
+    """qdesc: the descriptors' address, or src: an L.PackedSrc with idx, its record selector (None: query i is record i).
+    mask: (bits address, n_rows, row_words, int32 rows [nq]).  -> Out(res, rank, detail)"""
+    epochs = np.ascontiguousarray(epochs, np.int32).reshape(-1)
+    nq = len(epochs)
+    rk, ro, det = _rank(nq, ranked, detail) if ranked is not None or detail else (None, None, None)
+    if lb is None:
+        lb, ub = L.default_thresholds()
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        if len(idx) != nq:
+            raise ValueError("the source names %d records for %d epochs" % (len(idx), nq))
+    cm = None
+    if mask is not None:
+        bits, n_rows, row_words, rows = mask
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        if len(rows) != nq:
+            raise ValueError("the mask names rows for %d queries, the call has %d" % (len(rows), nq))
+        cm = L.ScanMaskC(bits, int(n_rows), int(row_words), rows.ctypes.data)
+        mask = (rows, cm)
+    res = np.zeros(nq, L.query_result_dt)
+    mid = (nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub), res.ctypes.data, knn, knn_cnt, stream)
+    if cm is not None:
+        fn, args = "cc_db_query_submit_masked", (db, qdesc, _a(src), _a(idx)) + mid + (_a(ro), _a(det), _a(cm))
+    elif src is not None:
+        fn, args = "cc_db_query_submit_packed", (db, _a(src), _a(idx)) + mid + (_a(ro), _a(det))
+    elif ranked is not None:
+        fn, tail = _ranked_fn("cc_db_query_submit", ro, det)
+        args = (db, qdesc) + mid + tail
+    else:
+        fn, args = "cc_db_query_batch" if wait else "cc_db_query_submit", (db, qdesc) + mid
+    held = (src, idx, epochs, lb, ub, res, rk, ro, det, mask)
+    _call(lib, db, fn, args, wait, tolerate, keep, held)
+    return Out(held, res=res, rank=rk, detail=det)
+
+
+def cand_table(cands):
+    """an int array [n, <= VERIFY_CANDS_MAX] padded with -1, or a list of lists -> int32 [n, VERIFY_CANDS_MAX] padded with -1"""
+    if isinstance(cands, np.ndarray):
+        rows = np.asarray(cands, np.int64).reshape(len(cands), -1)
+    else:
+        rows = [list(c) for c in cands]
+    tab = np.full((len(rows), L.VERIFY_CANDS_MAX), -1, np.int32)
+    for i, c in enumerate(rows):
+        if len(c) > L.VERIFY_CANDS_MAX:
+            if any(int(v) != -1 for v in c[L.VERIFY_CANDS_MAX:]):
+                raise ValueError("item %d: more than VERIFY_CANDS_MAX = %d candidates" % (i, L.VERIFY_CANDS_MAX))
+            c = c[:L.VERIFY_CANDS_MAX]
+        tab[i, :len(c)] = c
+    return tab
+
+
+def level_mask(levels):
+    """hint levels 1..4 -> cc_verify_cfg_t.level_mask; None: 0, which the library reads as all four"""
+    if levels is None:
+        return 0
+    mask = 0
+    for lv in levels:
+        if not 1 <= int(lv) <= 4:
+            raise ValueError("hint levels are 1..4")
+        mask |= 1 << (int(lv) - 1)
+    if mask == 0:
+        raise ValueError("no hint level given")
+    return mask
+
+
+def verify(lib, db, cands, qdesc=None, n_desc=0, src=None, idx=None, qidx=None, levels=(1, 2, 3, 4), max_fine_opt=10, max_key_dist_sq=1000.0,
+           lb=None, ub=None, hints=None, n_hints=None, stream=None, ranked=None, detail=False, wait=True, tolerate=(), keep=None):
+    """cands: see cand_table; item i is descriptor (or record) qidx[i] (None: i).  levels: see level_mask.  hints / n_hints: device addresses of the generated hint lists.  -> Out(res, rank, detail)"""
+    if lb is None:
+        lb, ub = L.default_thresholds()
+    if src is not None:
+        if idx is not None and qidx is not None:
+            raise ValueError("name the records by the source's idx or by qidx, not both")
+        qidx = idx if qidx is None else qidx
+    tab = cand_table(cands)
+    n = len(tab)
+    if qidx is not None:
+        qidx = np.ascontiguousarray(qidx, np.int32)
+        if len(qidx) != n:
+            raise ValueError("qidx must name one descriptor per item")
+    cfg = L.VerifyCfg(level_mask(levels), int(max_fine_opt), float(max_key_dist_sq), 0)
+    rk, ro, det = _rank(n, ranked, detail)
+    res = np.zeros(n, L.query_result_dt)
+    mid = (_a(qidx), _a(tab), n, _a(cfg), _a(lb), _a(ub), _a(res), hints, n_hints, stream)
+    if src is not None:
+        fn, args = "cc_db_verify_submit_packed", (db, _a(src)) + mid + (_a(ro), _a(det))
+    elif ranked is not None:
+        fn, tail = _ranked_fn("cc_db_verify_submit", ro, det)
+        args = (db, qdesc, n_desc) + mid + tail
+    else:
+        fn, args = "cc_db_verify_batch" if wait else "cc_db_verify_submit", (db, qdesc, n_desc) + mid
+    held = (src, qidx, tab, cfg, lb, ub, res, rk, ro, det)
+    _call(lib, db, fn, args, wait, tolerate, keep, held)
+    return Out(held, res=res, rank=rk, detail=det)
+
+
+def check_hints(lib, db, qdesc, hints, lb=None, ub=None, max_fine_opt=10, stream=None, ranked=None, detail=False):
+    """qdesc: the address of the query scan's descriptor; hints: array of L.hint_dt.  -> Out(res [1], scores, rank, detail)"""
+    rk, ro, det = _rank(1, ranked, detail)
+    if lb is None:
+        lb, ub = L.default_thresholds()
+    hints = np.ascontiguousarray(hints, L.hint_dt)
+    res = np.zeros(1, L.query_result_dt)
+    sc = np.zeros(len(hints), L.hint_score_dt)
+    fn, tail = ("cc_db_check_hints", ()) if ranked is None else _ranked_fn("cc_db_check_hints", ro, det)
+    chk(lib, getattr(lib, fn)(db, qdesc, _a(hints), len(hints), _a(lb), _a(ub), int(max_fine_opt), _a(res), _a(sc), stream, *tail), fn)
+    return Out((), res=res, scores=sc, rank=rk, detail=det)
+
+
+def pose(lib, db, q, gidx, tf, qdesc=None, n_desc=0, src=None, idx=None, refine=True, min_corr=None, tries=None, curvature=False,
+         stream=None, wait=True, tolerate=(), keep=None):
+    """Item i: descriptor (or record of src) q[i] against database scan gidx[i] at tf[i].  -> Out(res, try_corr, curv)"""
+    if src is not None and idx is not None:
+        raise ValueError("score_poses names the records by q: give the source without idx")
+    q = np.asarray(q).reshape(-1)
+    n = len(q)
+    if len(np.asarray(gidx).reshape(-1)) != n or np.asarray(tf).size != 3 * n:
+        raise ValueError("q, gidx and tf must name one item each: [n], [n] and [n, 3]")
+    items = L.pose_items(q, gidx, tf)
+    tr = tc = None
+    nt = 0
+    if tries is not None:
+        tr = np.ascontiguousarray(tries, np.float64)
+        if tr.ndim != 3 or tr.shape[0] != n or tr.shape[2] != 3:
+            raise ValueError("tries must have shape [n, T, 3]")
+        nt = tr.shape[1]
+        tc = np.zeros((n, nt), np.float64)
+    if min_corr is None:
+        min_corr = L.default_thresholds()[0].correlation
+    cfg = L.PoseCfg(int(refine), float(min_corr), nt, 0)
+    res = np.zeros(n, L.pose_result_dt)
+    cv = np.zeros(n, L.pose_curv_dt) if curvature else None
+    tail = (_a(items), n, _a(cfg), _a(tr) if nt else None, _a(res), _a(tc) if nt else None, _a(cv), stream)
+    if src is not None:
+        fn, args = "cc_db_pose_submit_packed", (db, _a(src)) + tail
+    else:
+        fn, args = "cc_db_pose_batch" if wait else "cc_db_pose_submit", (db, qdesc, n_desc) + tail
+    held = (src, items, tr, cfg, res, tc, cv)
+    _call(lib, db, fn, args, wait, tolerate, keep, held)
+    return Out(held, res=res, try_corr=tc, curv=cv)

@@ -19,6 +19,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import evaluator as E  # noqa: E402
+import abi             # noqa: E402
 import layouts as L    # noqa: E402
 import pr_eval         # noqa: E402
 
@@ -83,8 +84,7 @@ def run(config_path, lib_path=None, chunk=256, verbose=True, dynamic_thres=False
         sys.modules["contour_context_amd"] = pkg
         spec.loader.exec_module(pkg)
         lib_path = pkg.LIB_PATH
-    lib = C.CDLL(lib_path)
-    lib.cc_last_error.restype = C.c_char_p
+    lib = abi.bind(C.CDLL(lib_path))
 
     def chk(rc, what):
         if rc != 0:

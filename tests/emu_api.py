@@ -6,6 +6,9 @@ import subprocess
 
 import numpy as np
 
+import cc_amd
+
+abi, calls = cc_amd.load().abi, cc_amd.load().calls
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "emu", "libcc_emu.so")
 
@@ -27,19 +30,19 @@ def build(variant=None, flags=()):
 SMALL_GRIDS = {"CC_B1_GRID": "6", "CC_B2_GRID": "6", "CC_GMM_GRID": "6"}
 
 
+def levels_of(mask):
+    """a cc_verify_cfg_t.level_mask -> the levels= of calls.verify (0, the library's "all four", is None)"""
+    return [lv for lv in (1, 2, 3, 4) if mask >> (lv - 1) & 1] or None
+
+
 class EmuApi:
     def __init__(self, L, so=None):
         self.L = L
-        self.lib = C.CDLL(so or build())
-        self.lib.cc_last_error.restype = C.c_char_p
-        self.lib.cc_packed_sizes.restype = None
-        for f in ("cc_create", "cc_destroy", "cc_ingest_batch", "cc_ingest_host", "cc_db_create", "cc_db_destroy", "cc_db_size",
-                  "cc_db_add_scans", "cc_db_add_scans_prepare", "cc_db_query_batch", "cc_db_query_submit", "cc_db_query_wait", "cc_db_bucket_state", "cc_db_check_hints", "cc_pack_scans", "cc_db_add_packed"):
-            getattr(self.lib, f).restype = C.c_int
+        self.lib = abi.bind(C.CDLL(so or build()))
+        self.keep = []  # what the submits in flight read and write, until db_query_wait
 
     def chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError("%s failed (%d): %s" % (what, rc, self.lib.cc_last_error().decode()))
+        calls.chk(self.lib, rc, what)
 
     def create(self, cfg=None, max_batch=8):
         cfg = cfg or self.L.default_manager_cfg()
@@ -123,46 +126,29 @@ class EmuApi:
 
     def db_query(self, db, qdesc, epochs, lb=None, ub=None, want_knn=False):
         L = self.L
-        if lb is None:
-            lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
-        epochs = np.ascontiguousarray(epochs, np.int32)
         nq = len(qdesc)
-        res = np.zeros(nq, L.query_result_dt)
         knn = np.zeros((nq, 3, L.NPIV, L.KNN_MAX), L.knn_hit_dt) if want_knn else None
         cnt = np.zeros((nq, 3, L.NPIV), np.int32) if want_knn else None
-        self.chk(self.lib.cc_db_query_batch(db, C.c_void_p(qdesc.ctypes.data), nq, C.c_void_p(epochs.ctypes.data), C.byref(lb),
-                                            C.byref(ub), C.c_void_p(res.ctypes.data),
-                                            C.c_void_p(knn.ctypes.data) if want_knn else None,
-                                            C.c_void_p(cnt.ctypes.data) if want_knn else None, None), "cc_db_query_batch")
+        res = calls.query(self.lib, db, epochs, qdesc=qdesc.ctypes.data, lb=lb, ub=ub, knn=knn.ctypes.data if want_knn else None,
+                          knn_cnt=cnt.ctypes.data if want_knn else None).res
         return (res, knn, cnt) if want_knn else res
 
     def db_query_submit(self, db, qdesc, epochs):
         """cc_db_query_submit: returns (result array, keep-alive tuple); valid after db_query_wait."""
-        L = self.L
-        lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
-        epochs = np.ascontiguousarray(epochs, np.int32)
-        res = np.zeros(len(qdesc), L.query_result_dt)
-        self.chk(self.lib.cc_db_query_submit(db, C.c_void_p(qdesc.ctypes.data), len(qdesc), C.c_void_p(epochs.ctypes.data), C.byref(lb),
-                                             C.byref(ub), C.c_void_p(res.ctypes.data), None, None, None), "cc_db_query_submit")
-        return res, (qdesc, epochs)
+        self.keep.append(qdesc)
+        r = calls.query(self.lib, db, epochs, qdesc=qdesc.ctypes.data, wait=False, keep=self.keep)
+        return r.res, (qdesc, r.keep)
 
     def db_query_wait(self, db):
         self.chk(self.lib.cc_db_query_wait(db), "cc_db_query_wait")
+        self.keep = []
 
     def check_hints(self, db, qdesc, hints, lb=None, ub=None, max_fine_opt=10):
-        L = self.L
-        if lb is None:
-            lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
-        hints = np.ascontiguousarray(hints, L.hint_dt)
-        res = np.zeros(1, L.query_result_dt)
-        sc = np.zeros(len(hints), L.hint_score_dt)
-        self.chk(self.lib.cc_db_check_hints(db, C.c_void_p(qdesc.ctypes.data), C.c_void_p(hints.ctypes.data), len(hints), C.byref(lb),
-                                            C.byref(ub), int(max_fine_opt), C.c_void_p(res.ctypes.data), C.c_void_p(sc.ctypes.data),
-                                            None), "cc_db_check_hints")
-        return res[0], sc
+        r = calls.check_hints(self.lib, db, qdesc.ctypes.data, hints, lb, ub, max_fine_opt)
+        return r.res[0], r.scores
 
     def bucket_state(self, db):
         sizes = np.zeros((3, 6), np.int32)

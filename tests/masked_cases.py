@@ -2,8 +2,6 @@
 (tests/test_emu_masked_query.py) and the GPU (tests/test_gpu_masked_query.py).  A case takes a `dev`: an adapter with
 open / add / query / raw_rc / gates / close over one of the two (EmuDev below, GpuDev in the GPU test file).  The oracle is
 tests/masked_oracle.py: the reference's query on trees filtered to the allowed scans."""
-import ctypes as C
-
 import numpy as np
 
 import masked_oracle
@@ -36,15 +34,6 @@ class EmuDev:
 
     def open(self, dcfg, cap, lanes=None, dyn=False):
         self.e = P.PackedEmu(self.L, dcfg, cap=cap, lanes=lanes, dyn=dyn)
-        lib = self.e.lib
-        V = C.c_void_p
-        for f in ("cc_db_query_submit_masked", "cc_db_query_batch_host_masked", "cc_mask_gates"):
-            getattr(lib, f).restype = C.c_int
-        lib.cc_db_query_submit_masked.argtypes = [V, V, V, V, C.c_int] + [V] * 10
-        lib.cc_db_query_batch_host_masked.argtypes = [V, V, C.c_int] + [V] * 7
-        lib.cc_mask_gates.argtypes = [V, V, C.c_int, V, C.c_int, V, C.c_int, V]
-        lib.cc_db_debug_knn_chunks.argtypes = [V, V]
-        lib.cc_db_debug_knn_chunks.restype = C.c_int
         return self
 
     def close(self):
@@ -59,44 +48,47 @@ class EmuDev:
     def set_dyn(self, on):
         self.e.api.chk(self.e.lib.cc_db_set_dynamic_thres(self.e.db, on), "cc_db_set_dynamic_thres")
 
-    def _mask(self, table, rows):
-        if table is None:
-            return None
-        table = np.ascontiguousarray(table, np.uint32)
-        rows = np.ascontiguousarray(rows, np.int32)
-        m = self.L.ScanMaskC(table.ctypes.data, table.shape[0], table.shape[1], rows.ctypes.data)
-        self.e.keep.append((table, rows, m))
-        return m
-
     def query(self, qdesc, epochs, table=None, rows=None, want_knn=True, ranked=None, detail=False, src="desc", rec=None, host=False):
         """src: "desc" (qdesc: descriptors), "stored" (rec: database indices) or "packed" (qdesc packed here, rec: its rows);
         host: cc_db_query_batch_host_masked (descriptors only, no hit lists)."""
         L, e = self.L, self.e
-        lb, ub = L.default_thresholds()
-        epochs = np.ascontiguousarray(epochs, np.int32)
-        nq = len(epochs)
-        res = np.zeros(nq, L.query_result_dt)
-        ro, rc_, rn_, det = e._modes(nq, ranked, detail)
+        nq = len(np.asarray(epochs).reshape(-1))
         ks = e.lib.cc_db_knn_stride(e.db)
         knn = np.zeros((nq, 3, L.NPIV, ks), L.knn_hit_dt) if want_knn and not host else None
         cnt = np.zeros((nq, 3, L.NPIV), np.int32) if want_knn and not host else None
-        m = self._mask(table, rows)
-        qd = source = r = None
-        if src == "desc":
-            qd = np.ascontiguousarray(qdesc)
-        else:
-            source = e.src(None if src == "stored" else e.pack(qdesc))
-            r = None if rec is None else np.ascontiguousarray(rec, np.int32)
-        e.keep.append((qd, source, r, epochs, res, ro, rc_, rn_, det, knn, cnt, lb, ub))
+        if table is not None:
+            table = np.ascontiguousarray(table, np.uint32)
         if host:
+            lb, ub = L.default_thresholds()
+            epochs, rows = np.ascontiguousarray(epochs, np.int32), np.ascontiguousarray(rows, np.int32)
+            qd = np.ascontiguousarray(qdesc)
+            res = np.zeros(nq, L.query_result_dt)
+            ro, rc_, rn_, det = e._modes(nq, ranked, detail)
+            m = None if table is None else L.ScanMaskC(table.ctypes.data, table.shape[0], table.shape[1], rows.ctypes.data)
             rc = e.lib.cc_db_query_batch_host_masked(e.db, P._p(qd), nq, P._p(epochs), P._b(lb), P._b(ub), P._p(res), P._b(ro), P._p(det), P._b(m))
             e.api.chk(rc, "cc_db_query_batch_host_masked")
-        else:
-            rc = e.lib.cc_db_query_submit_masked(e.db, P._p(qd), P._b(source), P._p(r), nq, P._p(epochs), P._b(lb), P._b(ub), P._p(res), P._p(knn),
-                                                 P._p(cnt), None, P._b(ro), P._p(det), P._b(m))
-            e.api.chk(rc, "cc_db_query_submit_masked")
+            return P.PackedEmu._out(res, rc_, rn_, det)
+        if table is None:  # the masked entry point with mask NULL: a form of the C-ABI alone
+            assert src == "desc" and ranked is None
+            lb, ub = L.default_thresholds()
+            epochs, qd, res = np.ascontiguousarray(epochs, np.int32), np.ascontiguousarray(qdesc), np.zeros(nq, L.query_result_dt)
+            e.keep.append((qd, epochs, res, knn, cnt, lb, ub))
+            e.api.chk(e.lib.cc_db_query_submit_masked(e.db, P._p(qd), None, None, nq, P._p(epochs), P._b(lb), P._b(ub), P._p(res), P._p(knn),
+                                                      P._p(cnt), None, None, None, None), "cc_db_query_submit_masked")
             e.wait()
-        return P.PackedEmu._out(res, rc_, rn_, det, knn=knn, knn_cnt=cnt)
+            return P.PackedEmu._out(res, None, None, None, knn=knn, knn_cnt=cnt)
+        kw = {"mask": (table.ctypes.data, table.shape[0], table.shape[1], rows)}
+        if src == "desc":
+            qd = np.ascontiguousarray(qdesc)
+            kw["qdesc"] = qd.ctypes.data
+        else:
+            qd = e.src(None if src == "stored" else e.pack(qdesc))
+            kw.update(src=qd, idx=rec)
+        e.keep.append((qd, table, knn, cnt))
+        r = P.calls.query(e.lib, e.db, epochs, knn=P._p(knn), knn_cnt=P._p(cnt), ranked=ranked, detail=detail, wait=False, keep=e.keep, **kw)
+        e.wait()
+        rk = r.rank or (None, None)
+        return P.PackedEmu._out(r.res, rk[0], rk[1], r.detail, knn=knn, knn_cnt=cnt)
 
     def unmasked(self, qdesc, epochs, want_knn=True, ranked=None, detail=False):
         """the descriptor form's existing entry points (cc_db_query_submit[_ranked[_detail]])"""

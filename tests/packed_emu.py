@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 import emu_api
+from emu_api import calls
 
 CMAX = 8  # CC_VERIFY_CANDS_MAX
 CC_EINVAL = -1
@@ -21,7 +22,7 @@ def aligned(shape, dtype, align=16, off=0):
 
 
 def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
+    return None if a is None else a.ctypes.data
 
 
 def _b(s):
@@ -33,26 +34,6 @@ class PackedEmu:
         self.L = L
         self.api = emu_api.EmuApi(L, so)
         lib = self.lib = self.api.lib
-        for f in ("cc_db_query_submit_packed", "cc_db_verify_submit_packed", "cc_db_pose_submit_packed", "cc_db_query_submit_ranked",
-                  "cc_db_query_submit_ranked_detail", "cc_db_verify_submit", "cc_db_verify_submit_ranked", "cc_db_verify_submit_ranked_detail",
-                  "cc_db_pose_submit", "cc_db_set_lanes", "cc_db_set_dynamic_thres", "cc_db_knn_stride"):
-            getattr(lib, f).restype = C.c_int
-        V = C.c_void_p
-        lib.cc_db_query_submit_packed.argtypes = [V, V, V, C.c_int] + [V] * 9
-        lib.cc_db_verify_submit_packed.argtypes = [V, V, V, V, C.c_int] + [V] * 9
-        lib.cc_db_pose_submit_packed.argtypes = [V, V, V, C.c_int] + [V] * 6
-        lib.cc_db_query_submit.argtypes = [V, V, C.c_int] + [V] * 7
-        lib.cc_db_query_submit_ranked.argtypes = [V, V, C.c_int] + [V] * 8
-        lib.cc_db_query_submit_ranked_detail.argtypes = [V, V, C.c_int] + [V] * 9
-        lib.cc_db_verify_submit.argtypes = [V, V, C.c_int, V, V, C.c_int] + [V] * 7
-        lib.cc_db_verify_submit_ranked.argtypes = [V, V, C.c_int, V, V, C.c_int] + [V] * 8
-        lib.cc_db_verify_submit_ranked_detail.argtypes = [V, V, C.c_int, V, V, C.c_int] + [V] * 9
-        lib.cc_db_pose_submit.argtypes = [V, V, C.c_int, V, C.c_int] + [V] * 6
-        lib.cc_db_set_lanes.argtypes = [V, C.c_int]
-        lib.cc_db_set_dynamic_thres.argtypes = [V, C.c_int]
-        lib.cc_db_knn_stride.argtypes = [V]
-        lib.cc_db_query_wait.argtypes = [V]
-        lib.cc_db_size.argtypes = [V]
         self.ctx = self.api.create(max_batch=8)
         self.db = self.api.db_create(self.ctx, dcfg, cap=cap)
         if lanes is not None:
@@ -62,9 +43,7 @@ class PackedEmu:
         self.keep = []
 
     def close(self):
-        self.lib.cc_db_destroy.argtypes = [C.c_void_p]
         self.lib.cc_db_destroy(self.db)
-        self.lib.cc_destroy.argtypes = [C.c_void_p]
         self.lib.cc_destroy(self.ctx)
 
     def add(self, desc, ts, seeds):
@@ -110,109 +89,66 @@ class PackedEmu:
         o.update({k: v for k, v in more.items() if v is not None})
         return o
 
+    def _run(self, flow, wait, raw_rc, source, *args, **kw):
+        """A flow of `calls` as its submit form on `source`: a descriptor array or a cc_packed_src_t.  -> (Out, its rank pair), or
+        with raw_rc (None, the submit's return code); the wait is this driver's.  raw_rc reaches the library's own validation only
+        with inputs that pass the checks calls.py makes first (the lengths of idx and qidx, the shape of tries, at most
+        VERIFY_CANDS_MAX candidates): those raise ValueError here; a refusal test of such an input calls self.lib directly."""
+        if isinstance(source, self.L.PackedSrc):
+            kw["src"] = source
+        else:
+            qd = np.ascontiguousarray(source)
+            self.keep.append(qd)
+            kw["qdesc"] = qd.ctypes.data
+            if flow is not calls.query:
+                kw["n_desc"] = len(qd)
+        try:
+            r = flow(self.lib, self.db, *args, wait=False, keep=self.keep, **kw)
+        except calls.CCError as e:
+            if raw_rc:
+                return None, e.rc
+            raise
+        if raw_rc:
+            return None, 0
+        if wait:
+            self.wait()
+        rk = r.rank if getattr(r, "rank", None) is not None else (None, None)
+        return r, rk
+
     # ---- query ----
     def query(self, source, rec, epochs, ranked=None, detail=False, want_knn=False, wait=True, lb=None, ub=None, raw_rc=False):
         """source: a descriptor array (the descriptor path on desc[rec]) or a cc_packed_src_t (the packed path on records rec;
         rec None: record i).  Returns the outputs (valid after wait()); raw_rc: the submit's return code instead."""
         L = self.L
-        if lb is None:
-            lb, ub = L.default_thresholds()
-        epochs = np.ascontiguousarray(epochs, np.int32)
-        nq = len(epochs)
-        res = np.zeros(nq, L.query_result_dt)
-        ro, rc_, rn_, det = self._modes(nq, ranked, detail)
+        nq = len(np.asarray(epochs).reshape(-1))
         ks = self.lib.cc_db_knn_stride(self.db)
         knn = np.zeros((nq, 3, L.NPIV, ks), L.knn_hit_dt) if want_knn else None
         cnt = np.zeros((nq, 3, L.NPIV), np.int32) if want_knn else None
+        self.keep.append((knn, cnt))
+        kw = {}
         if isinstance(source, L.PackedSrc):
-            r = None if rec is None else np.ascontiguousarray(rec, np.int32)
-            self.keep.append((source, r, epochs, res, ro, rc_, rn_, det, knn, cnt))
-            rc = self.lib.cc_db_query_submit_packed(self.db, _b(source), _p(r), nq, _p(epochs), _b(lb), _b(ub), _p(res), _p(knn), _p(cnt), None,
-                                                    _b(ro), _p(det))
-        else:
-            qd = np.ascontiguousarray(source if rec is None else source[np.asarray(rec)])
-            self.keep.append((qd, epochs, res, ro, rc_, rn_, det, knn, cnt))
-            head = (self.db, _p(qd), nq, _p(epochs), _b(lb), _b(ub), _p(res), _p(knn), _p(cnt), None)
-            if det is not None:
-                rc = self.lib.cc_db_query_submit_ranked_detail(*head, _b(ro), _p(det))
-            elif ro is not None:
-                rc = self.lib.cc_db_query_submit_ranked(*head, _b(ro))
-            else:
-                rc = self.lib.cc_db_query_submit(*head)
-        if raw_rc:
-            return rc
-        self.api.chk(rc, "query submit")
-        if wait:
-            self.wait()
-        return self._out(res, rc_, rn_, det, knn=knn, knn_cnt=cnt)
+            kw["idx"] = rec
+        elif rec is not None:
+            source = source[np.asarray(rec)]
+        r, rk = self._run(calls.query, wait, raw_rc, source, epochs, lb=lb, ub=ub, knn=_p(knn), knn_cnt=_p(cnt), ranked=ranked, detail=detail, **kw)
+        return rk if r is None else self._out(r.res, rk[0], rk[1], r.detail, knn=knn, knn_cnt=cnt)
 
     # ---- verify ----
-    @staticmethod
-    def table(cands):
-        tab = np.full((len(cands), CMAX), -1, np.int32)
-        for i, c in enumerate(cands):
-            tab[i, :len(c)] = c
-        return tab
+    table = staticmethod(calls.cand_table)
 
     def verify(self, source, qidx, cands, ranked=None, detail=False, mask=0, mfo=10, bound=1000.0, wait=True, raw_rc=False):
-        L = self.L
-        lb, ub = L.default_thresholds()
-        tab = self.table(cands)
-        n = len(tab)
-        qi = None if qidx is None else np.ascontiguousarray(qidx, np.int32)
-        cfg = L.VerifyCfg(mask, mfo, bound, 0)
-        res = np.zeros(n, L.query_result_dt)
-        hints = np.zeros((max(n, 1), L.HINT_MAX), L.hint_dt)
+        n = len(cands)
+        hints = np.zeros((max(n, 1), self.L.HINT_MAX), self.L.hint_dt)
         hcnt = np.zeros(max(n, 1), np.int32)
-        ro, rc_, rn_, det = self._modes(n, ranked, detail)
-        self.keep.append((source, tab, qi, cfg, res, hints, hcnt, ro, rc_, rn_, det))
-        if isinstance(source, L.PackedSrc):
-            rc = self.lib.cc_db_verify_submit_packed(self.db, _b(source), _p(qi), _p(tab), n, _b(cfg), _b(lb), _b(ub), _p(res), _p(hints), _p(hcnt), None,
-                                                     _b(ro), _p(det))
-        else:
-            qd = np.ascontiguousarray(source)
-            self.keep.append(qd)
-            head = (self.db, _p(qd), len(qd), _p(qi), _p(tab), n, _b(cfg), _b(lb), _b(ub), _p(res), _p(hints), _p(hcnt), None)
-            if det is not None:
-                rc = self.lib.cc_db_verify_submit_ranked_detail(*head, _b(ro), _p(det))
-            elif ro is not None:
-                rc = self.lib.cc_db_verify_submit_ranked(*head, _b(ro))
-            else:
-                rc = self.lib.cc_db_verify_submit(*head)
-        if raw_rc:
-            return rc
-        self.api.chk(rc, "verify submit")
-        if wait:
-            self.wait()
-        return self._out(res, rc_, rn_, det, hints=hints, hint_cnt=hcnt)
+        self.keep.append((hints, hcnt))
+        r, rk = self._run(calls.verify, wait, raw_rc, source, cands, qidx=qidx, levels=emu_api.levels_of(mask), max_fine_opt=mfo, max_key_dist_sq=bound,
+                          hints=_p(hints), n_hints=_p(hcnt), ranked=ranked, detail=detail)
+        return rk if r is None else self._out(r.res, rk[0], rk[1], r.detail, hints=hints, hint_cnt=hcnt)
 
     # ---- pose ----
     def pose(self, source, q, gidx, tf, tries=None, curvature=False, refine=1, min_corr=0.3, wait=True, raw_rc=False):
-        L = self.L
-        items = L.pose_items(q, gidx, tf)
-        n = len(items)
-        tr = tc = None
-        nt = 0
-        if tries is not None:
-            tr = np.ascontiguousarray(tries, np.float64)
-            nt = tr.shape[1]
-            tc = np.zeros((n, nt), np.float64)
-        cfg = L.PoseCfg(int(refine), float(min_corr), nt, 0)
-        res = np.zeros(n, L.pose_result_dt)
-        cv = np.zeros(n, L.pose_curv_dt) if curvature else None
-        self.keep.append((source, items, tr, tc, cfg, res, cv))
-        if isinstance(source, L.PackedSrc):
-            rc = self.lib.cc_db_pose_submit_packed(self.db, _b(source), _p(items), n, _b(cfg), _p(tr), _p(res), _p(tc), _p(cv), None)
-        else:
-            qd = np.ascontiguousarray(source)
-            self.keep.append(qd)
-            rc = self.lib.cc_db_pose_submit(self.db, _p(qd), len(qd), _p(items), n, _b(cfg), _p(tr), _p(res), _p(tc), _p(cv), None)
-        if raw_rc:
-            return rc
-        self.api.chk(rc, "pose submit")
-        if wait:
-            self.wait()
-        return self._out(res, None, None, None, try_corr=tc, curv=cv)
+        r, rk = self._run(calls.pose, wait, raw_rc, source, q, gidx, tf, tries=tries, curvature=curvature, refine=refine, min_corr=min_corr)
+        return rk if r is None else self._out(r.res, None, None, None, try_corr=r.try_corr, curv=r.curv)
 
 
 def same_bytes(a, b):

@@ -81,14 +81,6 @@ class Layout(C.Structure):
 class PointsApi(emu_api.EmuApi):
     """emu_api.EmuApi plus the calls that take a point layout and a per-scan transform."""
 
-    def __init__(self, L):
-        super().__init__(L)
-        for f in ("cc_ingest_points", "cc_ingest_points_host", "cc_scan_ingest_points", "cc_scan_ingest_points_batch", "cc_scan_desc",
-                  "cc_scan_release", "cc_stage_points_cancel"):
-            getattr(self.lib, f).restype = C.c_int   # (AttributeError where the library lacks them)
-        self.lib.cc_stage_points_slot.restype = C.c_void_p
-        self.lib.cc_stage_points_slot.argtypes = [C.c_void_p, C.c_int64, C.c_int]
-
     @staticmethod
     def _lay(layout):
         return None if layout is None else C.byref(Layout(int(layout[0]), int(layout[1])))

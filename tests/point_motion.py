@@ -77,12 +77,6 @@ def random_knots(n_scans, n_knots, seed, max_shift=4.0):
 class MotionApi(PointsApi):
     """point_layouts.PointsApi plus the calls that take a time word and knots."""
 
-    def __init__(self, L):
-        super().__init__(L)
-        for f in ("cc_ingest_points_motion", "cc_ingest_points_motion_host", "cc_scan_ingest_points_motion"):
-            getattr(self.lib, f).restype = C.c_int   # (AttributeError where the library lacks them)
-        self.lib.cc_motion_knots.restype = None
-
     @staticmethod
     def _args(motion, t_begin, scale, knots, n):
         mo = None if motion is None else Motion(int(motion[0]), int(motion[1]), int(motion[2]), 0)

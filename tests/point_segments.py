@@ -65,11 +65,6 @@ class Segments:
 class SegmentsApi(PointsApi):
     """point_layouts.PointsApi plus the calls that take a scan as a list of segments."""
 
-    def __init__(self, L):
-        super().__init__(L)
-        for f in ("cc_ingest_segments", "cc_ingest_segments_host", "cc_scan_ingest_segments", "cc_scan_bev"):
-            getattr(self.lib, f).restype = C.c_int   # (AttributeError where the library lacks them)
-
     def _dbg(self, n):
         ncell = self._cfg.n_row * self._cfg.n_col
         dbg = {"bev": np.zeros((n, ncell), np.float32), "pix_rc": np.zeros((n, ncell, 2), np.float32),

@@ -336,12 +336,6 @@ def edge_words(word, n):
 class RangesApi(PointsApi):
     """point_layouts.PointsApi plus the calls that take a range sensor."""
 
-    def __init__(self, L):
-        super().__init__(L)
-        for f in ("cc_range_sensor_create", "cc_range_sensor_destroy", "cc_ingest_ranges", "cc_ingest_ranges_host", "cc_scan_ingest_ranges"):
-            getattr(self.lib, f).restype = C.c_int   # (AttributeError where the library lacks them)
-        self.lib.cc_motion_knots.restype = None
-
     def sensor_rc(self, ctx, sensor=None, model=None):
         """cc_range_sensor_create -> (rc, handle)"""
         keep = None

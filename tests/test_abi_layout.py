@@ -21,6 +21,31 @@ def test_header_symbols_all_exported(cc):
         assert hasattr(lib, s), s
 
 
+def test_signature_table_matches_the_header(cc):
+    """Every prototype of include/cont2_amd.h, classified by the binding convention (a pointer or array is c_void_p, int and
+    int32_t c_int, int64_t c_int64, size_t c_size_t, double and float themselves; the return c_int, None, c_char_p for
+    const char * and c_void_p for any other pointer), is the entry abi.SIGNATURES has for the symbol -- all 109 of them."""
+    hdr = open(os.path.join(ROOT, "include", "cont2_amd.h")).read()
+    hdr = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+    protos = re.findall(r"^[ \t]*((?:const\s+)?\w+(?:\s*\*)?)\s*\b(cc_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)
+    scalar = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "size_t": C.c_size_t, "double": C.c_double, "float": C.c_float}
+
+    def param(p):
+        return C.c_void_p if "*" in p or "[" in p else scalar[[t for t in re.findall(r"\w+", p) if t != "const"][0]]
+
+    def ret(r):
+        r = " ".join(r.replace("*", " * ").split())
+        return {"int": C.c_int, "void": None, "const char *": C.c_char_p}.get(r, C.c_void_p if "*" in r else r)
+
+    parsed = {name: (ret(r), [param(p) for p in params.split(",") if p.strip() not in ("", "void")]) for r, name, params in protos}
+    assert len(protos) == len(parsed) == 109
+    assert parsed.keys() == cc.abi.SIGNATURES.keys(), parsed.keys() ^ cc.abi.SIGNATURES.keys()
+    for name, sig in parsed.items():
+        assert cc.abi.SIGNATURES[name] == sig, name
+    others = sorted(n for n, (r, _a) in parsed.items() if r not in (C.c_int, None))
+    assert others == ["cc_db_feat_ptr", "cc_db_hot_ptr", "cc_last_error", "cc_stage_points", "cc_stage_points_slot"]
+
+
 def test_layout_sizes(cc, oracle):
     L = cc.L
     oracle.lib().orc_sizeof_desc.restype = C.c_size_t
@@ -28,9 +53,8 @@ def test_layout_sizes(cc, oracle):
     assert L.contour_dt.itemsize == 76 and L.bci_dt.itemsize == 600 and L.relpt_dt.itemsize == 12
     assert C.sizeof(L.ManagerCfg) == 80 and C.sizeof(L.DbCfg) == 64 and C.sizeof(L.Score) == 32
     # the compact per-scan records (hot record + correlation inputs): sizes as the library reports them
-    lib = C.CDLL(cc.build())
+    lib = cc.abi.bind(C.CDLL(cc.build()))
     hb, fb = C.c_size_t(), C.c_size_t()
-    lib.cc_packed_sizes.restype = None
     lib.cc_packed_sizes(C.byref(hb), C.byref(fb))
     assert hb.value == L.hot_desc_dt.itemsize == 18448 and fb.value == 16 + 16 + 8 + 4 * 320 * 32  # CC_MAXC ellipses per correlation level
 
@@ -75,8 +99,7 @@ def test_no_cpu_fallback(cc):
         pytest.skip("GPU present")
     with pytest.raises(cc.CCError):
         cc.Context(0)
-    lib = C.CDLL(cc.build())
-    lib.cc_last_error.restype = C.c_char_p
+    lib = cc.abi.bind(C.CDLL(cc.build()))
     h = C.c_void_p()
     cfg = cc.L.default_manager_cfg()
     rc = lib.cc_create(0, C.byref(cfg), 4, C.byref(h))

@@ -1,7 +1,5 @@
 """cc_db_set_dynamic_thres (the reference's DYNAMIC_THRES=1 build) on the CPU harness: the device query path and hint flow
 in dynamic mode vs the dynamic CPU oracle (tests/dyn_thres_oracle.cpp), mode 0 vs the static oracle, per-submit modes."""
-import ctypes as C
-
 import numpy as np
 
 import dyn_oracle
@@ -11,7 +9,6 @@ from test_emu_hints import _demo_hints
 
 
 def _set_dyn(api, db, on):
-    api.lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
     return api.lib.cc_db_set_dynamic_thres(db, on)
 
 

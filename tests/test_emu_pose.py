@@ -11,11 +11,10 @@ Observed on the harness: 19 items with 0, 78, 235-236, 275-1 242 and 1 306-1 323
 oracle's line search fails; corr_init / correlation / pose within 2.6e-15 / 1.4e-15 / 2.9e-13 of the oracle, try values within
 3.3e-15, gradient within 1.0e-15 sqrt(H_kk), Hessian within 3.0e-12 of the half-step reference; the verify flow's six entries
 reproduced exactly.  Every part prints its figures (pytest -s)."""
-import ctypes as C
-
 import numpy as np
 
 import pose_common as PC
+from emu_api import calls
 from test_emu_ranked_detail import RankedDetail
 
 _state = {}
@@ -29,10 +28,6 @@ class EmuBack(PC.Back):
         n = len(self.desc)
         self.v = RankedDetail(L, self.desc, np.arange(n) * 100.0, np.arange(n, dtype=np.int32), L.default_db_cfg())
         self.lib, self.db, self.api = self.v.lib, self.v.db, self.v.api
-        for f in POSE_FNS:
-            getattr(self.lib, f).restype = C.c_int
-        self.lib.cc_db_pose_submit.argtypes = self.lib.cc_db_pose_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
-        self.lib.cc_db_pose_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
         self.keep = []
 
     def verify_d(self, lists, qidx, k):
@@ -42,6 +37,12 @@ class EmuBack(PC.Back):
         """synchronous: cc_db_pose_batch_host; submit=True: cc_db_pose_submit + wait; submit="no-wait": the caller waits"""
         L, p, b = self.L, self.v.p, self.v.b
         items = np.ascontiguousarray(items)
+        if submit:
+            r = calls.pose(self.lib, self.db, items["q"], items["gidx"], items["tf"], qdesc=self.desc.ctypes.data, n_desc=len(self.desc), refine=refine,
+                           min_corr=min_corr, tries=tries, curvature=curv, wait=False, keep=self.keep)
+            if submit is True:
+                self.wait()
+            return r.res, (r.try_corr if r.try_corr is not None and r.try_corr.shape[1] else None), r.curv
         n = len(items)
         nt = 0 if tries is None else tries.shape[1]
         tr = None if tries is None else np.ascontiguousarray(tries, np.float64)
@@ -49,15 +50,8 @@ class EmuBack(PC.Back):
         res = np.zeros(n, L.pose_result_dt)
         tc = np.zeros((n, nt)) if nt else None
         cv = np.zeros(n, L.pose_curv_dt) if curv else None
-        self.keep.append((items, tr, cfg, res, tc, cv))
-        if submit:
-            rc = self.lib.cc_db_pose_submit(self.db, p(self.desc), len(self.desc), p(items), n, b(cfg), p(tr), p(res), p(tc), p(cv), None)
-            self.api.chk(rc, "cc_db_pose_submit")
-            if submit is True:
-                self.wait()
-        else:
-            self.api.chk(self.lib.cc_db_pose_batch_host(self.db, p(self.desc), len(self.desc), p(items), n, b(cfg), p(tr), p(res), p(tc), p(cv)),
-                         "cc_db_pose_batch_host")
+        self.api.chk(self.lib.cc_db_pose_batch_host(self.db, p(self.desc), len(self.desc), p(items), n, b(cfg), p(tr), p(res), p(tc), p(cv)),
+                     "cc_db_pose_batch_host")
         return res, tc, cv
 
     def query(self, qs):

@@ -7,6 +7,7 @@ import numpy as np
 
 import ranked_common as RC
 from test_dyn_thres_oracle import INT_FIELDS
+from emu_api import calls
 from test_emu_verify import Verify
 
 EINVAL = -1
@@ -15,19 +16,6 @@ _state = {}
 
 class Ranked(Verify):
     """ctypes helper for the five *_ranked entry points on the harness ("device" pointers are host pointers there)."""
-
-    def __init__(self, L, desc, ts, seeds, dcfg):
-        super().__init__(L, desc, ts, seeds, dcfg)
-        lib = self.lib
-        for f in ("cc_db_query_submit_ranked", "cc_db_query_batch_host_ranked", "cc_db_verify_submit_ranked", "cc_db_check_hints_ranked",
-                  "cc_db_query_scan_batch_submit_ranked", "cc_db_set_lanes"):
-            getattr(lib, f).restype = C.c_int
-        lib.cc_db_query_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
-        lib.cc_db_query_batch_host_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        lib.cc_db_query_scan_batch_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        lib.cc_db_verify_submit_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
-        lib.cc_db_check_hints_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-        lib.cc_db_set_lanes.argtypes = [C.c_void_p, C.c_int]
 
     @staticmethod
     def p(a):
@@ -40,22 +28,22 @@ class Ranked(Verify):
     def query(self, qdesc, epochs, k, submit=False, lb=None, ub=None):
         """-> (results, cands [n, k], counts [n]); with submit valid after api.db_query_wait"""
         L = self.L
+        qdesc = np.ascontiguousarray(qdesc)
+        if submit:
+            self.keep.append(qdesc)
+            r = calls.query(self.lib, self.db, epochs, qdesc=qdesc.ctypes.data, lb=lb, ub=ub, ranked=k, wait=False, keep=self.keep)
+            return (r.res,) + r.rank
         if lb is None:
             lb, ub = L.default_thresholds()
-        qdesc = np.ascontiguousarray(qdesc)
         epochs = np.ascontiguousarray(epochs, np.int32)
         res = np.zeros(len(qdesc), L.query_result_dt)
         cands, cnt, ro = L.rank_buffers(len(qdesc), k)
-        self.keep.append((qdesc, epochs, res, cands, cnt, ro, lb, ub))
-        if submit:
-            rc = self.lib.cc_db_query_submit_ranked(self.db, self.p(qdesc), len(qdesc), self.p(epochs), self.b(lb), self.b(ub), self.p(res), None, None,
-                                                    None, self.b(ro))
-        else:
-            rc = self.lib.cc_db_query_batch_host_ranked(self.db, self.p(qdesc), len(qdesc), self.p(epochs), self.b(lb), self.b(ub), self.p(res), self.b(ro))
+        rc = self.lib.cc_db_query_batch_host_ranked(self.db, self.p(qdesc), len(qdesc), self.p(epochs), self.b(lb), self.b(ub), self.p(res), self.b(ro))
         self.api.chk(rc, "ranked query")
         return res, cands, cnt
 
     def hints(self, qdesc, hints, k, mfo=10):
+        """cc_db_check_hints_ranked with h_scores NULL, a form calls.check_hints does not have"""
         L = self.L
         lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
@@ -70,23 +58,14 @@ class Ranked(Verify):
     def verify(self, qdesc, cand_lists, k, qidx=None, mfo=10, submit=False, bound=1000.0):
         """-> (results, cands [n, k], counts [n], hint lists); the synchronous form is submit + wait"""
         L = self.L
-        lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
-        tab = self.table(cand_lists)
-        n = len(tab)
-        qi = None if qidx is None else np.ascontiguousarray(qidx, np.int32)
-        cfg = L.VerifyCfg(0, mfo, bound, 0)
-        res = np.zeros(n, L.query_result_dt)
+        n = len(cand_lists)
         hints = np.zeros((max(n, 1), L.HINT_MAX), L.hint_dt)
         hcnt = np.zeros(max(n, 1), np.int32)
-        cands, cnt, ro = L.rank_buffers(n, k)
-        self.keep.append((qdesc, tab, qi, cfg, res, hints, hcnt, cands, cnt, ro, lb, ub))
-        rc = self.lib.cc_db_verify_submit_ranked(self.db, self.p(qdesc), len(qdesc), self.p(qi), self.p(tab), n, self.b(cfg), self.b(lb), self.b(ub),
-                                                 self.p(res), self.p(hints), self.p(hcnt), None, self.b(ro))
-        self.api.chk(rc, "cc_db_verify_submit_ranked")
-        if not submit:
-            self.api.db_query_wait(self.db)
-        return res, cands, cnt, (hints, hcnt)
+        self.keep.append((qdesc, hints, hcnt))
+        r = calls.verify(self.lib, self.db, cand_lists, qdesc=qdesc.ctypes.data, n_desc=len(qdesc), qidx=qidx, levels=None, max_fine_opt=mfo,
+                         max_key_dist_sq=bound, hints=hints.ctypes.data, n_hints=hcnt.ctypes.data, ranked=k, wait=not submit, keep=self.keep)
+        return (r.res,) + r.rank + ((hints, hcnt),)
 
 
 def ranked_setup(cc, oracle):
@@ -289,9 +268,6 @@ def test_refusals(cc, oracle):
     # thresholds that fail lb.strictSmaller(ub), which the ranked call tests before the handles are gathered
     x, _, _ = cc.synth.make_sequence(64, world=cc.synth.World(loop_len=40.0), beams=16, azim=450)
     pts = np.ascontiguousarray(x[38].numpy().reshape(-1, 4), np.float32)
-    v.lib.cc_scan_ingest.restype = v.lib.cc_scan_release.restype = C.c_int
-    v.lib.cc_scan_ingest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-    v.lib.cc_scan_release.argtypes = [C.c_void_p]
     h = C.c_void_p()
     v.api.chk(v.lib.cc_scan_ingest(v.ctx, p(pts), len(pts), 0, C.byref(h)), "cc_scan_ingest")
     hs = (C.c_void_p * 1)(h)

@@ -13,6 +13,7 @@ import numpy as np
 import ranked_common as RC
 import ranked_detail_common as RD
 from test_emu_large_nnk import _db_cfg
+from emu_api import calls
 from test_emu_ranked import Ranked
 
 EINVAL = -1
@@ -25,55 +26,48 @@ RANKED = ("cc_db_query_submit_ranked", "cc_db_query_batch_host_ranked", "cc_db_q
 class RankedDetail(Ranked):
     """ctypes helper for the *_ranked_detail entry points on the harness ("device" pointers are host pointers there)"""
 
-    def __init__(self, L, desc, ts, seeds, dcfg):
-        super().__init__(L, desc, ts, seeds, dcfg)
-        lib = self.lib
-        lib.cc_db_verify_batch_host_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        lib.cc_db_check_hints_host_ranked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
-        for f in RANKED:
-            getattr(lib, f + "_detail").restype = C.c_int
-            getattr(lib, f + "_detail").argtypes = getattr(lib, f).argtypes + [C.c_void_p]
-
     def query_d(self, qdesc, epochs, k, submit=False):
         """-> (results, cands [n, k], counts [n], detail [n, k])"""
         L = self.L
-        lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
+        if submit:
+            self.keep.append(qdesc)
+            r = calls.query(self.lib, self.db, epochs, qdesc=qdesc.ctypes.data, ranked=k, detail=True, wait=False, keep=self.keep)
+            return (r.res,) + r.rank + (r.detail,)
+        lb, ub = L.default_thresholds()
         epochs = np.ascontiguousarray(epochs, np.int32)
         res = np.zeros(len(qdesc), L.query_result_dt)
         cands, cnt, ro = L.rank_buffers(len(qdesc), k)
         det = L.rank_detail_buffer(len(qdesc), k)
-        self.keep.append((qdesc, epochs, res, cands, cnt, ro, lb, ub, det))
-        if submit:
-            rc = self.lib.cc_db_query_submit_ranked_detail(self.db, self.p(qdesc), len(qdesc), self.p(epochs), self.b(lb), self.b(ub), self.p(res),
-                                                           None, None, None, self.b(ro), self.p(det))
-        else:
-            rc = self.lib.cc_db_query_batch_host_ranked_detail(self.db, self.p(qdesc), len(qdesc), self.p(epochs), self.b(lb), self.b(ub),
-                                                               self.p(res), self.b(ro), self.p(det))
+        rc = self.lib.cc_db_query_batch_host_ranked_detail(self.db, self.p(qdesc), len(qdesc), self.p(epochs), self.b(lb), self.b(ub),
+                                                           self.p(res), self.b(ro), self.p(det))
         self.api.chk(rc, "ranked detail query")
         return res, cands, cnt, det
 
     def hints_d(self, qdesc, hints, k, mfo=10, host=False):
         L = self.L
-        lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
+        if not host:
+            r = calls.check_hints(self.lib, self.db, qdesc.ctypes.data, hints, max_fine_opt=mfo, ranked=k, detail=True)
+            return (r.res[0],) + r.rank + (r.detail,)
+        lb, ub = L.default_thresholds()
         hints = np.ascontiguousarray(hints, L.hint_dt)
         res = np.zeros(1, L.query_result_dt)
         cands, cnt, ro = L.rank_buffers(1, k)
         det = L.rank_detail_buffer(1, k)
-        if host:
-            rc = self.lib.cc_db_check_hints_host_ranked_detail(self.db, self.p(qdesc), self.p(hints), len(hints), self.b(lb), self.b(ub), int(mfo),
-                                                               self.p(res), None, self.b(ro), self.p(det))
-        else:
-            rc = self.lib.cc_db_check_hints_ranked_detail(self.db, self.p(qdesc), self.p(hints), len(hints), self.b(lb), self.b(ub), int(mfo),
-                                                          self.p(res), None, None, self.b(ro), self.p(det))
+        rc = self.lib.cc_db_check_hints_host_ranked_detail(self.db, self.p(qdesc), self.p(hints), len(hints), self.b(lb), self.b(ub), int(mfo),
+                                                           self.p(res), None, self.b(ro), self.p(det))
         self.api.chk(rc, "cc_db_check_hints_ranked_detail")
         return res[0], cands, cnt, det
 
     def verify_d(self, qdesc, cand_lists, k, qidx=None, mfo=10, bound=1000.0, host=False):
         L = self.L
-        lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
+        if not host:  # the submit followed by the wait
+            r = calls.verify(self.lib, self.db, cand_lists, qdesc=qdesc.ctypes.data, n_desc=len(qdesc), qidx=qidx, levels=None, max_fine_opt=mfo,
+                             max_key_dist_sq=bound, ranked=k, detail=True)
+            return (r.res,) + r.rank + (r.detail,)
+        lb, ub = L.default_thresholds()
         tab = self.table(cand_lists)
         n = len(tab)
         qi = None if qidx is None else np.ascontiguousarray(qidx, np.int32)
@@ -81,16 +75,9 @@ class RankedDetail(Ranked):
         res = np.zeros(n, L.query_result_dt)
         cands, cnt, ro = L.rank_buffers(n, k)
         det = L.rank_detail_buffer(n, k)
-        self.keep.append((qdesc, tab, qi, cfg, res, cands, cnt, ro, lb, ub, det))
-        if host:
-            rc = self.lib.cc_db_verify_batch_host_ranked_detail(self.db, self.p(qdesc), len(qdesc), self.p(qi), self.p(tab), n, self.b(cfg),
-                                                                self.b(lb), self.b(ub), self.p(res), self.b(ro), self.p(det))
-            self.api.chk(rc, "cc_db_verify_batch_host_ranked_detail")
-            return res, cands, cnt, det
-        rc = self.lib.cc_db_verify_submit_ranked_detail(self.db, self.p(qdesc), len(qdesc), self.p(qi), self.p(tab), n, self.b(cfg), self.b(lb),
-                                                        self.b(ub), self.p(res), None, None, None, self.b(ro), self.p(det))
-        self.api.chk(rc, "cc_db_verify_submit_ranked_detail")
-        self.api.db_query_wait(self.db)
+        rc = self.lib.cc_db_verify_batch_host_ranked_detail(self.db, self.p(qdesc), len(qdesc), self.p(qi), self.p(tab), n, self.b(cfg),
+                                                            self.b(lb), self.b(ub), self.p(res), self.b(ro), self.p(det))
+        self.api.chk(rc, "cc_db_verify_batch_host_ranked_detail")
         return res, cands, cnt, det
 
 
@@ -295,10 +282,7 @@ def test_est_sens_info(cc, oracle):
     """Part (f): J^-T H J^-1 with J from central differences of cc_est_sens_tf (affine in the translation; the theta column by a
     five-point difference, whose error at h = 1e-3 is h^4 / 30 of the lever arm's fifth derivative: ~3e-12 relative)"""
     import emu_api
-    lib = C.CDLL(emu_api.build())
-    lib.cc_est_sens_info.restype = lib.cc_est_sens_tf.restype = None
-    lib.cc_est_sens_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    lib.cc_est_sens_tf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib = emu_api.abi.bind(C.CDLL(emu_api.build()))
     rng = np.random.default_rng(5)
 
     def sens(tf, nr, nc):

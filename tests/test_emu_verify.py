@@ -28,23 +28,12 @@ class Verify:
         self.L = L
         self.api = emu_api.EmuApi(L)
         self.lib = self.api.lib
-        for f in ("cc_db_verify_submit", "cc_db_verify_batch", "cc_db_verify_batch_host", "cc_db_set_dynamic_thres"):
-            getattr(self.lib, f).restype = C.c_int
-        self.lib.cc_db_verify_submit.argtypes = self.lib.cc_db_verify_batch.argtypes = \
-            [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        self.lib.cc_db_verify_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-        self.lib.cc_db_set_dynamic_thres.argtypes = [C.c_void_p, C.c_int]
         self.ctx = self.api.create(max_batch=8)
         self.db = self.api.db_create(self.ctx, dcfg, cap=len(desc))
         self.api.db_add(self.db, desc, ts, seeds)
         self.keep = []
 
-    @staticmethod
-    def table(cands):
-        tab = np.full((len(cands), CMAX), -1, np.int32)
-        for i, c in enumerate(cands):
-            tab[i, :len(c)] = c
-        return tab
+    table = staticmethod(emu_api.calls.cand_table)
 
     def raw(self, fn, qdesc, n_desc, qidx, tab, n, cfg, lb, ub, res, hints=None, cnt=None, host=False):
         p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
@@ -56,20 +45,22 @@ class Verify:
     def run(self, qdesc, cands, qidx=None, mask=0, mfo=10, bound=1000.0, lb=None, ub=None, submit=False, host=False):
         """-> (results, list of hint arrays per item); with submit the results are valid after api.db_query_wait"""
         L = self.L
-        if lb is None:
-            lb, ub = L.default_thresholds()
         qdesc = np.ascontiguousarray(qdesc)
-        tab = self.table(cands)
-        n = len(tab)
-        qi = None if qidx is None else np.ascontiguousarray(qidx, np.int32)
-        cfg = L.VerifyCfg(mask, mfo, bound, 0)
-        res = np.zeros(n, L.query_result_dt)
+        n = len(cands)
         hints = np.zeros((max(n, 1), L.HINT_MAX), L.hint_dt)
         cnt = np.zeros(max(n, 1), np.int32)
-        self.keep.append((qdesc, tab, qi, res, hints, cnt))
-        rc = self.raw("cc_db_verify_submit" if submit else "cc_db_verify_batch", qdesc, len(qdesc), qi, tab, n, cfg, lb, ub, res,
-                      None if host else hints, None if host else cnt, host=host)
-        self.api.chk(rc, "cc_db_verify")
+        self.keep.append((qdesc, hints, cnt))
+        if host:
+            if lb is None:
+                lb, ub = L.default_thresholds()
+            tab = self.table(cands)
+            qi = None if qidx is None else np.ascontiguousarray(qidx, np.int32)
+            res = np.zeros(n, L.query_result_dt)
+            self.api.chk(self.raw(None, qdesc, len(qdesc), qi, tab, n, L.VerifyCfg(mask, mfo, bound, 0), lb, ub, res, host=True), "cc_db_verify")
+        else:
+            r = emu_api.calls.verify(self.lib, self.db, cands, qdesc=qdesc.ctypes.data, n_desc=len(qdesc), qidx=qidx, levels=emu_api.levels_of(mask),
+                                     max_fine_opt=mfo, max_key_dist_sq=bound, lb=lb, ub=ub, hints=hints.ctypes.data, n_hints=cnt.ctypes.data, wait=not submit, keep=self.keep)
+            res = r.res
         return res, [hints[i, :cnt[i]] for i in range(n)]
 
 

@@ -199,10 +199,6 @@ def test_per_scan_path(cc, oracle):
     L = cc.L
     lib = cc.lib()
     ctx, d, db = ranked_setup(cc, oracle)[:3]
-    lib.cc_scan_ingest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-    lib.cc_scan_desc.argtypes = [C.c_void_p, C.c_void_p]
-    lib.cc_scan_release.argtypes = [C.c_void_p]
-    lib.cc_db_query_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     x, poses, ts2 = cc.synth.make_sequence(64, world=cc.synth.World(loop_len=40.0), beams=16, azim=450)
     qs = np.arange(36, 44, dtype=np.int32)
     hs = (C.c_void_p * 8)()

@@ -93,10 +93,6 @@ def test_drive_query_hint_and_scan_handle_flows(cc, oracle):
     RD.check_structure(L, ch, nh, dh, 16)
     RD.check_rows(oracle, desc, "drive", [q], ch, nh, dh, "hints", RD.new_stats())
     # scan handles: the rows of the batch call on the handles' descriptors; the reference on the device's descriptor of the query
-    lib.cc_scan_ingest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-    lib.cc_scan_desc.argtypes = [C.c_void_p, C.c_void_p]
-    lib.cc_scan_release.argtypes = [C.c_void_p]
-    lib.cc_db_query_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     x, _, _ = cc.synth.make_sequence(64, world=cc.synth.World(loop_len=40.0), beams=16, azim=450)
     qs = np.arange(36, 40, dtype=np.int32)
     hs = (C.c_void_p * 4)()

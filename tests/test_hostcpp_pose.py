@@ -3,7 +3,6 @@ tests/pose_mirror_check.cpp on the CPU harness: its rows are the C-ABI's (cc_db_
 chunk composition: one call per scorePoses call, one descriptor) bit for bit, T_best's angle within a few ulp (it passes through
 an Isometry2d); a query with fewer try poses than the call's longest list gets its own count back; and with default-constructed
 drivers nothing changes: the unchanged offline driver writes the outcome file it always wrote."""
-import ctypes as C
 import os
 import subprocess
 
@@ -42,8 +41,6 @@ def test_score_poses_rows_are_the_c_abi_rows(cc, oracle, tmp_path):
     L = oracle.L
     v = setup(cc, oracle)[0]
     lib = v.lib
-    lib.cc_db_pose_batch_host.restype = C.c_int
-    lib.cc_db_pose_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
     exe = _build(tmp_path, "pose_mirror_check.cpp", "pose_mirror_check", gpu=False)
     lst, pos = _lists(cc, tmp_path, 64, 16, 450, 1.0)
     env = dict(os.environ, CC_EVAL_TIMERS="1", CC_DB_READ_AHEAD="0", CC_EVAL_AHEAD="4", CC_EVAL_INGEST_BATCH="1", **emu_api.SMALL_GRIDS)
