@@ -24,7 +24,7 @@ import synth  # noqa: E402,F401
 import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
-_SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_contours.h", "k_contours_list.h",
+_SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_image.h", "k_contours.h", "k_contours_list.h",
          "k_knn.h", "k_mask.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 # how every gfx950 code object of this project that includes csrc/ headers is compiled: the library below and the device
@@ -34,7 +34,7 @@ HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17"
 
 def build(force=False, verbose=False):
     """Compile the HIP library for gfx950 (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_HERE, "csrc", s) for s in _SRCS] + [os.path.join(_HERE, "..", "include", "cont2_amd.h")]
+    srcs = [os.path.join(_HERE, "csrc", s) for s in _SRCS] + [os.path.join(_HERE, "..", "include", h) for h in ["cont2_amd.h"] + list(abi.EXTENSIONS)]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(s) <= os.path.getmtime(LIB_PATH) for s in srcs):
         return LIB_PATH
     cmd = ["hipcc"] + HIPCC_FLAGS + [os.path.join(_HERE, "csrc", "cont2_amd.hip"), "-ldl", "-o", LIB_PATH]
@@ -47,6 +47,7 @@ def build(force=False, verbose=False):
 _lib = None
 
 EXPORTS = list(abi.SIGNATURES)  # every symbol include/cont2_amd.h declares
+EXPORTS_EXT = [s for table in abi.EXTENSIONS.values() for s in table]  # ... and every symbol of the extension headers beside it
 
 
 def lib():
@@ -380,6 +381,54 @@ class Context:
         _chk(lib().cc_ingest_ranges_host(self.h, sensor.h, ranges.ctypes.data, n, kn.ctypes.data if kn is not None else None, out.ctypes.data, None),
              "cc_ingest_ranges_host")
         return out
+
+    def _images(self, height, pos_rc):
+        """the shape checks ingest_images / ingest_images_host share (torch tensors or numpy arrays) -> the number of images"""
+        if height.ndim not in (2, 3):
+            raise ValueError("height must be [n, n_cell] or [n, n_row, n_col], got %s" % (tuple(height.shape),))
+        n = int(height.shape[0])
+        if (height.ndim == 2 and height.shape[1] != self.n_cell) or (height.ndim == 3 and tuple(height.shape[1:]) != (self.cfg.n_row, self.cfg.n_col)):
+            raise ValueError("height must hold %d x %d images, got %s" % (self.cfg.n_row, self.cfg.n_col, tuple(height.shape)))
+        if pos_rc is not None and (pos_rc.shape[0] != n or pos_rc.shape[-1] != 2 or int(np.prod(pos_rc.shape[1:])) != 2 * self.n_cell):
+            raise ValueError("pos_rc must be [%d, %d, 2], got %s" % (n, self.n_cell, tuple(pos_rc.shape)))
+        return n
+
+    def ingest_images(self, height, pos_rc=None, min_height=None, out=None, debug=False):
+        """Descriptors from caller-made max-height images (cc_ingest_images, include/cont2_amd_images.h): no points are read.
+        height: float32 CUDA tensor [n, n_cell] or [n, n_row, n_col], contiguous -- image heights (z + lidar_height), the layout of
+        ingest(debug=True)'s "bev"; pos_rc: float32 CUDA [n, n_cell, 2] of (row_f, col_f) like "pix_rc", or None for the cell
+        centres; min_height: n host values that become min_bin_val, or None for the minimum over the occupied cells.  A cell is
+        occupied iff row >= 1 and h > -1000 (NaN is empty); a position component that is NaN or more than half a cell from its
+        cell's centre is replaced by the centre's.  Returns what ingest() returns."""
+        import torch
+        assert height.is_cuda and height.is_contiguous() and height.dtype == torch.float32
+        assert pos_rc is None or (pos_rc.is_cuda and pos_rc.is_contiguous() and pos_rc.dtype == torch.float32)
+        n = self._images(height, pos_rc)
+        if out is None:
+            out = torch.empty((n, DESC_BYTES), dtype=torch.uint8, device=height.device)
+        dbg_p, dbg = None, None
+        if debug:
+            dbg = {"bev": torch.empty((n, self.n_cell), dtype=torch.float32, device=height.device),
+                   "pix_rc": torch.empty((n, self.n_cell, 2), dtype=torch.float32, device=height.device),
+                   "labels": torch.empty((n, L.NLEV, self.n_cell), dtype=torch.int16, device=height.device)}
+            st = IngestDebug(dbg["bev"].data_ptr(), dbg["pix_rc"].data_ptr(), dbg["labels"].data_ptr())
+            dbg_p = C.addressof(st)
+        stream = torch.cuda.current_stream(height.device).cuda_stream
+        _chk(calls.ingest_images(lib(), self.h, height.data_ptr(), None if pos_rc is None else pos_rc.data_ptr(), n, min_height, out.data_ptr(), dbg_p,
+                                 stream), "cc_ingest_images")
+        return (out, dbg) if debug else out
+
+    def ingest_images_host(self, height, pos_rc=None, min_height=None, want_bev=False):
+        """ingest_images() from host arrays (numpy f32, the same shapes): host descriptors out (cc_ingest_images_host); with want_bev
+        followed by the images as the library read them [n, n_cell]."""
+        height = np.ascontiguousarray(height, np.float32)
+        pos_rc = None if pos_rc is None else np.ascontiguousarray(pos_rc, np.float32)
+        n = self._images(height, pos_rc)
+        out = np.zeros(n, L.scan_desc_dt)
+        bev = np.zeros((n, self.n_cell), np.float32) if want_bev else None
+        _chk(calls.ingest_images(lib(), self.h, height.ctypes.data, None if pos_rc is None else pos_rc.ctypes.data, n, min_height, out.ctypes.data,
+                                 host=True, bev=bev.ctypes.data if want_bev else None), "cc_ingest_images_host")
+        return (out, bev) if want_bev else out
 
     def ingest_segments(self, scans, out=None, debug=False):
         """Every scan from an ordered list of point segments, each with its own record shape and transform (cc_ingest_segments):

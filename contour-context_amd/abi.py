@@ -1,5 +1,6 @@
 """The ctypes signature of every function include/cont2_amd.h declares, in one table, and bind() to apply it to a loaded
 library (the product's, the CPU harness's, another build).  tests/test_abi_layout.py holds the table against the header.
+The extension headers beside it (include/cont2_amd_images.h) have tables of their own, EXTENSIONS, which bind() applies as well.
 
 One line per prototype, in the header's order: return code, name, one code per parameter.
   parameters   P any pointer or array   I int / int32_t   Q int64_t   Z size_t   D double   F float   (- : none)
@@ -121,13 +122,30 @@ V cc_est_sens_info PPIIP
 _ARG = {"P": C.c_void_p, "I": C.c_int, "Q": C.c_int64, "Z": C.c_size_t, "D": C.c_double, "F": C.c_float}
 _RET = {"I": C.c_int, "V": None, "S": C.c_char_p, "P": C.c_void_p}
 
+
+def _table(spec):
+    return {name: (_RET[ret], [_ARG[a] for a in args.strip("-")]) for ret, name, args in (ln.split() for ln in spec.split("\n") if ln)}
+
+
 # symbol -> (restype, argtypes)
-SIGNATURES = {name: (_RET[ret], [_ARG[a] for a in args.strip("-")]) for ret, name, args in (ln.split() for ln in _SPEC.split("\n") if ln)}
+SIGNATURES = _table(_SPEC)
+
+# The extension headers beside include/cont2_amd.h, each with a table of its own in the same codes: header -> {symbol: (restype, argtypes)}.
+# tests/test_abi_images.py holds them against their headers.
+_EXT_SPEC = {
+    "cont2_amd_images.h": """
+I cc_ingest_images PPPIPPPP
+I cc_ingest_images_host PPPIPPP
+I cc_scan_ingest_image PPPPIP
+""",
+}
+EXTENSIONS = {hdr: _table(spec) for hdr, spec in _EXT_SPEC.items()}
 
 
 def bind(cdll):
-    """Give every function of the table its restype and argtypes on `cdll` (a library that lacks one is an AttributeError)."""
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(cdll, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    """Give every function of the tables its restype and argtypes on `cdll` (a library that lacks one is an AttributeError)."""
+    for table in [SIGNATURES] + list(EXTENSIONS.values()):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(cdll, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return cdll

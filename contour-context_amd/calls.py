@@ -13,7 +13,8 @@ entry point runs is behaviour (a synchronous *_batch cuts one chunk per lane, a 
   verify   descriptors: cc_db_verify_batch (wait) / cc_db_verify_submit; ranked: cc_db_verify_submit_ranked[_detail];
            a record source: cc_db_verify_submit_packed
   hints    cc_db_check_hints[_ranked[_detail]] (synchronous by itself)
-  pose     descriptors: cc_db_pose_batch (wait) / cc_db_pose_submit; a record source: cc_db_pose_submit_packed"""
+  pose     descriptors: cc_db_pose_batch (wait) / cc_db_pose_submit; a record source: cc_db_pose_submit_packed
+Beside the scoring flows: ingest_images / scan_ingest_image, the calls of include/cont2_amd_images.h (descriptors from max-height images)."""
 import ctypes as C
 
 import numpy as np
@@ -68,6 +69,28 @@ def _call(lib, db, fn, args, wait, tolerate, keep, held):
         lib.cc_db_query_wait(db)
         raise _error(fn, rc, msg)
     return chk(lib, lib.cc_db_query_wait(db), "cc_db_query_wait", tolerate)
+
+
+def ingest_images(lib, ctx, height, pos_rc, n, min_height=None, out=None, dbg=None, stream=None, host=False, bev=None):
+    """Descriptors from n max-height images (include/cont2_amd_images.h).  height / pos_rc / out: addresses (pos_rc may be None) --
+    device ones for cc_ingest_images (dbg: the address of a cc_ingest_debug_t or None), host ones for host=True
+    (cc_ingest_images_host; bev: the address of the host image output or None).  min_height: None or n host f32 values, copied by
+    the library before it returns.  -> the return code (the caller checks it)"""
+    mh = None
+    if min_height is not None:
+        mh = np.ascontiguousarray(np.asarray(min_height, np.float32).reshape(-1))
+        if len(mh) != n:
+            raise ValueError("min_height must hold one value per image: %d for %d images" % (len(mh), n))
+    if host:
+        return lib.cc_ingest_images_host(ctx, height, pos_rc, n, _a(mh), out, bev)
+    return lib.cc_ingest_images(ctx, height, pos_rc, n, _a(mh), out, dbg, stream)
+
+
+def scan_ingest_image(lib, ctx, height, pos_rc, min_height, want_bev, out_handle):
+    """cc_scan_ingest_image: height / pos_rc host addresses (pos_rc may be None), min_height None or one value; out_handle: a
+    ctypes c_void_p that receives the cc_scan.  -> the return code"""
+    mh = None if min_height is None else np.asarray([min_height], np.float32)
+    return lib.cc_scan_ingest_image(ctx, height, pos_rc, _a(mh), int(bool(want_bev)), C.byref(out_handle))
 
 
 def detail_buffer(n, ranked, detail):

@@ -21,8 +21,10 @@
 #include <vector>
 
 #include "../../include/cont2_amd.h"
+#include "../../include/cont2_amd_images.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
+#include "k_image.h"
 #include "k_contours.h"
 #include "k_contours_list.h"
 #include "k_knn.h"
@@ -38,6 +40,9 @@
 
 #ifndef CC_INGEST_BLOCK
 #define CC_INGEST_BLOCK 1024  // threads per workgroup of the per-scan ingest kernels
+#endif
+#ifndef CC_IMAGE_BLOCK
+#define CC_IMAGE_BLOCK CC_INGEST_BLOCK  // ... and of cc_k_image_list (256 and 512 measured: DESIGN.md 3.0)
 #endif
 
 static thread_local std::string g_err;
@@ -420,6 +425,10 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: grid larger than 150 x 150 cells");
   }
+  if (nc % 4 != 0) {  // (an even grid: cc_make_dev_cfg) image b0 of a cc_ingest_images call starts b0 * n_cell floats in, 16-byte aligned like the base
+    cc_destroy(c);
+    return set_err(CC_EINVAL, "cc_create: n_row * n_col must be a multiple of 4");
+  }
   if (k1_lds<cc_src_rng<CC_K1_WORD_U16>>(c) > 160 * 1024) {
     cc_destroy(c);
     return set_err(CC_EINVAL, "cc_create: the range-image kernels' tables do not fit the LDS behind this grid");
@@ -513,8 +522,8 @@ static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
 // points.  ingest_on reads DEVICE addresses; scan_ingest_points and the *_host calls are handed the caller's host addresses and put the
 // device ones in before they pass it on.
 struct k1_source {
-  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS } kind;
-  const void *points = nullptr;              // POINTS, MOTION: the records; RANGES: the range words (a "point" is a pixel)
+  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES } kind;
+  const void *points = nullptr;              // POINTS, MOTION: the records; RANGES: the range words (a "point" is a pixel); IMAGES: the heights (a "point" is a cell)
   cc_point_layout_t lay = {16, 0};           // POINTS, MOTION (has passed point_layout)
   const float *h_tf = nullptr;               // POINTS: [n_scans][12] or nullptr
   cc_point_motion_t mot = {};                // MOTION (has passed motion_check), with
@@ -524,6 +533,8 @@ struct k1_source {
   cc_k1_seg *segs = nullptr;                 // SEGMENTS (segs_check's table): one entry per segment, `base` the address of its first x;
   const int32_t *scan_segs = nullptr;        //   [n_scans + 1], relative to segs[0]; the scans' point totals are the call's offsets
   const cc_point_segment_t *h_segs = nullptr;  //   the caller's entries of the same segments (what the host calls copy from)
+  const float *pos_rc = nullptr;             // IMAGES: [n_scans][n_cell][2] or nullptr (the cell centres); the scans' offsets are the cells' (i * n_cell)
+  const float *h_min = nullptr;              // IMAGES: [n_scans] or nullptr (the minimum over the occupied cells)
 };
 static k1_source k1_points(const void *points, const cc_point_layout_t &lay, const float *h_tf) {
   k1_source s = {k1_source::POINTS, points, lay, h_tf};
@@ -539,6 +550,12 @@ static k1_source k1_ranges(const struct cc_range_sensor *sensor, const void *wor
 }
 static k1_source k1_segments(cc_k1_seg *segs, const int32_t *scan_segs, const cc_point_segment_t *h_segs) {
   k1_source s = {k1_source::SEGMENTS, nullptr, {16, 0}, nullptr, {}, nullptr, nullptr, nullptr, segs, scan_segs, h_segs};
+  return s;
+}
+static k1_source k1_images(const float *height, const float *pos_rc, const float *h_min) {
+  k1_source s = {k1_source::IMAGES, height};
+  s.pos_rc = pos_rc;
+  s.h_min = h_min;
   return s;
 }
 static_assert(CC_K1_MOT_KNOTS_MAX == CC_MOTION_KNOTS_MAX, "k_rasterize.h's knot table holds CC_MOTION_KNOTS_MAX matrices");
@@ -597,7 +614,7 @@ static char *slot_stage(cc_ctx *c, int slot, size_t bytes) {
 }
 // What a chunk's K1 reads on the device besides the points and the offsets: set by the staging functions, read by k1_dispatch.
 struct k1_staged {
-  const float *d_tf = nullptr;  // POINTS
+  const float *d_tf = nullptr;  // POINTS; IMAGES: the chunk's min_height values
   cc_k1_motion mot = {};        // MOTION
   cc_k1_range rng = {};         // RANGES
   cc_k1_segs segs = {};         // SEGMENTS
@@ -657,6 +674,14 @@ static int k1_stage(cc_ctx *c, cc_ctx::Scratch &S, int slot, long long *off, con
       const float *none = nullptr;
       return st.rng.n_knots > 0 ? stage_knots(c, S, slot, nullptr, src.h_knots, st.rng.n_knots, b0, nb, stream, none, st.rng.knots) : CC_OK;
     }
+    case k1_source::IMAGES:
+      if (src.h_min) {  // the chunk's minima ride where a chunk's transforms do (an image call has none), and wait in S.d_tf
+        float *mins = (float *)(off + c->off_cap + 1);
+        memcpy(mins, src.h_min + (size_t)b0, sizeof(float) * (size_t)nb);
+        HIPCHK(hipMemcpyAsync(S.d_tf, mins, sizeof(float) * (size_t)nb, hipMemcpyHostToDevice, stream));
+        st.d_tf = S.d_tf;
+      }
+      return CC_OK;
   }
   return CC_OK;
 }
@@ -689,6 +714,10 @@ static int k1_dispatch(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, cons
       }
     case k1_source::SEGMENTS:
       return k1_launch(c, S, cc_src_seg{st.segs}, nb, want_dense, stream);
+    case k1_source::IMAGES:  // first = b0 * n_cell, a multiple of 4 floats (cc_create): the chunk's base is 16-byte aligned like the call's
+      hipLaunchKernelGGL((cc_k_image_list<CC_IMAGE_BLOCK>), dim3(nb), dim3(CC_IMAGE_BLOCK), 0, stream, c->dcfg, (const float4 *)((const float *)src.points + first),
+                         src.pos_rc ? (const float2 *)src.pos_rc + first : nullptr, st.d_tf, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);
+      return CC_OK;
   }
   return CC_OK;
 }
@@ -697,7 +726,7 @@ static int k1_dispatch(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, cons
 static int ingest_on(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg,
                      hipStream_t stream, const char *who) {
   HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < n_scans; i++) {
+  for (int i = 0; i < n_scans && src.kind != k1_source::IMAGES; i++) {  // (an image is the caller's: no rule on points)
     const int64_t n = h_offsets[i + 1] - h_offsets[i];
     if (!(n > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
     if (n >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": scan with >= 2^21 points"));
@@ -834,6 +863,7 @@ static int ingest_host(cc_ctx *c, k1_source src, size_t pts_bytes, const int64_t
   int rc = e == hipSuccess ? CC_OK : set_err(CC_EHIP, CC_WHO(": H2D"), e);
   if (rc == CC_OK) {
     src.points = d_x;
+    if (src.kind == k1_source::IMAGES && src.pos_rc) src.pos_rc = (const float *)d_x + offsets[n_scans];  // the positions lie behind the heights
     std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
     rc = ingest_on(c, c->main, src, offsets, n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
   }
@@ -995,6 +1025,54 @@ int cc_ingest_ranges_host(cc_ctx *c, const cc_range_sensor *sensor, const void *
   const size_t img_bytes = (size_t)off[n_scans] * (size_t)sensor->word_bytes;
   return ingest_host(c, k1_ranges(sensor, nullptr, h_knots), img_bytes, off.data(), n_scans, h_out, h_bev, who,
                      [&](char *d_x, cc_scan_desc_t *) { return hipMemcpy(d_x, h_ranges, img_bytes, hipMemcpyHostToDevice); });
+}
+
+// ---- descriptors from caller-made max-height images (include/cont2_amd_images.h) ----
+// the scans' offsets in "points": an image's cells
+static std::vector<int64_t> images_offsets(const cc_ctx *c, int n_scans) {
+  std::vector<int64_t> off((size_t)n_scans + 1);
+  for (int i = 0; i <= n_scans; i++) off[i] = (int64_t)i * c->dcfg.n_cell;
+  return off;
+}
+static int images_check(const cc_ctx *c, const void *height, const void *out, int n_scans, const char *who) {
+  const char *why = nullptr;
+  if (!c) why = "ctx must not be NULL";
+  else if (!height) why = "height must not be NULL";
+  else if (!out) why = "out must not be NULL";
+  else if (n_scans < 0) why = "n_scans must not be negative";
+  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
+  return CC_OK;
+}
+
+int cc_ingest_images(cc_ctx *c, const float *d_height, const float *d_pos_rc, int n_scans, const float *h_min_height, cc_scan_desc_t *d_out,
+                     const cc_ingest_debug_t *dbg, void *stream_) {
+  const char *who = "cc_ingest_images";
+  const int rcc = images_check(c, d_height, d_out, n_scans, who);
+  if (rcc != CC_OK) return rcc;
+  if (((uintptr_t)d_height & 15u) != 0) return set_err(CC_EINVAL, CC_WHO(": d_height must be 16-byte aligned"));
+  if (((uintptr_t)d_pos_rc & 7u) != 0) return set_err(CC_EINVAL, CC_WHO(": d_pos_rc must be 8-byte aligned"));
+  if (n_scans == 0) return CC_OK;
+  const std::vector<int64_t> off = images_offsets(c, n_scans);
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+  return ingest_on(c, c->main, k1_images(d_height, d_pos_rc, h_min_height), off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who);
+}
+
+int cc_ingest_images_host(cc_ctx *c, const float *h_height, const float *h_pos_rc, int n_scans, const float *h_min_height, cc_scan_desc_t *h_out,
+                          float *h_bev) {
+  const char *who = "cc_ingest_images_host";
+  const int rcc = images_check(c, h_height, h_out, n_scans, who);
+  if (rcc != CC_OK) return rcc;
+  if (n_scans == 0) return CC_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const std::vector<int64_t> off = images_offsets(c, n_scans);
+  const size_t h_bytes = sizeof(float) * (size_t)off[n_scans], p_bytes = h_pos_rc ? 2 * h_bytes : 0;  // the positions go behind the heights
+  return ingest_host(c, k1_images(nullptr, h_pos_rc, h_min_height), h_bytes + p_bytes, off.data(), n_scans, h_out, h_bev, who,
+                     [&](char *d_x, cc_scan_desc_t *d_o) {
+                       hipError_t e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
+                       if (e == hipSuccess) e = hipMemcpy(d_x, h_height, h_bytes, hipMemcpyHostToDevice);
+                       if (e == hipSuccess && h_pos_rc) e = hipMemcpy(d_x + h_bytes, h_pos_rc, p_bytes, hipMemcpyHostToDevice);
+                       return e;
+                     });
 }
 
 // SO(3) in f64 for cc_motion_knots: R row-major 3 x 3.
@@ -1332,9 +1410,17 @@ int cc_scan_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *
   return scan_ingest_points(c, k1_ranges(sensor, h_ranges, h_knots), nullptr, (int64_t)sensor->kr.n_rows * sensor->kr.n_cols, 0, want_bev, out, who);
 }
 
+int cc_scan_ingest_image(cc_ctx *c, const float *h_height, const float *h_pos_rc, const float *h_min_height, int want_bev, cc_scan **out) {
+  const char *who = "cc_scan_ingest_image";
+  const int rcc = images_check(c, h_height, out, 0, who);
+  if (rcc != CC_OK) return rcc;
+  return scan_ingest_points(c, k1_images(h_height, h_pos_rc, h_min_height), nullptr, (int64_t)c->dcfg.n_cell, 0, want_bev, out, who);
+}
+
 // One scan of the per-scan loop.  src: the caller's arguments with HOST addresses, checked here but for a range image's (cc_scan_ingest_ranges
 // has): POINTS, MOTION: src.points are n_points records of `layout` (src.lay is set here); RANGES: n_points words; SEGMENTS: src.h_segs are
-// the scan's n_segs segments -- their records go to the staging buffer one segment after the other, each at a 16-byte boundary.
+// the scan's n_segs segments -- their records go to the staging buffer one segment after the other, each at a 16-byte boundary; IMAGES: src.points
+// are the n_points = n_cell heights and src.pos_rc the positions or nullptr -- the positions go behind the heights (always through the context's own slot).
 static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t *layout, int64_t n_points, int n_segs, int want_bev, cc_scan **out, const char *who) {
   const void *h_xyzi = src.points;
   const cc_point_segment_t *h_segs = src.h_segs;
@@ -1351,7 +1437,7 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
     src.segs = seg_tab.data();
     src.scan_segs = seg_scan;
     n_points = seg_qoff[1];
-  } else if (src.kind != k1_source::RANGES) {
+  } else if (src.kind != k1_source::RANGES && src.kind != k1_source::IMAGES) {
     const int rcl = point_layout(layout, nullptr, who, &src.lay);  // (the records go through a staging buffer to aligned device memory)
     if (rcl != CC_OK) return rcl;
     if (src.kind == k1_source::MOTION) {
@@ -1359,19 +1445,26 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
       if (rcm != CC_OK) return rcm;
     }
   }
-  const size_t n_bytes = h_segs ? seg_bytes : (size_t)n_points * (size_t)(src.kind == k1_source::RANGES ? src.sensor->word_bytes : src.lay.stride_bytes);   // the records travel as they are
+  const bool is_img = src.kind == k1_source::IMAGES;
+  const size_t img_bytes = is_img ? sizeof(float) * (size_t)n_points : 0;
+  const size_t n_bytes = is_img   ? img_bytes * (src.pos_rc ? 3 : 1)
+                         : h_segs ? seg_bytes
+                                  : (size_t)n_points * (size_t)(src.kind == k1_source::RANGES ? src.sensor->word_bytes : src.lay.stride_bytes);   // the records travel as they are
   const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);  // d_pts, the slots, the scratch behind cc_ingest_batch
   HIPCHK(hipSetDevice(c->device));
   int slot = -1;
   for (int i = 0; i < cc_ctx::NPTS; i++)
-    if (c->h_pts[i] && h_xyzi == c->h_pts[i]) slot = i;
+    if (c->h_pts[i] && h_xyzi == c->h_pts[i] && !is_img) slot = i;
   if (slot < 0) {
     float *dst = stage_slot_locked(c, n_stage, cc_ctx::OWN_SLOT, lk);  // waits for the slot's holder and its previous copy, grows the buffers if need be
     if (!dst) return set_err(CC_EHIP, CC_WHO(": staging buffer"));
     if (h_segs) {
       for (int k = 0; k < n_segs; k++)
         if (seg_tab[k].n > 0) memcpy((char *)dst + seg_place[k], h_segs[k].points, (size_t)seg_tab[k].n * seg_tab[k].stride);
+    } else if (is_img) {
+      memcpy(dst, h_xyzi, img_bytes);
+      if (src.pos_rc) memcpy((char *)dst + img_bytes, src.pos_rc, 2 * img_bytes);
     } else {
       memcpy(dst, h_xyzi, n_bytes);
     }
@@ -1421,7 +1514,7 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
   dbg.d_bev = want_bev ? ch.d_bev_copy : nullptr;
   dbg.d_pix_rc = nullptr;
   dbg.d_labels = nullptr;
-  if (h_segs) {  // a pool slot holds an earlier scan's rows: zero, as cc_ingest_segments_host does, for the same bytes
+  if (h_segs || is_img) {  // a pool slot holds an earlier scan's rows: zero, as cc_ingest_segments_host does, for the same bytes
     const hipError_t e_ = hipMemsetAsync(sc->d_desc, 0, sizeof(cc_scan_desc_t), ch.s);
     if (e_ != hipSuccess) {
       give_back();
@@ -1430,6 +1523,7 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
   }
   for (int k = 0; k < n_segs; k++) seg_tab[k].base = (const char *)ch.d_pts + seg_place[k] + (seg_tab[k].base - (const char *)h_segs[k].points);
   src.points = ch.d_pts;
+  if (is_img && src.pos_rc) src.pos_rc = ch.d_pts + n_points;
   const int rc = ingest_on(c, ch.scr, src, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
   if (rc != CC_OK) {
     give_back();

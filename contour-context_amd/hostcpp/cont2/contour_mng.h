@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../../include/cont2_amd.h"
+#include "../../../include/cont2_amd_images.h"
 #include "../compat/compat.h"
 
 typedef float KeyFloatType;
@@ -455,6 +456,26 @@ class ContourManager {
     want_images_ = keepImages();
     if (cc_scan_ingest_ranges(ctx, image.sensor, image.words, image.knots.empty() ? nullptr : image.knots[0].data(), want_images_ ? 1 : 0, &scan_) != CC_OK)
       die();
+    str_id_ = std::move(str_id);
+  }
+
+  // Mirror-only: makeBEV for a scan that already IS a max-height image (cc_scan_ingest_image, include/cont2_amd_images.h, has the
+  // rules): n_row_ * n_col_ image heights (z + lidar_height_, what getBevImage() returns), row-major, and optionally the continuous
+  // (row_f, col_f) of every occupied cell's point -- the reference's bev_pixfs_, from which resumeImage() rebuilds bev_; without them
+  // the cell centres.  min_height (has_min) becomes the descriptor's min_bin_val: an image cannot tell the lowest accepted point.  getBevImage()
+  // of a manager made from a cloud, fed back with its pillar positions and its minimum, gives that manager's contours again.
+  struct HeightImage {
+    const float *height;
+    const float *pos_rc = nullptr;
+    bool has_min = false;
+    float min_height = 0;
+  };
+  void makeBEV(const HeightImage &image, std::string str_id = "") {
+    CC_CHECK(image.height);
+    CC_CHECK(!scan_);
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_image(ctx, image.height, image.pos_rc, image.has_min ? &image.min_height : nullptr, want_images_ ? 1 : 0, &scan_) != CC_OK) die();
     str_id_ = std::move(str_id);
   }
 
