@@ -34,7 +34,7 @@ HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17"
 
 def build(force=False, verbose=False):
     """Compile the HIP library for gfx950 (cross-compiles without a GPU)."""
-    srcs = [os.path.join(_HERE, "csrc", s) for s in _SRCS] + [os.path.join(_HERE, "..", "include", h) for h in ["cont2_amd.h"] + list(abi.EXTENSIONS)]
+    srcs = [os.path.join(_HERE, "csrc", s) for s in _SRCS] + [os.path.join(_HERE, "..", "include", h) for h in ["cont2_amd.h"] + list(abi.EXTENSIONS) + list(abi.ADDONS)]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(s) <= os.path.getmtime(LIB_PATH) for s in srcs):
         return LIB_PATH
     cmd = ["hipcc"] + HIPCC_FLAGS + [os.path.join(_HERE, "csrc", "cont2_amd.hip"), "-ldl", "-o", LIB_PATH]
@@ -48,6 +48,7 @@ _lib = None
 
 EXPORTS = list(abi.SIGNATURES)  # every symbol include/cont2_amd.h declares
 EXPORTS_EXT = [s for table in abi.EXTENSIONS.values() for s in table]  # ... and every symbol of the extension headers beside it
+EXPORTS_ADDON = [s for table in abi.ADDONS.values() for s in table]  # ... and of the add-on headers (abi.ADDONS: open-ended)
 
 
 def lib():
@@ -122,6 +123,35 @@ def _scan_motion(motion, t_begin, scale, knots, tf, n):
     tb = t_begin.astype(np.uint32).view(np.float32) if t_begin.dtype.kind in "ui" else t_begin.astype(np.float32)
     tm = np.ascontiguousarray(np.stack([tb.reshape(n), np.asarray(scale, np.float32).reshape(n)], 1))
     return L.PointMotion(int(time_offset), TIME_TYPES[time_type], knots.shape[1] // 12, 0), tm, knots
+
+
+class PointFilter:
+    """Which records an ingest keeps, by ONE word of the record itself (include/cont2_amd_filter.h): the keep= of Context.ingest /
+    ingest_host.  The result is ingest()'s for the kept records alone, in their order.  Made by classes() or range()."""
+
+    def __init__(self, c_struct, bits):
+        self._c, self._bits = c_struct, bits   # (the struct points into bits)
+
+    @classmethod
+    def classes(cls, offset, dtype, keep=None, drop=None, n_classes=None, shift=0, mask=None, other="keep"):
+        """An integer word ("u8" | "u16" | "u32") at byte `offset` of every record: class = (word >> shift) & mask.  Exactly one of
+        keep / drop lists classes; n_classes (default: the largest one listed + 1, at most 4096) bounds the table, and a class at or
+        beyond it is kept or dropped as other = "keep" | "drop" says.  SemanticKITTI's moving objects:
+        PointFilter.classes(12, "u32", drop=range(252, 260), mask=0xFFFF)."""
+        return cls(*calls.class_filter(offset, dtype, keep, drop, n_classes, shift, mask, other))
+
+    @classmethod
+    def range(cls, offset, lo, hi):
+        """An f32 word at byte `offset`: kept iff lo <= v <= hi (a NaN is dropped; lo / hi may be infinite)."""
+        return cls(*calls.range_filter(offset, lo, hi))
+
+
+def _keep_filter(keep, motion):
+    if not isinstance(keep, PointFilter):
+        raise ValueError("keep must be a PointFilter (PointFilter.classes / PointFilter.range)")
+    if motion is not None:
+        raise ValueError("keep and motion exclude each other")
+    return keep._c
 
 
 def motion_knots(pose_begin, pose_end, ref=1.0, K=32):
@@ -285,7 +315,7 @@ class Context:
         except Exception:
             pass
 
-    def ingest(self, xyzi, offsets, out=None, debug=False, layout=None, tf=None, motion=None, t_begin=None, scale=None, knots=None):
+    def ingest(self, xyzi, offsets, out=None, debug=False, layout=None, tf=None, motion=None, t_begin=None, scale=None, knots=None, keep=None):
         """xyzi: torch float32 CUDA tensor [total_points, 4]; offsets: int64 host array [n+1] (in points).
         layout: where x, y, z sit in a record -- None / "xyzi" (16-byte KITTI records), "xyz" (packed, 12 bytes) or a
         (stride_bytes, xyz_offset) pair; with a layout `xyzi` is any contiguous CUDA tensor holding the records (cc_ingest_points).
@@ -293,10 +323,13 @@ class Context:
         motion: (time_offset, "f32" | "u32") -- every record carries a 4-byte time word at that byte offset and every point is
         moved by the knot matrix of its time bin (cc_ingest_points_motion): knots [n, K, 3, 4] or [n, K, 12], t_begin [n] and
         scale [n] (bins per time unit), all host; bin = trunc(clamp((t - t_begin) * scale, 0, K - 1)).  Not together with tf.
+        keep: a PointFilter -- records are dropped by a label / ring / intensity word of their own while they are rasterised
+        (cc_ingest_points_filtered): the result is that of the kept records alone.  With layout and tf, not with motion.
         Returns a torch uint8 CUDA tensor [n, DESC_BYTES] (array of cc_scan_desc_t) (+ debug dict)."""
         import torch
         if motion is None and (knots is not None or t_begin is not None or scale is not None):
             raise ValueError("knots, t_begin and scale come with motion=(time_offset, type)")
+        flt = None if keep is None else _keep_filter(keep, motion)
         assert xyzi.is_cuda and xyzi.is_contiguous() and (layout is not None or xyzi.dtype == torch.float32)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(offsets) - 1
@@ -316,6 +349,9 @@ class Context:
             _chk(lib().cc_ingest_points_motion(self.h, xyzi.data_ptr(), C.addressof(lay) if lay is not None else None, C.addressof(mo),
                                                offsets.ctypes.data, n, tm.ctypes.data, kn.ctypes.data, out.data_ptr(), dbg_p, stream),
                  "cc_ingest_points_motion")
+        elif flt is not None:
+            _chk(calls.ingest_points_filtered(lib(), self.h, xyzi.data_ptr(), _point_layout(layout), flt, offsets, _scan_tf(tf, n), out.data_ptr(), dbg_p,
+                                              stream), "cc_ingest_points_filtered")
         elif layout is None and tf is None:
             _chk(lib().cc_ingest_batch(self.h, xyzi.data_ptr(), offsets.ctypes.data, n, out.data_ptr(), dbg_p, stream),
                  "cc_ingest_batch")
@@ -488,14 +524,20 @@ class Context:
         _chk(lib().cc_mask_gates(self.h, xy.data_ptr(), n, gates.data_ptr(), nr, bits.data_ptr(), rw, stream), "cc_mask_gates")
         return bits
 
-    def ingest_host(self, xyzi, offsets, layout=None, tf=None, motion=None, t_begin=None, scale=None, knots=None):
-        """Host records in, host descriptors out.  layout / tf / motion, t_begin, scale, knots: as for ingest(); with a layout
+    def ingest_host(self, xyzi, offsets, layout=None, tf=None, motion=None, t_begin=None, scale=None, knots=None, keep=None):
+        """Host records in, host descriptors out.  layout / tf / motion, t_begin, scale, knots, keep: as for ingest(); with a layout
         `xyzi` is a contiguous numpy array of any dtype holding the records as they are."""
         offsets = np.ascontiguousarray(offsets, np.int64)
         n = len(offsets) - 1
         out = np.zeros(n, L.scan_desc_dt)
         if motion is None and (knots is not None or t_begin is not None or scale is not None):
             raise ValueError("knots, t_begin and scale come with motion=(time_offset, type)")
+        if keep is not None:
+            flt = _keep_filter(keep, motion)
+            xyzi = np.ascontiguousarray(xyzi, np.float32) if layout is None else np.ascontiguousarray(xyzi)
+            _chk(calls.ingest_points_filtered(lib(), self.h, xyzi.ctypes.data, _point_layout(layout), flt, offsets, _scan_tf(tf, n), out.ctypes.data,
+                                              host=True), "cc_ingest_points_filtered_host")
+            return out
         if motion is not None:
             lay = _point_layout(layout)
             mo, tm, kn = _scan_motion(motion, t_begin, scale, knots, tf, n)

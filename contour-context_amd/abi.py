@@ -1,6 +1,7 @@
 """The ctypes signature of every function include/cont2_amd.h declares, in one table, and bind() to apply it to a loaded
 library (the product's, the CPU harness's, another build).  tests/test_abi_layout.py holds the table against the header.
-The extension headers beside it (include/cont2_amd_images.h) have tables of their own, EXTENSIONS, which bind() applies as well.
+The extension headers beside it have tables of their own, which bind() applies as well: EXTENSIONS (include/cont2_amd_images.h) and
+the open-ended ADDONS (include/cont2_amd_filter.h and whatever follows).
 
 One line per prototype, in the header's order: return code, name, one code per parameter.
   parameters   P any pointer or array   I int / int32_t   Q int64_t   Z size_t   D double   F float   (- : none)
@@ -141,10 +142,22 @@ I cc_scan_ingest_image PPPPIP
 }
 EXTENSIONS = {hdr: _table(spec) for hdr, spec in _EXT_SPEC.items()}
 
+# The add-on headers: every later header of include/ joins HERE, one entry each, and nothing else has to know how many there are.
+# (EXTENSIONS stays the one header it was made for: its test holds the dictionary itself to that header.)  Each add-on's own test
+# holds its entry against its header, as tests/test_abi_filter.py does.
+_ADDON_SPEC = {
+    "cont2_amd_filter.h": """
+I cc_ingest_points_filtered PPPPPIPPPP
+I cc_ingest_points_filtered_host PPPPPIPPP
+I cc_scan_ingest_points_filtered PPPPQPIP
+""",
+}
+ADDONS = {hdr: _table(spec) for hdr, spec in _ADDON_SPEC.items()}
+
 
 def bind(cdll):
     """Give every function of the tables its restype and argtypes on `cdll` (a library that lacks one is an AttributeError)."""
-    for table in [SIGNATURES] + list(EXTENSIONS.values()):
+    for table in [SIGNATURES] + list(EXTENSIONS.values()) + list(ADDONS.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(cdll, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -14,7 +14,9 @@ entry point runs is behaviour (a synchronous *_batch cuts one chunk per lane, a 
            a record source: cc_db_verify_submit_packed
   hints    cc_db_check_hints[_ranked[_detail]] (synchronous by itself)
   pose     descriptors: cc_db_pose_batch (wait) / cc_db_pose_submit; a record source: cc_db_pose_submit_packed
-Beside the scoring flows: ingest_images / scan_ingest_image, the calls of include/cont2_amd_images.h (descriptors from max-height images)."""
+Beside the scoring flows: ingest_images / scan_ingest_image, the calls of include/cont2_amd_images.h (descriptors from max-height images),
+and class_filter / range_filter / ingest_points_filtered / scan_ingest_points_filtered, those of include/cont2_amd_filter.h (records
+dropped by a label, ring or intensity word of their own)."""
 import ctypes as C
 
 import numpy as np
@@ -91,6 +93,54 @@ def scan_ingest_image(lib, ctx, height, pos_rc, min_height, want_bev, out_handle
     ctypes c_void_p that receives the cc_scan.  -> the return code"""
     mh = None if min_height is None else np.asarray([min_height], np.float32)
     return lib.cc_scan_ingest_image(ctx, height, pos_rc, _a(mh), int(bool(want_bev)), C.byref(out_handle))
+
+
+FILTER_WORDS = {"u8": (L.FILTER_U8, 8), "u16": (L.FILTER_U16, 16), "u32": (L.FILTER_U32, 32)}   # names of the class rule's word types -> (CC_FILTER_*, bits)
+
+
+def class_filter(offset, dtype, keep=None, drop=None, n_classes=None, shift=0, mask=None, other="keep"):
+    """The class rule of include/cont2_amd_filter.h -> (L.PointFilterC, its keep_bits array, which the struct points into): the record's
+    word (dtype "u8" | "u16" | "u32" or the numpy dtype) at byte `offset`, class = (word >> shift) & mask (mask None: all ones); kept
+    are the classes of `keep`, or all but those of `drop` (exactly one is given); n_classes defaults to the largest class named + 1,
+    and a class at or beyond it is kept or dropped as other = "keep" | "drop" says."""
+    name = dtype if isinstance(dtype, str) else {1: "u8", 2: "u16", 4: "u32"}.get(np.dtype(dtype).itemsize if np.dtype(dtype).kind == "u" else 0)
+    if name not in FILTER_WORDS:
+        raise ValueError("unknown class word %r (known: %s)" % (dtype, sorted(FILTER_WORDS)))
+    if other not in ("keep", "drop"):
+        raise ValueError('other must be "keep" or "drop"')
+    if (keep is None) == (drop is None):
+        raise ValueError("give exactly one of keep and drop")
+    named = [int(v) for v in (keep if keep is not None else drop)]
+    if n_classes is None:
+        n_classes = max(named) + 1 if named else 1
+    n_classes = int(n_classes)
+    if not 1 <= n_classes <= L.FILTER_CLASSES_MAX:
+        raise ValueError("n_classes must be 1 .. %d" % L.FILTER_CLASSES_MAX)
+    bits = L.class_bits(n_classes, keep=None if keep is None else named, drop=None if drop is None else named)
+    f = L.PointFilterC(int(offset), FILTER_WORDS[name][0], int(shift), 0xFFFFFFFF if mask is None else int(mask) & 0xFFFFFFFF, n_classes,
+                       int(other == "keep"), 0.0, 0.0, bits.ctypes.data)
+    return f, bits
+
+
+def range_filter(offset, lo, hi):
+    """The range rule: the record's f32 at byte `offset` is kept iff lo <= v <= hi (a NaN is dropped; lo / hi may be infinite)."""
+    return L.PointFilterC(int(offset), L.FILTER_F32, 0, 0, 0, 0, float(lo), float(hi), None), None
+
+
+def ingest_points_filtered(lib, ctx, points, layout, flt, offsets, tf=None, out=None, dbg=None, stream=None, host=False, bev=None):
+    """cc_ingest_points_filtered / (host=True) cc_ingest_points_filtered_host.  points / out: addresses (device, or host with host=True);
+    layout: an L.PointLayout or None; flt: an L.PointFilterC (or None: the library refuses it); offsets: int64 [n + 1]; tf: f32 [n, 12]
+    or None; dbg: the address of a cc_ingest_debug_t (device form), bev: of the host image output (host form).  -> the return code"""
+    n = len(offsets) - 1
+    if host:
+        return lib.cc_ingest_points_filtered_host(ctx, points, _a(layout), _a(flt), _a(offsets), n, _a(tf), out, bev)
+    return lib.cc_ingest_points_filtered(ctx, points, _a(layout), _a(flt), _a(offsets), n, _a(tf), out, dbg, stream)
+
+
+def scan_ingest_points_filtered(lib, ctx, points, layout, flt, n_points, tf, want_bev, out_handle):
+    """cc_scan_ingest_points_filtered: points a host address, tf None or 12 f32; out_handle: a ctypes c_void_p that receives the cc_scan.
+    -> the return code"""
+    return lib.cc_scan_ingest_points_filtered(ctx, points, _a(layout), _a(flt), int(n_points), _a(tf), int(bool(want_bev)), C.byref(out_handle))
 
 
 def detail_buffer(n, ranked, detail):

@@ -22,6 +22,7 @@
 
 #include "../../include/cont2_amd.h"
 #include "../../include/cont2_amd_images.h"
+#include "../../include/cont2_amd_filter.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
 #include "k_image.h"
@@ -80,6 +81,7 @@ struct cc_ctx {
     long long *d_offsets = nullptr;
     float *d_tf = nullptr;  // [cap][12]: the per-scan transforms of a call that brings some (cc_ingest_points)
     float *d_mot = nullptr;  // a chunk's [nb][2] times, then its [nb][K][12] knots (cc_ingest_points_motion); allocated at first use
+    unsigned *d_flt = nullptr;  // a call's class table (cc_ingest_points_filtered): CC_K1_FLT_TAB_WORDS words; allocated at first use
     char *d_seg = nullptr;  // a chunk's segment table (cc_ingest_segments): int scan_seg[cap + 1], then up to cap * CC_SEG_MAX cc_k1_seg; allocated at first use
     // the slow path of K2 (scans with more than CC_MAXC components on a level): queue filled by the fast launch, a few
     // workgroups with CC_NC_BIG-sized tables in global memory
@@ -204,6 +206,7 @@ static void scratch_free(cc_ctx::Scratch &S) {
   hipFree(S.d_tf);
   hipFree(S.d_seg);
   hipFree(S.d_mot);
+  hipFree(S.d_flt);
   hipFree(S.d_bigq);
   hipFree(S.d_midq);
   if (S.h_mid_seen) hipHostFree(S.h_mid_seen);
@@ -222,7 +225,7 @@ static void scratch_free(cc_ctx::Scratch &S) {
 template <typename... SRC>
 struct k1_list {};
 typedef k1_list<cc_src_kitti, cc_src_rec<12>, cc_src_rec<16>, cc_src_rec<0>, cc_src_mot<16>, cc_src_mot<32>, cc_src_mot<0>, cc_src_seg, cc_src_rng<CC_K1_WORD_U16>,
-                cc_src_rng<CC_K1_WORD_U32>, cc_src_rng<CC_K1_WORD_F32>>
+                cc_src_rng<CC_K1_WORD_U32>, cc_src_rng<CC_K1_WORD_F32>, cc_src_flt<CC_K1_FLT_CLASS>, cc_src_flt<CC_K1_FLT_RANGE>>
     k1_sources;
 template <typename S, typename... SRC>
 static constexpr bool k1_listed(k1_list<SRC...>) {
@@ -522,10 +525,10 @@ static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
 // points.  ingest_on reads DEVICE addresses; scan_ingest_points and the *_host calls are handed the caller's host addresses and put the
 // device ones in before they pass it on.
 struct k1_source {
-  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES } kind;
+  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES, FILTERED } kind;
   const void *points = nullptr;              // POINTS, MOTION: the records; RANGES: the range words (a "point" is a pixel); IMAGES: the heights (a "point" is a cell)
-  cc_point_layout_t lay = {16, 0};           // POINTS, MOTION (has passed point_layout)
-  const float *h_tf = nullptr;               // POINTS: [n_scans][12] or nullptr
+  cc_point_layout_t lay = {16, 0};           // POINTS, MOTION, FILTERED (has passed point_layout)
+  const float *h_tf = nullptr;               // POINTS, FILTERED: [n_scans][12] or nullptr
   cc_point_motion_t mot = {};                // MOTION (has passed motion_check), with
   const float *h_time = nullptr;             //   [n_scans][2]
   const float *h_knots = nullptr;            // MOTION, RANGES: [n_scans][K][12] (RANGES: nullptr iff K == 0)
@@ -535,6 +538,7 @@ struct k1_source {
   const cc_point_segment_t *h_segs = nullptr;  //   the caller's entries of the same segments (what the host calls copy from)
   const float *pos_rc = nullptr;             // IMAGES: [n_scans][n_cell][2] or nullptr (the cell centres); the scans' offsets are the cells' (i * n_cell)
   const float *h_min = nullptr;              // IMAGES: [n_scans] or nullptr (the minimum over the occupied cells)
+  cc_point_filter_t flt = {};                // FILTERED (has passed filter_check); the records, layout and h_tf are POINTS'
 };
 static k1_source k1_points(const void *points, const cc_point_layout_t &lay, const float *h_tf) {
   k1_source s = {k1_source::POINTS, points, lay, h_tf};
@@ -558,6 +562,12 @@ static k1_source k1_images(const float *height, const float *pos_rc, const float
   s.h_min = h_min;
   return s;
 }
+static k1_source k1_filtered(const void *points, const cc_point_layout_t &lay, const float *h_tf, const cc_point_filter_t &flt) {
+  k1_source s = {k1_source::FILTERED, points, lay, h_tf};
+  s.flt = flt;
+  return s;
+}
+static_assert(CC_K1_FLT_CLASSES_MAX == CC_FILTER_CLASSES_MAX, "k_rasterize.h's class table holds CC_FILTER_CLASSES_MAX classes");
 static_assert(CC_K1_MOT_KNOTS_MAX == CC_MOTION_KNOTS_MAX, "k_rasterize.h's knot table holds CC_MOTION_KNOTS_MAX matrices");
 // A range sensor: the checked model with its tables on the device (cc_range_sensor_create).
 struct cc_range_sensor {
@@ -595,6 +605,25 @@ static int motion_check(const cc_point_layout_t &lay, const cc_point_motion_t *m
   if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
   return CC_OK;
 }
+// Everything the header promises to check about the filter (`lay` has passed point_layout), before anything is queued or read.
+static int filter_bytes(int type) { return type == CC_FILTER_U8 ? 1 : type == CC_FILTER_U16 ? 2 : 4; }
+static int filter_check(const cc_point_layout_t &lay, const cc_point_filter_t *f, const char *who) {
+  const char *why = nullptr;
+  if (!f) why = "filter must not be NULL";
+  else if (f->type != CC_FILTER_U8 && f->type != CC_FILTER_U16 && f->type != CC_FILTER_U32 && f->type != CC_FILTER_F32) why = "type must be CC_FILTER_U8, _U16, _U32 or _F32";
+  else {
+    const int size = filter_bytes(f->type);
+    if (f->offset < 0 || f->offset % size != 0 || f->offset > lay.stride_bytes - size) why = "offset must be a multiple of the word's size with offset + size <= stride_bytes";
+    else if (f->offset + size > lay.xyz_offset && f->offset < lay.xyz_offset + 12) why = "the filter word overlaps x, y, z";
+    else if (f->type == CC_FILTER_F32) {
+      if (std::isnan(f->lo) || std::isnan(f->hi)) why = "lo and hi must not be NaN";
+    } else if (f->shift < 0 || f->shift >= 8 * size) why = "shift must be 0 .. the word's bit width - 1";
+    else if (f->n_classes < 1 || f->n_classes > CC_FILTER_CLASSES_MAX) why = "n_classes must be 1 .. CC_FILTER_CLASSES_MAX";
+    else if (!f->keep_bits) why = "keep_bits must not be NULL for an integer type";
+  }
+  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
+  return CC_OK;
+}
 // `bytes` of pinned memory in slot `slot` of the staging ring (the buffer the chunk's segment table, times and knots ride in), grown
 // when it is too small; nullptr with the error set when the allocation fails.
 static char *slot_stage(cc_ctx *c, int slot, size_t bytes) {
@@ -618,7 +647,35 @@ struct k1_staged {
   cc_k1_motion mot = {};        // MOTION
   cc_k1_range rng = {};         // RANGES
   cc_k1_segs segs = {};         // SEGMENTS
+  cc_k1_filter flt = {};        // FILTERED
 };
+// What the kernels take of a checked filter.  The class rule reads the aligned dword that holds the word: the word's byte position
+// and width go into the shift and the mask, so one instance serves u8, u16 and u32.  Its table rides in slot `slot` of the staging
+// ring (the segment tables' buffer: a call has one or the other) to S.d_flt, with keep_other as bit n_classes and zeros behind it.
+static int stage_filter(cc_ctx *c, cc_ctx::Scratch &S, int slot, const k1_source &src, hipStream_t stream, cc_k1_filter &kf) {
+  const cc_point_filter_t &f = src.flt;
+  kf.w_off = (f.offset & ~3) - src.lay.xyz_offset;
+  kf.lo = f.lo;
+  kf.hi = f.hi;
+  if (f.type == CC_FILTER_F32) return CC_OK;
+  const int size = filter_bytes(f.type);
+  const unsigned typemask = size == 4 ? 0xFFFFFFFFu : ((1u << (8 * size)) - 1u);
+  kf.shift = (unsigned)(8 * (f.offset & 3) + f.shift);
+  kf.mask = f.mask & (typemask >> f.shift);
+  kf.n_classes = (unsigned)f.n_classes;
+  const size_t bytes = sizeof(unsigned) * CC_K1_FLT_TAB_WORDS;
+  if (!S.d_flt) HIPCHK(hipMalloc(&S.d_flt, bytes));
+  if (!slot_stage(c, slot, bytes)) return CC_EHIP;
+  unsigned *tab = (unsigned *)c->h_seg[slot];
+  const int nw = (f.n_classes + 31) / 32;
+  memset(tab, 0, bytes);
+  memcpy(tab, f.keep_bits, sizeof(unsigned) * (size_t)nw);
+  if (f.n_classes % 32) tab[nw - 1] &= (1u << (f.n_classes % 32)) - 1u;  // (the caller's bits behind n_classes are not part of the table)
+  if (f.keep_other) tab[f.n_classes >> 5] |= 1u << (f.n_classes & 31);
+  HIPCHK(hipMemcpyAsync(S.d_flt, tab, bytes, hipMemcpyHostToDevice, stream));
+  kf.bits = S.d_flt;
+  return CC_OK;
+}
 // A chunk's knots (behind its [nb][2] times when h_time is given) to S.d_mot.  They ride in slot `slot` of the staging ring, in the
 // segment tables' buffer: a call has one or the other.
 static int stage_knots(cc_ctx *c, cc_ctx::Scratch &S, int slot, const float *h_time, const float *h_knots, int n_knots, int b0, int nb, hipStream_t stream,
@@ -652,6 +709,11 @@ static int stage_segments(cc_ctx *c, cc_ctx::Scratch &S, int slot, const k1_sour
 static int k1_stage(cc_ctx *c, cc_ctx::Scratch &S, int slot, long long *off, const k1_source &src, const int64_t *h_offsets, int b0, int nb, hipStream_t stream,
                     k1_staged &st) {
   switch (src.kind) {
+    case k1_source::FILTERED: {
+      const int rcf = stage_filter(c, S, slot, src, stream, st.flt);
+      if (rcf != CC_OK) return rcf;
+    }
+      [[fallthrough]];  // the transforms: as for POINTS
     case k1_source::POINTS:
       if (src.h_tf) {  // the chunk's transforms ride in the same slot, behind the offsets
         float *tfs = (float *)(off + c->off_cap + 1);
@@ -690,7 +752,7 @@ static int k1_stage(cc_ctx *c, cc_ctx::Scratch &S, int slot, long long *off, con
 static int k1_dispatch(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, const k1_staged &st, int64_t first, int nb, int want_dense, hipStream_t stream) {
   const int stride = src.lay.stride_bytes;
   const char *rpts = nullptr;  // POINTS, MOTION: x of the chunk's first point
-  if (src.kind == k1_source::POINTS || src.kind == k1_source::MOTION) rpts = (const char *)src.points + (long long)first * stride + src.lay.xyz_offset;
+  if (src.kind == k1_source::POINTS || src.kind == k1_source::MOTION || src.kind == k1_source::FILTERED) rpts = (const char *)src.points + (long long)first * stride + src.lay.xyz_offset;
   switch (src.kind) {
     case k1_source::POINTS:
       if (stride == 16 && src.lay.xyz_offset == 0 && !src.h_tf && ((uintptr_t)src.points & 15u) == 0)
@@ -714,6 +776,9 @@ static int k1_dispatch(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, cons
       }
     case k1_source::SEGMENTS:
       return k1_launch(c, S, cc_src_seg{st.segs}, nb, want_dense, stream);
+    case k1_source::FILTERED:
+      if (src.flt.type == CC_FILTER_F32) return k1_launch(c, S, cc_src_flt<CC_K1_FLT_RANGE>{rpts, stride, st.d_tf, st.flt}, nb, want_dense, stream);
+      return k1_launch(c, S, cc_src_flt<CC_K1_FLT_CLASS>{rpts, stride, st.d_tf, st.flt}, nb, want_dense, stream);
     case k1_source::IMAGES:  // first = b0 * n_cell, a multiple of 4 floats (cc_create): the chunk's base is 16-byte aligned like the call's
       hipLaunchKernelGGL((cc_k_image_list<CC_IMAGE_BLOCK>), dim3(nb), dim3(CC_IMAGE_BLOCK), 0, stream, c->dcfg, (const float4 *)((const float *)src.points + first),
                          src.pos_rc ? (const float2 *)src.pos_rc + first : nullptr, st.d_tf, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);
@@ -913,6 +978,43 @@ int cc_ingest_points_motion_host(cc_ctx *c, const void *h_points, const cc_point
   const char *who = "cc_ingest_points_motion_host";
   if (!motion) return set_err(CC_EINVAL, CC_WHO(": motion, h_time and h_knots must not be NULL"));
   return ingest_points_host(c, h_points, layout, h_offsets, n_scans, nullptr, h_out, h_bev, who, motion, h_time, h_knots);
+}
+
+// ---- records dropped by a word of their own (include/cont2_amd_filter.h) ----
+int cc_ingest_points_filtered(cc_ctx *c, const void *d_points, const cc_point_layout_t *layout, const cc_point_filter_t *filter, const int64_t *h_offsets,
+                              int n_scans, const float *h_tf, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
+  const char *who = "cc_ingest_points_filtered";
+  if (!c || !d_points || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, d_points, who, &lay);
+  if (rcl != CC_OK) return rcl;
+  const int rcf = filter_check(lay, filter, who);
+  if (rcf != CC_OK) return rcf;
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+  return ingest_on(c, c->main, k1_filtered(d_points, lay, h_tf, *filter), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who);
+}
+
+int cc_ingest_points_filtered_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_filter_t *filter, const int64_t *h_offsets,
+                                   int n_scans, const float *h_tf, cc_scan_desc_t *h_out, float *h_bev) {
+  const char *who = "cc_ingest_points_filtered_host";
+  if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  cc_point_layout_t lay;
+  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records are copied to aligned device memory)
+  if (rcl != CC_OK) return rcl;
+  const int rcf = filter_check(lay, filter, who);
+  if (rcf != CC_OK) return rcf;
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t base = h_offsets[0];
+  const size_t pts_bytes = (size_t)lay.stride_bytes * (size_t)(h_offsets[n_scans] - base);
+  std::vector<int64_t> off(n_scans + 1);
+  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
+  const char *h_first = (const char *)h_points + (size_t)lay.stride_bytes * (size_t)base;
+  return ingest_host(c, k1_filtered(nullptr, lay, h_tf, *filter), pts_bytes, off.data(), n_scans, h_out, h_bev, who, [&](char *d_x, cc_scan_desc_t *d_o) {
+    // (zeroed as cc_ingest_images_host does: the kernels never write behind a descriptor's counts, and the host gets the bytes of a device call into zeroed memory)
+    hipError_t e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(d_x, h_first, pts_bytes, hipMemcpyHostToDevice);
+    return e;
+  });
 }
 
 // ---- a sensor's range image rasterised in place (cc_ingest_ranges and its siblings) ----
@@ -1402,6 +1504,12 @@ int cc_scan_ingest_points_motion(cc_ctx *c, const void *h_points, const cc_point
   return scan_ingest_points(c, k1_motion(h_points, CC_LAYOUT_KITTI, *motion, h_time, h_knots), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points_motion");
 }
 
+int cc_scan_ingest_points_filtered(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_filter_t *filter, int64_t n_points,
+                                   const float *h_tf, int want_bev, cc_scan **out) {
+  if (!filter) return set_err(CC_EINVAL, "cc_scan_ingest_points_filtered: filter must not be NULL");
+  return scan_ingest_points(c, k1_filtered(h_points, CC_LAYOUT_KITTI, h_tf, *filter), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points_filtered");
+}
+
 int cc_scan_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, const float *h_knots, int want_bev, cc_scan **out) {
   const char *who = "cc_scan_ingest_ranges";
   if (!c || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
@@ -1443,6 +1551,10 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
     if (src.kind == k1_source::MOTION) {
       const int rcm = motion_check(src.lay, &src.mot, src.h_time, src.h_knots, 1, who);
       if (rcm != CC_OK) return rcm;
+    }
+    if (src.kind == k1_source::FILTERED) {
+      const int rcf = filter_check(src.lay, &src.flt, who);
+      if (rcf != CC_OK) return rcf;
     }
   }
   const bool is_img = src.kind == k1_source::IMAGES;

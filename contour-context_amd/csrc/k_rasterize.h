@@ -1136,6 +1136,80 @@ struct cc_ld_range {
   }
 };
 
+// ---- records DROPPED by a word of their own (cc_ingest_points_filtered, include/cont2_amd_filter.h): every record carries a label, ring,
+// tag or intensity word, and a rule on that word says whether the record is kept.  A dropped record gets x = NaN after cc_ld_rec::xyz's
+// operations, as a range image's pixel without a return does: cc_point_cell rejects it, so it owns no cell, takes part in no tie and
+// counts in no minimum -- no new branch, and the result is cc_ingest_points' for the records with those x replaced by NaN.
+//   CC_K1_FLT_CLASS : class = (dword >> shift) & mask of the ALIGNED dword that holds the word -- records are 4-byte aligned and
+//                     strides multiples of 4, so that dword is in bounds wherever the word is; the host folds the word's byte
+//                     position and width into the one shift and the one mask, which makes u8, u16 and u32 words ONE instance.
+//                     kept = bit min(class, n_classes) of the call's table: bit n_classes holds keep_other, so a class beyond the
+//                     table costs one v_min_u32, not a compare and two selects.  The table (CC_K1_FLT_CLASSES_MAX + 1 bits, 528 B
+//                     with the padding) sits in LDS behind cc_k1_sweep's layout: one ds_read_b32 at a per-lane address, a shift and
+//                     an AND per point.  The records of a wave are neighbouring firings, mostly of one class: equal addresses are a
+//                     broadcast.
+//   CC_K1_FLT_RANGE : kept = lo <= v && v <= hi on the f32 word (a NaN fails both compares); no table.
+// The stride is a run-time value and has_tf cc_ld_rec's workgroup-uniform switch: 4 sweep instances and 1 merge instance per kind.
+#define CC_K1_FLT_CLASSES_MAX 4096  // = CC_FILTER_CLASSES_MAX (include/cont2_amd_filter.h; checked where both are seen)
+#define CC_K1_FLT_TAB_WORDS (CC_K1_FLT_CLASSES_MAX / 32 + 1)
+#define CC_K1_FLT_LDS_BYTES ((CC_K1_FLT_TAB_WORDS * 4 + 15) & ~15)
+static_assert(((CC_MAX_CELLS * 4 + 15) & ~15) + ((CC_MAX_CELLS + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15) + CC_K1_FLT_LDS_BYTES <= 160 * 1024,
+              "cc_src_flt: grid, index fields, output tables and the class table fit a CU's 160 KB of LDS");
+enum { CC_K1_FLT_CLASS = 0, CC_K1_FLT_RANGE = 1 };
+struct cc_k1_filter {
+  const unsigned *bits;  // CLASS: the call's table, CC_K1_FLT_TAB_WORDS words (bit n_classes = keep_other, the bits behind it 0)
+  int w_off;             // byte offset from the record's x of the dword the loader reads (negative: the word sits in front of xyz)
+  unsigned shift, mask;  // CLASS: class = (dword >> shift) & mask
+  unsigned n_classes;
+  float lo, hi;          // RANGE
+};
+
+// The call's table to LDS (a barrier has to follow before xyz() is called).  T: CC_K1_FLT_LDS_BYTES.
+__device__ __forceinline__ void cc_k1_filter_table(unsigned *T, const cc_k1_filter &F) {
+  for (int i = threadIdx.x; i < CC_K1_FLT_TAB_WORDS; i += blockDim.x) T[i] = F.bits[i];
+}
+
+template <int KIND>
+struct cc_ld_rec_flt {
+  typedef cc_xyzt rec;         // (w: the filter word's dword as it lies in the record)
+  cc_ld_rec<0> R;              // base, run-time stride, the workgroup-uniform transform: cc_ld_rec's, used as they are
+  int w_off;
+  unsigned shift, mask, n_classes;  // workgroup-uniform: scalars
+  float lo, hi;
+  const unsigned *T;           // LDS (CLASS)
+  __device__ __forceinline__ cc_ld_rec_flt(const char *base, int stride_bytes, const float *__restrict__ tf, int scan, const cc_k1_filter &F, const unsigned *lds_tab)
+      : R(base, stride_bytes, tf, scan), w_off(F.w_off), shift(F.shift), mask(F.mask), n_classes(F.n_classes), lo(F.lo), hi(F.hi), T(lds_tab) {}
+  __device__ __forceinline__ void advance(long long n) { R.advance(n); }
+  // the coordinates and the filter word are requested together, neither under a branch
+  __device__ __forceinline__ rec load(int j) const {
+    cc_xyzt q;
+    const char *p = R.B + (unsigned)j * R.stride;
+    cc_load3f(p, q.x, q.y, q.z);
+    q.w = *(const unsigned *)(p + w_off);
+    return q;
+  }
+  __device__ __forceinline__ static rec zero() { return cc_xyzt{0.f, 0.f, 0.f, 0u}; }
+  __device__ __forceinline__ bool keep(unsigned w) const {
+    if (KIND == CC_K1_FLT_RANGE) {
+      const float v = __int_as_float((int)w);
+      return (lo <= v) & (v <= hi);  // (a NaN fails both)
+    }
+    unsigned cls = (w >> shift) & mask;
+    cls = cls < n_classes ? cls : n_classes;  // <= CC_K1_FLT_CLASSES_MAX: inside the table
+    return ((T[cls >> 5] >> (cls & 31u)) & 1u) != 0u;
+  }
+  __device__ __forceinline__ void xyz(const rec &q, float &x, float &y, float &z) const {
+    R.xyz(cc_xyz{q.x, q.y, q.z}, x, y, z);
+    x = keep(q.w) ? x : __int_as_float(0x7FC00000);  // cc_point_cell rejects a NaN x: the record owns nothing and counts nowhere
+  }
+  // (an owner is a kept record: testing it again changes nothing, and the one function keeps the bits the sweep saw)
+  __device__ __forceinline__ float2 owner_xy(int j) const {
+    float x, y, z;
+    xyz(load(j), x, y, z);
+    return make_float2(x, y);
+  }
+};
+
 
 // ---- point SOURCES: what a call hands the kernels, one by-value struct per family.  A source is the kernel argument and knows how
 // to make its family's loader:
@@ -1178,6 +1252,23 @@ struct cc_src_mot {
   __device__ __forceinline__ void tables(char *tab, int scan) const { cc_k1_knot_table((float *)tab, mot, scan); }
   __device__ __forceinline__ cc_ld_rec_motion<STRIDE> loader(int scan, const char *tab) const {
     return cc_ld_rec_motion<STRIDE>(pts, stride, mot, scan, (const float *)tab);
+  }
+};
+// Records dropped by a word of their own (cc_ingest_points_filtered).  KIND: CC_K1_FLT_CLASS (a table in LDS) / CC_K1_FLT_RANGE (none).
+// pts, stride, tf: cc_src_rec<0>'s.
+template <int KIND>
+struct cc_src_flt {
+  static constexpr int TAB_BYTES = KIND == CC_K1_FLT_CLASS ? CC_K1_FLT_LDS_BYTES : 0, TAB_ALIGN = KIND == CC_K1_FLT_CLASS ? 16 : 1;
+  static constexpr bool SEGMENTED = false;
+  const char *pts;
+  int stride;
+  const float *tf;
+  cc_k1_filter flt;
+  __device__ __forceinline__ void tables(char *tab, int) const {
+    if (KIND == CC_K1_FLT_CLASS) cc_k1_filter_table((unsigned *)tab, flt);
+  }
+  __device__ __forceinline__ cc_ld_rec_flt<KIND> loader(int scan, const char *tab) const {
+    return cc_ld_rec_flt<KIND>(pts, stride, tf, scan, flt, (const unsigned *)tab);
   }
 };
 // Range images (cc_ingest_ranges).  WORD: CC_K1_WORD_U16 / _U32 / _F32.  offsets: scan i's first pixel = i * n_rows * n_cols.

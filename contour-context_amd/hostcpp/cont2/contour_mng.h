@@ -17,6 +17,7 @@
 
 #include "../../../include/cont2_amd.h"
 #include "../../../include/cont2_amd_images.h"
+#include "../../../include/cont2_amd_filter.h"
 #include "../compat/compat.h"
 
 typedef float KeyFloatType;
@@ -411,6 +412,38 @@ class ContourManager {
     cc_ctx *ctx = cc_host::context(ccfg_);
     want_images_ = keepImages();
     if (cc_scan_ingest_points_motion(ctx, base, &lay, &mo, (int64_t)ptr_gapc->size(), h_time, motion.knots[0].data(), want_images_ ? 1 : 0, &scan_) != CC_OK)
+      die();
+    str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
+  }
+
+  // Mirror-only: makeBEV that DROPS points by a word of their own record while they are rasterised -- the moving-object classes of a
+  // semantic segmentation (SemanticKITTI: class = label & 0xFFFF, 252 .. 259 are moving), a driver's noise tag, a subset of rings, an
+  // intensity band (cc_scan_ingest_points_filtered, include/cont2_amd_filter.h).  `filter` is the C-ABI's struct as it is: offset and
+  // type of the word inside PointType, then the class rule (shift, mask, n_classes, keep_other, keep_bits: bit c set = class c is
+  // kept) or the f32 band (lo, hi).  The BEV is that of the kept points alone, in their order; the cloud's own records go to the
+  // device as they are: no mask, gather and second copy.  T_bev_sensor: as in the overload above, or nullptr; the filter looks at the
+  // record, not at the moved point.  The cloud must hold more than 10 records, however many are kept.
+  struct BevFilter {
+    cc_point_filter_t filter{};
+    const float (*T_bev_sensor)[12] = nullptr;
+  };
+  template <typename PointType>
+  void makeBEV(typename pcl::PointCloud<PointType>::ConstPtr &ptr_gapc, const BevFilter &flt, std::string str_id = "") {
+    CC_CHECK(ptr_gapc);
+    CC_CHECK(ptr_gapc->size() > 10);
+    CC_CHECK(!scan_);
+    static_assert(sizeof(PointType) % 4 == 0 && sizeof(PointType) <= CC_POINT_STRIDE_MAX, "makeBEV: a record the rasteriser's loaders do not take");
+    const PointType &p0 = ptr_gapc->points[0];
+    const char *base = reinterpret_cast<const char *>(&p0);
+    CC_CHECK(reinterpret_cast<const char *>(&p0.y) == reinterpret_cast<const char *>(&p0.x) + 4);
+    CC_CHECK(reinterpret_cast<const char *>(&p0.z) == reinterpret_cast<const char *>(&p0.x) + 8);
+    cc_point_layout_t lay;
+    lay.stride_bytes = (int32_t)sizeof(PointType);
+    lay.xyz_offset = (int32_t)(reinterpret_cast<const char *>(&p0.x) - base);
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_points_filtered(ctx, base, &lay, &flt.filter, (int64_t)ptr_gapc->size(), flt.T_bev_sensor ? *flt.T_bev_sensor : nullptr,
+                                       want_images_ ? 1 : 0, &scan_) != CC_OK)
       die();
     str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
   }

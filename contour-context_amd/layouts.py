@@ -194,6 +194,33 @@ class PointMotion(C.Structure):
 assert C.sizeof(PointMotion) == 16
 
 
+FILTER_CLASSES_MAX = 4096                                     # CC_FILTER_CLASSES_MAX (include/cont2_amd_filter.h)
+FILTER_U8, FILTER_U16, FILTER_U32, FILTER_F32 = 0, 1, 2, 3    # CC_FILTER_U8 / _U16 / _U32 / _F32
+
+
+class PointFilterC(C.Structure):
+    """cc_point_filter_t: the filter word of a record and the rule that keeps a record (class table or f32 band)."""
+    _fields_ = [("offset", C.c_int32), ("type", C.c_int32), ("shift", C.c_int32), ("mask", C.c_uint32), ("n_classes", C.c_int32),
+                ("keep_other", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("keep_bits", C.c_void_p)]
+
+
+assert C.sizeof(PointFilterC) == 40 and PointFilterC.lo.offset == 24 and PointFilterC.keep_bits.offset == 32
+
+
+def class_bits(n_classes, keep=None, drop=None):
+    """The keep_bits of a class rule: uint32 [(n_classes + 31) // 32] with bit c set iff class c is kept -- the classes of `keep`, or
+    all but those of `drop` (exactly one of the two is given; every class named must be below n_classes)."""
+    if (keep is None) == (drop is None):
+        raise ValueError("give exactly one of keep and drop")
+    named = np.asarray(list(keep if keep is not None else drop), np.int64).reshape(-1)
+    if named.size and (named.min() < 0 or named.max() >= n_classes):
+        raise ValueError("a class outside 0 .. n_classes - 1 = %d" % (n_classes - 1))
+    kept = np.zeros(((n_classes + 31) // 32) * 32, bool)
+    kept[:n_classes] = keep is None
+    kept[named] = keep is not None
+    return np.ascontiguousarray(np.packbits(kept, bitorder="little").view(np.uint32))
+
+
 RANGE_ROWS_MAX, RANGE_COLS_MAX = 128, 4096              # CC_RANGE_ROWS_MAX / CC_RANGE_COLS_MAX
 RANGE_U16, RANGE_U32, RANGE_F32 = 0, 1, 2               # CC_RANGE_U16 / _U32 / _F32
 RANGE_ROW_MAJOR, RANGE_COL_MAJOR = 0, 1                 # CC_RANGE_ROW_MAJOR / _COL_MAJOR
