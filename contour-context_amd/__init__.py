@@ -154,6 +154,32 @@ def _keep_filter(keep, motion):
     return keep._c
 
 
+def _coord_streams(xyz, on_device):
+    """The xyz of Context.ingest_coords / ingest_coords_host -> (address of the first x, y, z, dtype, stride in bytes, device).
+    One 2-D tensor / array [N, >= 3] of any strides, or three 1-D ones of equal dtype and stride; nothing is copied."""
+    def addr(t):
+        return t.data_ptr() if on_device else t.ctypes.data
+
+    def strides(t):
+        return [s * t.element_size() for s in t.stride()] if on_device else list(t.strides)
+
+    if isinstance(xyz, (tuple, list)):
+        if len(xyz) != 3 or any(getattr(t, "ndim", 0) != 1 for t in xyz):
+            raise ValueError("xyz must be one 2-D [N, >= 3] tensor or a tuple of three 1-D tensors")
+        a, b, c = xyz
+        if not (a.dtype == b.dtype == c.dtype and len(a) == len(b) == len(c) and strides(a) == strides(b) == strides(c)):
+            raise ValueError("the three coordinate columns must have one dtype, one length and one stride")
+        ptrs, stride, first = [addr(t) for t in xyz], strides(a)[0], a
+    else:
+        if getattr(xyz, "ndim", 0) != 2 or xyz.shape[1] < 3:
+            raise ValueError("xyz must be one 2-D [N, >= 3] tensor or a tuple of three 1-D tensors")
+        st = strides(xyz)
+        ptrs, stride, first = [addr(xyz) + k * st[1] for k in range(3)], st[0], xyz
+    if on_device and not all(t.is_cuda for t in (xyz if isinstance(xyz, (tuple, list)) else [xyz])):
+        raise ValueError("ingest_coords takes CUDA tensors (ingest_coords_host: numpy arrays)")
+    return ptrs[0], ptrs[1], ptrs[2], first.dtype, stride, (first.device if on_device else None)
+
+
 def motion_knots(pose_begin, pose_end, ref=1.0, K=32):
     """Knot matrices of a sweep from the poses (3 x 4 [R | p], sensor to world) at its begin and end (cc_motion_knots): knot k =
     T(ref)^-1 T((k + 0.5) / K) with the rotation interpolated on SO(3) and the position linearly; ref in [0, 1] is the instant the
@@ -360,6 +386,43 @@ class Context:
             _chk(lib().cc_ingest_points(self.h, xyzi.data_ptr(), C.addressof(lay) if lay is not None else None, offsets.ctypes.data, n,
                                         tfa.ctypes.data if tfa is not None else None, out.data_ptr(), dbg_p, stream), "cc_ingest_points")
         return (out, dbg) if debug else out
+
+    def ingest_coords(self, xyz, offsets, origin=None, scale=None, tf=None, out=None, debug=False):
+        """Coordinates of another type or shape than ingest()'s records, read where they lie (cc_ingest_coords,
+        include/cont2_amd_coords.h).  xyz: ONE 2-D CUDA tensor [N, >= 3] -- columns 0 - 2 are x, y, z, ANY strides are taken: a
+        float64 [N, 3], a view t[:, 2:5] of a wider tensor, a transposed [3, N].T, all without a copy -- or a tuple of three 1-D
+        CUDA tensors of equal dtype and stride (three columns).  dtype float32, float64 or int32 (anything else: ValueError).
+        origin: [n, 3] float64 on the host, subtracted in f64 BEFORE the narrowing to f32 (a georeferenced cloud's local origin);
+        scale: 3 values (or one), with int32 only -- p = float(double(v) * scale - origin), every step rounded once; tf: as for
+        ingest(), applied to p.  The result is ingest()'s for the packed f32 points p.  Returns ingest()'s outputs."""
+        import torch
+        x, y, z, dtype, stride, dev = _coord_streams(xyz, True)
+        src = calls.coord_src(x, y, z, dtype, stride, scale)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        if out is None:
+            out = torch.empty((n, DESC_BYTES), dtype=torch.uint8, device=dev)
+        dbg_p, dbg = None, None
+        if debug:
+            dbg = {"bev": torch.empty((n, self.n_cell), dtype=torch.float32, device=dev),
+                   "pix_rc": torch.empty((n, self.n_cell, 2), dtype=torch.float32, device=dev),
+                   "labels": torch.empty((n, L.NLEV, self.n_cell), dtype=torch.int16, device=dev)}
+            st = IngestDebug(dbg["bev"].data_ptr(), dbg["pix_rc"].data_ptr(), dbg["labels"].data_ptr())
+            dbg_p = C.addressof(st)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _chk(calls.ingest_coords(lib(), self.h, src, offsets, origin, _scan_tf(tf, n), out.data_ptr(), dbg_p, stream), "cc_ingest_coords")
+        return (out, dbg) if debug else out
+
+    def ingest_coords_host(self, xyz, offsets, origin=None, scale=None, tf=None):
+        """ingest_coords() with numpy arrays: host coordinates in (one 2-D array of any strides, or a tuple of three 1-D arrays), host
+        descriptors out (cc_ingest_coords_host).  Exactly the bytes the streams span are copied to the device."""
+        x, y, z, dtype, stride, _ = _coord_streams(xyz, False)
+        src = calls.coord_src(x, y, z, dtype, stride, scale)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        n = len(offsets) - 1
+        out = np.zeros(n, L.scan_desc_dt)
+        _chk(calls.ingest_coords(lib(), self.h, src, offsets, origin, _scan_tf(tf, n), out.ctypes.data, host=True), "cc_ingest_coords_host")
+        return out
 
     def range_sensor(self, rows, cols, word="u16", order="row", range_scale=0.001, beam_alt=None, beam_az_off=None, col_az=None, origin=(0.0, 0.0),
                      col_knot=None, K=0):

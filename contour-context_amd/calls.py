@@ -15,8 +15,9 @@ entry point runs is behaviour (a synchronous *_batch cuts one chunk per lane, a 
   hints    cc_db_check_hints[_ranked[_detail]] (synchronous by itself)
   pose     descriptors: cc_db_pose_batch (wait) / cc_db_pose_submit; a record source: cc_db_pose_submit_packed
 Beside the scoring flows: ingest_images / scan_ingest_image, the calls of include/cont2_amd_images.h (descriptors from max-height images),
-and class_filter / range_filter / ingest_points_filtered / scan_ingest_points_filtered, those of include/cont2_amd_filter.h (records
-dropped by a label, ring or intensity word of their own)."""
+class_filter / range_filter / ingest_points_filtered / scan_ingest_points_filtered, those of include/cont2_amd_filter.h (records
+dropped by a label, ring or intensity word of their own), and coord_src / ingest_coords / scan_ingest_coords, those of
+include/cont2_amd_coords.h (f64, scaled-i32 and split-stream coordinates read in place)."""
 import ctypes as C
 
 import numpy as np
@@ -141,6 +142,49 @@ def scan_ingest_points_filtered(lib, ctx, points, layout, flt, n_points, tf, wan
     """cc_scan_ingest_points_filtered: points a host address, tf None or 12 f32; out_handle: a ctypes c_void_p that receives the cc_scan.
     -> the return code"""
     return lib.cc_scan_ingest_points_filtered(ctx, points, _a(layout), _a(flt), int(n_points), _a(tf), int(bool(want_bev)), C.byref(out_handle))
+
+
+COORD_TYPES = {"float32": L.COORD_F32, "float64": L.COORD_F64, "int32": L.COORD_I32}   # dtype names -> CC_COORD_*
+
+
+def coord_src(x, y, z, dtype, stride_bytes, scale=None):
+    """A cc_coord_src_t (L.CoordSrc) from the addresses of the first point's x, y and z, the element dtype's name ("float32" |
+    "float64" | "int32"; anything else is a ValueError) and the stride between points.  scale: 3 values (or one for all three),
+    with "int32" only; None there means 1.0."""
+    name = str(dtype).replace("torch.", "")
+    if name not in COORD_TYPES:
+        raise ValueError("coordinates must be float32, float64 or int32, not %s" % name)
+    if scale is not None and name != "int32":
+        raise ValueError("scale comes with int32 coordinates")
+    sc = np.ones(3) if scale is None else np.broadcast_to(np.asarray(scale, np.float64).reshape(-1), (3,))
+    return L.CoordSrc(x, y, z, COORD_TYPES[name], int(stride_bytes), (C.c_double * 3)(*[float(v) for v in sc]))
+
+
+def _origin_tf(origin, tf, n):
+    o = None if origin is None else np.ascontiguousarray(np.asarray(origin, np.float64).reshape(-1, 3))
+    t = None if tf is None else np.ascontiguousarray(np.asarray(tf, np.float32).reshape(-1, 12))
+    if (o is not None and len(o) != n) or (t is not None and len(t) != n):
+        raise ValueError("origin must be [n, 3] and tf [n, 12] for the call's n = %d scans" % n)
+    return o, t
+
+
+def ingest_coords(lib, ctx, src, offsets, origin=None, tf=None, out=None, dbg=None, stream=None, host=False, bev=None):
+    """cc_ingest_coords / (host=True) cc_ingest_coords_host.  src: an L.CoordSrc (or None: the library refuses it) whose streams
+    are device addresses, or host ones with host=True; offsets: int64 [n + 1]; origin: f64 [n, 3] or None; tf: f32 [n, 12] or None;
+    out: an address; dbg: the address of a cc_ingest_debug_t (device form), bev: of the host image output (host form).
+    -> the return code"""
+    n = len(offsets) - 1
+    o, t = _origin_tf(origin, tf, n)
+    if host:
+        return lib.cc_ingest_coords_host(ctx, _a(src), _a(offsets), n, _a(o), _a(t), out, bev)
+    return lib.cc_ingest_coords(ctx, _a(src), _a(offsets), n, _a(o), _a(t), out, dbg, stream)
+
+
+def scan_ingest_coords(lib, ctx, src, n_points, origin, tf, want_bev, out_handle):
+    """cc_scan_ingest_coords: src's streams are host addresses, origin None or 3 f64, tf None or 12 f32; out_handle: a ctypes
+    c_void_p that receives the cc_scan.  -> the return code"""
+    o, t = _origin_tf(origin, tf, 1)
+    return lib.cc_scan_ingest_coords(ctx, _a(src), int(n_points), _a(o), _a(t), int(bool(want_bev)), C.byref(out_handle))
 
 
 def detail_buffer(n, ranked, detail):

@@ -23,6 +23,7 @@
 #include "../../include/cont2_amd.h"
 #include "../../include/cont2_amd_images.h"
 #include "../../include/cont2_amd_filter.h"
+#include "../../include/cont2_amd_coords.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
 #include "k_image.h"
@@ -82,6 +83,7 @@ struct cc_ctx {
     float *d_tf = nullptr;  // [cap][12]: the per-scan transforms of a call that brings some (cc_ingest_points)
     float *d_mot = nullptr;  // a chunk's [nb][2] times, then its [nb][K][12] knots (cc_ingest_points_motion); allocated at first use
     unsigned *d_flt = nullptr;  // a call's class table (cc_ingest_points_filtered): CC_K1_FLT_TAB_WORDS words; allocated at first use
+    double *d_org = nullptr;  // a chunk's [nb][3] origins (cc_ingest_coords); allocated at first use
     char *d_seg = nullptr;  // a chunk's segment table (cc_ingest_segments): int scan_seg[cap + 1], then up to cap * CC_SEG_MAX cc_k1_seg; allocated at first use
     // the slow path of K2 (scans with more than CC_MAXC components on a level): queue filled by the fast launch, a few
     // workgroups with CC_NC_BIG-sized tables in global memory
@@ -98,7 +100,7 @@ struct cc_ctx {
   static const int N_BIG_SLOTS = 8;
   Scratch main;
   // pinned staging ring for the per-chunk point offsets (and, behind them, the chunk's 12 floats per scan of a call with
-  // transforms): a slot is reused only after the copies that read it have finished
+  // transforms, then the 3 doubles per scan of a call with origins): a slot is reused only after the copies that read it have finished
   static const int NSLOT = 4;
   long long *h_off[NSLOT] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t off_ev[NSLOT] = {nullptr, nullptr, nullptr, nullptr};
@@ -207,6 +209,7 @@ static void scratch_free(cc_ctx::Scratch &S) {
   hipFree(S.d_seg);
   hipFree(S.d_mot);
   hipFree(S.d_flt);
+  hipFree(S.d_org);
   hipFree(S.d_bigq);
   hipFree(S.d_midq);
   if (S.h_mid_seen) hipHostFree(S.h_mid_seen);
@@ -225,7 +228,8 @@ static void scratch_free(cc_ctx::Scratch &S) {
 template <typename... SRC>
 struct k1_list {};
 typedef k1_list<cc_src_kitti, cc_src_rec<12>, cc_src_rec<16>, cc_src_rec<0>, cc_src_mot<16>, cc_src_mot<32>, cc_src_mot<0>, cc_src_seg, cc_src_rng<CC_K1_WORD_U16>,
-                cc_src_rng<CC_K1_WORD_U32>, cc_src_rng<CC_K1_WORD_F32>, cc_src_flt<CC_K1_FLT_CLASS>, cc_src_flt<CC_K1_FLT_RANGE>>
+                cc_src_rng<CC_K1_WORD_U32>, cc_src_rng<CC_K1_WORD_F32>, cc_src_flt<CC_K1_FLT_CLASS>, cc_src_flt<CC_K1_FLT_RANGE>, cc_src_coord<CC_K1_COORD_F32>,
+                cc_src_coord<CC_K1_COORD_F64>, cc_src_coord<CC_K1_COORD_I32>>
     k1_sources;
 template <typename S, typename... SRC>
 static constexpr bool k1_listed(k1_list<SRC...>) {
@@ -415,7 +419,7 @@ int cc_create(int device, const cc_manager_cfg_t *cfg, int max_batch_scans, cc_c
   }
   c->off_cap = max_batch_scans > CC_SCAN_BATCH_MAX ? max_batch_scans : CC_SCAN_BATCH_MAX;
   for (int i = 0; i < cc_ctx::NSLOT; i++) {
-    CREATE_CHK(hipHostMalloc((void **)&c->h_off[i], (sizeof(long long) + sizeof(float) * 12) * (size_t)(c->off_cap + 1), hipHostMallocDefault));
+    CREATE_CHK(hipHostMalloc((void **)&c->h_off[i], (sizeof(long long) + sizeof(float) * 12 + sizeof(double) * 3) * (size_t)(c->off_cap + 1), hipHostMallocDefault));
     CREATE_CHK(hipEventCreateWithFlags(&c->off_ev[i], hipEventDisableTiming));
   }
   c->lds1 = ((nc * 4 + 15) & ~(size_t)15) + ((nc + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15);
@@ -525,10 +529,10 @@ static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
 // points.  ingest_on reads DEVICE addresses; scan_ingest_points and the *_host calls are handed the caller's host addresses and put the
 // device ones in before they pass it on.
 struct k1_source {
-  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES, FILTERED } kind;
+  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES, FILTERED, COORDS } kind;
   const void *points = nullptr;              // POINTS, MOTION: the records; RANGES: the range words (a "point" is a pixel); IMAGES: the heights (a "point" is a cell)
   cc_point_layout_t lay = {16, 0};           // POINTS, MOTION, FILTERED (has passed point_layout)
-  const float *h_tf = nullptr;               // POINTS, FILTERED: [n_scans][12] or nullptr
+  const float *h_tf = nullptr;               // POINTS, FILTERED, COORDS: [n_scans][12] or nullptr
   cc_point_motion_t mot = {};                // MOTION (has passed motion_check), with
   const float *h_time = nullptr;             //   [n_scans][2]
   const float *h_knots = nullptr;            // MOTION, RANGES: [n_scans][K][12] (RANGES: nullptr iff K == 0)
@@ -539,6 +543,9 @@ struct k1_source {
   const float *pos_rc = nullptr;             // IMAGES: [n_scans][n_cell][2] or nullptr (the cell centres); the scans' offsets are the cells' (i * n_cell)
   const float *h_min = nullptr;              // IMAGES: [n_scans] or nullptr (the minimum over the occupied cells)
   cc_point_filter_t flt = {};                // FILTERED (has passed filter_check); the records, layout and h_tf are POINTS'
+  cc_coord_src_t crd = {};                   // COORDS (has passed coords_check): the three streams of the call's point 0, stride, type, scales
+  const double *h_origin = nullptr;          //   [n_scans][3] or nullptr
+  size_t crd_at[3] = {0, 0, 0};              //   the host calls: where each stream begins in the device copy (coords_plan)
 };
 static k1_source k1_points(const void *points, const cc_point_layout_t &lay, const float *h_tf) {
   k1_source s = {k1_source::POINTS, points, lay, h_tf};
@@ -567,6 +574,14 @@ static k1_source k1_filtered(const void *points, const cc_point_layout_t &lay, c
   s.flt = flt;
   return s;
 }
+static k1_source k1_coords(const cc_coord_src_t &crd, const double *h_origin, const float *h_tf) {
+  k1_source s = {k1_source::COORDS, crd.x, {16, 0}, h_tf};
+  s.crd = crd;
+  s.h_origin = h_origin;
+  return s;
+}
+static_assert((int)CC_K1_COORD_F32 == (int)CC_COORD_F32 && (int)CC_K1_COORD_F64 == (int)CC_COORD_F64 && (int)CC_K1_COORD_I32 == (int)CC_COORD_I32,
+              "k_rasterize.h's coordinate types are the header's");
 static_assert(CC_K1_FLT_CLASSES_MAX == CC_FILTER_CLASSES_MAX, "k_rasterize.h's class table holds CC_FILTER_CLASSES_MAX classes");
 static_assert(CC_K1_MOT_KNOTS_MAX == CC_MOTION_KNOTS_MAX, "k_rasterize.h's knot table holds CC_MOTION_KNOTS_MAX matrices");
 // A range sensor: the checked model with its tables on the device (cc_range_sensor_create).
@@ -624,6 +639,69 @@ static int filter_check(const cc_point_layout_t &lay, const cc_point_filter_t *f
   if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
   return CC_OK;
 }
+// Everything the header promises to check about a cc_*_coords call, before anything is queued or read: the source, the origins, and
+// what ingest_on refuses about the scans' sizes (the host forms size their copies by them).
+static int coord_bytes(int type) { return type == CC_COORD_F64 ? 8 : 4; }
+static int coords_check(const cc_coord_src_t *s, const int64_t *h_offsets, int n_scans, const double *h_origin, const char *who) {
+  const char *why = nullptr;
+  if (!s) why = "src must not be NULL";
+  else if (!s->x || !s->y || !s->z) why = "the x, y and z streams must not be NULL";
+  else if (s->type != CC_COORD_F32 && s->type != CC_COORD_F64 && s->type != CC_COORD_I32) why = "type must be CC_COORD_F32, _F64 or _I32";
+  else {
+    const int size = coord_bytes(s->type);
+    if (s->stride_bytes < size || s->stride_bytes % size != 0) why = "stride_bytes must be a multiple of the element size and not below it";
+    else if (s->stride_bytes > CC_POINT_STRIDE_MAX) why = "stride_bytes above CC_POINT_STRIDE_MAX";
+    else if ((((uintptr_t)s->x | (uintptr_t)s->y | (uintptr_t)s->z) & (uintptr_t)(size - 1)) != 0) why = "every stream must be aligned to the element size";
+    else if (s->type == CC_COORD_I32 && !(std::isfinite(s->scale[0]) && std::isfinite(s->scale[1]) && std::isfinite(s->scale[2]))) why = "every scale must be finite";
+  }
+  for (size_t i = 0; !why && h_origin && i < (size_t)n_scans * 3; i++)
+    if (!std::isfinite(h_origin[i])) why = "every origin component must be finite";
+  for (int i = 0; !why && i < n_scans; i++) {
+    const int64_t n = h_offsets[i + 1] - h_offsets[i];
+    if (!(n > 10)) why = "scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)";
+    else if (n >= (1 << CC_K1_IDX_BITS)) why = "scan with >= 2^21 points";
+  }
+  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
+  return CC_OK;
+}
+// What a host form copies of `points` points from point `first` on, and where the streams begin in the device copy: exactly the bytes
+// the streams span.  The highest stream's element within stride_bytes of the lowest stream: ONE record array, one copy from the lowest
+// pointer; otherwise three arrays, three copies, each at a 16-byte boundary of the device buffer.
+struct coord_plan {
+  int n_copies;
+  const char *h[3];
+  size_t bytes[3], at[3];  // the copies: from, how much, to where in the device buffer
+  size_t strm[3];          // x, y, z of the first point in the device buffer
+  size_t total;
+};
+static coord_plan coords_plan(const cc_coord_src_t &s, int64_t first, int64_t points) {
+  coord_plan p = {};
+  const size_t stride = (size_t)s.stride_bytes, elem = (size_t)coord_bytes(s.type), run = (size_t)(points - 1) * stride;
+  const char *q[3] = {(const char *)s.x + (size_t)first * stride, (const char *)s.y + (size_t)first * stride, (const char *)s.z + (size_t)first * stride};
+  const char *lo = q[0], *hi = q[0];
+  for (int k = 1; k < 3; k++) {
+    lo = (uintptr_t)q[k] < (uintptr_t)lo ? q[k] : lo;
+    hi = (uintptr_t)q[k] > (uintptr_t)hi ? q[k] : hi;
+  }
+  const size_t span = (size_t)((uintptr_t)hi - (uintptr_t)lo) + elem;
+  if (span <= stride) {
+    p.n_copies = 1;
+    p.h[0] = lo;
+    p.bytes[0] = run + span;
+    for (int k = 0; k < 3; k++) p.strm[k] = (size_t)((uintptr_t)q[k] - (uintptr_t)lo);
+    p.total = p.bytes[0];
+  } else {
+    p.n_copies = 3;
+    const size_t piece = (run + elem + 15) & ~(size_t)15;
+    for (int k = 0; k < 3; k++) {
+      p.h[k] = q[k];
+      p.bytes[k] = run + elem;
+      p.at[k] = p.strm[k] = (size_t)k * piece;
+    }
+    p.total = 2 * piece + run + elem;
+  }
+  return p;
+}
 // `bytes` of pinned memory in slot `slot` of the staging ring (the buffer the chunk's segment table, times and knots ride in), grown
 // when it is too small; nullptr with the error set when the allocation fails.
 static char *slot_stage(cc_ctx *c, int slot, size_t bytes) {
@@ -648,6 +726,7 @@ struct k1_staged {
   cc_k1_range rng = {};         // RANGES
   cc_k1_segs segs = {};         // SEGMENTS
   cc_k1_filter flt = {};        // FILTERED
+  const double *d_org = nullptr;  // COORDS: the chunk's origins, or nullptr
 };
 // What the kernels take of a checked filter.  The class rule reads the aligned dword that holds the word: the word's byte position
 // and width go into the shift and the mask, so one instance serves u8, u16 and u32.  Its table rides in slot `slot` of the staging
@@ -709,10 +788,20 @@ static int stage_segments(cc_ctx *c, cc_ctx::Scratch &S, int slot, const k1_sour
 static int k1_stage(cc_ctx *c, cc_ctx::Scratch &S, int slot, long long *off, const k1_source &src, const int64_t *h_offsets, int b0, int nb, hipStream_t stream,
                     k1_staged &st) {
   switch (src.kind) {
-    case k1_source::FILTERED: {
-      const int rcf = stage_filter(c, S, slot, src, stream, st.flt);
-      if (rcf != CC_OK) return rcf;
-    }
+    case k1_source::COORDS:
+      if (src.h_origin) {  // the chunk's origins ride in the same slot, behind the room of the transforms: 24 bytes per scan
+        double *org = (double *)((char *)off + (sizeof(long long) + sizeof(float) * 12) * (size_t)(c->off_cap + 1));
+        if (!S.d_org) HIPCHK(hipMalloc(&S.d_org, sizeof(double) * 3 * (size_t)S.cap));
+        memcpy(org, src.h_origin + (size_t)b0 * 3, sizeof(double) * 3 * (size_t)nb);
+        HIPCHK(hipMemcpyAsync(S.d_org, org, sizeof(double) * 3 * (size_t)nb, hipMemcpyHostToDevice, stream));
+        st.d_org = S.d_org;
+      }
+      [[fallthrough]];  // the transforms: as for POINTS
+    case k1_source::FILTERED:
+      if (src.kind == k1_source::FILTERED) {
+        const int rcf = stage_filter(c, S, slot, src, stream, st.flt);
+        if (rcf != CC_OK) return rcf;
+      }
       [[fallthrough]];  // the transforms: as for POINTS
     case k1_source::POINTS:
       if (src.h_tf) {  // the chunk's transforms ride in the same slot, behind the offsets
@@ -779,6 +868,17 @@ static int k1_dispatch(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, cons
     case k1_source::FILTERED:
       if (src.flt.type == CC_FILTER_F32) return k1_launch(c, S, cc_src_flt<CC_K1_FLT_RANGE>{rpts, stride, st.d_tf, st.flt}, nb, want_dense, stream);
       return k1_launch(c, S, cc_src_flt<CC_K1_FLT_CLASS>{rpts, stride, st.d_tf, st.flt}, nb, want_dense, stream);
+    case k1_source::COORDS: {
+      const long long at = (long long)first * src.crd.stride_bytes;
+      cc_k1_coords kc = {(const char *)src.crd.x + at, (const char *)src.crd.y + at, (const char *)src.crd.z + at, src.crd.stride_bytes, {1.0, 1.0, 1.0}, st.d_org, st.d_tf};
+      switch (src.crd.type) {
+        case CC_COORD_F64: return k1_launch(c, S, cc_src_coord<CC_K1_COORD_F64>{kc}, nb, want_dense, stream);
+        case CC_COORD_I32:
+          for (int k = 0; k < 3; k++) kc.scale[k] = src.crd.scale[k];
+          return k1_launch(c, S, cc_src_coord<CC_K1_COORD_I32>{kc}, nb, want_dense, stream);
+        default: return k1_launch(c, S, cc_src_coord<CC_K1_COORD_F32>{kc}, nb, want_dense, stream);
+      }
+    }
     case k1_source::IMAGES:  // first = b0 * n_cell, a multiple of 4 floats (cc_create): the chunk's base is 16-byte aligned like the call's
       hipLaunchKernelGGL((cc_k_image_list<CC_IMAGE_BLOCK>), dim3(nb), dim3(CC_IMAGE_BLOCK), 0, stream, c->dcfg, (const float4 *)((const float *)src.points + first),
                          src.pos_rc ? (const float2 *)src.pos_rc + first : nullptr, st.d_tf, S.d_bev, S.d_pix, S.d_k1, S.list, want_dense);
@@ -929,6 +1029,11 @@ static int ingest_host(cc_ctx *c, k1_source src, size_t pts_bytes, const int64_t
   if (rc == CC_OK) {
     src.points = d_x;
     if (src.kind == k1_source::IMAGES && src.pos_rc) src.pos_rc = (const float *)d_x + offsets[n_scans];  // the positions lie behind the heights
+    if (src.kind == k1_source::COORDS) {  // the streams lie where coords_plan put them
+      src.crd.x = d_x + src.crd_at[0];
+      src.crd.y = d_x + src.crd_at[1];
+      src.crd.z = d_x + src.crd_at[2];
+    }
     std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
     rc = ingest_on(c, c->main, src, offsets, n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
   }
@@ -1013,6 +1118,38 @@ int cc_ingest_points_filtered_host(cc_ctx *c, const void *h_points, const cc_poi
     // (zeroed as cc_ingest_images_host does: the kernels never write behind a descriptor's counts, and the host gets the bytes of a device call into zeroed memory)
     hipError_t e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
     if (e == hipSuccess) e = hipMemcpy(d_x, h_first, pts_bytes, hipMemcpyHostToDevice);
+    return e;
+  });
+}
+
+// ---- f64, scaled-i32 and split-stream coordinates (include/cont2_amd_coords.h) ----
+int cc_ingest_coords(cc_ctx *c, const cc_coord_src_t *src, const int64_t *h_offsets, int n_scans, const double *h_origin, const float *h_tf, cc_scan_desc_t *d_out,
+                     const cc_ingest_debug_t *dbg, void *stream_) {
+  const char *who = "cc_ingest_coords";
+  if (!c || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  const int rcc = coords_check(src, h_offsets, n_scans, h_origin, who);
+  if (rcc != CC_OK) return rcc;
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
+  return ingest_on(c, c->main, k1_coords(*src, h_origin, h_tf), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who);
+}
+
+int cc_ingest_coords_host(cc_ctx *c, const cc_coord_src_t *src, const int64_t *h_offsets, int n_scans, const double *h_origin, const float *h_tf,
+                          cc_scan_desc_t *h_out, float *h_bev) {
+  const char *who = "cc_ingest_coords_host";
+  if (!c || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  const int rcc = coords_check(src, h_offsets, n_scans, h_origin, who);
+  if (rcc != CC_OK) return rcc;
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t base = h_offsets[0];
+  std::vector<int64_t> off(n_scans + 1);
+  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
+  const coord_plan plan = coords_plan(*src, base, off[n_scans]);
+  k1_source ks = k1_coords(*src, h_origin, h_tf);
+  for (int k = 0; k < 3; k++) ks.crd_at[k] = plan.strm[k];
+  return ingest_host(c, ks, plan.total, off.data(), n_scans, h_out, h_bev, who, [&](char *d_x, cc_scan_desc_t *d_o) {
+    // (zeroed as cc_ingest_points_filtered_host does: the host gets the bytes of a device call into zeroed memory)
+    hipError_t e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
+    for (int k = 0; k < plan.n_copies && e == hipSuccess; k++) e = hipMemcpy(d_x + plan.at[k], plan.h[k], plan.bytes[k], hipMemcpyHostToDevice);
     return e;
   });
 }
@@ -1510,6 +1647,15 @@ int cc_scan_ingest_points_filtered(cc_ctx *c, const void *h_points, const cc_poi
   return scan_ingest_points(c, k1_filtered(h_points, CC_LAYOUT_KITTI, h_tf, *filter), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points_filtered");
 }
 
+int cc_scan_ingest_coords(cc_ctx *c, const cc_coord_src_t *src, int64_t n_points, const double *origin, const float *h_tf, int want_bev, cc_scan **out) {
+  const char *who = "cc_scan_ingest_coords";
+  if (!c || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+  const int64_t off[2] = {0, n_points};
+  const int rcc = coords_check(src, off, 1, origin, who);
+  if (rcc != CC_OK) return rcc;
+  return scan_ingest_points(c, k1_coords(*src, origin, h_tf), nullptr, n_points, 0, want_bev, out, who);
+}
+
 int cc_scan_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, const float *h_knots, int want_bev, cc_scan **out) {
   const char *who = "cc_scan_ingest_ranges";
   if (!c || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
@@ -1545,7 +1691,7 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
     src.segs = seg_tab.data();
     src.scan_segs = seg_scan;
     n_points = seg_qoff[1];
-  } else if (src.kind != k1_source::RANGES && src.kind != k1_source::IMAGES) {
+  } else if (src.kind != k1_source::RANGES && src.kind != k1_source::IMAGES && src.kind != k1_source::COORDS) {
     const int rcl = point_layout(layout, nullptr, who, &src.lay);  // (the records go through a staging buffer to aligned device memory)
     if (rcl != CC_OK) return rcl;
     if (src.kind == k1_source::MOTION) {
@@ -1557,17 +1703,19 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
       if (rcf != CC_OK) return rcf;
     }
   }
-  const bool is_img = src.kind == k1_source::IMAGES;
+  const bool is_img = src.kind == k1_source::IMAGES, is_crd = src.kind == k1_source::COORDS;
+  const coord_plan crd_plan = is_crd ? coords_plan(src.crd, 0, n_points) : coord_plan();
   const size_t img_bytes = is_img ? sizeof(float) * (size_t)n_points : 0;
   const size_t n_bytes = is_img   ? img_bytes * (src.pos_rc ? 3 : 1)
                          : h_segs ? seg_bytes
+                         : is_crd ? crd_plan.total
                                   : (size_t)n_points * (size_t)(src.kind == k1_source::RANGES ? src.sensor->word_bytes : src.lay.stride_bytes);   // the records travel as they are
   const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);  // d_pts, the slots, the scratch behind cc_ingest_batch
   HIPCHK(hipSetDevice(c->device));
   int slot = -1;
   for (int i = 0; i < cc_ctx::NPTS; i++)
-    if (c->h_pts[i] && h_xyzi == c->h_pts[i] && !is_img) slot = i;
+    if (c->h_pts[i] && h_xyzi == c->h_pts[i] && !is_img && !is_crd) slot = i;
   if (slot < 0) {
     float *dst = stage_slot_locked(c, n_stage, cc_ctx::OWN_SLOT, lk);  // waits for the slot's holder and its previous copy, grows the buffers if need be
     if (!dst) return set_err(CC_EHIP, CC_WHO(": staging buffer"));
@@ -1577,6 +1725,8 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
     } else if (is_img) {
       memcpy(dst, h_xyzi, img_bytes);
       if (src.pos_rc) memcpy((char *)dst + img_bytes, src.pos_rc, 2 * img_bytes);
+    } else if (is_crd) {  // exactly the bytes the streams span: one record array, or three arrays
+      for (int k = 0; k < crd_plan.n_copies; k++) memcpy((char *)dst + crd_plan.at[k], crd_plan.h[k], crd_plan.bytes[k]);
     } else {
       memcpy(dst, h_xyzi, n_bytes);
     }
@@ -1626,7 +1776,7 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
   dbg.d_bev = want_bev ? ch.d_bev_copy : nullptr;
   dbg.d_pix_rc = nullptr;
   dbg.d_labels = nullptr;
-  if (h_segs || is_img) {  // a pool slot holds an earlier scan's rows: zero, as cc_ingest_segments_host does, for the same bytes
+  if (h_segs || is_img || is_crd) {  // a pool slot holds an earlier scan's rows: zero, as cc_ingest_segments_host does, for the same bytes
     const hipError_t e_ = hipMemsetAsync(sc->d_desc, 0, sizeof(cc_scan_desc_t), ch.s);
     if (e_ != hipSuccess) {
       give_back();
@@ -1636,6 +1786,11 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
   for (int k = 0; k < n_segs; k++) seg_tab[k].base = (const char *)ch.d_pts + seg_place[k] + (seg_tab[k].base - (const char *)h_segs[k].points);
   src.points = ch.d_pts;
   if (is_img && src.pos_rc) src.pos_rc = ch.d_pts + n_points;
+  if (is_crd) {
+    src.crd.x = (const char *)ch.d_pts + crd_plan.strm[0];
+    src.crd.y = (const char *)ch.d_pts + crd_plan.strm[1];
+    src.crd.z = (const char *)ch.d_pts + crd_plan.strm[2];
+  }
   const int rc = ingest_on(c, ch.scr, src, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
   if (rc != CC_OK) {
     give_back();

@@ -1210,6 +1210,90 @@ struct cc_ld_rec_flt {
   }
 };
 
+// ---- typed coordinate STREAMS (cc_ingest_coords, include/cont2_amd_coords.h): x, y and z are three streams of one element type --
+// f32, f64 or i32 -- and one stride, which may lie inside one record array (in any order, with anything between them) or in three
+// arrays.  A coordinate becomes the f32 everything downstream sees by the header's three steps, each rounded once:
+//     X = (double)v [* scale[k] for i32];   D = X - origin[scan][k];   p = (float)D
+// The f64 subtraction in front of the narrowing is what a georeferenced cloud needs (an f32 resolves 0.5 m at a UTM northing), and
+// the f64 rate to do it per point is there in a sweep bound by HBM and LDS.  The library is built with -ffp-contract=off: the product
+// and the difference are never fused.  load() requests the three RAW elements together (3 x 8 bytes for f64, 3 x 4 otherwise), none
+// under a branch, and the record carries them raw; the conversion is xyz()'s, which runs when the sweep resolves the chunk, a chunk
+// after the loads were issued.  The origin and the scales are workgroup-uniform: scalars.  The per-scan matrix is cc_ld_rec's.
+// The stride is a run-time value: 4 sweep instances and 1 merge instance per type.
+enum { CC_K1_COORD_F32 = 0, CC_K1_COORD_F64 = 1, CC_K1_COORD_I32 = 2 };  // = CC_COORD_* (checked where both are seen)
+struct cc_k1_coords {
+  const char *x, *y, *z;  // the first point's elements
+  int stride;
+  double scale[3];        // I32 (1.0 otherwise: not read)
+  const double *origin;   // [n_scans][3], or nullptr: 0.0
+  const float *tf;        // [n_scans][12] or nullptr
+};
+template <int TYPE>
+struct cc_coord_elem {
+  typedef float t;
+};
+template <>
+struct cc_coord_elem<CC_K1_COORD_F64> {
+  typedef double t;
+};
+template <>
+struct cc_coord_elem<CC_K1_COORD_I32> {
+  typedef int t;
+};
+__device__ __forceinline__ double cc_uniform_d(double v) {
+#ifndef CC_EMU
+  return __hiloint2double(cc_uniform_i(__double2hiint(v)), cc_uniform_i(__double2loint(v)));
+#else
+  return v;
+#endif
+}
+
+template <int TYPE>
+struct cc_ld_coord {
+  typedef typename cc_coord_elem<TYPE>::t elem;
+  struct rec {
+    elem x, y, z;
+  };
+  cc_ld_rec<0> R;  // the workgroup-uniform transform alone: cc_ld_rec's, used as it is
+  const char *__restrict__ X, *__restrict__ Y, *__restrict__ Z;
+  unsigned stride;  // j * stride < 2^29, as for cc_ld_rec
+  double s[3], o[3];
+  __device__ __forceinline__ cc_ld_coord(const cc_k1_coords &C, int scan) : R(nullptr, 0, C.tf, scan), X(C.x), Y(C.y), Z(C.z), stride((unsigned)C.stride) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      s[k] = C.scale[k];
+      o[k] = C.origin ? cc_uniform_d(C.origin[(size_t)scan * 3 + k]) : 0.0;
+    }
+  }
+  __device__ __forceinline__ void advance(long long n) {
+    const long long b = n * (long long)stride;
+    X += b;
+    Y += b;
+    Z += b;
+  }
+  __device__ __forceinline__ rec load(int j) const {
+    const unsigned at = (unsigned)j * stride;
+    rec q;
+    q.x = *(const elem *)(X + at);
+    q.y = *(const elem *)(Y + at);
+    q.z = *(const elem *)(Z + at);
+    return q;
+  }
+  __device__ __forceinline__ static rec zero() { return rec{(elem)0, (elem)0, (elem)0}; }
+  __device__ __forceinline__ float conv(elem v, int k) const {
+    double d = (double)v;                       // step 1 (exact for all three types)
+    if (TYPE == CC_K1_COORD_I32) d = d * s[k];  //   ... one f64 product
+    d = d - o[k];                               // step 2: one f64 subtraction
+    return (float)d;                            // step 3: round to nearest even
+  }
+  __device__ __forceinline__ void xyz(const rec &q, float &x, float &y, float &z) const { R.xyz(cc_xyz{conv(q.x, 0), conv(q.y, 1), conv(q.z, 2)}, x, y, z); }
+  __device__ __forceinline__ float2 owner_xy(int j) const {
+    float x, y, z;
+    xyz(load(j), x, y, z);
+    return make_float2(x, y);
+  }
+};
+
 
 // ---- point SOURCES: what a call hands the kernels, one by-value struct per family.  A source is the kernel argument and knows how
 // to make its family's loader:
@@ -1270,6 +1354,15 @@ struct cc_src_flt {
   __device__ __forceinline__ cc_ld_rec_flt<KIND> loader(int scan, const char *tab) const {
     return cc_ld_rec_flt<KIND>(pts, stride, tf, scan, flt, (const unsigned *)tab);
   }
+};
+// Typed coordinate streams (cc_ingest_coords).  TYPE: CC_K1_COORD_F32 / _F64 / _I32.  No table.
+template <int TYPE>
+struct cc_src_coord {
+  static constexpr int TAB_BYTES = 0, TAB_ALIGN = 1;
+  static constexpr bool SEGMENTED = false;
+  cc_k1_coords crd;
+  __device__ __forceinline__ void tables(char *, int) const {}
+  __device__ __forceinline__ cc_ld_coord<TYPE> loader(int scan, const char *) const { return cc_ld_coord<TYPE>(crd, scan); }
 };
 // Range images (cc_ingest_ranges).  WORD: CC_K1_WORD_U16 / _U32 / _F32.  offsets: scan i's first pixel = i * n_rows * n_cols.
 template <int WORD>

@@ -18,6 +18,7 @@
 #include "../../../include/cont2_amd.h"
 #include "../../../include/cont2_amd_images.h"
 #include "../../../include/cont2_amd_filter.h"
+#include "../../../include/cont2_amd_coords.h"
 #include "../compat/compat.h"
 
 typedef float KeyFloatType;
@@ -446,6 +447,38 @@ class ContourManager {
                                        want_images_ ? 1 : 0, &scan_) != CC_OK)
       die();
     str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
+  }
+
+  // Mirror-only: makeBEV from coordinates of another TYPE or SHAPE than a pcl cloud's three consecutive floats (cc_scan_ingest_coords,
+  // include/cont2_amd_coords.h): f64 clouds (Eigen / numpy / Open3D arrays, PCD files with double fields, everything in a georeferenced
+  // frame), scaled int32 X, Y, Z (the LAS convention), and x, y, z held as three columns or apart inside a record.  x, y, z point at
+  // the first point's elements, `type` is CC_COORD_F32 / _F64 / _I32 for all three, stride_bytes lies between consecutive points;
+  // scale: CC_COORD_I32 only.  Every coordinate becomes p = (float)((double)v [* scale] - origin), each step rounded once: the origin
+  // (3 doubles, e.g. the UTM position of the local frame; nullptr: none) is subtracted in f64 BEFORE the narrowing, which a cast in the
+  // caller's code gets wrong by up to 0.5 m at a UTM northing.  The BEV is that of the f32 points p, moved by T_bev_sensor if given.
+  // The coordinates go to the device as they are: no cast, subtraction, packing and second copy on the host.  n > 10.
+  struct BevCoords {
+    const void *x = nullptr, *y = nullptr, *z = nullptr;
+    int32_t type = CC_COORD_F64;
+    int32_t stride_bytes = 24;
+    double scale[3] = {1.0, 1.0, 1.0};
+    const double *origin = nullptr;
+    int64_t n = 0;
+  };
+  void makeBEV(const BevCoords &crd, const float (*T_bev_sensor)[12] = nullptr, std::string str_id = "") {
+    CC_CHECK(crd.n > 10);
+    CC_CHECK(!scan_);
+    cc_coord_src_t src;
+    src.x = crd.x;
+    src.y = crd.y;
+    src.z = crd.z;
+    src.type = crd.type;
+    src.stride_bytes = crd.stride_bytes;
+    for (int k = 0; k < 3; k++) src.scale[k] = crd.scale[k];
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_coords(ctx, &src, crd.n, crd.origin, T_bev_sensor ? *T_bev_sensor : nullptr, want_images_ ? 1 : 0, &scan_) != CC_OK) die();
+    str_id_ = std::move(str_id);
   }
 
   // Mirror-only: makeBEV for a scan that is still the sensor's RANGE IMAGE -- H x W range words (u16 / u32 / f32) as the driver has them,

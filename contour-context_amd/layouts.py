@@ -221,6 +221,18 @@ def class_bits(n_classes, keep=None, drop=None):
     return np.ascontiguousarray(np.packbits(kept, bitorder="little").view(np.uint32))
 
 
+COORD_F32, COORD_F64, COORD_I32 = 0, 1, 2                     # CC_COORD_F32 / _F64 / _I32 (include/cont2_amd_coords.h)
+COORD_BYTES = {COORD_F32: 4, COORD_F64: 8, COORD_I32: 4}
+
+
+class CoordSrc(C.Structure):
+    """cc_coord_src_t: three coordinate streams of one element type and one stride (scale: CC_COORD_I32 only)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("type", C.c_int32), ("stride_bytes", C.c_int32), ("scale", C.c_double * 3)]
+
+
+assert C.sizeof(CoordSrc) == 56 and CoordSrc.type.offset == 24 and CoordSrc.stride_bytes.offset == 28 and CoordSrc.scale.offset == 32
+
+
 RANGE_ROWS_MAX, RANGE_COLS_MAX = 128, 4096              # CC_RANGE_ROWS_MAX / CC_RANGE_COLS_MAX
 RANGE_U16, RANGE_U32, RANGE_F32 = 0, 1, 2               # CC_RANGE_U16 / _U32 / _F32
 RANGE_ROW_MAJOR, RANGE_COL_MAJOR = 0, 1                 # CC_RANGE_ROW_MAJOR / _COL_MAJOR
