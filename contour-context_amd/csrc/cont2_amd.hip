@@ -525,42 +525,47 @@ static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
 // an error text that names the entry point the caller called (the old entry points are thin calls of the new ones' bodies)
 #define CC_WHO(text) (std::string(who) + text).c_str()
 
-// What a call's scans are made of, as ingest_on and scan_ingest_points take it: the checked arguments of one of the four kinds of entry
-// points.  ingest_on reads DEVICE addresses; scan_ingest_points and the *_host calls are handed the caller's host addresses and put the
-// device ones in before they pass it on.
+// What a call's scans are made of, as ingest_on and scan_ingest_points take it: the arguments of one of the kinds of entry points, as
+// the caller gave them until k1_check has passed them.  ingest_on reads DEVICE addresses; the per-scan and the *_host calls are handed
+// the caller's host addresses and put the device ones in (k1_rebase) before they pass it on.  A checked SEGMENTS source points into
+// its own tables: it is handed on by reference, never copied.
 struct k1_source {
   enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES, FILTERED, COORDS } kind;
   const void *points = nullptr;              // POINTS, MOTION: the records; RANGES: the range words (a "point" is a pixel); IMAGES: the heights (a "point" is a cell)
-  cc_point_layout_t lay = {16, 0};           // POINTS, MOTION, FILTERED (has passed point_layout)
+  cc_point_layout_t lay = {16, 0};           // POINTS, MOTION, FILTERED (the caller's, or {16, 0})
   const float *h_tf = nullptr;               // POINTS, FILTERED, COORDS: [n_scans][12] or nullptr
-  cc_point_motion_t mot = {};                // MOTION (has passed motion_check), with
+  cc_point_motion_t mot = {};                // MOTION, with
   const float *h_time = nullptr;             //   [n_scans][2]
   const float *h_knots = nullptr;            // MOTION, RANGES: [n_scans][K][12] (RANGES: nullptr iff K == 0)
-  const struct cc_range_sensor *sensor = nullptr;  // RANGES (has passed ranges_check); the scans' offsets are the pixels' (i * H * W)
-  cc_k1_seg *segs = nullptr;                 // SEGMENTS (segs_check's table): one entry per segment, `base` the address of its first x;
-  const int32_t *scan_segs = nullptr;        //   [n_scans + 1], relative to segs[0]; the scans' point totals are the call's offsets
-  const cc_point_segment_t *h_segs = nullptr;  //   the caller's entries of the same segments (what the host calls copy from)
+  const struct cc_range_sensor *sensor = nullptr;  // RANGES; the scans' offsets are the pixels' (i * H * W)
+  cc_k1_seg *segs = nullptr;                 // SEGMENTS (k1_check: seg_tab's entries): one entry per segment, `base` the address of its first x;
+  const int32_t *scan_segs = nullptr;        //   [n_scans + 1]: the caller's, and once checked relative to segs[0] (seg_scan)
+  const cc_point_segment_t *h_segs = nullptr;  //   the caller's entries, and once checked those of the same segments (what the host calls copy from)
   const float *pos_rc = nullptr;             // IMAGES: [n_scans][n_cell][2] or nullptr (the cell centres); the scans' offsets are the cells' (i * n_cell)
   const float *h_min = nullptr;              // IMAGES: [n_scans] or nullptr (the minimum over the occupied cells)
-  cc_point_filter_t flt = {};                // FILTERED (has passed filter_check); the records, layout and h_tf are POINTS'
-  cc_coord_src_t crd = {};                   // COORDS (has passed coords_check): the three streams of the call's point 0, stride, type, scales
+  cc_point_filter_t flt = {};                // FILTERED; the records, layout and h_tf are POINTS'
+  cc_coord_src_t crd = {};                   // COORDS: the three streams of the call's point 0, stride, type, scales
   const double *h_origin = nullptr;          //   [n_scans][3] or nullptr
-  size_t crd_at[3] = {0, 0, 0};              //   the host calls: where each stream begins in the device copy (coords_plan)
+  bool missing = false;                      // MOTION, FILTERED, COORDS: the caller's struct was NULL (k1_check refuses it in its place)
+  std::vector<cc_k1_seg> seg_tab;            // SEGMENTS: segs_check's table,
+  std::vector<int32_t> seg_scan;             //   the scans' first segments in it,
+  std::vector<int64_t> own_off;              //   and the scans' point totals as offsets; RANGES, IMAGES: the pixels' / cells' offsets (k1_check)
 };
-static k1_source k1_points(const void *points, const cc_point_layout_t &lay, const float *h_tf) {
-  k1_source s = {k1_source::POINTS, points, lay, h_tf};
+static k1_source k1_points(const void *points, const cc_point_layout_t *layout, const float *h_tf) {
+  k1_source s = {k1_source::POINTS, points, layout ? *layout : CC_LAYOUT_KITTI, h_tf};
   return s;
 }
-static k1_source k1_motion(const void *points, const cc_point_layout_t &lay, const cc_point_motion_t &mot, const float *h_time, const float *h_knots) {
-  k1_source s = {k1_source::MOTION, points, lay, nullptr, mot, h_time, h_knots};
+static k1_source k1_motion(const void *points, const cc_point_layout_t *layout, const cc_point_motion_t *mot, const float *h_time, const float *h_knots) {
+  k1_source s = {k1_source::MOTION, points, layout ? *layout : CC_LAYOUT_KITTI, nullptr, mot ? *mot : cc_point_motion_t(), h_time, h_knots};
+  s.missing = !mot;
   return s;
 }
 static k1_source k1_ranges(const struct cc_range_sensor *sensor, const void *words, const float *h_knots) {
   k1_source s = {k1_source::RANGES, words, {16, 0}, nullptr, {}, nullptr, h_knots, sensor};
   return s;
 }
-static k1_source k1_segments(cc_k1_seg *segs, const int32_t *scan_segs, const cc_point_segment_t *h_segs) {
-  k1_source s = {k1_source::SEGMENTS, nullptr, {16, 0}, nullptr, {}, nullptr, nullptr, nullptr, segs, scan_segs, h_segs};
+static k1_source k1_segments(const cc_point_segment_t *h_segs, const int32_t *h_scan_segs) {
+  k1_source s = {k1_source::SEGMENTS, nullptr, {16, 0}, nullptr, {}, nullptr, nullptr, nullptr, nullptr, h_scan_segs, h_segs};
   return s;
 }
 static k1_source k1_images(const float *height, const float *pos_rc, const float *h_min) {
@@ -569,15 +574,17 @@ static k1_source k1_images(const float *height, const float *pos_rc, const float
   s.h_min = h_min;
   return s;
 }
-static k1_source k1_filtered(const void *points, const cc_point_layout_t &lay, const float *h_tf, const cc_point_filter_t &flt) {
-  k1_source s = {k1_source::FILTERED, points, lay, h_tf};
-  s.flt = flt;
+static k1_source k1_filtered(const void *points, const cc_point_layout_t *layout, const float *h_tf, const cc_point_filter_t *flt) {
+  k1_source s = {k1_source::FILTERED, points, layout ? *layout : CC_LAYOUT_KITTI, h_tf};
+  if (flt) s.flt = *flt;
+  s.missing = !flt;
   return s;
 }
-static k1_source k1_coords(const cc_coord_src_t &crd, const double *h_origin, const float *h_tf) {
-  k1_source s = {k1_source::COORDS, crd.x, {16, 0}, h_tf};
-  s.crd = crd;
+static k1_source k1_coords(const cc_coord_src_t *crd, const double *h_origin, const float *h_tf) {
+  k1_source s = {k1_source::COORDS, crd ? crd->x : nullptr, {16, 0}, h_tf};
+  if (crd) s.crd = *crd;
   s.h_origin = h_origin;
+  s.missing = !crd;
   return s;
 }
 static_assert((int)CC_K1_COORD_F32 == (int)CC_COORD_F32 && (int)CC_K1_COORD_F64 == (int)CC_COORD_F64 && (int)CC_K1_COORD_I32 == (int)CC_COORD_I32,
@@ -664,44 +671,203 @@ static int coords_check(const cc_coord_src_t *s, const int64_t *h_offsets, int n
   if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
   return CC_OK;
 }
-// What a host form copies of `points` points from point `first` on, and where the streams begin in the device copy: exactly the bytes
-// the streams span.  The highest stream's element within stride_bytes of the lowest stream: ONE record array, one copy from the lowest
-// pointer; otherwise three arrays, three copies, each at a 16-byte boundary of the device buffer.
-struct coord_plan {
-  int n_copies;
-  const char *h[3];
-  size_t bytes[3], at[3];  // the copies: from, how much, to where in the device buffer
-  size_t strm[3];          // x, y, z of the first point in the device buffer
-  size_t total;
-};
-static coord_plan coords_plan(const cc_coord_src_t &s, int64_t first, int64_t points) {
-  coord_plan p = {};
-  const size_t stride = (size_t)s.stride_bytes, elem = (size_t)coord_bytes(s.type), run = (size_t)(points - 1) * stride;
-  const char *q[3] = {(const char *)s.x + (size_t)first * stride, (const char *)s.y + (size_t)first * stride, (const char *)s.z + (size_t)first * stride};
-  const char *lo = q[0], *hi = q[0];
-  for (int k = 1; k < 3; k++) {
-    lo = (uintptr_t)q[k] < (uintptr_t)lo ? q[k] : lo;
-    hi = (uintptr_t)q[k] > (uintptr_t)hi ? q[k] : hi;
-  }
-  const size_t span = (size_t)((uintptr_t)hi - (uintptr_t)lo) + elem;
-  if (span <= stride) {
-    p.n_copies = 1;
-    p.h[0] = lo;
-    p.bytes[0] = run + span;
-    for (int k = 0; k < 3; k++) p.strm[k] = (size_t)((uintptr_t)q[k] - (uintptr_t)lo);
-    p.total = p.bytes[0];
-  } else {
-    p.n_copies = 3;
-    const size_t piece = (run + elem + 15) & ~(size_t)15;
-    for (int k = 0; k < 3; k++) {
-      p.h[k] = q[k];
-      p.bytes[k] = run + elem;
-      p.at[k] = p.strm[k] = (size_t)k * piece;
+static int images_check(const cc_ctx *c, const void *height, const void *out, int n_scans, const char *who) {
+  const char *why = nullptr;
+  if (!c) why = "ctx must not be NULL";
+  else if (!height) why = "height must not be NULL";
+  else if (!out) why = "out must not be NULL";
+  else if (n_scans < 0) why = "n_scans must not be negative";
+  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
+  return CC_OK;
+}
+// Everything the header promises to check about a cc_*_segments call, before anything is queued or read.  tab: one entry per segment,
+// `base` = the caller's pointer + xyz_offset (the host calls replace it with where the records went on the device); q_off: the scans'
+// point totals as offsets.
+static int segs_check(const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, const char *who, std::vector<cc_k1_seg> &tab,
+                      std::vector<int64_t> &q_off) {
+  q_off.assign(1, 0);
+  for (int i = 0; i < n_scans; i++) {
+    const int64_t ns = (int64_t)h_scan_segs[i + 1] - h_scan_segs[i];
+    if (h_scan_segs[i] < 0 || ns < 1 || ns > CC_SEG_MAX) return set_err(CC_EINVAL, CC_WHO(": a scan has 1 .. CC_SEG_MAX segments"));
+    int64_t total = 0;
+    for (int k = h_scan_segs[i]; k < h_scan_segs[i + 1]; k++) {
+      const cc_point_segment_t &g = h_segs[k];
+      if (g.n_points < 0 || g.n_points >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": a segment's n_points is negative or >= 2^21"));
+      if (g.n_points > 0 && !g.points) return set_err(CC_EINVAL, CC_WHO(": a segment with points has a NULL pointer"));
+      cc_point_layout_t lay;
+      const bool dflt = g.layout.stride_bytes == 0 && g.layout.xyz_offset == 0;
+      const int rcl = point_layout(dflt ? nullptr : &g.layout, g.n_points > 0 ? g.points : nullptr, who, &lay);
+      if (rcl != CC_OK) return rcl;
+      cc_k1_seg e;
+      e.base = (const char *)g.points + lay.xyz_offset;
+      e.stride = (unsigned)lay.stride_bytes;
+      e.first = (int)total;
+      e.n = (int)g.n_points;
+      e.has_tf = g.has_tf != 0;
+      for (int m = 0; m < 12; m++) e.m[m] = g.has_tf ? g.tf[m] : 0.f;
+      tab.push_back(e);
+      total += g.n_points;
+      if (total >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": scan with >= 2^21 points"));
     }
-    p.total = 2 * piece + run + elem;
+    if (!(total > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
+    q_off.push_back(q_off.back() + total);
+  }
+  return CC_OK;
+}
+
+// The three forms of every family's entry points: the records on the device, a batch of host records (*_host), one scan of the
+// per-scan loop (cc_scan_ingest*: n_scans = 1, h_offsets = {0, n_points}).
+enum k1_form { K1_DEVICE, K1_HOST, K1_SCAN };
+// What is checked of a call before anything is queued, read or touched, once per family: the arguments every form refuses (`out`: where
+// the form's results go), then the family's own checks.  The *_host and per-scan forms copy their records to aligned device memory: a
+// base's alignment counts in the device forms only (a range word's and a coordinate's in all: their checks read it off the host address).
+// An IMAGES call of no scans passes (it is CC_OK and does nothing).  Behind it a SEGMENTS source holds its tables, with h_segs and
+// scan_segs those of the call's first segment on, and a RANGES or IMAGES source its scans' offsets (own_off).
+static int k1_check(cc_ctx *c, k1_source &src, k1_form form, const int64_t *h_offsets, int n_scans, const void *out, const char *who) {
+  const bool few = n_scans < (form == K1_DEVICE ? 0 : 1);
+  const void *base = form == K1_DEVICE ? src.points : nullptr;
+  int rc = CC_OK;
+  switch (src.kind) {
+    case k1_source::POINTS:
+    case k1_source::MOTION:
+    case k1_source::FILTERED:
+      if (!c || !src.points || !h_offsets || !out || few || (form == K1_SCAN && h_offsets[1] < 1)) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+      rc = point_layout(&src.lay, base, who, &src.lay);
+      if (rc == CC_OK && src.kind == k1_source::MOTION) rc = motion_check(src.lay, src.missing ? nullptr : &src.mot, src.h_time, src.h_knots, n_scans, who);
+      if (rc == CC_OK && src.kind == k1_source::FILTERED) rc = filter_check(src.lay, src.missing ? nullptr : &src.flt, who);
+      return rc;
+    case k1_source::COORDS:
+      if (!c || !h_offsets || !out || few) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+      return coords_check(src.missing ? nullptr : &src.crd, h_offsets, n_scans, src.h_origin, who);
+    case k1_source::RANGES:
+      if (!c || !out || few) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+      rc = ranges_check(c, src.sensor, src.points, src.h_knots, who);
+      for (int i = 0; rc == CC_OK && i <= n_scans; i++) src.own_off.push_back((int64_t)src.sensor->kr.n_rows * src.sensor->kr.n_cols * i);
+      return rc;
+    case k1_source::IMAGES:
+      rc = images_check(c, src.points, out, n_scans, who);
+      if (rc != CC_OK) return rc;
+      if (form == K1_DEVICE && ((uintptr_t)src.points & 15u) != 0) return set_err(CC_EINVAL, CC_WHO(": d_height must be 16-byte aligned"));
+      if (form == K1_DEVICE && ((uintptr_t)src.pos_rc & 7u) != 0) return set_err(CC_EINVAL, CC_WHO(": d_pos_rc must be 8-byte aligned"));
+      for (int i = 0; i <= n_scans; i++) src.own_off.push_back((int64_t)i * c->dcfg.n_cell);
+      return CC_OK;
+    case k1_source::SEGMENTS:
+      if (!c || !src.h_segs || !src.scan_segs || !out || few) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+      rc = segs_check(src.h_segs, src.scan_segs, n_scans, who, src.seg_tab, src.own_off);
+      if (rc != CC_OK) return rc;
+      for (int i = 0; i <= n_scans; i++) src.seg_scan.push_back(src.scan_segs[i] - src.scan_segs[0]);  // (seg_tab begins with the call's first segment)
+      src.h_segs += src.scan_segs[0];
+      src.segs = src.seg_tab.data();
+      src.scan_segs = src.seg_scan.data();
+      return CC_OK;
+  }
+  return CC_OK;
+}
+// the scans' offsets in points: the caller's, or the checked source's own
+static const int64_t *k1_offsets(const k1_source &src, const int64_t *h_offsets) { return src.own_off.empty() ? h_offsets : src.own_off.data(); }
+
+// Where the host bytes of a *_host or per-scan call go in ONE device buffer, and where the source's pointers lie in it then.
+struct k1_host_plan {
+  struct copy {
+    const void *from;
+    size_t bytes, at;
+  };
+  std::vector<copy> copies;
+  size_t total = 0;              // the buffer's bytes
+  bool zero_out = false;         // the call's descriptors are zeroed before its kernels run
+  const void *staged = nullptr;  // the per-scan forms: the address a caller of cc_stage_points* hands over in place of records (nullptr: never staged)
+  size_t pos_rc = 0, crd[3] = {0, 0, 0};  // IMAGES: the positions; COORDS: x, y, z of the first point (`points` lies at 0)
+  std::vector<size_t> seg_base;  // SEGMENTS: x of every segment's first record
+  void add(const void *from, size_t bytes, size_t at) { copies.push_back({from, bytes, at}); }
+};
+// The plan of `n_points` points from point `first` on of a checked source with host addresses (SEGMENTS: of all its segments).
+static k1_host_plan k1_plan(const k1_source &src, k1_form form, int64_t first, int64_t n_points) {
+  k1_host_plan p;
+  const size_t n = (size_t)n_points;
+  switch (src.kind) {
+    case k1_source::POINTS:
+    case k1_source::MOTION:
+    case k1_source::FILTERED: {  // the records travel as they are, in ONE copy
+      const size_t stride = (size_t)src.lay.stride_bytes;
+      p.add((const char *)src.points + stride * (size_t)first, stride * n, 0);
+      p.total = stride * n;
+      p.staged = src.points;
+      break;
+    }
+    case k1_source::RANGES: {
+      const size_t word = (size_t)src.sensor->word_bytes;
+      p.add((const char *)src.points + word * (size_t)first, word * n, 0);
+      p.total = word * n;
+      p.staged = src.points;
+      break;
+    }
+    case k1_source::IMAGES:  // the heights, and the positions behind them
+      p.add((const float *)src.points + first, sizeof(float) * n, 0);
+      p.pos_rc = sizeof(float) * n;
+      if (src.pos_rc) p.add(src.pos_rc + 2 * first, 2 * sizeof(float) * n, p.pos_rc);
+      p.total = sizeof(float) * n * (src.pos_rc ? 3 : 1);
+      break;
+    case k1_source::COORDS: {
+      // Exactly the bytes the streams span.  The highest stream's element within stride_bytes of the lowest stream: ONE record array,
+      // one copy from the lowest pointer; otherwise three arrays, three copies, each at a 16-byte boundary of the device buffer.
+      const cc_coord_src_t &s = src.crd;
+      const size_t stride = (size_t)s.stride_bytes, elem = (size_t)coord_bytes(s.type), run = (n - 1) * stride;
+      const char *q[3] = {(const char *)s.x + (size_t)first * stride, (const char *)s.y + (size_t)first * stride, (const char *)s.z + (size_t)first * stride};
+      const char *lo = q[0], *hi = q[0];
+      for (int k = 1; k < 3; k++) {
+        lo = (uintptr_t)q[k] < (uintptr_t)lo ? q[k] : lo;
+        hi = (uintptr_t)q[k] > (uintptr_t)hi ? q[k] : hi;
+      }
+      const size_t span = (size_t)((uintptr_t)hi - (uintptr_t)lo) + elem;
+      if (span <= stride) {
+        p.add(lo, run + span, 0);
+        for (int k = 0; k < 3; k++) p.crd[k] = (size_t)((uintptr_t)q[k] - (uintptr_t)lo);
+        p.total = run + span;
+      } else {
+        const size_t piece = (run + elem + 15) & ~(size_t)15;
+        for (int k = 0; k < 3; k++) {
+          p.crd[k] = (size_t)k * piece;
+          p.add(q[k], run + elem, p.crd[k]);
+        }
+        p.total = 2 * piece + run + elem;
+      }
+      break;
+    }
+    case k1_source::SEGMENTS:  // one segment after the other, each at a 16-byte boundary, whole records
+      for (size_t k = 0; k < src.seg_tab.size(); k++) {
+        const cc_k1_seg &g = src.seg_tab[k];
+        if (g.n > 0) p.add(src.h_segs[k].points, (size_t)g.n * g.stride, p.total);
+        p.seg_base.push_back(p.total + (size_t)(g.base - (const char *)src.h_segs[k].points));
+        p.total += ((size_t)g.n * g.stride + 15) & ~(size_t)15;
+      }
+      break;
+  }
+  // The rows of a descriptor that its counts do not cover are not written by the kernels, and a pool slot holds an earlier scan's rows:
+  // where a form zeroes, its bytes are those of the family's device call into zeroed memory.
+  switch (src.kind) {
+    case k1_source::SEGMENTS:
+    case k1_source::IMAGES:
+    case k1_source::COORDS: p.zero_out = true; break;
+    case k1_source::FILTERED: p.zero_out = form == K1_HOST; break;  // (the batch form as cc_ingest_images_host does; the per-scan form as POINTS')
+    case k1_source::POINTS:
+    case k1_source::MOTION:
+    case k1_source::RANGES: p.zero_out = false; break;  // (what lies behind the counts is the allocation's, or the pool slot's)
   }
   return p;
 }
+// The device addresses of a planned source whose buffer lies at d_base.
+static void k1_rebase(k1_source &src, const k1_host_plan &plan, const void *d_base) {
+  const char *d = (const char *)d_base;
+  src.points = d;
+  if (src.pos_rc) src.pos_rc = (const float *)(d + plan.pos_rc);
+  if (src.kind == k1_source::COORDS) {
+    src.crd.x = d + plan.crd[0];
+    src.crd.y = d + plan.crd[1];
+    src.crd.z = d + plan.crd[2];
+  }
+  for (size_t k = 0; k < plan.seg_base.size(); k++) src.seg_tab[k].base = d + plan.seg_base[k];
+}
+
 // `bytes` of pinned memory in slot `slot` of the staging ring (the buffer the chunk's segment table, times and knots ride in), grown
 // when it is too small; nullptr with the error set when the allocation fails.
 static char *slot_stage(cc_ctx *c, int slot, size_t bytes) {
@@ -962,34 +1128,16 @@ int cc_ingest_batch(cc_ctx *c, const float *d_xyzi, const int64_t *h_offsets, in
                     const cc_ingest_debug_t *dbg, void *stream_) {
   if (!c || !d_xyzi || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, "cc_ingest_batch: bad argument");
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);  // offsets ring, K1/K2 scratch, ev_last: one call at a time
-  return ingest_on(c, c->main, k1_points(d_xyzi, CC_LAYOUT_KITTI, nullptr), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_batch");
+  return ingest_on(c, c->main, k1_points(d_xyzi, nullptr, nullptr), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_batch");
 }
 
-static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const cc_point_motion_t *motion = nullptr, const float *h_time = nullptr,
-                              const float *h_knots = nullptr);
-
-int cc_ingest_host(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out) {
-  return cc_ingest_host_bev(c, h_xyzi, h_offsets, n_scans, h_out, nullptr);
-}
-
-int cc_ingest_points(cc_ctx *c, const void *d_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
-  if (!c || !d_points || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, "cc_ingest_points: bad argument");
-  cc_point_layout_t lay;
-  const int rcl = point_layout(layout, d_points, "cc_ingest_points", &lay);
-  if (rcl != CC_OK) return rcl;
+// The body of the device forms: the check, then the call itself on the context's own scratch set.
+static int ingest_device(cc_ctx *c, k1_source src, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_,
+                         const char *who) {
+  const int rc = k1_check(c, src, K1_DEVICE, h_offsets, n_scans, d_out, who);
+  if (rc != CC_OK || n_scans == 0) return rc;  // (no scans: nothing to queue)
   std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, k1_points(d_points, lay, h_tf), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, "cc_ingest_points");
-}
-
-int cc_ingest_host_bev(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out, float *h_bev) {
-  return ingest_points_host(c, h_xyzi, nullptr, h_offsets, n_scans, nullptr, h_out, h_bev, "cc_ingest_host");
-}
-
-int cc_ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                          cc_scan_desc_t *h_out, float *h_bev) {
-  return ingest_points_host(c, h_points, layout, h_offsets, n_scans, h_tf, h_out, h_bev, "cc_ingest_points_host");
+  return ingest_on(c, c->main, src, k1_offsets(src, h_offsets), n_scans, d_out, dbg, (hipStream_t)stream_, who);
 }
 
 // the results of a host call back to the host (blocking copies: they wait for the call's kernels); CC_ECAPACITY for an inexact descriptor
@@ -1004,15 +1152,21 @@ static int host_results(const cc_scan_desc_t *d_o, const float *d_b, size_t bev_
   return CC_OK;
 }
 
-// The body of the *_host calls, behind their checks: device memory for the call's pts_bytes of records, its descriptors and (h_bev) its
-// images; copy_in(d_x, d_o) brings the records over; then the call itself (src reads its records at d_x), and the results back.
-static int ingest_host(cc_ctx *c, k1_source src, size_t pts_bytes, const int64_t *offsets, int n_scans, cc_scan_desc_t *h_out, float *h_bev, const char *who,
-                       const std::function<hipError_t(char *, cc_scan_desc_t *)> &copy_in) {
+// The body of the *_host forms: the check; device memory for the planned copy of the call's records (the scans' offsets made relative to
+// the call's first point), for its descriptors and (h_bev) its images; the planned copies; then the call itself, and the results back.
+static int ingest_host(cc_ctx *c, k1_source src, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out, float *h_bev, const char *who) {
+  const int rcc = k1_check(c, src, K1_HOST, h_offsets, n_scans, h_out, who);
+  if (rcc != CC_OK || n_scans == 0) return rcc;  // (an IMAGES call of no scans)
+  HIPCHK(hipSetDevice(c->device));
+  h_offsets = k1_offsets(src, h_offsets);
+  std::vector<int64_t> off(n_scans + 1);
+  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - h_offsets[0];
+  const k1_host_plan plan = k1_plan(src, K1_HOST, h_offsets[0], off[n_scans]);
   const size_t bev_bytes = sizeof(float) * (size_t)c->dcfg.n_cell * (size_t)n_scans;
   char *d_x = nullptr;
   float *d_b = nullptr;
   cc_scan_desc_t *d_o = nullptr;
-  HIPCHK(hipMalloc(&d_x, pts_bytes));
+  HIPCHK(hipMalloc(&d_x, plan.total));
   hipError_t e = hipMalloc(&d_o, sizeof(cc_scan_desc_t) * (size_t)n_scans);
   if (e == hipSuccess && h_bev) e = hipMalloc(&d_b, bev_bytes);
   if (e != hipSuccess) {
@@ -1024,18 +1178,14 @@ static int ingest_host(cc_ctx *c, k1_source src, size_t pts_bytes, const int64_t
   dbg.d_bev = d_b;
   dbg.d_pix_rc = nullptr;
   dbg.d_labels = nullptr;
-  e = copy_in(d_x, d_o);
+  if (plan.zero_out) e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
+  for (size_t k = 0; k < plan.copies.size() && e == hipSuccess; k++)
+    e = hipMemcpy(d_x + plan.copies[k].at, plan.copies[k].from, plan.copies[k].bytes, hipMemcpyHostToDevice);
   int rc = e == hipSuccess ? CC_OK : set_err(CC_EHIP, CC_WHO(": H2D"), e);
   if (rc == CC_OK) {
-    src.points = d_x;
-    if (src.kind == k1_source::IMAGES && src.pos_rc) src.pos_rc = (const float *)d_x + offsets[n_scans];  // the positions lie behind the heights
-    if (src.kind == k1_source::COORDS) {  // the streams lie where coords_plan put them
-      src.crd.x = d_x + src.crd_at[0];
-      src.crd.y = d_x + src.crd_at[1];
-      src.crd.z = d_x + src.crd_at[2];
-    }
+    k1_rebase(src, plan, d_x);
     std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-    rc = ingest_on(c, c->main, src, offsets, n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
+    rc = ingest_on(c, c->main, src, off.data(), n_scans, d_o, h_bev ? &dbg : nullptr, nullptr, who);
   }
   if (rc == CC_OK) rc = host_results(d_o, d_b, bev_bytes, n_scans, h_out, h_bev, who);
   hipFree(d_x);
@@ -1044,114 +1194,57 @@ static int ingest_host(cc_ctx *c, k1_source src, size_t pts_bytes, const int64_t
   return rc;
 }
 
-static int ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
-                              cc_scan_desc_t *h_out, float *h_bev, const char *who, const cc_point_motion_t *motion, const float *h_time, const float *h_knots) {
-  if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  cc_point_layout_t lay;
-  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records are copied to aligned device memory)
-  if (rcl != CC_OK) return rcl;
-  if (motion) {
-    const int rcm = motion_check(lay, motion, h_time, h_knots, n_scans, who);
-    if (rcm != CC_OK) return rcm;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t base = h_offsets[0];
-  const size_t pts_bytes = (size_t)lay.stride_bytes * (size_t)(h_offsets[n_scans] - base);
-  std::vector<int64_t> off(n_scans + 1);
-  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
-  const char *h_first = (const char *)h_points + (size_t)lay.stride_bytes * (size_t)base;
-  return ingest_host(c, motion ? k1_motion(nullptr, lay, *motion, h_time, h_knots) : k1_points(nullptr, lay, h_tf), pts_bytes, off.data(), n_scans, h_out, h_bev,
-                     who, [&](char *d_x, cc_scan_desc_t *) { return hipMemcpy(d_x, h_first, pts_bytes, hipMemcpyHostToDevice); });
+int cc_ingest_host(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out) {
+  return cc_ingest_host_bev(c, h_xyzi, h_offsets, n_scans, h_out, nullptr);
+}
+
+int cc_ingest_points(cc_ctx *c, const void *d_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
+                     cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
+  return ingest_device(c, k1_points(d_points, layout, h_tf), h_offsets, n_scans, d_out, dbg, stream_, "cc_ingest_points");
+}
+
+int cc_ingest_host_bev(cc_ctx *c, const float *h_xyzi, const int64_t *h_offsets, int n_scans, cc_scan_desc_t *h_out, float *h_bev) {
+  return ingest_host(c, k1_points(h_xyzi, nullptr, nullptr), h_offsets, n_scans, h_out, h_bev, "cc_ingest_host");
+}
+
+int cc_ingest_points_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const int64_t *h_offsets, int n_scans, const float *h_tf,
+                          cc_scan_desc_t *h_out, float *h_bev) {
+  return ingest_host(c, k1_points(h_points, layout, h_tf), h_offsets, n_scans, h_out, h_bev, "cc_ingest_points_host");
 }
 
 // ---- a sweep de-skewed by per-point time (cc_ingest_points_motion and its siblings) ----
 int cc_ingest_points_motion(cc_ctx *c, const void *d_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, const int64_t *h_offsets,
                             int n_scans, const float *h_time, const float *h_knots, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
-  const char *who = "cc_ingest_points_motion";
-  if (!c || !d_points || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  cc_point_layout_t lay;
-  const int rcl = point_layout(layout, d_points, who, &lay);
-  if (rcl != CC_OK) return rcl;
-  const int rcm = motion_check(lay, motion, h_time, h_knots, n_scans, who);
-  if (rcm != CC_OK) return rcm;
-  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, k1_motion(d_points, lay, *motion, h_time, h_knots), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who);
+  return ingest_device(c, k1_motion(d_points, layout, motion, h_time, h_knots), h_offsets, n_scans, d_out, dbg, stream_, "cc_ingest_points_motion");
 }
 
 int cc_ingest_points_motion_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, const int64_t *h_offsets,
                                  int n_scans, const float *h_time, const float *h_knots, cc_scan_desc_t *h_out, float *h_bev) {
   const char *who = "cc_ingest_points_motion_host";
   if (!motion) return set_err(CC_EINVAL, CC_WHO(": motion, h_time and h_knots must not be NULL"));
-  return ingest_points_host(c, h_points, layout, h_offsets, n_scans, nullptr, h_out, h_bev, who, motion, h_time, h_knots);
+  return ingest_host(c, k1_motion(h_points, layout, motion, h_time, h_knots), h_offsets, n_scans, h_out, h_bev, who);
 }
 
 // ---- records dropped by a word of their own (include/cont2_amd_filter.h) ----
 int cc_ingest_points_filtered(cc_ctx *c, const void *d_points, const cc_point_layout_t *layout, const cc_point_filter_t *filter, const int64_t *h_offsets,
                               int n_scans, const float *h_tf, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
-  const char *who = "cc_ingest_points_filtered";
-  if (!c || !d_points || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  cc_point_layout_t lay;
-  const int rcl = point_layout(layout, d_points, who, &lay);
-  if (rcl != CC_OK) return rcl;
-  const int rcf = filter_check(lay, filter, who);
-  if (rcf != CC_OK) return rcf;
-  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, k1_filtered(d_points, lay, h_tf, *filter), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who);
+  return ingest_device(c, k1_filtered(d_points, layout, h_tf, filter), h_offsets, n_scans, d_out, dbg, stream_, "cc_ingest_points_filtered");
 }
 
 int cc_ingest_points_filtered_host(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_filter_t *filter, const int64_t *h_offsets,
                                    int n_scans, const float *h_tf, cc_scan_desc_t *h_out, float *h_bev) {
-  const char *who = "cc_ingest_points_filtered_host";
-  if (!c || !h_points || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  cc_point_layout_t lay;
-  const int rcl = point_layout(layout, nullptr, who, &lay);  // (the records are copied to aligned device memory)
-  if (rcl != CC_OK) return rcl;
-  const int rcf = filter_check(lay, filter, who);
-  if (rcf != CC_OK) return rcf;
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t base = h_offsets[0];
-  const size_t pts_bytes = (size_t)lay.stride_bytes * (size_t)(h_offsets[n_scans] - base);
-  std::vector<int64_t> off(n_scans + 1);
-  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
-  const char *h_first = (const char *)h_points + (size_t)lay.stride_bytes * (size_t)base;
-  return ingest_host(c, k1_filtered(nullptr, lay, h_tf, *filter), pts_bytes, off.data(), n_scans, h_out, h_bev, who, [&](char *d_x, cc_scan_desc_t *d_o) {
-    // (zeroed as cc_ingest_images_host does: the kernels never write behind a descriptor's counts, and the host gets the bytes of a device call into zeroed memory)
-    hipError_t e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(d_x, h_first, pts_bytes, hipMemcpyHostToDevice);
-    return e;
-  });
+  return ingest_host(c, k1_filtered(h_points, layout, h_tf, filter), h_offsets, n_scans, h_out, h_bev, "cc_ingest_points_filtered_host");
 }
 
 // ---- f64, scaled-i32 and split-stream coordinates (include/cont2_amd_coords.h) ----
 int cc_ingest_coords(cc_ctx *c, const cc_coord_src_t *src, const int64_t *h_offsets, int n_scans, const double *h_origin, const float *h_tf, cc_scan_desc_t *d_out,
                      const cc_ingest_debug_t *dbg, void *stream_) {
-  const char *who = "cc_ingest_coords";
-  if (!c || !h_offsets || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  const int rcc = coords_check(src, h_offsets, n_scans, h_origin, who);
-  if (rcc != CC_OK) return rcc;
-  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, k1_coords(*src, h_origin, h_tf), h_offsets, n_scans, d_out, dbg, (hipStream_t)stream_, who);
+  return ingest_device(c, k1_coords(src, h_origin, h_tf), h_offsets, n_scans, d_out, dbg, stream_, "cc_ingest_coords");
 }
 
 int cc_ingest_coords_host(cc_ctx *c, const cc_coord_src_t *src, const int64_t *h_offsets, int n_scans, const double *h_origin, const float *h_tf,
                           cc_scan_desc_t *h_out, float *h_bev) {
-  const char *who = "cc_ingest_coords_host";
-  if (!c || !h_offsets || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  const int rcc = coords_check(src, h_offsets, n_scans, h_origin, who);
-  if (rcc != CC_OK) return rcc;
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t base = h_offsets[0];
-  std::vector<int64_t> off(n_scans + 1);
-  for (int i = 0; i <= n_scans; i++) off[i] = h_offsets[i] - base;
-  const coord_plan plan = coords_plan(*src, base, off[n_scans]);
-  k1_source ks = k1_coords(*src, h_origin, h_tf);
-  for (int k = 0; k < 3; k++) ks.crd_at[k] = plan.strm[k];
-  return ingest_host(c, ks, plan.total, off.data(), n_scans, h_out, h_bev, who, [&](char *d_x, cc_scan_desc_t *d_o) {
-    // (zeroed as cc_ingest_points_filtered_host does: the host gets the bytes of a device call into zeroed memory)
-    hipError_t e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
-    for (int k = 0; k < plan.n_copies && e == hipSuccess; k++) e = hipMemcpy(d_x + plan.at[k], plan.h[k], plan.bytes[k], hipMemcpyHostToDevice);
-    return e;
-  });
+  return ingest_host(c, k1_coords(src, h_origin, h_tf), h_offsets, n_scans, h_out, h_bev, "cc_ingest_coords_host");
 }
 
 // ---- a sensor's range image rasterised in place (cc_ingest_ranges and its siblings) ----
@@ -1234,84 +1327,25 @@ int cc_range_sensor_destroy(cc_range_sensor *s) {
   return CC_OK;
 }
 
-// the pixels' offsets of n_scans images: what ingest_on takes as h_offsets
-static std::vector<int64_t> ranges_offsets(const cc_range_sensor *s, int n_scans) {
-  std::vector<int64_t> off((size_t)n_scans + 1);
-  const int64_t hw = (int64_t)s->kr.n_rows * s->kr.n_cols;
-  for (int i = 0; i <= n_scans; i++) off[i] = hw * i;
-  return off;
-}
-
 int cc_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *d_ranges, int n_scans, const float *h_knots, cc_scan_desc_t *d_out,
                      const cc_ingest_debug_t *dbg, void *stream_) {
-  const char *who = "cc_ingest_ranges";
-  if (!c || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  const int rcr = ranges_check(c, sensor, d_ranges, h_knots, who);
-  if (rcr != CC_OK) return rcr;
-  const std::vector<int64_t> off = ranges_offsets(sensor, n_scans);
-  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, k1_ranges(sensor, d_ranges, h_knots), off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who);
+  return ingest_device(c, k1_ranges(sensor, d_ranges, h_knots), nullptr, n_scans, d_out, dbg, stream_, "cc_ingest_ranges");
 }
 
 int cc_ingest_ranges_host(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, int n_scans, const float *h_knots, cc_scan_desc_t *h_out,
                           float *h_bev) {
-  const char *who = "cc_ingest_ranges_host";
-  if (!c || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  const int rcr = ranges_check(c, sensor, h_ranges, h_knots, who);
-  if (rcr != CC_OK) return rcr;
-  HIPCHK(hipSetDevice(c->device));
-  const std::vector<int64_t> off = ranges_offsets(sensor, n_scans);
-  const size_t img_bytes = (size_t)off[n_scans] * (size_t)sensor->word_bytes;
-  return ingest_host(c, k1_ranges(sensor, nullptr, h_knots), img_bytes, off.data(), n_scans, h_out, h_bev, who,
-                     [&](char *d_x, cc_scan_desc_t *) { return hipMemcpy(d_x, h_ranges, img_bytes, hipMemcpyHostToDevice); });
+  return ingest_host(c, k1_ranges(sensor, h_ranges, h_knots), nullptr, n_scans, h_out, h_bev, "cc_ingest_ranges_host");
 }
 
 // ---- descriptors from caller-made max-height images (include/cont2_amd_images.h) ----
-// the scans' offsets in "points": an image's cells
-static std::vector<int64_t> images_offsets(const cc_ctx *c, int n_scans) {
-  std::vector<int64_t> off((size_t)n_scans + 1);
-  for (int i = 0; i <= n_scans; i++) off[i] = (int64_t)i * c->dcfg.n_cell;
-  return off;
-}
-static int images_check(const cc_ctx *c, const void *height, const void *out, int n_scans, const char *who) {
-  const char *why = nullptr;
-  if (!c) why = "ctx must not be NULL";
-  else if (!height) why = "height must not be NULL";
-  else if (!out) why = "out must not be NULL";
-  else if (n_scans < 0) why = "n_scans must not be negative";
-  if (why) return set_err(CC_EINVAL, (std::string(who) + ": " + why).c_str());
-  return CC_OK;
-}
-
 int cc_ingest_images(cc_ctx *c, const float *d_height, const float *d_pos_rc, int n_scans, const float *h_min_height, cc_scan_desc_t *d_out,
                      const cc_ingest_debug_t *dbg, void *stream_) {
-  const char *who = "cc_ingest_images";
-  const int rcc = images_check(c, d_height, d_out, n_scans, who);
-  if (rcc != CC_OK) return rcc;
-  if (((uintptr_t)d_height & 15u) != 0) return set_err(CC_EINVAL, CC_WHO(": d_height must be 16-byte aligned"));
-  if (((uintptr_t)d_pos_rc & 7u) != 0) return set_err(CC_EINVAL, CC_WHO(": d_pos_rc must be 8-byte aligned"));
-  if (n_scans == 0) return CC_OK;
-  const std::vector<int64_t> off = images_offsets(c, n_scans);
-  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, k1_images(d_height, d_pos_rc, h_min_height), off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who);
+  return ingest_device(c, k1_images(d_height, d_pos_rc, h_min_height), nullptr, n_scans, d_out, dbg, stream_, "cc_ingest_images");
 }
 
 int cc_ingest_images_host(cc_ctx *c, const float *h_height, const float *h_pos_rc, int n_scans, const float *h_min_height, cc_scan_desc_t *h_out,
                           float *h_bev) {
-  const char *who = "cc_ingest_images_host";
-  const int rcc = images_check(c, h_height, h_out, n_scans, who);
-  if (rcc != CC_OK) return rcc;
-  if (n_scans == 0) return CC_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const std::vector<int64_t> off = images_offsets(c, n_scans);
-  const size_t h_bytes = sizeof(float) * (size_t)off[n_scans], p_bytes = h_pos_rc ? 2 * h_bytes : 0;  // the positions go behind the heights
-  return ingest_host(c, k1_images(nullptr, h_pos_rc, h_min_height), h_bytes + p_bytes, off.data(), n_scans, h_out, h_bev, who,
-                     [&](char *d_x, cc_scan_desc_t *d_o) {
-                       hipError_t e = hipMemsetAsync(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans, nullptr);
-                       if (e == hipSuccess) e = hipMemcpy(d_x, h_height, h_bytes, hipMemcpyHostToDevice);
-                       if (e == hipSuccess && h_pos_rc) e = hipMemcpy(d_x + h_bytes, h_pos_rc, p_bytes, hipMemcpyHostToDevice);
-                       return e;
-                     });
+  return ingest_host(c, k1_images(h_height, h_pos_rc, h_min_height), nullptr, n_scans, h_out, h_bev, "cc_ingest_images_host");
 }
 
 // SO(3) in f64 for cc_motion_knots: R row-major 3 x 3.
@@ -1386,89 +1420,13 @@ void cc_motion_knots(const double pb[12], const double pe[12], double ref, int K
 }
 
 // ---- scans made of segments (cc_ingest_segments and its siblings) ----
-// Everything the header promises to check, before anything is queued or read.  tab: one entry per segment, `base` = the caller's
-// pointer + xyz_offset (the host calls replace it with where the records went on the device); q_off: the scans' point totals as offsets.
-static int segs_check(const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, const char *who, std::vector<cc_k1_seg> &tab,
-                      std::vector<int64_t> &q_off) {
-  q_off.assign(1, 0);
-  for (int i = 0; i < n_scans; i++) {
-    const int64_t ns = (int64_t)h_scan_segs[i + 1] - h_scan_segs[i];
-    if (h_scan_segs[i] < 0 || ns < 1 || ns > CC_SEG_MAX) return set_err(CC_EINVAL, CC_WHO(": a scan has 1 .. CC_SEG_MAX segments"));
-    int64_t total = 0;
-    for (int k = h_scan_segs[i]; k < h_scan_segs[i + 1]; k++) {
-      const cc_point_segment_t &g = h_segs[k];
-      if (g.n_points < 0 || g.n_points >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": a segment's n_points is negative or >= 2^21"));
-      if (g.n_points > 0 && !g.points) return set_err(CC_EINVAL, CC_WHO(": a segment with points has a NULL pointer"));
-      cc_point_layout_t lay;
-      const bool dflt = g.layout.stride_bytes == 0 && g.layout.xyz_offset == 0;
-      const int rcl = point_layout(dflt ? nullptr : &g.layout, g.n_points > 0 ? g.points : nullptr, who, &lay);
-      if (rcl != CC_OK) return rcl;
-      cc_k1_seg e;
-      e.base = (const char *)g.points + lay.xyz_offset;
-      e.stride = (unsigned)lay.stride_bytes;
-      e.first = (int)total;
-      e.n = (int)g.n_points;
-      e.has_tf = g.has_tf != 0;
-      for (int m = 0; m < 12; m++) e.m[m] = g.has_tf ? g.tf[m] : 0.f;
-      tab.push_back(e);
-      total += g.n_points;
-      if (total >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": scan with >= 2^21 points"));
-    }
-    if (!(total > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
-    q_off.push_back(q_off.back() + total);
-  }
-  return CC_OK;
-}
-
 int cc_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, cc_scan_desc_t *d_out,
                        const cc_ingest_debug_t *dbg, void *stream_) {
-  const char *who = "cc_ingest_segments";
-  if (!c || !h_segs || !h_scan_segs || !d_out || n_scans < 0) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  std::vector<cc_k1_seg> tab;
-  std::vector<int64_t> q_off;
-  const int rcs = segs_check(h_segs, h_scan_segs, n_scans, who, tab, q_off);
-  if (rcs != CC_OK) return rcs;
-  std::vector<int32_t> ss(n_scans + 1);
-  for (int i = 0; i <= n_scans; i++) ss[i] = h_scan_segs[i] - h_scan_segs[0];  // (tab begins with the call's first segment)
-  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);
-  return ingest_on(c, c->main, k1_segments(tab.data(), ss.data(), h_segs + h_scan_segs[0]), q_off.data(), n_scans, d_out, dbg, (hipStream_t)stream_, who);
-}
-
-// Where the records of the checked segments `tab` (host pointers) go in ONE buffer: every segment at a 16-byte boundary, whole records.
-// Returns the buffer's bytes; off[k]: segment k's place.
-static size_t segs_place(const cc_point_segment_t *h_segs, const std::vector<cc_k1_seg> &tab, std::vector<size_t> &off) {
-  size_t bytes = 0;
-  for (size_t k = 0; k < tab.size(); k++) {
-    off.push_back(bytes);
-    bytes += ((size_t)h_segs[k].n_points * tab[k].stride + 15) & ~(size_t)15;
-  }
-  return bytes;
+  return ingest_device(c, k1_segments(h_segs, h_scan_segs), nullptr, n_scans, d_out, dbg, stream_, "cc_ingest_segments");
 }
 
 int cc_ingest_segments_host(cc_ctx *c, const cc_point_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, cc_scan_desc_t *h_out, float *h_bev) {
-  const char *who = "cc_ingest_segments_host";
-  if (!c || !h_segs || !h_scan_segs || !h_out || n_scans < 1) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  std::vector<cc_k1_seg> tab;
-  std::vector<int64_t> q_off;
-  const int rcs = segs_check(h_segs, h_scan_segs, n_scans, who, tab, q_off);
-  if (rcs != CC_OK) return rcs;
-  h_segs += h_scan_segs[0];
-  HIPCHK(hipSetDevice(c->device));
-  std::vector<size_t> off;
-  const size_t pts_bytes = segs_place(h_segs, tab, off);
-  std::vector<int32_t> ss(n_scans + 1);
-  for (int i = 0; i <= n_scans; i++) ss[i] = h_scan_segs[i] - h_scan_segs[0];
-  return ingest_host(c, k1_segments(tab.data(), ss.data(), h_segs), pts_bytes, q_off.data(), n_scans, h_out, h_bev, who, [&](char *d_x, cc_scan_desc_t *d_o) {
-    hipError_t e = hipSuccess;
-    for (size_t k = 0; k < tab.size() && e == hipSuccess; k++) {
-      if (tab[k].n > 0) e = hipMemcpy(d_x + off[k], h_segs[k].points, (size_t)tab[k].n * tab[k].stride, hipMemcpyHostToDevice);
-      tab[k].base = d_x + off[k] + (tab[k].base - (const char *)h_segs[k].points);
-    }
-    // (the rows of a descriptor that its counts do not cover are not written by the kernels: zero here, so that the call's bytes are
-    // those of cc_ingest_segments into zeroed memory)
-    if (e == hipSuccess) e = hipMemset(d_o, 0, sizeof(cc_scan_desc_t) * (size_t)n_scans);
-    return e;
-  });
+  return ingest_host(c, k1_segments(h_segs, h_scan_segs), nullptr, n_scans, h_out, h_bev, "cc_ingest_segments_host");
 }
 
 void cc_est_sens_tf(const double tf_bev[3], int n_row, int n_col, double tf_sens[3]) {
@@ -1620,116 +1578,121 @@ int cc_stage_points_cancel(cc_ctx *c, const float *staged) {
   return set_err(CC_EINVAL, "cc_stage_points_cancel: not a staging buffer of this context");
 }
 
-static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t *layout, int64_t n_points, int n_segs, int want_bev, cc_scan **out, const char *who);
+static int scan_ingest_points(cc_ctx *c, k1_source src, int64_t n_points, int want_bev, cc_scan **out, const char *who);
 
 int cc_scan_ingest(cc_ctx *c, const float *h_xyzi, int64_t n_points, int want_bev, cc_scan **out) {
-  return scan_ingest_points(c, k1_points(h_xyzi, CC_LAYOUT_KITTI, nullptr), nullptr, n_points, 0, want_bev, out, "cc_scan_ingest");
+  return scan_ingest_points(c, k1_points(h_xyzi, nullptr, nullptr), n_points, want_bev, out, "cc_scan_ingest");
 }
 
 int cc_scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t *layout, int64_t n_points, const float *h_tf, int want_bev, cc_scan **out) {
-  return scan_ingest_points(c, k1_points(h_xyzi, CC_LAYOUT_KITTI, h_tf), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points");
+  return scan_ingest_points(c, k1_points(h_xyzi, layout, h_tf), n_points, want_bev, out, "cc_scan_ingest_points");
 }
 
 int cc_scan_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, int n_segs, int want_bev, cc_scan **out) {
-  if (!h_segs) return set_err(CC_EINVAL, "cc_scan_ingest_segments: bad argument");
-  return scan_ingest_points(c, k1_segments(nullptr, nullptr, h_segs), nullptr, 0, n_segs, want_bev, out, "cc_scan_ingest_segments");
+  const int32_t scan_segs[2] = {0, n_segs};
+  return scan_ingest_points(c, k1_segments(h_segs, scan_segs), 0, want_bev, out, "cc_scan_ingest_segments");
 }
 
 int cc_scan_ingest_points_motion(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, int64_t n_points,
                                  const float *h_time, const float *h_knots, int want_bev, cc_scan **out) {
   if (!motion) return set_err(CC_EINVAL, "cc_scan_ingest_points_motion: motion, h_time and h_knots must not be NULL");
-  return scan_ingest_points(c, k1_motion(h_points, CC_LAYOUT_KITTI, *motion, h_time, h_knots), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points_motion");
+  return scan_ingest_points(c, k1_motion(h_points, layout, motion, h_time, h_knots), n_points, want_bev, out, "cc_scan_ingest_points_motion");
 }
 
 int cc_scan_ingest_points_filtered(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_filter_t *filter, int64_t n_points,
                                    const float *h_tf, int want_bev, cc_scan **out) {
   if (!filter) return set_err(CC_EINVAL, "cc_scan_ingest_points_filtered: filter must not be NULL");
-  return scan_ingest_points(c, k1_filtered(h_points, CC_LAYOUT_KITTI, h_tf, *filter), layout, n_points, 0, want_bev, out, "cc_scan_ingest_points_filtered");
+  return scan_ingest_points(c, k1_filtered(h_points, layout, h_tf, filter), n_points, want_bev, out, "cc_scan_ingest_points_filtered");
 }
 
 int cc_scan_ingest_coords(cc_ctx *c, const cc_coord_src_t *src, int64_t n_points, const double *origin, const float *h_tf, int want_bev, cc_scan **out) {
-  const char *who = "cc_scan_ingest_coords";
-  if (!c || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  const int64_t off[2] = {0, n_points};
-  const int rcc = coords_check(src, off, 1, origin, who);
-  if (rcc != CC_OK) return rcc;
-  return scan_ingest_points(c, k1_coords(*src, origin, h_tf), nullptr, n_points, 0, want_bev, out, who);
+  return scan_ingest_points(c, k1_coords(src, origin, h_tf), n_points, want_bev, out, "cc_scan_ingest_coords");
 }
 
+// (a range image's and a height image's size is the sensor's and the context's: k1_check has it)
 int cc_scan_ingest_ranges(cc_ctx *c, const cc_range_sensor *sensor, const void *h_ranges, const float *h_knots, int want_bev, cc_scan **out) {
-  const char *who = "cc_scan_ingest_ranges";
-  if (!c || !out) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  const int rcr = ranges_check(c, sensor, h_ranges, h_knots, who);
-  if (rcr != CC_OK) return rcr;
-  return scan_ingest_points(c, k1_ranges(sensor, h_ranges, h_knots), nullptr, (int64_t)sensor->kr.n_rows * sensor->kr.n_cols, 0, want_bev, out, who);
+  return scan_ingest_points(c, k1_ranges(sensor, h_ranges, h_knots), 0, want_bev, out, "cc_scan_ingest_ranges");
 }
 
 int cc_scan_ingest_image(cc_ctx *c, const float *h_height, const float *h_pos_rc, const float *h_min_height, int want_bev, cc_scan **out) {
-  const char *who = "cc_scan_ingest_image";
-  const int rcc = images_check(c, h_height, out, 0, who);
-  if (rcc != CC_OK) return rcc;
-  return scan_ingest_points(c, k1_images(h_height, h_pos_rc, h_min_height), nullptr, (int64_t)c->dcfg.n_cell, 0, want_bev, out, who);
+  return scan_ingest_points(c, k1_images(h_height, h_pos_rc, h_min_height), 0, want_bev, out, "cc_scan_ingest_image");
 }
 
-// One scan of the per-scan loop.  src: the caller's arguments with HOST addresses, checked here but for a range image's (cc_scan_ingest_ranges
-// has): POINTS, MOTION: src.points are n_points records of `layout` (src.lay is set here); RANGES: n_points words; SEGMENTS: src.h_segs are
-// the scan's n_segs segments -- their records go to the staging buffer one segment after the other, each at a 16-byte boundary; IMAGES: src.points
-// are the n_points = n_cell heights and src.pos_rc the positions or nullptr -- the positions go behind the heights (always through the context's own slot).
-static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t *layout, int64_t n_points, int n_segs, int want_bev, cc_scan **out, const char *who) {
-  const void *h_xyzi = src.points;
-  const cc_point_segment_t *h_segs = src.h_segs;
-  if (!c || (!h_xyzi && !h_segs) || !out || (!h_segs && n_points < 1)) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
-  std::vector<cc_k1_seg> seg_tab;
-  std::vector<int64_t> seg_qoff;
-  std::vector<size_t> seg_place;
-  const int32_t seg_scan[2] = {0, n_segs};
-  size_t seg_bytes = 0;
-  if (h_segs) {
-    const int rcs = segs_check(h_segs, seg_scan, 1, who, seg_tab, seg_qoff);
-    if (rcs != CC_OK) return rcs;
-    seg_bytes = segs_place(h_segs, seg_tab, seg_place);
-    src.segs = seg_tab.data();
-    src.scan_segs = seg_scan;
-    n_points = seg_qoff[1];
-  } else if (src.kind != k1_source::RANGES && src.kind != k1_source::IMAGES && src.kind != k1_source::COORDS) {
-    const int rcl = point_layout(layout, nullptr, who, &src.lay);  // (the records go through a staging buffer to aligned device memory)
-    if (rcl != CC_OK) return rcl;
-    if (src.kind == k1_source::MOTION) {
-      const int rcm = motion_check(src.lay, &src.mot, src.h_time, src.h_knots, 1, who);
-      if (rcm != CC_OK) return rcm;
+// The staging slots of a per-scan call go back to the threads waiting for them when the call ends, however it ends: from where this
+// stands on the buffers are no longer the caller's.
+struct stage_return {
+  cc_ctx *c;
+  const int *slot;
+  int n;
+  ~stage_return() {
+    for (int i = 0; i < n; i++) c->pts_handed[slot[i]] = false;
+    c->pts_cv.notify_all();
+  }
+};
+// The freshly taken descriptor slots of a per-scan call and their cc_scan handles.  Unless the call has handed them to its caller
+// (ready), the slots go back to the pool and the handles are freed, with their events and images.
+struct scan_hold {
+  cc_ctx *c;
+  cc_scan *sc[CC_SCAN_BATCH_MAX] = {};
+  int n = 0;
+  int take(int n_take, const char *who) {  // all or none
+    cc_scan_desc_t *d[CC_SCAN_BATCH_MAX];
+    const hipError_t e_ = slot_take(c, n_take, d);
+    if (e_ != hipSuccess) return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_);
+    for (; n < n_take; n++) {
+      sc[n] = new cc_scan();
+      sc[n]->ctx = c;
+      sc[n]->d_desc = d[n];
     }
-    if (src.kind == k1_source::FILTERED) {
-      const int rcf = filter_check(src.lay, &src.flt, who);
-      if (rcf != CC_OK) return rcf;
+    return CC_OK;
+  }
+  // The handles' ready events behind everything the call queued on `s` (e_: what queueing the last of it gave), then the handles to
+  // out[].  On a failure the stream is drained: the queued kernels write the slots that go back.
+  int ready(hipError_t e_, hipStream_t s, const char *what, const char *who, cc_scan **out) {
+    for (int i = 0; i < n && e_ == hipSuccess; i++) {
+      e_ = hipEventCreateWithFlags(&sc[i]->ready, hipEventDisableTiming);
+      if (e_ == hipSuccess) e_ = hipEventRecord(sc[i]->ready, s);
+    }
+    if (e_ != hipSuccess) {
+      hipStreamSynchronize(s);
+      return set_err(CC_EHIP, (std::string(who) + what).c_str(), e_);
+    }
+    for (int i = 0; i < n; i++) out[i] = sc[i];
+    n = 0;
+    return CC_OK;
+  }
+  ~scan_hold() {
+    {
+      std::lock_guard<std::mutex> slk(c->slot_mu);
+      for (int i = 0; i < n; i++) c->slot_free.push_back(sc[i]->d_desc);
+    }
+    for (int i = 0; i < n; i++) {
+      if (sc[i]->ready) hipEventDestroy(sc[i]->ready);
+      free(sc[i]->h_bev);
+      delete sc[i];
     }
   }
-  const bool is_img = src.kind == k1_source::IMAGES, is_crd = src.kind == k1_source::COORDS;
-  const coord_plan crd_plan = is_crd ? coords_plan(src.crd, 0, n_points) : coord_plan();
-  const size_t img_bytes = is_img ? sizeof(float) * (size_t)n_points : 0;
-  const size_t n_bytes = is_img   ? img_bytes * (src.pos_rc ? 3 : 1)
-                         : h_segs ? seg_bytes
-                         : is_crd ? crd_plan.total
-                                  : (size_t)n_points * (size_t)(src.kind == k1_source::RANGES ? src.sensor->word_bytes : src.lay.stride_bytes);   // the records travel as they are
-  const int64_t n_stage = (int64_t)((n_bytes + 15) / 16);                // ... in buffers counted in 16-byte points
+};
+
+// One scan of the per-scan loop.  src: the caller's arguments with HOST addresses; n_points: the caller's count where the source has
+// none of its own.  The planned copies go through the context's own staging slot to the channel's point buffer -- unless the records
+// are a staging buffer that cc_stage_points* handed out, which travels as it is.
+static int scan_ingest_points(cc_ctx *c, k1_source src, int64_t n_points, int want_bev, cc_scan **out, const char *who) {
+  int64_t off[2] = {0, n_points};
+  const int rcc = k1_check(c, src, K1_SCAN, off, 1, out, who);
+  if (rcc != CC_OK) return rcc;
+  off[1] = k1_offsets(src, off)[1];
+  const k1_host_plan plan = k1_plan(src, K1_SCAN, 0, off[1]);
+  const int64_t n_stage = (int64_t)((plan.total + 15) / 16);  // the buffers are counted in 16-byte points
   std::unique_lock<std::recursive_mutex> lk(c->ing_mu);  // d_pts, the slots, the scratch behind cc_ingest_batch
   HIPCHK(hipSetDevice(c->device));
   int slot = -1;
   for (int i = 0; i < cc_ctx::NPTS; i++)
-    if (c->h_pts[i] && h_xyzi == c->h_pts[i] && !is_img && !is_crd) slot = i;
+    if (c->h_pts[i] && plan.staged == c->h_pts[i]) slot = i;
   if (slot < 0) {
     float *dst = stage_slot_locked(c, n_stage, cc_ctx::OWN_SLOT, lk);  // waits for the slot's holder and its previous copy, grows the buffers if need be
     if (!dst) return set_err(CC_EHIP, CC_WHO(": staging buffer"));
-    if (h_segs) {
-      for (int k = 0; k < n_segs; k++)
-        if (seg_tab[k].n > 0) memcpy((char *)dst + seg_place[k], h_segs[k].points, (size_t)seg_tab[k].n * seg_tab[k].stride);
-    } else if (is_img) {
-      memcpy(dst, h_xyzi, img_bytes);
-      if (src.pos_rc) memcpy((char *)dst + img_bytes, src.pos_rc, 2 * img_bytes);
-    } else if (is_crd) {  // exactly the bytes the streams span: one record array, or three arrays
-      for (int k = 0; k < crd_plan.n_copies; k++) memcpy((char *)dst + crd_plan.at[k], crd_plan.h[k], crd_plan.bytes[k]);
-    } else {
-      memcpy(dst, h_xyzi, n_bytes);
-    }
+    for (const k1_host_plan::copy &cp : plan.copies) memcpy((char *)dst + cp.at, cp.from, cp.bytes);
     slot = cc_ctx::OWN_SLOT;
   } else if (!c->pts_handed[slot] || c->pts_owner[slot] != std::this_thread::get_id()) {
     return set_err(CC_EINVAL, CC_WHO(": the staging buffer was not handed to this thread by cc_stage_points* (or was ingested already)"));
@@ -1738,86 +1701,39 @@ static int scan_ingest_points(cc_ctx *c, k1_source src, const cc_point_layout_t 
   }
   // whatever happens below, the buffer is no longer the caller's: the next thread waiting for the slot may have it once this
   // call has queued (or given up on) the copy
-  struct hand_back {
-    cc_ctx *c;
-    int slot;
-    ~hand_back() {
-      c->pts_handed[slot] = false;
-      c->pts_cv.notify_all();
-    }
-  } hb{c, slot};
+  const stage_return hb{c, &slot, 1};
   // The scan goes to the next channel: its own stream, device point buffer and one-scan scratch set, so that it can run next to
   // the scan before it (a caller may ingest scans i + 1, i + 2 -- from a helper thread, as the evaluator mirror does -- while scan i
   // is queried and added on the loop stream); whoever reads the descriptor waits for `ready`.
   cc_ctx::Channel &ch = c->chan[c->chan_next];
   c->chan_next = (c->chan_next + 1) % cc_ctx::NCHAN;
   if (want_bev && !ch.d_bev_copy) HIPCHK(hipMalloc(&ch.d_bev_copy, sizeof(float) * (size_t)c->dcfg.n_cell));
-  HIPCHK(hipMemcpyAsync(ch.d_pts, c->h_pts[slot], n_bytes, hipMemcpyHostToDevice, ch.s));
+  HIPCHK(hipMemcpyAsync(ch.d_pts, c->h_pts[slot], plan.total, hipMemcpyHostToDevice, ch.s));
   HIPCHK(hipEventRecord(c->pts_ev[slot], ch.s));
   c->pts_busy[slot] = true;
-  cc_scan *sc = new cc_scan();  // from here on every failure path gives the handle (and, once taken, the descriptor slot) back
-  sc->ctx = c;
-  const hipError_t e_slot = slot_take(c, 1, &sc->d_desc);
-  if (e_slot != hipSuccess) {
-    delete sc;
-    return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_slot);
-  }
-  auto give_back = [&](void) {
-    {
-      std::lock_guard<std::mutex> lk(c->slot_mu);
-      c->slot_free.push_back(sc->d_desc);
-    }
-    if (sc->ready) hipEventDestroy(sc->ready);
-    free(sc->h_bev);
-    delete sc;
-  };
-  const int64_t off[2] = {0, n_points};
+  scan_hold hold{c};  // from here on every failure path gives the handle and its descriptor slot back
+  const int rct = hold.take(1, who);
+  if (rct != CC_OK) return rct;
+  cc_scan *sc = hold.sc[0];
   cc_ingest_debug_t dbg;
   dbg.d_bev = want_bev ? ch.d_bev_copy : nullptr;
   dbg.d_pix_rc = nullptr;
   dbg.d_labels = nullptr;
-  if (h_segs || is_img || is_crd) {  // a pool slot holds an earlier scan's rows: zero, as cc_ingest_segments_host does, for the same bytes
+  if (plan.zero_out) {
     const hipError_t e_ = hipMemsetAsync(sc->d_desc, 0, sizeof(cc_scan_desc_t), ch.s);
-    if (e_ != hipSuccess) {
-      give_back();
-      return set_err(CC_EHIP, CC_WHO(": hipMemsetAsync"), e_);
-    }
+    if (e_ != hipSuccess) return set_err(CC_EHIP, CC_WHO(": hipMemsetAsync"), e_);
   }
-  for (int k = 0; k < n_segs; k++) seg_tab[k].base = (const char *)ch.d_pts + seg_place[k] + (seg_tab[k].base - (const char *)h_segs[k].points);
-  src.points = ch.d_pts;
-  if (is_img && src.pos_rc) src.pos_rc = ch.d_pts + n_points;
-  if (is_crd) {
-    src.crd.x = (const char *)ch.d_pts + crd_plan.strm[0];
-    src.crd.y = (const char *)ch.d_pts + crd_plan.strm[1];
-    src.crd.z = (const char *)ch.d_pts + crd_plan.strm[2];
-  }
-  const int rc = ingest_on(c, ch.scr, src, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);
-  if (rc != CC_OK) {
-    give_back();
-    return rc;
-  }
+  k1_rebase(src, plan, ch.d_pts);
+  const int rc = ingest_on(c, ch.scr, src, off, 1, sc->d_desc, want_bev ? &dbg : nullptr, ch.s, who);  // (writes straight into the pool slot)
+  if (rc != CC_OK) return rc;
   if (want_bev) {  // the image scratch is shared: bring it over now (asynchronously, into the handle's own buffer)
     sc->h_bev = (float *)malloc(sizeof(float) * (size_t)c->dcfg.n_cell);
-    if (!sc->h_bev) {
-      give_back();
-      return set_err(CC_ENOMEM, CC_WHO(": out of host memory"));
-    }
+    if (!sc->h_bev) return set_err(CC_ENOMEM, CC_WHO(": out of host memory"));
     const hipError_t e_ = hipMemcpyAsync(sc->h_bev, ch.d_bev_copy, sizeof(float) * (size_t)c->dcfg.n_cell, hipMemcpyDeviceToHost, ch.s);
-    if (e_ != hipSuccess) {
-      give_back();
-      return set_err(CC_EHIP, CC_WHO(": copy of the BEV image"), e_);
-    }
+    if (e_ != hipSuccess) return set_err(CC_EHIP, CC_WHO(": copy of the BEV image"), e_);
     sc->bev_pending = true;
   }
-  hipError_t e_ = hipEventCreateWithFlags(&sc->ready, hipEventDisableTiming);
-  if (e_ == hipSuccess) e_ = hipEventRecord(sc->ready, ch.s);
-  if (e_ != hipSuccess) {
-    hipStreamSynchronize(ch.s);  // the queued kernels write the slot
-    give_back();
-    return set_err(CC_EHIP, CC_WHO(": ready event"), e_);
-  }
-  *out = sc;
-  return CC_OK;
+  return hold.ready(hipSuccess, ch.s, ": ready event", who, out);
 }
 
 // cc_scan_ingest for 1..CC_SCAN_BATCH_MAX staged scans at once: ONE K1/K2 launch chain for all of them on the next channel (a
@@ -1878,16 +1794,7 @@ static int scan_ingest_points_batch(cc_ctx *c, const void *const *h_xyzi, const 
     if (!(n_points[i] > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
     off[i + 1] = off[i] + n_points[i];
   }
-  // from here on the buffers are no longer the caller's, whatever happens
-  struct hand_back {
-    cc_ctx *c;
-    const int *slot;
-    int n;
-    ~hand_back() {
-      for (int i = 0; i < n; i++) c->pts_handed[slot[i]] = false;
-      c->pts_cv.notify_all();
-    }
-  } hb{c, slot, n};
+  const stage_return hb{c, slot, n};  // from here on the buffers are no longer the caller's, whatever happens
   cc_ctx::Channel &ch = c->chan[c->chan_next];
   c->chan_next = (c->chan_next + 1) % cc_ctx::NCHAN;
   // the channel's point buffer, scratch set and descriptor row grow to a batch's size the first time a batch comes by
@@ -1912,48 +1819,15 @@ static int scan_ingest_points_batch(cc_ctx *c, const void *const *h_xyzi, const 
     HIPCHK(hipEventRecord(c->pts_ev[slot[i]], ch.s));
     c->pts_busy[slot[i]] = true;
   }
-  cc_scan *sc[CC_SCAN_BATCH_MAX] = {};
+  scan_hold hold{c};
+  const int rct = hold.take(n, who);
+  if (rct != CC_OK) return rct;
   cc_desc_out_tab tab;
-  for (int i = 0; i < CC_SCAN_BATCH_MAX; i++) tab.p[i] = nullptr;
-  int n_have = 0;
-  auto give_back = [&](void) {
-    {
-      std::lock_guard<std::mutex> slk(c->slot_mu);
-      for (int i = 0; i < n_have; i++)
-        if (sc[i] && sc[i]->d_desc) c->slot_free.push_back(sc[i]->d_desc);
-    }
-    for (int i = 0; i < n_have; i++) {
-      if (!sc[i]) continue;
-      if (sc[i]->ready) hipEventDestroy(sc[i]->ready);
-      delete sc[i];
-    }
-  };
-  const hipError_t e_slot = slot_take(c, n, tab.p);
-  if (e_slot != hipSuccess) return set_err(CC_EHIP, CC_WHO(": descriptor slots"), e_slot);
-  for (int i = 0; i < n; i++) {
-    sc[i] = new cc_scan();
-    sc[i]->ctx = c;
-    sc[i]->d_desc = tab.p[i];
-  }
-  n_have = n;
-  const int rc = ingest_on(c, ch.scr, k1_points(ch.d_pts, lay, h_tf), off, n, ch.d_desc_tmp, nullptr, ch.s, who);
-  if (rc != CC_OK) {
-    give_back();
-    return rc;
-  }
+  for (int i = 0; i < CC_SCAN_BATCH_MAX; i++) tab.p[i] = i < n ? hold.sc[i]->d_desc : nullptr;
+  const int rc = ingest_on(c, ch.scr, k1_points(ch.d_pts, &lay, h_tf), off, n, ch.d_desc_tmp, nullptr, ch.s, who);
+  if (rc != CC_OK) return rc;
   hipLaunchKernelGGL(cc_k_scatter_desc, dim3(n * CC_SCATTER_BLOCKS), dim3(256), 0, ch.s, tab, n, (const cc_scan_desc_t *)ch.d_desc_tmp);
-  hipError_t e_ = hipGetLastError();
-  for (int i = 0; i < n && e_ == hipSuccess; i++) {
-    e_ = hipEventCreateWithFlags(&sc[i]->ready, hipEventDisableTiming);
-    if (e_ == hipSuccess) e_ = hipEventRecord(sc[i]->ready, ch.s);
-  }
-  if (e_ != hipSuccess) {
-    hipStreamSynchronize(ch.s);  // the queued kernels write the slots
-    give_back();
-    return set_err(CC_EHIP, CC_WHO(": launch / ready events"), e_);
-  }
-  for (int i = 0; i < n; i++) out[i] = sc[i];
-  return CC_OK;
+  return hold.ready(hipGetLastError(), ch.s, ": launch / ready events", who, out);
 }
 
 // 1: the scan's ingest has finished on the device (its descriptor can be read without waiting), 0: still in flight

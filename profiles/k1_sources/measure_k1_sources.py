@@ -1,6 +1,6 @@
 """Every K1 instance's answers and launches, to compare two builds of the library: the leaf walk of tests/k1_instances.py on the device
 (11 point sources x two resolutions x the split and the whole-scan path, scans of 40 001 points and 32 x 1 251 range images), then one
-*_host call and one cc_scan_ingest* call per family.  Prints one line per call with a digest of the descriptors it returned.
+*_host call and one cc_scan_ingest* call per family (coordinates as one record array and as three arrays, images with positions).  Prints one line per call with a digest of the descriptors it returned.
 
   drive:    rocprofv3 --kernel-trace --memory-copy-trace --output-format csv json -d DIR -o r -- \\
                 python profiles/k1_sources/measure_k1_sources.py                (CC_AMD_LIB=<other build> for the other side)
@@ -69,6 +69,25 @@ def drive():
                                                         t_begin=np.full(nb, -0.25, np.float32), scale=np.full(nb, 7.5, np.float32), knots=tfs.reshape(nb, 1, 12)))
     say("cc_ingest_segments_host", ctx.ingest_segments_host(seg_host))
     say("cc_ingest_ranges_host", ctx.ingest_ranges_host(sensor, inp.images["u16"][:nb]))
+    # the later families: records dropped by a u8 class word at byte 12; f64 coordinates as ONE record array (a [N, 3] view of [N, 4]
+    # rows) and as three arrays, an origin per scan; images with positions (K1's own of the same scans, made on the device first)
+    words = (np.arange(len(cat)) % 7).astype(np.uint8)
+    rec = repack(cat, 16, 0).reshape(-1, 16).copy()
+    rec[:, 12] = words
+    rec = rec.reshape(-1)
+    keep = cc.PointFilter.classes(12, "u8", drop=[3, 5])
+    say("cc_ingest_points_filtered_host", ctx.ingest_host(rec, offs, layout=(16, 0), tf=tfs, keep=keep))
+    org = np.tile(np.array([[448000.0, 5412000.0, 300.0]]), (nb, 1)) + np.arange(nb)[:, None]
+    xyz = np.zeros((len(cat), 4), np.float64)
+    xyz[:, :3] = cat[:, :3].astype(np.float64) + np.repeat(org, np.diff(offs), 0)
+    cols = tuple(np.ascontiguousarray(xyz[:, k]) for k in range(3))
+    say("cc_ingest_coords_host records", ctx.ingest_coords_host(xyz[:, :3], offs, origin=org, tf=tfs))
+    say("cc_ingest_coords_host columns", ctx.ingest_coords_host(cols, offs, origin=org, tf=tfs))
+    dimg, dbg = ctx.ingest(torch.from_numpy(np.ascontiguousarray(cat, np.float32)).cuda(), offs, debug=True)
+    torch.cuda.synchronize()
+    height, pos = dbg["bev"].cpu().numpy(), dbg["pix_rc"].cpu().numpy()
+    mins = cc.desc_to_numpy(dimg)["min_bin_val"]
+    say("cc_ingest_images_host", ctx.ingest_images_host(height, pos, mins))
 
     lib = cc.lib()
     for f in ("cc_scan_ingest", "cc_scan_ingest_points", "cc_scan_ingest_points_motion", "cc_scan_ingest_segments", "cc_scan_ingest_ranges", "cc_scan_desc",
@@ -99,6 +118,17 @@ def drive():
     take("cc_scan_ingest_segments", lib.cc_scan_ingest_segments(ctx.h, C.cast(hs.arr, C.c_void_p), 3, 0, C.byref(sc)), sc)
     im = np.ascontiguousarray(inp.images["u16"][0])
     take("cc_scan_ingest_ranges", lib.cc_scan_ingest_ranges(ctx.h, sensor.h, im.ctypes.data, None, 0, C.byref(sc)), sc)
+    calls = cc.calls
+    lay = L.PointLayout(16, 0)
+    take("cc_scan_ingest_points_filtered", calls.scan_ingest_points_filtered(lib, ctx.h, rec.ctypes.data, lay, keep._c, n1, tf1, 0, sc), sc)
+    x1 = np.ascontiguousarray(xyz[:n1])
+    src = calls.coord_src(x1.ctypes.data, x1.ctypes.data + 8, x1.ctypes.data + 16, "float64", 32)
+    take("cc_scan_ingest_coords records", calls.scan_ingest_coords(lib, ctx.h, src, n1, org[0], tf1, 0, sc), sc)
+    c1 = [np.ascontiguousarray(c[:n1]) for c in cols]
+    src = calls.coord_src(c1[0].ctypes.data, c1[1].ctypes.data, c1[2].ctypes.data, "float64", 8)
+    take("cc_scan_ingest_coords columns", calls.scan_ingest_coords(lib, ctx.h, src, n1, org[0], tf1, 0, sc), sc)
+    h1, p1 = np.ascontiguousarray(height[0]), np.ascontiguousarray(pos[0])
+    take("cc_scan_ingest_image", calls.scan_ingest_image(lib, ctx.h, h1.ctypes.data, p1.ctypes.data, float(mins[0]), 0, sc), sc)
     torch.cuda.synchronize()
     sensor.close()
     ctx.close()

@@ -145,6 +145,28 @@ def test_per_scan_and_host_calls(oracle):
     api.lib.cc_destroy(ctx)
 
 
+def test_host_and_per_scan_calls_return_the_device_calls_bytes(oracle):
+    """Three images, with positions and minima and without: cc_ingest_images_host and cc_scan_ingest_image return the BYTES of
+    cc_ingest_images into zeroed memory -- also behind a descriptor's counts, where the per-scan call's pool slot holds an earlier
+    scan's rows (scan 0 comes by again behind scan 2).  A position read at a wrong place in the staged copy changes the bytes:
+    the case without positions differs from the one with them."""
+    api = HI.ImagesApi(oracle.L)
+    ctx = api.create(max_batch=3)
+    clouds = HI.round_trip_clouds()[:3]
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in clouds])]).astype(np.int64)
+    ref, rdbg = api.ingest(ctx, np.concatenate(clouds, 0), offs, debug=True)
+    dev = {}
+    for pos, mins in ((rdbg["pix_rc"], ref["min_bin_val"]), (None, None)):
+        d3 = dev[pos is None] = api.ingest_images(ctx, rdbg["bev"], pos, mins)
+        rc, dh, _ = api.ingest_images_host_rc(ctx, rdbg["bev"], pos, mins)
+        assert rc == 0 and dh.tobytes() == d3.tobytes()
+        for i in (0, 1, 2, 0):
+            rc, d, _ = api.scan_ingest_image_rc(ctx, rdbg["bev"][i], None if pos is None else pos[i], None if mins is None else mins[i])
+            assert rc == 0 and d.tobytes() == d3[i].tobytes(), i
+    assert dev[False].tobytes() == ref.tobytes() and dev[True].tobytes() != ref.tobytes()
+    api.lib.cc_destroy(ctx)
+
+
 def test_a_drive_through_images_answers_like_the_drive_through_points(cc, oracle):
     """64 scans of a short drive: ingest -> add_scans -> query, and the same with the scans handed over as images: equal result records"""
     L = oracle.L

@@ -124,6 +124,25 @@ def test_per_scan_and_host_calls(cc, oracle):
     be.close(ctx)
 
 
+def test_host_and_per_scan_calls_return_the_device_calls_bytes(cc, oracle):
+    """Three images, with positions and minima and without: cc_ingest_images_host and cc_scan_ingest_image return the BYTES of
+    cc_ingest_images into zeroed memory -- also behind a descriptor's counts, where the per-scan call's pool slot holds an earlier
+    scan's rows (scan 0 comes by again behind scan 2)"""
+    cfg = oracle.L.default_manager_cfg()
+    be = GpuBack(cc)
+    ctx = be.open(cfg, 3)
+    ref, rdbg = be.points(ctx, HI.round_trip_clouds()[:3], True)
+    api = HI.ImagesApi(oracle.L, so=cc.LIB_PATH)   # the product library through the C-ABI driver: the calls here take host pointers
+    api._cfg = cfg
+    for pos, mins in ((rdbg["pix_rc"], ref["min_bin_val"]), (None, None)):
+        d3, _ = be.images(ctx, rdbg["bev"], pos, mins, False)
+        assert ctx.ingest_images_host(rdbg["bev"], pos, mins).tobytes() == d3.tobytes()
+        for i in (0, 1, 2, 0):
+            rc, d, _ = api.scan_ingest_image_rc(ctx.h, rdbg["bev"][i], None if pos is None else pos[i], None if mins is None else mins[i])
+            assert rc == 0 and d.tobytes() == d3[i].tobytes(), i
+    be.close(ctx)
+
+
 def test_a_drive_through_images_answers_like_the_drive_through_points(cc, oracle):
     """64 scans of a short drive: ingest -> add_scans -> query, and the same with the scans handed over as images: equal result records"""
     import torch

@@ -168,7 +168,7 @@ def test_host_call_and_chunks(cc, oracle, drv):
     """Case 11 through the Python API: ingest_host(keep=) returns the batch call's descriptors; a context of 2 scans takes 3 in chunks.
     (The per-scan call is the class mirror's: tests/test_hostcpp_point_filter.py runs it on the device.)"""
     cfg = cc.L.default_manager_cfg()
-    for case in (PF.case_layout(1, n_scans=3), PF.case_with_tf(3)):
+    for case in (PF.case_layout(1, n_scans=3), PF.case_with_tf(3), PF.case_range(0, n_scans=3)):
         ctx = drv.context(cfg, 2)
         ref, _ = PF.check_case(drv, oracle, cfg, case, ctx)
         dh = ctx.ingest_host(case.buffer(), case.offs(), layout=case.layout, tf=case.tfs, keep=case.rule.python(cc))
