@@ -529,6 +529,15 @@ class Context:
                                  host=True, bev=bev.ctypes.data if want_bev else None), "cc_ingest_images_host")
         return (out, bev) if want_bev else out
 
+    def path_counts(self):
+        """Which body of K2 took the context's scans so far (cc_ingest_path_counts, include/cont2_amd_paths.h; waits for the queued ingest calls):
+        {"mid": scans the list kernel handed to cc_k_contours_mid, "why": those by reason (configuration, entries / slots, components
+        per level, member-list padding), "big": scans handed on to cc_k_contours_big}.  The difference of two readings counts the
+        calls between them."""
+        out = (C.c_int32 * 6)()
+        _chk(lib().cc_ingest_path_counts(self.h, out), "cc_ingest_path_counts")
+        return {"mid": int(out[0]), "why": [int(v) for v in out[1:5]], "big": int(out[5])}
+
     def ingest_segments(self, scans, out=None, debug=False):
         """Every scan from an ordered list of point segments, each with its own record shape and transform (cc_ingest_segments):
         scans = [[(points, layout, tf), ...], ...] with `points` a contiguous CUDA tensor holding the segment's records (read in

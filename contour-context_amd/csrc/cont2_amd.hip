@@ -24,6 +24,7 @@
 #include "../../include/cont2_amd_images.h"
 #include "../../include/cont2_amd_filter.h"
 #include "../../include/cont2_amd_coords.h"
+#include "../../include/cont2_amd_paths.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
 #include "k_image.h"
@@ -467,6 +468,26 @@ int cc_profile_read(cc_ctx *c, double ms_out[2], int *n_launches) {
   if (n_launches) *n_launches = c->launches;
   c->ms_acc[0] = c->ms_acc[1] = 0;
   c->launches = 0;
+  return CC_OK;
+}
+
+int cc_ingest_path_counts(cc_ctx *c, int32_t out[6]) {
+  if (!c || !out) return set_err(CC_EINVAL, "cc_ingest_path_counts: bad argument");
+  std::lock_guard<std::recursive_mutex> ing_lk(c->ing_mu);  // no ingest call queues work on a lane while it is read
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < 6; i++) out[i] = 0;
+  cc_ctx::Scratch *lanes[1 + cc_ctx::NCHAN] = {&c->main};
+  for (int i = 0; i < cc_ctx::NCHAN; i++) lanes[1 + i] = &c->chan[i].scr;
+  for (cc_ctx::Scratch *S : lanes) {
+    if (S->cap == 0) continue;  // (a channel of the per-scan loop that no scan has come by)
+    if (S->has_last) HIPCHK(hipEventSynchronize(S->ev_last));
+    cc_k2_big_queue q;  // (the header: the scan indices behind it stay where they are)
+    HIPCHK(hipMemcpy(&q, S->d_midq, sizeof(q), hipMemcpyDeviceToHost));
+    out[0] += q.total;
+    for (int k = 0; k < 4; k++) out[1 + k] += q.why[k];
+    HIPCHK(hipMemcpy(&q, S->d_bigq, sizeof(q), hipMemcpyDeviceToHost));
+    out[5] += q.total;
+  }
   return CC_OK;
 }
 

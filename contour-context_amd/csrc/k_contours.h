@@ -1121,6 +1121,7 @@ __device__ __forceinline__ void cc_k2_body(const cc_dev_cfg &cfg, const float *_
   if (!BIG && queue != nullptr && (sh[2] & 2)) {
     if (tid == 0) {
       queue->scan[atomicAdd(&queue->n_flagged, 1)] = scan;
+      atomicAdd(&queue->total, 1);  // (as the list kernel counts its hand-offs: cc_ingest_path_counts reads it)
       desc_out[scan].flags = CC_DESC_INEXACT_COMPONENTS;  // stands until the slow path has rewritten the descriptor
     }
     return;

@@ -7,6 +7,7 @@ the CPU harness, test_gpu_height_images.py: the device).  A back end has
     points(handle, clouds, debug) -> (descriptors, debug dict or None)        one cc_ingest_batch call, numpy out
     images(handle, height, pos, mins, debug) -> (descriptors, debug dict or None)   one cc_ingest_images call, numpy out
     paths() -> {"list": set, "mid": set, "big": set} of scan indices of the last call, or None where the build cannot say.
+    path_counts() -> {"list": n, "mid": n, "big": n, "why": [4]} of the last images() call: the difference of two cc_ingest_path_counts readings
 References come from cc_ingest_batch on clouds (the defining property) and from the oracle, never from the new code alone."""
 import ctypes as C
 
@@ -362,6 +363,8 @@ def case_list_edges(be, oracle, which):
     same(ref, d, rdbg, dbg)
     plain, _ = be.images(h, imgs, None, None, False)   # without the debug outputs: the dense branch only where the list overflows
     paths = be.paths()
+    pc = be.path_counts()                              # the call's counts by body, from cc_ingest_path_counts: every back end has them
+    assert all(len(w) == 1 for w in want) and {k: pc[k] for k in ("list", "mid", "big")} == {k: sum(w == {k} for w in want) for k in ("list", "mid", "big")}, (which, pc)
     same(ref, plain)
     be.close(h)
     for i in range(len(scenes)):

@@ -2,6 +2,7 @@
 test_gpu_keys.py: the device).  A back end has
     ingest(list of point arrays, manager config, debug=False) -> numpy descriptors (scan_desc_dt), one ingest call
     paths() -> {"list": set, "mid": set, "big": set} of scan indices of the last ingest call, or None where the build cannot say.
+    path_counts() -> {"list": n, "mid": n, "big": n} of the last ingest call: the difference of two cc_ingest_path_counts readings.
 
 Reference inputs always come from the oracle (its max-height image, cell positions and contour rows), never from the code under
 test; tests/key_reference.py restates the key phase on them.  Every scan's oracle keys must pass check_keys first (a wrong
@@ -302,6 +303,9 @@ def run(be, oracle, names, cfg_kw=(), debug=False, refs=None, want_path=None):
     paths = be.paths()
     if want_path is not None and paths is not None:
         assert paths[want_path] == set(range(len(refs))), (want_path, paths)
+    if want_path is not None:
+        pc = be.path_counts()
+        assert {k: pc[k] for k in ("list", "mid", "big")} == {k: len(refs) if k == want_path else 0 for k in ("list", "mid", "big")}, (want_path, pc)
     assert_cap()
     return refs, d
 

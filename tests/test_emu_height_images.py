@@ -17,7 +17,7 @@ class EmuBack:
     def __init__(self, oracle, capfd=None):
         self.api = HI.ImagesApi(oracle.L)
         self.capfd = capfd
-        self._paths = None
+        self._paths = self._counts = None
 
     def open(self, cfg, max_batch):
         return self.api.create(cfg=cfg, max_batch=max_batch)
@@ -30,10 +30,18 @@ class EmuBack:
         out = self.api.ingest(h, np.concatenate(clouds, 0), offs, debug=debug)
         return out if debug else (out, None)
 
+    def read_counts(self, h):
+        out = (C.c_int32 * 6)()
+        self.api.chk(self.api.lib.cc_ingest_path_counts(h, out), "cc_ingest_path_counts")
+        return np.array(out[:], np.int64)
+
     def images(self, h, height, pos, mins, debug):
         if self.capfd is not None:
             self.capfd.readouterr()
+        before = self.read_counts(h)
         out = self.api.ingest_images(h, height, pos, mins, debug=debug)
+        d = self.read_counts(h) - before
+        self._counts = {"list": len(height) - int(d[0]), "mid": int(d[0] - d[5]), "big": int(d[5]), "why": [int(v) for v in d[1:5]]}
         if self.capfd is not None:   # (test_emu_keys.py's reading of the trace)
             err = self.capfd.readouterr().err.splitlines()
             handed = {int(l.split("scan")[1].split()[0]) for l in err if "handed to the mid path" in l}
@@ -41,10 +49,18 @@ class EmuBack:
             every = set(range(len(height)))
             assert big <= handed <= every, (handed, big)
             self._paths = {"list": every - handed, "mid": handed - big, "big": big}
+            # the getter's own test: the counters of cc_ingest_path_counts agree with the trace lines -- the counts per body, the sum of
+            # the reasons, and as many reasons in use as the trace names hand-off lines (topology_cases._call holds each reason's count)
+            lines = {int(l.split("line")[1].split(")")[0]) for l in err if "handed to the mid path" in l}
+            assert {k: len(v) for k, v in self._paths.items()} == {k: self._counts[k] for k in ("list", "mid", "big")}, (self._paths, self._counts)
+            assert sum(self._counts["why"]) == len(handed) and sum(1 for w in self._counts["why"] if w) == len(lines), (self._counts, lines)
         return out if debug else (out, None)
 
     def paths(self):
         return self._paths
+
+    def path_counts(self):
+        return self._counts
 
 
 @pytest.mark.parametrize("n,max_batch", [(1, 9), (9, 9), (9, 4)])   # one scan; one chunk; three chunks (the minima cross chunks)

@@ -1,5 +1,7 @@
 """The retrieval keys of the ingest path on the CPU harness, against tests/key_reference.py on the oracle's inputs, at the edges of
 the key phase (tests/key_cases.py).  The harness build prints which K2 path took each scan (CC_EMU_TRACE_K2); the cases assert it."""
+import ctypes as C
+
 import numpy as np
 
 import emu_api
@@ -10,7 +12,7 @@ class EmuBackEnd:
     def __init__(self, oracle, capfd):
         self.api = emu_api.EmuApi(oracle.L)
         self.capfd = capfd
-        self._paths = None
+        self._paths = self._counts = None
 
     def ingest(self, scans, cfg, debug=False):
         ctx = self.api.create(cfg=cfg, max_batch=len(scans))
@@ -24,11 +26,18 @@ class EmuBackEnd:
         every = set(range(len(scans)))   # (a scan the list kernel turns away at its door is handed on before it is counted)
         assert big <= handed <= every and seen | handed == every, (seen, handed, big)
         self._paths = {"list": every - handed, "mid": handed - big, "big": big}
+        pc = (C.c_int32 * 6)()                # a context of this call alone: its counters are the call's
+        self.api.chk(self.api.lib.cc_ingest_path_counts(ctx, pc), "cc_ingest_path_counts")
+        self._counts = {"list": len(scans) - pc[0], "mid": pc[0] - pc[5], "big": pc[5]}
+        assert self._counts == {k: len(v) for k, v in self._paths.items()} and sum(pc[1:5]) == pc[0], (self._counts, self._paths, pc[:])
         self.api.lib.cc_destroy(ctx)
         return out[0] if debug else out
 
     def paths(self):
         return self._paths
+
+    def path_counts(self):
+        return self._counts
 
 
 def _be(oracle, capfd, monkeypatch):

@@ -1,6 +1,7 @@
 """cc_ingest_images and its siblings (include/cont2_amd_images.h) on the MI355X: cc_k_image_list's 1 024-thread shape (24 cells per
 lane in registers, v_mbcnt ranks, DPP scans) exists on hardware only.  The cases are tests/height_images.py's -- the same inputs took
-the list, mid and big bodies of K2 on the CPU harness (test_emu_height_images.py asserts that); here they are trusted to.  Against
+the list, mid and big bodies of K2 on the CPU harness (test_emu_height_images.py asserts that); here the capacity cases assert it on
+the counters of cc_ingest_path_counts.  Against
 the oracle the ring components of the keys are compared under parity.compare_desc's own bar (the device's exp), everything else to
 the bit; against cc_ingest_batch every byte."""
 
@@ -22,6 +23,7 @@ class GpuBack:
 
     def __init__(self, cc):
         self.cc = cc
+        self._counts = None
 
     def open(self, cfg, max_batch):
         return self.cc.Context(0, cfg, max_batch=max_batch)
@@ -45,12 +47,21 @@ class GpuBack:
         import torch
         h = torch.from_numpy(np.ascontiguousarray(height, np.float32)).cuda()
         p = None if pos is None else torch.from_numpy(np.ascontiguousarray(pos, np.float32)).cuda()
+        before = ctx.path_counts()
         out = ctx.ingest_images(h, p, mins, out=self._zeros(len(height)), debug=debug)
+        after = ctx.path_counts()
         torch.cuda.synchronize()
+        mid, big = after["mid"] - before["mid"], after["big"] - before["big"]
+        self._counts = {"list": len(height) - mid, "mid": mid - big, "big": big, "why": [a - b for a, b in zip(after["why"], before["why"])]}
         return (self.cc.desc_to_numpy(out[0]).copy(), _np(out[1])) if debug else (self.cc.desc_to_numpy(out).copy(), None)
 
     def paths(self):
-        return None
+        """per scan only where the counts of the last images() call decide it: all of its scans on one body"""
+        c, n = self._counts, sum(self._counts[k] for k in ("list", "mid", "big"))
+        return next(({kk: set(range(n)) if kk == k else set() for kk in ("list", "mid", "big")} for k in ("list", "mid", "big") if c[k] == n), None)
+
+    def path_counts(self):
+        return self._counts
 
 
 @pytest.mark.parametrize("n,max_batch", [(1, 9), (9, 9), (9, 4)])   # one scan (K1: split sweep); one chunk; three chunks (the minima cross chunks)

@@ -1,7 +1,8 @@
 """The retrieval keys of the ingest path on the MI355X, held to the bit against tests/key_reference.py on the oracle's inputs, at the
 edges of the key phase (tests/key_cases.py): the quad's tail lanes and the order of its four additions (DPP broadcasts), the
 ballot-ordered lists, the second anchor group in reused LDS and the clamp exist in this form on hardware only.  The same inputs took
-the list, mid and big paths on the CPU harness (test_emu_keys.py asserts that); here they are trusted to."""
+the list, mid and big paths on the CPU harness (test_emu_keys.py asserts that); here the counters of cc_ingest_path_counts say which
+body took a call's scans, and the cases assert it."""
 import numpy as np
 import pytest
 
@@ -13,6 +14,7 @@ pytestmark = pytest.mark.gpu
 class GpuBackEnd:
     def __init__(self, cc):
         self.cc = cc
+        self._counts = None
 
     def ingest(self, scans, cfg, debug=False):
         import torch
@@ -23,11 +25,19 @@ class GpuBackEnd:
         out = ctx.ingest(x, offs, out=zeroed, debug=debug)
         torch.cuda.synchronize()
         d = self.cc.desc_to_numpy(out[0] if debug else out).copy()
+        pc = ctx.path_counts()                # a context of this call alone: its counters are the call's
+        self._counts = {"list": len(scans) - pc["mid"], "mid": pc["mid"] - pc["big"], "big": pc["big"]}
+        assert sum(pc["why"]) == pc["mid"], pc
         ctx.close()
         return d
 
     def paths(self):
-        return None
+        """per scan only where the counts decide it: all of the call's scans on one body"""
+        n = sum(self._counts.values())
+        return next(({kk: set(range(n)) if kk == k else set() for kk in self._counts} for k, v in self._counts.items() if v == n), None)
+
+    def path_counts(self):
+        return self._counts
 
 
 def test_quad_tails_and_empty_list(cc, oracle):
