@@ -932,6 +932,14 @@ class Database:
         _chk(lib().cc_db_debug_passes(self.h, out.ctypes.data, cap, C.byref(n)), "cc_db_debug_passes")
         return out[:n.value]
 
+    def debug_cands(self, cap=1152):
+        """Every candidate of the last check_hints call as the merge left it, in first-appearance order: numpy array of
+        L.cand_dbg_dt (cc_db_debug_cands, include/cont2_amd_cands.h)."""
+        out = np.zeros(cap, L.cand_dbg_dt)
+        n = C.c_int()
+        _chk(lib().cc_db_debug_cands(self.h, out.ctypes.data, cap, C.byref(n)), "cc_db_debug_cands")
+        return out[:n.value]
+
     def set_lanes(self, n):
         """1 = query chunks one after the other, 2 (default) = two 256-query chunks in flight on internal streams."""
         _chk(lib().cc_db_set_lanes(self.h, int(n)), "cc_db_set_lanes")

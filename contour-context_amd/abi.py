@@ -1,7 +1,7 @@
 """The ctypes signature of every function include/cont2_amd.h declares, in one table, and bind() to apply it to a loaded
 library (the product's, the CPU harness's, another build).  tests/test_abi_layout.py holds the table against the header.
 The extension headers beside it have tables of their own, which bind() applies as well: EXTENSIONS (include/cont2_amd_images.h) and
-the open-ended ADDONS (include/cont2_amd_filter.h, include/cont2_amd_coords.h, include/cont2_amd_paths.h and whatever follows).
+the open-ended ADDONS (include/cont2_amd_filter.h, include/cont2_amd_coords.h, include/cont2_amd_paths.h, include/cont2_amd_cands.h and whatever follows).
 
 One line per prototype, in the header's order: return code, name, one code per parameter.
   parameters   P any pointer or array   I int / int32_t   Q int64_t   Z size_t   D double   F float   (- : none)
@@ -158,6 +158,9 @@ I cc_scan_ingest_coords PPQPPIP
 """,
     "cont2_amd_paths.h": """
 I cc_ingest_path_counts PP
+""",
+    "cont2_amd_cands.h": """
+I cc_db_debug_cands PPIP
 """,
 }
 ADDONS = {hdr: _table(spec) for hdr, spec in _ADDON_SPEC.items()}

@@ -1994,6 +1994,37 @@ int cc_db_debug_passes(cc_db *db, cc_pass_dbg_t *h_out, int cap, int *n_out) {
   return CC_OK;
 }
 
+// include/cont2_amd_cands.h: query 0 of lane 0 is the hint flow's; cc_k_merge left the candidates in first-appearance order in
+// d_cands, their number in d_qstate, and the correlation problem of a candidate that went on at d_prob[gmm_idx]
+int cc_db_debug_cands(cc_db *db, cc_cand_dbg_t *h_out, int cap, int *n_out) {
+  if (!db || !h_out || cap < 0 || !n_out) return set_err(CC_EINVAL, "cc_db_debug_cands: bad argument");
+  HIPCHK(hipSetDevice(db->device));
+  DB_DRAIN(db);
+  cc_qlane &ln = db->lane[0];
+  cc_qstate st;
+  HIPCHK(hipMemcpy(&st, ln.d_qstate, sizeof(st), hipMemcpyDeviceToHost));
+  int n = st.n_cand < 0 ? 0 : (st.n_cand > CC_MAXCAND ? CC_MAXCAND : st.n_cand);
+  if (n > cap) n = cap;
+  std::vector<cc_cand_out> cd(n > 0 ? n : 1);
+  if (n > 0) HIPCHK(hipMemcpy(cd.data(), ln.d_cands, sizeof(cc_cand_out) * (size_t)n, hipMemcpyDeviceToHost));
+  for (int k = 0; k < n; k++) {
+    cc_cand_dbg_t o;
+    o.cand_gidx = cd[k].gidx;
+    o.n_props = cd[k].nprops;
+    o.refined = cd[k].gmm_idx >= 0 ? 1 : 0;
+    o.pad_ = 0;
+    o.tf_init[0] = o.tf_init[1] = o.tf_init[2] = 0.0;
+    if (cd[k].gmm_idx >= 0 && cd[k].gmm_idx < ln.prob_cap) {
+      cc_gmm_problem pb;
+      HIPCHK(hipMemcpy(&pb, ln.d_prob + cd[k].gmm_idx, sizeof(pb), hipMemcpyDeviceToHost));
+      for (int j = 0; j < 3; j++) o.tf_init[j] = pb.tf[j];
+    }
+    h_out[k] = o;
+  }
+  *n_out = n;
+  return CC_OK;
+}
+
 static int check_hints_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                  const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
                                  const cc_rank_out_t *rank,

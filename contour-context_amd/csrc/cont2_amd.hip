@@ -25,6 +25,7 @@
 #include "../../include/cont2_amd_filter.h"
 #include "../../include/cont2_amd_coords.h"
 #include "../../include/cont2_amd_paths.h"
+#include "../../include/cont2_amd_cands.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
 #include "k_image.h"

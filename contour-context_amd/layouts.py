@@ -155,6 +155,9 @@ def pack_mask_rows(allowed, n_db=None, row_words=None):
 
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
+# cc_cand_dbg_t (include/cont2_amd_cands.h): a candidate of the last hint call as the merge left it
+cand_dbg_dt = np.dtype([("cand_gidx", "<i4"), ("n_props", "<i4"), ("refined", "<i4"), ("pad_", "<i4"), ("tf_init", "<f8", (3,))], align=True)
+assert cand_dbg_dt.itemsize == 40
 
 
 class ManagerCfg(C.Structure):

@@ -445,6 +445,66 @@ void orc_check_hints(void *tgt, void **cands, int n_cands, const int32_t *hints 
     res->tf[2] = std::atan2(tfs[0](1, 0), tfs[0](0, 0));
   }
 }
+// The candidates of the hint flow as the merge leaves them, for tests/constell_cases.py: checkCandWithHint for every hint in the
+// given order, then per candidate in candidates_ order (first appearance) a record of 40 int32 / 12 doubles:
+//   ci[0] index into cands[], ci[1] proposals, ci[2] idx_sel of tidyUpCandidates (first proposal with the most votes),
+//   ci[3] 1 if the candidate survives tidyUpCandidates, ci[4 + p] vote_cnt, ci[8 + p] constell_.size() of proposal p;
+//   cf[p] area_perc_ of proposal p (tidyUpCandidates' expression); cd[3 p ..] = x, y, theta of T_delta_ of proposal p.
+// Returns the number of candidates (at most cap are written).
+int orc_check_hints_cands(void *tgt, void **cands, int n_cands, const int32_t *hints /*[n][4]*/, int n_hints, const cc_sim_cfg_t *sim,
+                          const cc_score_t *lb, const cc_score_t *ub, int cap, int32_t *ci /*[cap][12]*/, float *cf /*[cap][4]*/,
+                          double *cd /*[cap][12]*/) {
+  ContourSimThresConfig cs;
+  cs.ta_cell_cnt = sim->ta_cell_cnt;
+  cs.tp_cell_cnt = sim->tp_cell_cnt;
+  cs.tp_eigval = sim->tp_eigval;
+  cs.ta_h_bar = sim->ta_h_bar;
+  cs.ta_rcom = sim->ta_rcom;
+  cs.tp_rcom = sim->tp_rcom;
+  auto tcm = ((ScanH *)tgt)->cm;
+  CandidateManager mng(tcm, toScore(lb), toScore(ub));
+  for (int i = 0; i < n_hints; i++) {
+    const int32_t *h = hints + 4 * i;
+    mng.checkCandWithHint(((ScanH *)cands[h[0]])->cm, ConstellationPair(h[1], h[2], h[3]), cs);
+  }
+  const int n = (int)mng.candidates_.size();
+  std::vector<const ContourManager *> who(n);
+  for (int k = 0; k < n; k++) {
+    const auto &c = mng.candidates_[k];
+    who[k] = c.cm_cand_.get();
+    if (k >= cap) continue;
+    int32_t *oi = ci + 12 * k;
+    float *of = cf + 4 * k;
+    double *od = cd + 12 * k;
+    for (int j = 0; j < 12; j++) oi[j] = 0, od[j] = 0;
+    for (int j = 0; j < 4; j++) of[j] = 0;
+    oi[0] = -1;
+    for (int j = 0; j < n_cands; j++)
+      if (((ScanH *)cands[j])->cm.get() == who[k]) oi[0] = j;
+    oi[1] = (int)c.anch_props_.size();
+    int idx_sel = 0;
+    for (size_t p = 0; p < c.anch_props_.size() && p < 4; p++) {
+      const auto &pr = c.anch_props_[p];
+      std::vector<float> lev_perc(tcm->getConfig().lv_grads_.size(), 0);
+      for (const auto &e : pr.constell_) lev_perc[e.first.level] += e.second;
+      float perc = 0;
+      for (int j = 0; j < NUM_BIN_KEY_LAYER; j++) perc += LAYER_AREA_WEIGHTS[j] * lev_perc[DIST_BIN_LAYERS[j]];
+      of[p] = perc;
+      if (pr.vote_cnt_ > c.anch_props_[idx_sel].vote_cnt_) idx_sel = (int)p;
+      oi[4 + p] = pr.vote_cnt_;
+      oi[8 + p] = (int)pr.constell_.size();
+      od[3 * p] = pr.T_delta_(0, 2);
+      od[3 * p + 1] = pr.T_delta_(1, 2);
+      od[3 * p + 2] = std::atan2(pr.T_delta_(1, 0), pr.T_delta_(0, 0));
+    }
+    oi[2] = idx_sel;
+  }
+  mng.tidyUpCandidates();
+  for (const auto &c : mng.candidates_)
+    for (int k = 0; k < n && k < cap; k++)
+      if (who[k] == c.cm_cand_.get()) ci[12 * k + 3] = 1;
+  return n;
+}
 // GMM: init correlation at T_init and the refined (correlation, x, y, theta) after <=10 L-BFGS iterations
 void orc_gmm(void *src, void *tgt, const double tf_init[3], double *corr_init, double *corr_opt, double tf_opt[3],
              int32_t *iters) {

@@ -65,6 +65,8 @@ def lib():
         _lib.orc_check_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
         _lib.orc_check_hints.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_void_p, C.c_void_p]
+        _lib.orc_check_hints_cands.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.orc_gmm.argtypes = [C.c_void_p] * 7
         _lib.orc_gmm_eval.argtypes = [C.c_void_p] * 7
         _lib.orc_gmm_trace.argtypes = [C.c_void_p] * 5
@@ -237,6 +239,29 @@ def check_hints(tgt, cands, hints, sim=None, lb=None, ub=None, max_fine_opt=10):
     lib().orc_check_hints(tgt.h, hs, len(cands), _p(hints), len(hints), C.addressof(sim), C.addressof(lb), C.addressof(ub),
                           int(max_fine_opt), _p(res), _p(sc))
     return res[0], sc
+
+
+CAND_DT = np.dtype([("cand", "<i4"), ("n_props", "<i4"), ("idx_sel", "<i4"), ("survived", "<i4"), ("vote_cnt", "<i4", (4,)),
+                    ("n_constell", "<i4", (4,)), ("area_perc", "<f4", (4,)), ("tf", "<f8", (4, 3))])
+
+
+def check_hints_cands(tgt, cands, hints, sim=None, lb=None, ub=None):
+    """the candidates of check_hints() as the merge leaves them, in candidates_ order (first appearance): array of CAND_DT -- the
+    index into cands, the proposals (vote_cnt, T_delta as x, y, theta, constellation size, area_perc), tidyUpCandidates' idx_sel
+    and whether the candidate survives it"""
+    sim = sim or L.default_db_cfg().cont_sim
+    if lb is None:
+        lb, ub = L.default_thresholds()
+    hints = np.ascontiguousarray(hints, np.int32).reshape(-1, 4)
+    hs = (C.c_void_p * len(cands))(*[c.h for c in cands])
+    cap = max(len(cands), 1)
+    ci, cf, cd = np.zeros((cap, 12), np.int32), np.zeros((cap, 4), np.float32), np.zeros((cap, 12), np.float64)
+    n = lib().orc_check_hints_cands(tgt.h, hs, len(cands), _p(hints), len(hints), C.addressof(sim), C.addressof(lb), C.addressof(ub),
+                                    cap, _p(ci), _p(cf), _p(cd))
+    out = np.zeros(n, CAND_DT)
+    out["cand"], out["n_props"], out["idx_sel"], out["survived"] = ci[:n, 0], ci[:n, 1], ci[:n, 2], ci[:n, 3]
+    out["vote_cnt"], out["n_constell"], out["area_perc"], out["tf"] = ci[:n, 4:8], ci[:n, 8:12], cf[:n], cd[:n].reshape(n, 4, 3)
+    return out
 
 
 def gmm(src, tgt, tf_init):
