@@ -150,7 +150,7 @@ def _keep_filter(keep, motion):
     if not isinstance(keep, PointFilter):
         raise ValueError("keep must be a PointFilter (PointFilter.classes / PointFilter.range)")
     if motion is not None:
-        raise ValueError("keep and motion exclude each other")
+        raise ValueError("keep together with motion is Context.ingest_rig's (one SegMotion segment per scan, its keep_offset the word's offset)")
     return keep._c
 
 
@@ -294,6 +294,75 @@ def _segment_table(scans, device):
     return arr, scan_segs
 
 
+class SegMotion:
+    """The motion mode of a segment of Context.ingest_rig (include/cont2_amd_rig.h): the record's 4-byte time word at byte
+    `time_offset` ("f32" | "u32"), t_begin (for "u32" an integer: its bits are passed on) and scale (bins per time unit), and the
+    segment's slice [knot0, knot0 + n_knots) of its scan's knot pool: the record is moved by knot
+    knot0 + trunc(clamp((t - t_begin) * scale, 0, n_knots - 1))."""
+
+    def __init__(self, time_offset, type, t_begin, scale, knot0, n_knots):
+        if type not in TIME_TYPES:
+            raise ValueError("unknown time type %r (known: %s)" % (type, sorted(TIME_TYPES)))
+        self.time_offset, self.type, self.scale, self.knot0, self.n_knots = int(time_offset), type, float(scale), int(knot0), int(n_knots)
+        tb = np.asarray(t_begin)
+        self.t_begin = (tb.astype(np.uint32) if type == "u32" and tb.dtype.kind in "ui" else tb.astype(np.float32)).reshape(1).tobytes()   # the slot's 4 bytes
+
+
+def _rig_table(scans, device):
+    """[[(points, layout, mode, keep_offset), ...], ...] -> (array of L.RigSegment, int32 [n + 1] first-segment indices); points and
+    layout as _segment_table takes them; mode: None, a 3 x 4 / 12-value matrix or a SegMotion; keep_offset: the byte offset of the
+    segment's filter word, or None."""
+    n_seg = sum(len(sc) for sc in scans)
+    arr = (L.RigSegment * max(n_seg, 1))()
+    scan_segs = np.zeros(len(scans) + 1, np.int32)
+    k = 0
+    for i, sc in enumerate(scans):
+        for (pts, layout, mode, keep_offset) in sc:
+            g = arr[k]
+            lay = _point_layout(layout)
+            stride = 16 if lay is None else lay.stride_bytes
+            if lay is not None:
+                g.layout = lay
+            if pts is not None:
+                if device:
+                    assert pts.is_cuda and pts.is_contiguous()
+                    nbytes, ptr = pts.numel() * pts.element_size(), pts.data_ptr()
+                else:
+                    assert pts.flags["C_CONTIGUOUS"]
+                    nbytes, ptr = pts.nbytes, pts.ctypes.data
+                if stride <= 0 or nbytes % stride != 0:
+                    raise ValueError("segment %d of scan %d: %d bytes are not whole records of %d bytes" % (k - scan_segs[i], i, nbytes, stride))
+                g.n_points = nbytes // stride
+                g.points = ptr if nbytes else None
+            if isinstance(mode, SegMotion):
+                g.mode = L.RIG_MOTION
+                g.time_offset, g.time_type, g.scale, g.knot0, g.n_knots = mode.time_offset, TIME_TYPES[mode.type], mode.scale, mode.knot0, mode.n_knots
+                C.memmove(C.addressof(g) + L.RigSegment.t_begin.offset, mode.t_begin, 4)   # (a u32's bits, untouched by a float conversion)
+            elif mode is not None:
+                tf = np.asarray(mode, np.float32).reshape(-1)
+                if tf.shape != (12,):
+                    raise ValueError("a segment's mode is None, a 3 x 4 matrix (12 values) or a SegMotion")
+                g.mode = L.RIG_TF
+                g.tf[:] = tf.tolist()
+            g.filter_offset = -1 if keep_offset is None else int(keep_offset)
+            k += 1
+        scan_segs[i + 1] = k
+    return arr, scan_segs
+
+
+def _rig_args(knots, keep, n):
+    """knots [n, P, 3, 4] / [n, P, 12] or None, keep: a PointFilter or None -> (f32 [n, P * 12] or None, P, L.PointFilterC or None)"""
+    kn, n_pool = None, 0
+    if knots is not None:
+        kn = np.ascontiguousarray(np.asarray(knots, np.float32).reshape(len(knots), -1))
+        if kn.shape[0] != n or kn.shape[1] == 0 or kn.shape[1] % 12 != 0:
+            raise ValueError("knots must hold a pool of P 3 x 4 matrices per scan: [%d, P, 3, 4] or [%d, P, 12], got %s" % (n, n, kn.shape))
+        n_pool = kn.shape[1] // 12
+    if keep is not None and not isinstance(keep, PointFilter):
+        raise ValueError("keep must be a PointFilter (PointFilter.classes / PointFilter.range)")
+    return kn, n_pool, (None if keep is None else keep._c)
+
+
 def comm_from_env():
     """cc_comm_create_from_env: (handle, rank, world) from RANK / WORLD_SIZE / LOCAL_RANK / MASTER_PORT (one node)."""
     h, r, w = C.c_void_p(), C.c_int(), C.c_int()
@@ -350,7 +419,8 @@ class Context:
         moved by the knot matrix of its time bin (cc_ingest_points_motion): knots [n, K, 3, 4] or [n, K, 12], t_begin [n] and
         scale [n] (bins per time unit), all host; bin = trunc(clamp((t - t_begin) * scale, 0, K - 1)).  Not together with tf.
         keep: a PointFilter -- records are dropped by a label / ring / intensity word of their own while they are rasterised
-        (cc_ingest_points_filtered): the result is that of the kept records alone.  With layout and tf, not with motion.
+        (cc_ingest_points_filtered): the result is that of the kept records alone.  With layout and tf; together with motion it is
+        ingest_rig()'s (one SegMotion segment per scan).
         Returns a torch uint8 CUDA tensor [n, DESC_BYTES] (array of cc_scan_desc_t) (+ debug dict)."""
         import torch
         if motion is None and (knots is not None or t_begin is not None or scale is not None):
@@ -567,6 +637,44 @@ class Context:
         out = np.zeros(len(scans), L.scan_desc_dt)
         _chk(lib().cc_ingest_segments_host(self.h, C.addressof(arr), scan_segs.ctypes.data, len(scans), out.ctypes.data, None),
              "cc_ingest_segments_host")
+        return out
+
+    def ingest_rig(self, scans, knots=None, keep=None, out=None, debug=False):
+        """A rig's sensors de-skewed, filtered and joined in one sweep (cc_ingest_rig, include/cont2_amd_rig.h): scans =
+        [[(points, layout, mode, keep_offset), ...], ...], at most RIG_SEG_MAX segments per scan.  points, layout: as for
+        ingest_segments(); mode: None (the points as they are), a 3 x 4 / 12-value matrix, or a SegMotion(time_offset, type, t_begin,
+        scale, knot0, n_knots) -- the record is de-skewed by its time word with the segment's slice of the scan's knot pool;
+        keep_offset: the byte offset of the segment's filter word, or None for a segment that is not filtered.  knots: the pools,
+        [n, P, 3, 4] or [n, P, 12] on the host (None: no segment is in motion mode); keep: ONE PointFilter for all segments (its own
+        offset is not read).  The result is ingest()'s for the moved records of every scan in the order given, the dropped ones left
+        out.  Returns a torch uint8 CUDA tensor [n, DESC_BYTES] (+ debug dict)."""
+        import torch
+        arr, scan_segs = _rig_table(scans, device=True)
+        n = len(scans)
+        kn, n_pool, flt = _rig_args(knots, keep, n)
+        dev = next((p.device for sc in scans for (p, _l, _m, _k) in sc if p is not None), torch.device("cuda", self.device))
+        if out is None:
+            out = torch.empty((n, DESC_BYTES), dtype=torch.uint8, device=dev)
+        dbg_p, dbg = None, None
+        if debug:
+            dbg = {"bev": torch.empty((n, self.n_cell), dtype=torch.float32, device=dev),
+                   "pix_rc": torch.empty((n, self.n_cell, 2), dtype=torch.float32, device=dev),
+                   "labels": torch.empty((n, L.NLEV, self.n_cell), dtype=torch.int16, device=dev)}
+            st = IngestDebug(dbg["bev"].data_ptr(), dbg["pix_rc"].data_ptr(), dbg["labels"].data_ptr())
+            dbg_p = C.addressof(st)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _chk(lib().cc_ingest_rig(self.h, C.addressof(arr), scan_segs.ctypes.data, n, kn.ctypes.data if kn is not None else None, n_pool,
+                                 C.addressof(flt) if flt is not None else None, out.data_ptr(), dbg_p, stream), "cc_ingest_rig")
+        return (out, dbg) if debug else out
+
+    def ingest_rig_host(self, scans, knots=None, keep=None):
+        """ingest_rig() from host records (numpy arrays of any dtype holding the records as they are): host descriptors out."""
+        arr, scan_segs = _rig_table(scans, device=False)
+        n = len(scans)
+        kn, n_pool, flt = _rig_args(knots, keep, n)
+        out = np.zeros(n, L.scan_desc_dt)
+        _chk(lib().cc_ingest_rig_host(self.h, C.addressof(arr), scan_segs.ctypes.data, n, kn.ctypes.data if kn is not None else None, n_pool,
+                                      C.addressof(flt) if flt is not None else None, out.ctypes.data, None), "cc_ingest_rig_host")
         return out
 
     def pack(self, desc):

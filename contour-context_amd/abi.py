@@ -162,6 +162,11 @@ I cc_ingest_path_counts PP
     "cont2_amd_cands.h": """
 I cc_db_debug_cands PPIP
 """,
+    "cont2_amd_rig.h": """
+I cc_ingest_rig PPPIPIPPPP
+I cc_ingest_rig_host PPPIPIPPP
+I cc_scan_ingest_rig PPIPIPIP
+""",
 }
 ADDONS = {hdr: _table(spec) for hdr, spec in _ADDON_SPEC.items()}
 

@@ -24,6 +24,7 @@
 #include "../../include/cont2_amd_images.h"
 #include "../../include/cont2_amd_filter.h"
 #include "../../include/cont2_amd_coords.h"
+#include "../../include/cont2_amd_rig.h"
 #include "../../include/cont2_amd_paths.h"
 #include "../../include/cont2_amd_cands.h"
 #include "cc_hostcfg.h"
@@ -86,6 +87,7 @@ struct cc_ctx {
     float *d_mot = nullptr;  // a chunk's [nb][2] times, then its [nb][K][12] knots (cc_ingest_points_motion); allocated at first use
     unsigned *d_flt = nullptr;  // a call's class table (cc_ingest_points_filtered): CC_K1_FLT_TAB_WORDS words; allocated at first use
     double *d_org = nullptr;  // a chunk's [nb][3] origins (cc_ingest_coords); allocated at first use
+    char *d_rig = nullptr;  // a chunk's tables of a rig call (cc_ingest_rig): scan_seg, the cc_k1_rseg entries, the knot pools, the class table; allocated at first use
     char *d_seg = nullptr;  // a chunk's segment table (cc_ingest_segments): int scan_seg[cap + 1], then up to cap * CC_SEG_MAX cc_k1_seg; allocated at first use
     // the slow path of K2 (scans with more than CC_MAXC components on a level): queue filled by the fast launch, a few
     // workgroups with CC_NC_BIG-sized tables in global memory
@@ -209,6 +211,7 @@ static void scratch_free(cc_ctx::Scratch &S) {
   hipFree(S.d_offsets);
   hipFree(S.d_tf);
   hipFree(S.d_seg);
+  hipFree(S.d_rig);
   hipFree(S.d_mot);
   hipFree(S.d_flt);
   hipFree(S.d_org);
@@ -231,7 +234,7 @@ template <typename... SRC>
 struct k1_list {};
 typedef k1_list<cc_src_kitti, cc_src_rec<12>, cc_src_rec<16>, cc_src_rec<0>, cc_src_mot<16>, cc_src_mot<32>, cc_src_mot<0>, cc_src_seg, cc_src_rng<CC_K1_WORD_U16>,
                 cc_src_rng<CC_K1_WORD_U32>, cc_src_rng<CC_K1_WORD_F32>, cc_src_flt<CC_K1_FLT_CLASS>, cc_src_flt<CC_K1_FLT_RANGE>, cc_src_coord<CC_K1_COORD_F32>,
-                cc_src_coord<CC_K1_COORD_F64>, cc_src_coord<CC_K1_COORD_I32>>
+                cc_src_coord<CC_K1_COORD_F64>, cc_src_coord<CC_K1_COORD_I32>, cc_src_rig>
     k1_sources;
 template <typename S, typename... SRC>
 static constexpr bool k1_listed(k1_list<SRC...>) {
@@ -552,7 +555,7 @@ static const cc_point_layout_t CC_LAYOUT_KITTI = {16, 0};
 // the caller's host addresses and put the device ones in (k1_rebase) before they pass it on.  A checked SEGMENTS source points into
 // its own tables: it is handed on by reference, never copied.
 struct k1_source {
-  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES, FILTERED, COORDS } kind;
+  enum kind_t { POINTS, MOTION, RANGES, SEGMENTS, IMAGES, FILTERED, COORDS, RIG } kind;
   const void *points = nullptr;              // POINTS, MOTION: the records; RANGES: the range words (a "point" is a pixel); IMAGES: the heights (a "point" is a cell)
   cc_point_layout_t lay = {16, 0};           // POINTS, MOTION, FILTERED (the caller's, or {16, 0})
   const float *h_tf = nullptr;               // POINTS, FILTERED, COORDS: [n_scans][12] or nullptr
@@ -569,6 +572,10 @@ struct k1_source {
   cc_coord_src_t crd = {};                   // COORDS: the three streams of the call's point 0, stride, type, scales
   const double *h_origin = nullptr;          //   [n_scans][3] or nullptr
   bool missing = false;                      // MOTION, FILTERED, COORDS: the caller's struct was NULL (k1_check refuses it in its place)
+  const cc_rig_segment_t *h_rsegs = nullptr;  // RIG: the caller's entries (once checked: from the call's first segment on); scan_segs, seg_scan, own_off as SEGMENTS';
+  int n_pool = 0;                            //   h_knots: [n_scans][n_pool][12] or nullptr; flt: the rule (has_flt: the caller brought one)
+  bool has_flt = false;
+  std::vector<cc_k1_rseg> rig_tab;           //   rig_check's table
   std::vector<cc_k1_seg> seg_tab;            // SEGMENTS: segs_check's table,
   std::vector<int32_t> seg_scan;             //   the scans' first segments in it,
   std::vector<int64_t> own_off;              //   and the scans' point totals as offsets; RANGES, IMAGES: the pixels' / cells' offsets (k1_check)
@@ -600,6 +607,16 @@ static k1_source k1_filtered(const void *points, const cc_point_layout_t *layout
   k1_source s = {k1_source::FILTERED, points, layout ? *layout : CC_LAYOUT_KITTI, h_tf};
   if (flt) s.flt = *flt;
   s.missing = !flt;
+  return s;
+}
+static k1_source k1_rig(const cc_rig_segment_t *h_segs, const int32_t *h_scan_segs, const float *h_knots, int n_pool, const cc_point_filter_t *flt) {
+  k1_source s = {k1_source::RIG};
+  s.h_rsegs = h_segs;
+  s.scan_segs = h_scan_segs;
+  s.h_knots = h_knots;
+  s.n_pool = h_knots ? n_pool : 0;
+  if (flt) s.flt = *flt;
+  s.has_flt = flt != nullptr;
   return s;
 }
 static k1_source k1_coords(const cc_coord_src_t *crd, const double *h_origin, const float *h_tf) {
@@ -736,6 +753,81 @@ static int segs_check(const cc_point_segment_t *h_segs, const int32_t *h_scan_se
   }
   return CC_OK;
 }
+static_assert(CC_K1_RIG_SEG_MAX == CC_RIG_SEG_MAX && (int)CC_K1_RIG_NONE == (int)CC_RIG_NONE && (int)CC_K1_RIG_TF == (int)CC_RIG_TF &&
+                  (int)CC_K1_RIG_MOTION == (int)CC_RIG_MOTION,
+              "k_rasterize.h's rig table and modes are the header's");
+// Everything the header promises to check about a cc_*_rig call, before anything is queued or read: per segment what segs_check,
+// motion_check and filter_check refuse (against the segment's own layout), then the rig's own rules.  tab, q_off: as segs_check's.
+// What the kernels take of the rule -- the class rule's word position and width folded into a shift per segment and one mask, as
+// stage_filter does it -- goes into the entries here.
+static int rig_check(const k1_source &src, int n_scans, const char *who, std::vector<cc_k1_rseg> &tab, std::vector<int64_t> &q_off) {
+  const cc_rig_segment_t *h_segs = src.h_rsegs;
+  const int32_t *h_scan_segs = src.scan_segs;
+  if (src.h_knots && (src.n_pool < 1 || src.n_pool > CC_MOTION_KNOTS_MAX)) return set_err(CC_EINVAL, CC_WHO(": n_pool must be 1 .. CC_MOTION_KNOTS_MAX"));
+  q_off.assign(1, 0);
+  for (int i = 0; i < n_scans; i++) {
+    const int64_t ns = (int64_t)h_scan_segs[i + 1] - h_scan_segs[i];
+    if (h_scan_segs[i] < 0 || ns < 1 || ns > CC_RIG_SEG_MAX) return set_err(CC_EINVAL, CC_WHO(": a scan has 1 .. CC_RIG_SEG_MAX segments"));
+    int64_t total = 0;
+    for (int k = h_scan_segs[i]; k < h_scan_segs[i + 1]; k++) {
+      const cc_rig_segment_t &g = h_segs[k];
+      if (g.n_points < 0 || g.n_points >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": a segment's n_points is negative or >= 2^21"));
+      if (g.n_points > 0 && !g.points) return set_err(CC_EINVAL, CC_WHO(": a segment with points has a NULL pointer"));
+      cc_point_layout_t lay;
+      const bool dflt = g.layout.stride_bytes == 0 && g.layout.xyz_offset == 0;
+      int rc = point_layout(dflt ? nullptr : &g.layout, g.n_points > 0 ? g.points : nullptr, who, &lay);
+      if (rc != CC_OK) return rc;
+      cc_k1_rseg e = {};
+      e.base = (const char *)g.points + lay.xyz_offset;
+      e.stride = (unsigned)lay.stride_bytes;
+      e.first = (int)total;
+      e.n = (int)g.n_points;
+      if (g.mode == CC_RIG_TF) {
+        e.flags = CC_K1_RIG_TF;
+        for (int m = 0; m < 12; m++) e.m[m] = g.tf[m];
+      } else if (g.mode == CC_RIG_MOTION) {
+        if (!src.h_knots) return set_err(CC_EINVAL, CC_WHO(": a segment in motion mode needs h_knots"));
+        const cc_point_motion_t mo = {g.time_offset, g.time_type, g.n_knots, 0};
+        const float tm[2] = {g.t_begin, g.scale};
+        rc = motion_check(lay, &mo, tm, src.h_knots, 1, who);
+        if (rc != CC_OK) return rc;
+        if (g.knot0 < 0 || (int64_t)g.knot0 + g.n_knots > src.n_pool) return set_err(CC_EINVAL, CC_WHO(": a segment's slice [knot0, knot0 + n_knots) lies outside the pool"));
+        e.flags = CC_K1_RIG_MOTION | (g.time_type == CC_TIME_U32 ? CC_K1_RIG_TIME_U32 : 0u);
+        e.t_off = g.time_offset - lay.xyz_offset;
+        e.m[0] = g.t_begin;
+        e.m[1] = g.scale;
+        memcpy(&e.m[2], &g.knot0, 4);
+        memcpy(&e.m[3], &g.n_knots, 4);
+      } else if (g.mode != CC_RIG_NONE) {
+        return set_err(CC_EINVAL, CC_WHO(": a segment's mode must be CC_RIG_NONE, CC_RIG_TF or CC_RIG_MOTION"));
+      }
+      if (g.filter_offset < -1) return set_err(CC_EINVAL, CC_WHO(": a segment's filter_offset must be -1 or an offset inside the record"));
+      if (g.filter_offset >= 0) {
+        if (!src.has_flt) return set_err(CC_EINVAL, CC_WHO(": a segment with a filter word needs the filter"));
+        cc_point_filter_t f = src.flt;
+        f.offset = g.filter_offset;
+        rc = filter_check(lay, &f, who);
+        if (rc != CC_OK) return rc;
+        e.flags |= CC_K1_RIG_FILTERED;
+        e.w_off = (f.offset & ~3) - lay.xyz_offset;
+        if (f.type != CC_FILTER_F32) e.flags |= (unsigned)(8 * (f.offset & 3) + f.shift) << CC_K1_RIG_SHIFT_POS;
+      }
+      tab.push_back(e);
+      total += g.n_points;
+      if (total >= (1 << CC_K1_IDX_BITS)) return set_err(CC_EINVAL, CC_WHO(": scan with >= 2^21 points"));
+    }
+    if (!(total > 10)) return set_err(CC_EINVAL, CC_WHO(": scan with <= 10 points (CHECK_GT(size, 10), contour_mng.h:507)"));
+    q_off.push_back(q_off.back() + total);
+  }
+  if (src.has_flt) {  // the rule itself, also when no segment of this call uses it (its offset is not read: a word that passes every layout)
+    cc_point_filter_t f = src.flt;
+    f.offset = 0;
+    const cc_point_layout_t wide = {CC_POINT_STRIDE_MAX, CC_POINT_STRIDE_MAX - 12};
+    const int rc = filter_check(wide, &f, who);
+    if (rc != CC_OK) return rc;
+  }
+  return CC_OK;
+}
 
 // The three forms of every family's entry points: the records on the device, a batch of host records (*_host), one scan of the
 // per-scan loop (cc_scan_ingest*: n_scans = 1, h_offsets = {0, n_points}).
@@ -780,6 +872,14 @@ static int k1_check(cc_ctx *c, k1_source &src, k1_form form, const int64_t *h_of
       for (int i = 0; i <= n_scans; i++) src.seg_scan.push_back(src.scan_segs[i] - src.scan_segs[0]);  // (seg_tab begins with the call's first segment)
       src.h_segs += src.scan_segs[0];
       src.segs = src.seg_tab.data();
+      src.scan_segs = src.seg_scan.data();
+      return CC_OK;
+    case k1_source::RIG:
+      if (!c || !src.h_rsegs || !src.scan_segs || !out || few) return set_err(CC_EINVAL, CC_WHO(": bad argument"));
+      rc = rig_check(src, n_scans, who, src.rig_tab, src.own_off);
+      if (rc != CC_OK) return rc;
+      for (int i = 0; i <= n_scans; i++) src.seg_scan.push_back(src.scan_segs[i] - src.scan_segs[0]);  // (rig_tab begins with the call's first segment)
+      src.h_rsegs += src.scan_segs[0];
       src.scan_segs = src.seg_scan.data();
       return CC_OK;
   }
@@ -863,11 +963,20 @@ static k1_host_plan k1_plan(const k1_source &src, k1_form form, int64_t first, i
         p.total += ((size_t)g.n * g.stride + 15) & ~(size_t)15;
       }
       break;
+    case k1_source::RIG:  // as SEGMENTS
+      for (size_t k = 0; k < src.rig_tab.size(); k++) {
+        const cc_k1_rseg &g = src.rig_tab[k];
+        if (g.n > 0) p.add(src.h_rsegs[k].points, (size_t)g.n * g.stride, p.total);
+        p.seg_base.push_back(p.total + (size_t)(g.base - (const char *)src.h_rsegs[k].points));
+        p.total += ((size_t)g.n * g.stride + 15) & ~(size_t)15;
+      }
+      break;
   }
   // The rows of a descriptor that its counts do not cover are not written by the kernels, and a pool slot holds an earlier scan's rows:
   // where a form zeroes, its bytes are those of the family's device call into zeroed memory.
   switch (src.kind) {
     case k1_source::SEGMENTS:
+    case k1_source::RIG:
     case k1_source::IMAGES:
     case k1_source::COORDS: p.zero_out = true; break;
     case k1_source::FILTERED: p.zero_out = form == K1_HOST; break;  // (the batch form as cc_ingest_images_host does; the per-scan form as POINTS')
@@ -887,7 +996,10 @@ static void k1_rebase(k1_source &src, const k1_host_plan &plan, const void *d_ba
     src.crd.y = d + plan.crd[1];
     src.crd.z = d + plan.crd[2];
   }
-  for (size_t k = 0; k < plan.seg_base.size(); k++) src.seg_tab[k].base = d + plan.seg_base[k];
+  for (size_t k = 0; k < plan.seg_base.size(); k++) {
+    if (src.kind == k1_source::RIG) src.rig_tab[k].base = d + plan.seg_base[k];
+    else src.seg_tab[k].base = d + plan.seg_base[k];
+  }
 }
 
 // `bytes` of pinned memory in slot `slot` of the staging ring (the buffer the chunk's segment table, times and knots ride in), grown
@@ -914,6 +1026,7 @@ struct k1_staged {
   cc_k1_range rng = {};         // RANGES
   cc_k1_segs segs = {};         // SEGMENTS
   cc_k1_filter flt = {};        // FILTERED
+  cc_k1_rig rig = {};           // RIG
   const double *d_org = nullptr;  // COORDS: the chunk's origins, or nullptr
 };
 // What the kernels take of a checked filter.  The class rule reads the aligned dword that holds the word: the word's byte position
@@ -972,6 +1085,51 @@ static int stage_segments(cc_ctx *c, cc_ctx::Scratch &S, int slot, const k1_sour
   d_segs.seg = (const cc_k1_seg *)(S.d_seg + ent_off);
   return CC_OK;
 }
+// A rig chunk's tables to S.d_rig, in the same slot of the ring and in ONE copy: scan_seg[nb + 1] relative to the chunk's first segment,
+// the entries, the chunk's knot pools, the rule's class table (stage_filter's: keep_other as bit n_classes, zeros behind it).
+static int stage_rig(cc_ctx *c, cc_ctx::Scratch &S, int slot, const k1_source &src, int b0, int nb, hipStream_t stream, cc_k1_rig &kr) {
+  const int s0 = src.scan_segs[b0], ns = src.scan_segs[b0 + nb] - s0;
+  const bool cls = src.has_flt && src.flt.type != CC_FILTER_F32;
+  const size_t pool = sizeof(float) * 12 * (size_t)src.n_pool, tabw = sizeof(unsigned) * CC_K1_FLT_TAB_WORDS;
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t ent_off = up16(sizeof(int) * (size_t)(nb + 1)), kn_off = ent_off + sizeof(cc_k1_rseg) * (size_t)ns, bit_off = up16(kn_off + pool * (size_t)nb),
+               bytes = bit_off + (cls ? tabw : 0);
+  if (!S.d_rig)
+    HIPCHK(hipMalloc(&S.d_rig, up16(sizeof(int) * (size_t)(S.cap + 1)) + (sizeof(cc_k1_rseg) * CC_RIG_SEG_MAX + sizeof(float) * 12 * CC_MOTION_KNOTS_MAX) * (size_t)S.cap + 16 + tabw));
+  if (!slot_stage(c, slot, bytes)) return CC_EHIP;
+  char *h = c->h_seg[slot];
+  int *ss = (int *)h;
+  for (int i = 0; i <= nb; i++) ss[i] = src.scan_segs[b0 + i] - s0;
+  memcpy(h + ent_off, src.rig_tab.data() + s0, sizeof(cc_k1_rseg) * (size_t)ns);
+  if (src.h_knots) memcpy(h + kn_off, src.h_knots + (size_t)b0 * 12 * (size_t)src.n_pool, pool * (size_t)nb);
+  kr = cc_k1_rig();
+  kr.kind = -1;
+  if (src.has_flt) {
+    const cc_point_filter_t &f = src.flt;
+    kr.kind = cls ? CC_K1_FLT_CLASS : CC_K1_FLT_RANGE;
+    kr.lo = f.lo;
+    kr.hi = f.hi;
+    if (cls) {
+      const int size = filter_bytes(f.type);
+      const unsigned typemask = size == 4 ? 0xFFFFFFFFu : ((1u << (8 * size)) - 1u);
+      kr.mask = f.mask & (typemask >> f.shift);
+      kr.n_classes = (unsigned)f.n_classes;
+      unsigned *tab = (unsigned *)(h + bit_off);
+      const int nw = (f.n_classes + 31) / 32;
+      memset(tab, 0, tabw);
+      memcpy(tab, f.keep_bits, sizeof(unsigned) * (size_t)nw);
+      if (f.n_classes % 32) tab[nw - 1] &= (1u << (f.n_classes % 32)) - 1u;  // (the caller's bits behind n_classes are not part of the table)
+      if (f.keep_other) tab[f.n_classes >> 5] |= 1u << (f.n_classes & 31);
+      kr.bits = (const unsigned *)(S.d_rig + bit_off);
+    }
+  }
+  HIPCHK(hipMemcpyAsync(S.d_rig, h, bytes, hipMemcpyHostToDevice, stream));
+  kr.scan_seg = (const int *)S.d_rig;
+  kr.seg = (const cc_k1_rseg *)(S.d_rig + ent_off);
+  kr.knots = src.h_knots ? (const float *)(S.d_rig + kn_off) : nullptr;
+  kr.n_pool = src.n_pool;
+  return CC_OK;
+}
 // The copies of a chunk's tables (scans b0 .. b0 + nb - 1), queued behind its offsets; off: the ring slot's pinned offsets.
 static int k1_stage(cc_ctx *c, cc_ctx::Scratch &S, int slot, long long *off, const k1_source &src, const int64_t *h_offsets, int b0, int nb, hipStream_t stream,
                     k1_staged &st) {
@@ -1001,6 +1159,8 @@ static int k1_stage(cc_ctx *c, cc_ctx::Scratch &S, int slot, long long *off, con
       return CC_OK;
     case k1_source::SEGMENTS:
       return stage_segments(c, S, slot, src, b0, nb, stream, st.segs);
+    case k1_source::RIG:
+      return stage_rig(c, S, slot, src, b0, nb, stream, st.rig);
     case k1_source::MOTION:
       st.mot.t_off = src.mot.time_offset - src.lay.xyz_offset;
       st.mot.time_u32 = src.mot.time_type == CC_TIME_U32 ? 1 : 0;
@@ -1053,6 +1213,8 @@ static int k1_dispatch(cc_ctx *c, cc_ctx::Scratch &S, const k1_source &src, cons
       }
     case k1_source::SEGMENTS:
       return k1_launch(c, S, cc_src_seg{st.segs}, nb, want_dense, stream);
+    case k1_source::RIG:
+      return k1_launch(c, S, cc_src_rig{st.rig}, nb, want_dense, stream);
     case k1_source::FILTERED:
       if (src.flt.type == CC_FILTER_F32) return k1_launch(c, S, cc_src_flt<CC_K1_FLT_RANGE>{rpts, stride, st.d_tf, st.flt}, nb, want_dense, stream);
       return k1_launch(c, S, cc_src_flt<CC_K1_FLT_CLASS>{rpts, stride, st.d_tf, st.flt}, nb, want_dense, stream);
@@ -1451,6 +1613,17 @@ int cc_ingest_segments_host(cc_ctx *c, const cc_point_segment_t *h_segs, const i
   return ingest_host(c, k1_segments(h_segs, h_scan_segs), nullptr, n_scans, h_out, h_bev, "cc_ingest_segments_host");
 }
 
+// ---- a rig's sensors de-skewed, filtered and joined in one sweep (include/cont2_amd_rig.h) ----
+int cc_ingest_rig(cc_ctx *c, const cc_rig_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, const float *h_knots, int n_pool,
+                  const cc_point_filter_t *filter, cc_scan_desc_t *d_out, const cc_ingest_debug_t *dbg, void *stream_) {
+  return ingest_device(c, k1_rig(h_segs, h_scan_segs, h_knots, n_pool, filter), nullptr, n_scans, d_out, dbg, stream_, "cc_ingest_rig");
+}
+
+int cc_ingest_rig_host(cc_ctx *c, const cc_rig_segment_t *h_segs, const int32_t *h_scan_segs, int n_scans, const float *h_knots, int n_pool,
+                       const cc_point_filter_t *filter, cc_scan_desc_t *h_out, float *h_bev) {
+  return ingest_host(c, k1_rig(h_segs, h_scan_segs, h_knots, n_pool, filter), nullptr, n_scans, h_out, h_bev, "cc_ingest_rig_host");
+}
+
 void cc_est_sens_tf(const double tf_bev[3], int n_row, int n_col, double tf_sens[3]) {
   // T_to_tsen^-1 * T_delta * T_so_ssen with T_so_ssen = translate(n_row/2 - 0.5, n_col/2 - 0.5)
   const double ox = n_row / 2 - 0.5, oy = n_col / 2 - 0.5;
@@ -1613,6 +1786,12 @@ int cc_scan_ingest_points(cc_ctx *c, const void *h_xyzi, const cc_point_layout_t
 int cc_scan_ingest_segments(cc_ctx *c, const cc_point_segment_t *h_segs, int n_segs, int want_bev, cc_scan **out) {
   const int32_t scan_segs[2] = {0, n_segs};
   return scan_ingest_points(c, k1_segments(h_segs, scan_segs), 0, want_bev, out, "cc_scan_ingest_segments");
+}
+
+int cc_scan_ingest_rig(cc_ctx *c, const cc_rig_segment_t *h_segs, int n_segs, const float *h_knots, int n_pool, const cc_point_filter_t *filter, int want_bev,
+                       cc_scan **out) {
+  const int32_t scan_segs[2] = {0, n_segs};
+  return scan_ingest_points(c, k1_rig(h_segs, scan_segs, h_knots, n_pool, filter), 0, want_bev, out, "cc_scan_ingest_rig");
 }
 
 int cc_scan_ingest_points_motion(cc_ctx *c, const void *h_points, const cc_point_layout_t *layout, const cc_point_motion_t *motion, int64_t n_points,

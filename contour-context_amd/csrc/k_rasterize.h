@@ -1304,7 +1304,7 @@ struct cc_ld_coord {
 //                           cc_k1_sweep's first one, after it has cleared the grid; the merge kernel's own)
 //   loader(scan, tab)     : the loader, positioned at the first point of the call's first scan
 //   SEGMENTED             : the sweep is cc_k1_sweep_seg (which stages the table itself and re-seats a record loader per piece);
-//                           loader() is the output pass' only
+//                           loader() is the output pass' only.  (cc_src_rig, further down, has cc_k1_sweep_rig in the same way.)
 // KITTI float4 records, no transform (cc_ingest_batch; the other entry points with the default layout and no transform)
 struct cc_src_kitti {
   static constexpr int TAB_BYTES = 0, TAB_ALIGN = 1;
@@ -1384,6 +1384,302 @@ struct cc_src_seg {
   }
 };
 
+// ---- a RIG's scan (cc_ingest_rig, include/cont2_amd_rig.h): segments as in cc_ingest_segments, and every segment brings a MODE (none,
+// a matrix, or its time word and a slice of the scan's knot pool) and the place of its filter word (or none).  It is cc_k1_sweep_seg's
+// design carried further: the workgroup's range of Q is cut into pieces, one per segment; the loader is re-seated per piece from the
+// LDS table -- base, stride, matrix or (t_begin, scale, slice), the two word offsets and the filter shift are workgroup-uniform
+// scalars; a piece's last chunk prefetches the next piece's first records under no branch.  New in the loader:
+//   load()  requests x, y, z, the time word and the filter word's dword TOGETHER, none under a branch.  A segment without one of the
+//           words aims that load at its x (offset 0): a word it may read anyway, and xyz() never looks at it.
+//   xyz()   picks the matrix from the scalars (TF) or from the knot pool in LDS (MOTION: three 16-byte reads at the per-lane address
+//           knot0 + bin, the bin clamped to the SEGMENT's n_knots -- cc_ld_rec_motion's steps), then puts NaN into x of a record the
+//           rule drops (cc_ld_rec_flt's step).  The mode and "filtered" are scalar branches in the sweep.
+// The output pass and the merge kernel map an owner's index to its segment as cc_ld_segs does, seat the SAME loader on that segment's
+// entry per lane and re-read the record and both words through the same load() and xyz(): they see the bits the sweep saw.
+// ONE source, the rule's kind a run-time workgroup-uniform value (cc_ld_rec's has_tf is the precedent): the class rule costs the sweep
+// one LDS read per filtered point under a scalar branch and the range rule two compares; three instances per kind would triple the
+// 5 kernels for no register the whole-scan instance lacks (tests/kernel_resources.py: below the 128 VGPR of 16 waves, scratch 0).
+// LDS behind cc_k1_sweep's layout: the pool (3 072 B), the class table (528 B), the segment table (CC_K1_RIG_SEG_MAX x 80 B).  At
+// 150 x 150 the sweep leaves 5 504 B of the CU's 163 840: 1 904 B for the table, so 16 entries (1 280 B) fit and 32 (2 560 B) do not.
+#define CC_K1_RIG_SEG_MAX 16  // = CC_RIG_SEG_MAX (include/cont2_amd_rig.h; checked where both are seen)
+enum { CC_K1_RIG_NONE = 0, CC_K1_RIG_TF = 1, CC_K1_RIG_MOTION = 2 };  // = CC_RIG_*
+#define CC_K1_RIG_MODE_MASK 3u
+#define CC_K1_RIG_TIME_U32 4u   // flags: the time word is a u32
+#define CC_K1_RIG_FILTERED 8u   // flags: the segment has a filter word
+#define CC_K1_RIG_SHIFT_POS 8   // flags >> 8: class rule, the shift of THIS segment's word inside its dword (byte position and the rule's shift)
+struct cc_k1_rseg {
+  const char *base;  // x of the segment's first point
+  unsigned stride;   // bytes between records
+  int first;         // index within the scan of the segment's first point
+  int n;             // points (0: the segment is skipped)
+  unsigned flags;    // mode | CC_K1_RIG_TIME_U32 | CC_K1_RIG_FILTERED | shift << CC_K1_RIG_SHIFT_POS
+  int t_off;         // byte offset from x of the time word (0 without one)
+  int w_off;         // byte offset from x of the aligned dword that holds the filter word (0 without one)
+  float m[12];       // TF: row-major 3 x 4.  MOTION: [0] t_begin (TIME_U32: the u32's bits), [1] scale, [2] the bits of knot0, [3] of n_knots
+};
+static_assert(sizeof(cc_k1_rseg) == 80, "cc_k1_rseg: 80 bytes, 16 of them behind the pool and the class table");
+struct cc_k1_rig {
+  const cc_k1_rseg *seg;  // the call's segments, scan after scan
+  const int *scan_seg;    // [n_scans + 1]
+  const float *knots;     // [n_scans][n_pool][12], or nullptr (no segment is in motion mode)
+  int n_pool;
+  int kind;               // CC_K1_FLT_CLASS / CC_K1_FLT_RANGE; -1: no rule (no segment is filtered)
+  const unsigned *bits;   // CLASS: cc_k1_filter's table
+  unsigned mask, n_classes;
+  float lo, hi;           // RANGE
+};
+#define CC_K1_RIG_SEG_LDS_BYTES (CC_K1_RIG_SEG_MAX * (int)sizeof(cc_k1_rseg))
+#define CC_K1_RIG_LDS_BYTES (CC_K1_MOT_LDS_BYTES + CC_K1_FLT_LDS_BYTES + CC_K1_RIG_SEG_LDS_BYTES)
+static_assert(((CC_MAX_CELLS * 4 + 15) & ~15) + ((CC_MAX_CELLS + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15) + CC_K1_RIG_LDS_BYTES <= 160 * 1024,
+              "cc_src_rig: grid, index fields, output tables, knot pool, class table and segment table fit a CU's 160 KB of LDS");
+static_assert(((CC_MAX_CELLS * 4 + 15) & ~15) + ((CC_MAX_CELLS + 2) / 3) * 8 + 64 + ((CC_K1_EMIT_LDS_BYTES + 15) & ~15) + CC_K1_RIG_LDS_BYTES + CC_K1_RIG_SEG_LDS_BYTES > 160 * 1024,
+              "cc_src_rig: CC_K1_RIG_SEG_MAX is the largest power of two that fits");
+
+struct cc_rig_rec {
+  float x, y, z;
+  unsigned t, w;  // the time word and the filter word's dword as they lie in the record
+};
+// The call's rule and where the pool and the class table lie in LDS: the same for every segment.
+struct cc_rig_env {
+  const float4 *K;    // LDS: [n_pool][3] rows of the scan's matrices
+  const unsigned *T;  // LDS (CLASS)
+  int kind;
+  unsigned mask, n_classes;
+  float lo, hi;
+};
+// The loader seated on ONE segment.  UNIFORM: the entry's values are the workgroup's (the sweep: scalars); otherwise per lane (an owner's).
+struct cc_ld_rig {
+  typedef cc_rig_rec rec;
+  const char *B;
+  unsigned stride, flags;
+  int t_off, w_off;
+  float m[12];
+  cc_rig_env E;
+  template <bool UNIFORM>
+  __device__ __forceinline__ static cc_ld_rig seat(const cc_k1_rseg &g, const cc_rig_env &env, int lo) {
+    cc_ld_rig P;
+    P.E = env;
+    if (UNIFORM) {
+      P.stride = (unsigned)cc_uniform_i((int)g.stride);
+      P.B = cc_uniform_ptr(g.base) + (long long)lo * (long long)P.stride;
+      P.flags = (unsigned)cc_uniform_i((int)g.flags);
+      P.t_off = cc_uniform_i(g.t_off);
+      P.w_off = cc_uniform_i(g.w_off);
+#pragma unroll
+      for (int i = 0; i < 12; i++) P.m[i] = __int_as_float(cc_uniform_i(__float_as_int(g.m[i])));
+    } else {
+      P.stride = g.stride;
+      P.B = g.base + (long long)lo * (long long)P.stride;
+      P.flags = g.flags;
+      P.t_off = g.t_off;
+      P.w_off = g.w_off;
+#pragma unroll
+      for (int i = 0; i < 12; i++) P.m[i] = g.m[i];
+    }
+    return P;
+  }
+  // the coordinates and the two words are requested together, none under a branch
+  __device__ __forceinline__ static rec load_at(const char *p, int t_off, int w_off) {
+    cc_rig_rec q;
+    cc_load3f(p, q.x, q.y, q.z);
+    q.t = *(const unsigned *)(p + t_off);
+    q.w = *(const unsigned *)(p + w_off);
+    return q;
+  }
+  __device__ __forceinline__ rec load(int j) const { return load_at(B + (unsigned)j * stride, t_off, w_off); }
+  __device__ __forceinline__ bool keep(unsigned w) const {
+    if (E.kind == CC_K1_FLT_RANGE) {
+      const float v = __int_as_float((int)w);
+      return (E.lo <= v) & (v <= E.hi);  // (a NaN fails both)
+    }
+    unsigned cls = (w >> (flags >> CC_K1_RIG_SHIFT_POS)) & E.mask;
+    cls = cls < E.n_classes ? cls : E.n_classes;  // <= CC_K1_FLT_CLASSES_MAX: inside the table
+    return ((E.T[cls >> 5] >> (cls & 31u)) & 1u) != 0u;
+  }
+  __device__ __forceinline__ void xyz(const rec &q, float &x, float &y, float &z) const {
+    const unsigned mode = flags & CC_K1_RIG_MODE_MASK;
+    x = q.x;
+    y = q.y;
+    z = q.z;
+    if (mode == CC_K1_RIG_MOTION) {  // cc_ld_rec_motion's steps, K = the segment's n_knots, the knot counted from the slice's first
+      const unsigned tb_bits = (unsigned)__float_as_int(m[0]);
+      const float kmax = (float)(__float_as_int(m[3]) - 1);
+      float u = (flags & CC_K1_RIG_TIME_U32) ? (float)(q.t - tb_bits) * m[1] : (__int_as_float((int)q.t) - m[0]) * m[1];
+      u = u > 0.f ? u : 0.f;  // (a NaN fails the compare: bin 0)
+      u = u < kmax ? u : kmax;
+      const int b = __float_as_int(m[2]) + (int)u;  // < knot0 + n_knots <= n_pool: inside the pool
+      const float4 r0 = E.K[b * 3], r1 = E.K[b * 3 + 1], r2 = E.K[b * 3 + 2];
+      x = ((r0.x * q.x + r0.y * q.y) + r0.z * q.z) + r0.w;
+      y = ((r1.x * q.x + r1.y * q.y) + r1.z * q.z) + r1.w;
+      z = ((r2.x * q.x + r2.y * q.y) + r2.z * q.z) + r2.w;
+    } else if (mode == CC_K1_RIG_TF) {  // cc_ld_rec::xyz's operations in its order
+      x = ((m[0] * q.x + m[1] * q.y) + m[2] * q.z) + m[3];
+      y = ((m[4] * q.x + m[5] * q.y) + m[6] * q.z) + m[7];
+      z = ((m[8] * q.x + m[9] * q.y) + m[10] * q.z) + m[11];
+    }
+    if (flags & CC_K1_RIG_FILTERED) x = keep(q.w) ? x : __int_as_float(0x7FC00000);  // cc_point_cell rejects a NaN x: the record owns nothing and counts nowhere
+  }
+};
+
+// The scan's tables to LDS (a barrier has to follow): pool, class table, segments.  Returns the number of its segments.  T: CC_K1_RIG_LDS_BYTES.
+__device__ __forceinline__ int cc_k1_rig_tables(char *T, const cc_k1_rig &R, int scan) {
+  if (R.knots) {
+    float *kn = (float *)T;
+    const float *__restrict__ src = R.knots + (size_t)scan * (size_t)R.n_pool * 12;
+    for (int i = threadIdx.x; i < R.n_pool * 12; i += blockDim.x) kn[i] = src[i];
+  }
+  if (R.kind == CC_K1_FLT_CLASS) {
+    unsigned *bt = (unsigned *)(T + CC_K1_MOT_LDS_BYTES);
+    for (int i = threadIdx.x; i < CC_K1_FLT_TAB_WORDS; i += blockDim.x) bt[i] = R.bits[i];
+  }
+  const int s0 = R.scan_seg[scan], n_seg = R.scan_seg[scan + 1] - s0;
+  const unsigned *__restrict__ src = (const unsigned *)(R.seg + s0);
+  unsigned *dst = (unsigned *)(T + CC_K1_MOT_LDS_BYTES + CC_K1_FLT_LDS_BYTES);
+  for (int i = threadIdx.x; i < n_seg * (int)(sizeof(cc_k1_rseg) / 4); i += blockDim.x) dst[i] = src[i];
+  return n_seg;
+}
+__device__ __forceinline__ cc_rig_env cc_k1_rig_env(const char *T, const cc_k1_rig &R) {
+  return cc_rig_env{(const float4 *)T, (const unsigned *)(T + CC_K1_MOT_LDS_BYTES), R.kind, R.mask, R.n_classes, R.lo, R.hi};
+}
+
+// The output pass' loader: cc_ld_segs' search for the owner's segment, then the sweep's loader seated on that entry per lane.
+struct cc_ld_rigs {
+  const cc_k1_rseg *S;  // LDS
+  int n_seg;
+  cc_rig_env E;
+  __device__ __forceinline__ void advance(long long) {}
+  __device__ __forceinline__ float2 owner_xy(int j) const {
+    int s = 0;
+    for (int i = 1; i < n_seg; i++) s += j >= S[i].first ? 1 : 0;
+    const cc_ld_rig P = cc_ld_rig::seat<false>(S[s], E, j - S[s].first);
+    float x, y, z;
+    P.xyz(P.load(0), x, y, z);
+    return make_float2(x, y);
+  }
+};
+
+// cc_k1_sweep_seg for a rig's scan (its comment has the pieces and the prefetch across them).  tab_off: where the tables go in smem.
+template <int CC_K1_U, bool CC_K1_POW2, bool PART>
+__device__ __forceinline__ void cc_k1_sweep_rig(char *smem, int tab_off, const cc_dev_cfg &cfg, const cc_k1_rig &rig, const long long *__restrict__ offsets,
+                                                float *__restrict__ bev_out, float2 *__restrict__ pix_out, cc_k1_scan_out *__restrict__ scan_out,
+                                                const cc_k1_part &part, const cc_k1_list_out &list_out, int want_dense) {
+  const int n_cell = cfg.n_cell;
+  unsigned *hmax = (unsigned *)smem;  // (cc_k1_sweep's layout)
+  const int n_w3 = (n_cell + 2) / 3;
+  unsigned long long *idx3 = (unsigned long long *)(smem + (((size_t)n_cell * 4 + 15) & ~(size_t)15));
+  unsigned *red = (unsigned *)(idx3 + n_w3);
+  char *emit_tab = (char *)(red + 4);
+  unsigned *idle = (unsigned *)(emit_tab + CC_K1_EMIT_TAB_BYTES);
+  char *tab = smem + tab_off;
+  const cc_k1_rseg *T = (const cc_k1_rseg *)(tab + CC_K1_MOT_LDS_BYTES + CC_K1_FLT_LDS_BYTES);
+
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int unit = (int)blockIdx.x;
+  const int scan = PART ? unit / CC_K1_SPLIT : unit;
+  int n_pts = (int)(offsets[scan + 1] - offsets[scan]);  // of the whole scan: the segments' counts added up
+  int idx_base = 0;
+  if (PART) {  // the same ranges as cc_k1_sweep's
+    const int per = (n_pts + CC_K1_SPLIT - 1) / CC_K1_SPLIT, pi = unit % CC_K1_SPLIT;
+    idx_base = pi * per < n_pts ? pi * per : n_pts;
+    n_pts = n_pts - idx_base < per ? n_pts - idx_base : per;
+  }
+  const int n_seg = cc_k1_rig_tables(tab, rig, scan);
+  const cc_rig_env env = cc_k1_rig_env(tab, rig);
+  const unsigned KEY_EMPTY = cc_fkey(CC_BEV_EMPTY);
+  for (int i = tid; i < n_cell; i += nt) hmax[i] = KEY_EMPTY;
+  for (int i = tid; i < n_w3; i += nt) idx3[i] = ~0ull;
+  idle[tid] = 0u;
+  if (tid == 0) {
+    red[0] = cc_fkey(CC_BEV_EMPTY);
+    red[1] = cc_fkey(-CC_BEV_EMPTY);
+    red[2] = 0;
+  }
+  __syncthreads();
+
+  // the first segment from s on with points in the range: `lo` points into it, cnt of them (n_seg: none left)
+  const int q0 = idx_base, q1 = idx_base + n_pts;
+  auto piece = [&](int s, int &lo, int &cnt) {
+    for (; s < n_seg; s++) {
+      const int f = T[s].first, hi = q1 - f < T[s].n ? q1 - f : T[s].n;
+      lo = q0 > f ? q0 - f : 0;
+      cnt = hi - lo;
+      if (cnt > 0) break;
+    }
+    lo = cc_uniform_i(lo);
+    cnt = cc_uniform_i(cnt);
+    return cc_uniform_i(s);
+  };
+  unsigned kmin = cc_fkey(-CC_BEV_EMPTY);
+  const int chunk = CC_K1_U * nt;
+  int lo = 0, cnt = 0;
+  int s = piece(0, lo, cnt);
+  if (s < n_seg) {
+    cc_ld_rig P = cc_ld_rig::seat<true>(T[s], env, lo);
+    cc_rig_rec q[CC_K1_U];
+#pragma unroll
+    for (int u = 0; u < CC_K1_U; u++) {
+      const int j = tid + u * nt;
+      q[u] = P.load(j < cnt - 1 ? j : cnt - 1);
+    }
+    while (s < n_seg) {
+      int lo2 = 0, cnt2 = 0;
+      const int s2 = piece(s + 1, lo2, cnt2);
+      // what this piece's last chunk prefetches: the next piece's first records (the last piece: its own last record, dropped)
+      const char *nB = P.B;
+      unsigned nstride = P.stride;
+      int nt_off = P.t_off, nw_off = P.w_off, nlast = cnt - 1;
+      if (s2 < n_seg) {
+        nstride = (unsigned)cc_uniform_i((int)T[s2].stride);
+        nB = cc_uniform_ptr(T[s2].base) + (long long)lo2 * (long long)nstride;
+        nt_off = cc_uniform_i(T[s2].t_off);
+        nw_off = cc_uniform_i(T[s2].w_off);
+        nlast = cnt2 - 1;
+      }
+      const int j_piece = cc_uniform_i(T[s].first) + lo;  // index within the scan of the piece's first point
+      for (int base = 0; base < cnt; base += chunk) {
+        int cell[CC_K1_U];
+        unsigned key[CC_K1_U];
+        cc_k1_cells<CC_K1_U, CC_K1_POW2>(cfg, P, q, cnt - base, cell, key, kmin, tid, nt);
+        const bool more = base + chunk < cnt;
+        const char *lB = more ? P.B : nB;
+        const unsigned lstride = more ? P.stride : nstride;
+        const int lt_off = more ? P.t_off : nt_off, lw_off = more ? P.w_off : nw_off;
+        const int l0 = more ? base + chunk : 0, llast = more ? cnt - 1 : nlast;
+#pragma unroll
+        for (int u = 0; u < CC_K1_U; u++) {
+          const int j = l0 + tid + u * nt;
+          q[u] = cc_ld_rig::load_at(lB + (unsigned)(j < llast ? j : llast) * lstride, lt_off, lw_off);
+        }
+        cc_k1_resolve<CC_K1_U>(hmax, idx3, idle, n_w3, cell, key, j_piece + base, tid, nt);
+      }
+      s = s2;
+      lo = lo2;
+      cnt = cnt2;
+      if (s < n_seg) P = cc_ld_rig::seat<true>(T[s], env, lo);
+    }
+  }
+  cc_k1_finish<PART>(cfg, cc_ld_rigs{T, n_seg, env}, hmax, idx3, red, emit_tab, n_w3, kmin, unit, scan, n_pts, bev_out, pix_out, scan_out, part, list_out, want_dense, tid, nt);
+}
+
+// A rig's scans (cc_ingest_rig)
+struct cc_src_rig {
+  static constexpr int TAB_BYTES = CC_K1_RIG_LDS_BYTES, TAB_ALIGN = 16;
+  static constexpr bool SEGMENTED = false;  // (the sweep is cc_k1_sweep_rig: cc_k1_is_rig below)
+  cc_k1_rig rig;
+  __device__ __forceinline__ void tables(char *tab, int scan) const { cc_k1_rig_tables(tab, rig, scan); }
+  __device__ __forceinline__ cc_ld_rigs loader(int scan, const char *tab) const {
+    return cc_ld_rigs{(const cc_k1_rseg *)(tab + CC_K1_MOT_LDS_BYTES + CC_K1_FLT_LDS_BYTES), rig.scan_seg[scan + 1] - rig.scan_seg[scan], cc_k1_rig_env(tab, rig)};
+  }
+};
+template <typename SRC>
+struct cc_k1_is_rig {
+  static constexpr bool value = false;
+};
+template <>
+struct cc_k1_is_rig<cc_src_rig> {
+  static constexpr bool value = true;
+};
+
 // The sweep.  grid = n_scans (PART: n_scans * CC_K1_SPLIT), block = multiple of 64; dynamic LDS: tab_off + SRC::TAB_BYTES, tab_off =
 // cc_k1_sweep's bytes (n_cell*4 + ((n_cell+2)/3)*8 + 16 + CC_K1_EMIT_LDS_BYTES, the pieces 16-byte aligned) rounded up to SRC::TAB_ALIGN.
 template <int CC_K1_U, bool CC_K1_POW2, bool PART, typename SRC>
@@ -1391,7 +1687,9 @@ __global__ void __launch_bounds__(1024)
 cc_k_rasterize(cc_dev_cfg cfg, SRC src, int tab_off, const long long *__restrict__ offsets, float *__restrict__ bev_out, float2 *__restrict__ pix_out,
                cc_k1_scan_out *__restrict__ scan_out, cc_k1_part part, cc_k1_list_out list_out, int want_dense) {
   HIP_DYNAMIC_SHARED(char, smem)
-  if constexpr (SRC::SEGMENTED) {
+  if constexpr (cc_k1_is_rig<SRC>::value) {
+    cc_k1_sweep_rig<CC_K1_U, CC_K1_POW2, PART>(smem, tab_off, cfg, src.rig, offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
+  } else if constexpr (SRC::SEGMENTED) {
     cc_k1_sweep_seg<CC_K1_U, CC_K1_POW2, PART>(smem, tab_off, cfg, src.segs, offsets, bev_out, pix_out, scan_out, part, list_out, want_dense);
   } else {
     const int scan = PART ? (int)blockIdx.x / CC_K1_SPLIT : (int)blockIdx.x;

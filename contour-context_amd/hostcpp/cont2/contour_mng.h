@@ -19,6 +19,7 @@
 #include "../../../include/cont2_amd_images.h"
 #include "../../../include/cont2_amd_filter.h"
 #include "../../../include/cont2_amd_coords.h"
+#include "../../../include/cont2_amd_rig.h"
 #include "../compat/compat.h"
 
 typedef float KeyFloatType;
@@ -447,6 +448,71 @@ class ContourManager {
                                        want_images_ ? 1 : 0, &scan_) != CC_OK)
       die();
     str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(ptr_gapc->header.stamp);
+  }
+
+  // Mirror-only: ONE BEV from a rig's clouds with ALL the steps of the three overloads above at once (cc_scan_ingest_rig,
+  // include/cont2_amd_rig.h): every cloud is moved by its own T_bev_sensor, or -- motion -- de-skewed by ITS time words with its own slice
+  // [knot0, knot0 + n_knots) of `knots` (bin = trunc(clamp((t - t_begin) * scale, 0, n_knots - 1)), the point moved by knot knot0 + bin;
+  // fold the sensor's extrinsics into its knots), or left as it is; and a record is dropped when the rule of `flt` says so of the word at
+  // the cloud's own filter_offset (-1: the cloud is not filtered).  ONE rule for all clouds: flt->filter's offset and flt->T_bev_sensor
+  // are not read; flt may be nullptr when no cloud is filtered, `knots` empty when none is in motion mode.  The scan is the kept records
+  // of the clouds one after the other in the order given; at most CC_RIG_SEG_MAX clouds, together more than 10 records.
+  template <typename PointType>
+  struct BevRigSegment {
+    typename pcl::PointCloud<PointType>::ConstPtr cloud;
+    const float (*T_bev_sensor)[12] = nullptr;
+    bool motion = false;  // (not together with T_bev_sensor)
+    size_t time_offset = 0;
+    int time_type = CC_TIME_F32;
+    float t_begin_or_bits = 0.f;
+    float scale = 0.f;
+    int knot0 = 0, n_knots = 0;
+    int filter_offset = -1;
+  };
+  template <typename PointType>
+  void makeBEV(const std::vector<BevRigSegment<PointType>> &segments, const std::vector<std::array<float, 12>> &knots, const BevFilter *flt,
+               std::string str_id = "") {
+    CC_CHECK(!segments.empty() && segments.size() <= (size_t)CC_RIG_SEG_MAX);
+    CC_CHECK(knots.size() <= (size_t)CC_MOTION_KNOTS_MAX);
+    CC_CHECK(!scan_);
+    static_assert(sizeof(PointType) % 4 == 0 && sizeof(PointType) <= CC_POINT_STRIDE_MAX, "makeBEV: a record the rasteriser's loaders do not take");
+    static_assert(sizeof(std::array<float, 12>) == 12 * sizeof(float), "makeBEV: the knots are passed as [K][12] floats");
+    std::vector<cc_rig_segment_t> segs(segments.size());
+    size_t total = 0;
+    for (size_t i = 0; i < segments.size(); i++) {
+      const BevRigSegment<PointType> &s = segments[i];
+      CC_CHECK(s.cloud);
+      CC_CHECK(!(s.motion && s.T_bev_sensor));
+      cc_rig_segment_t &g = segs[i];
+      memset(&g, 0, sizeof(g));
+      g.n_points = (int64_t)s.cloud->size();
+      g.layout.stride_bytes = (int32_t)sizeof(PointType);
+      if (s.cloud->size() > 0) {
+        const PointType &p0 = s.cloud->points[0];
+        const char *base = reinterpret_cast<const char *>(&p0);
+        CC_CHECK(reinterpret_cast<const char *>(&p0.y) == reinterpret_cast<const char *>(&p0.x) + 4);
+        CC_CHECK(reinterpret_cast<const char *>(&p0.z) == reinterpret_cast<const char *>(&p0.x) + 8);
+        g.points = base;
+        g.layout.xyz_offset = (int32_t)(reinterpret_cast<const char *>(&p0.x) - base);
+      }
+      g.mode = s.motion ? CC_RIG_MOTION : s.T_bev_sensor ? CC_RIG_TF : CC_RIG_NONE;
+      if (s.T_bev_sensor) memcpy(g.tf, *s.T_bev_sensor, sizeof(g.tf));
+      g.time_offset = (int32_t)s.time_offset;
+      g.time_type = (int32_t)s.time_type;
+      g.t_begin = s.t_begin_or_bits;
+      g.scale = s.scale;
+      g.knot0 = (int32_t)s.knot0;
+      g.n_knots = (int32_t)s.n_knots;
+      g.filter_offset = (int32_t)s.filter_offset;
+      total += s.cloud->size();
+    }
+    CC_CHECK(total > 10);
+    cc_ctx *ctx = cc_host::context(ccfg_);
+    want_images_ = keepImages();
+    if (cc_scan_ingest_rig(ctx, segs.data(), (int)segs.size(), knots.empty() ? nullptr : knots[0].data(), (int)knots.size(), flt ? &flt->filter : nullptr,
+                           want_images_ ? 1 : 0, &scan_) != CC_OK)
+      die();
+    str_id_ = !str_id.empty() ? std::move(str_id) : std::to_string(segments[0].cloud->header.stamp);
   }
 
   // Mirror-only: makeBEV from coordinates of another TYPE or SHAPE than a pcl cloud's three consecutive floats (cc_scan_ingest_coords,

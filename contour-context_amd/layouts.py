@@ -210,6 +210,21 @@ class PointFilterC(C.Structure):
 assert C.sizeof(PointFilterC) == 40 and PointFilterC.lo.offset == 24 and PointFilterC.keep_bits.offset == 32
 
 
+RIG_SEG_MAX = 16                              # CC_RIG_SEG_MAX (include/cont2_amd_rig.h): segments per scan of cc_ingest_rig
+RIG_NONE, RIG_TF, RIG_MOTION = 0, 1, 2        # CC_RIG_NONE / _TF / _MOTION
+
+
+class RigSegment(C.Structure):
+    """cc_rig_segment_t: cc_point_segment_t's records with a mode (none, a matrix, or a time word and a slice of the scan's knot pool)
+    and the byte offset of the segment's filter word (-1: not filtered)."""
+    _fields_ = [("points", C.c_void_p), ("n_points", C.c_int64), ("layout", PointLayout), ("mode", C.c_int32), ("filter_offset", C.c_int32),
+                ("tf", C.c_float * 12), ("time_offset", C.c_int32), ("time_type", C.c_int32), ("t_begin", C.c_float), ("scale", C.c_float),
+                ("knot0", C.c_int32), ("n_knots", C.c_int32)]
+
+
+assert C.sizeof(RigSegment) == 104 and RigSegment.tf.offset == 32 and RigSegment.time_offset.offset == 80
+
+
 def class_bits(n_classes, keep=None, drop=None):
     """The keep_bits of a class rule: uint32 [(n_classes + 31) // 32] with bit c set iff class c is kept -- the classes of `keep`, or
     all but those of `drop` (exactly one of the two is given; every class named must be below n_classes)."""

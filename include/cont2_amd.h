@@ -379,8 +379,9 @@ int cc_ingest_segments_host(cc_ctx *ctx, const cc_point_segment_t *h_segs, const
  * rules; time_offset is a multiple of 4 with time_offset + 4 <= stride_bytes; the time word does not overlap the 12 bytes of
  * x, y, z; time_type is CC_TIME_F32 or CC_TIME_U32; 1 <= n_knots <= CC_MOTION_KNOTS_MAX; motion, h_time and h_knots are
  * non-NULL; every scale is finite.  h_time and h_knots are copied before the call returns.
- * Out of scope: f64 or 64-bit integer time stamps; a time per segment in cc_ingest_segments (its kernels leave no LDS for the
- * knots); interpolation between knots; a batch form of the per-scan call; 12-byte records, which have no room for a time.
+ * A time per segment of a scan made of segments is cont2_amd_rig.h's (cc_ingest_rig: every segment its own time word and its own
+ * slice of the scan's knots).  Out of scope: f64 or 64-bit integer time stamps; interpolation between knots; a batch form of the
+ * per-scan call; 12-byte records, which have no room for a time.
  * What the kernels cost next to cc_ingest_points': DESIGN.md 3.0. */
 #define CC_MOTION_KNOTS_MAX 64
 enum { CC_TIME_F32 = 0, CC_TIME_U32 = 1 };

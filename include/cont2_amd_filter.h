@@ -33,8 +33,9 @@
  * or not below the word's bit width; n_classes outside 1 .. CC_FILTER_CLASSES_MAX; a NULL keep_bits with an integer type; a NaN lo
  * or hi.  The fields of the other rule are not read.
  *
- * Out of scope: a filter together with segments, per-point motion or range images; a table per scan; 64-bit or f64 words; more
- * than one word per call; filtering on the MOVED coordinates (the border and blind-zone tests already do that).
+ * A filter together with segments or per-point motion is cont2_amd_rig.h's (cc_ingest_rig: one rule, a word offset per segment).
+ * Out of scope: a filter together with range images; a table per scan; 64-bit or f64 words; more than one word per call; filtering
+ * on the MOVED coordinates (the border and blind-zone tests already do that).
  *
  * What the kernels cost next to cc_ingest_points': DESIGN.md 3.0.
  */
