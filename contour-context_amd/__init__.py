@@ -25,7 +25,7 @@ import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
 _SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_image.h", "k_contours.h", "k_contours_list.h",
-         "k_knn.h", "k_mask.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
+         "k_knn.h", "k_mask.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_match.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 # how every gfx950 code object of this project that includes csrc/ headers is compiled: the library below and the device
 # probe library of the test suite (tests/dev_probe.py), so that what the probes measure is the code the library runs
@@ -742,6 +742,13 @@ def desc_to_numpy(desc_tensor):
     return desc_tensor.cpu().numpy().view(L.scan_desc_dt).reshape(-1)
 
 
+def match_pairs(row):
+    """The matched contour pairs of one L.ranked_match_dt record (an entry of the array matches=inlier_px returns), in key
+    order -> int8 [n_pairs, 3] of (level, seq_src, seq_tgt): the database scan's contour seq_src and the query's seq_tgt of that
+    level.  cc_match_pairs in C."""
+    return L.match_pairs(row)
+
+
 class Packed:
     """Packed records as the query of Database.query / verify / score_poses (and their _submit forms) in the place of `qdesc`:
     hot / feat are the tensors Context.pack returns (or records gathered from another rank, or a saved map), idx names the
@@ -890,7 +897,7 @@ class Database:
 
     _detail_args = staticmethod(calls.detail_buffer)  # (kept under this name for tests/test_emu_ranked_detail.py, which asks it for the refusal)
 
-    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False, mask=None):
+    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False, mask=None, matches=None):
         """qdesc: torch uint8 CUDA [nq, DESC_BYTES]; epochs int32 [nq] (DB state each query sees).
         In the place of qdesc: self.stored(idx) -- scans of this database by index -- or Packed(hot, feat, idx): the query comes
         from the packed records instead of from descriptors (cc_db_query_submit_packed + the wait), with the same answers.
@@ -905,7 +912,12 @@ class Database:
         -correlation at its pose (hess, grad) and the refinement's start, initial correlation, iterations, termination and pair
         count (cc_db_query_submit_ranked_detail).  Without ranked it is a ValueError.
         mask=ScanMask(...): only the scans of each query's row may answer (cc_db_query_submit_masked + the wait): the retrieval
-        runs as if the other scans' keys were not in the trees.  It combines with every form above."""
+        runs as if the other scans' keys were not in the trees.  It combines with every form above.
+        matches=inlier_px (with ranked=K; >= 0): followed by a [nq, K] array of L.ranked_match_dt as well -- per entry the matched
+        contour pairs its pose was built from (the selected proposal's constellation as a 400-bit set: match_pairs(row) lists
+        them), the proposal's votes and area, and the pairs' residuals at the entry's pose: rms, max and how many lie within
+        inlier_px pixels (cc_db_query_submit_matched).  It combines with stored / Packed queries, mask= and detail=True; a
+        database in dynamic-threshold mode refuses it.  Without ranked it is a ValueError."""
         import torch
         kw, dev, nq = self._query_kw(qdesc, epochs, mask)
         knn = cnt = None
@@ -914,21 +926,22 @@ class Database:
             knn = torch.zeros((nq, L.NQLEV, L.NPIV, ks, L.knn_hit_dt.itemsize), dtype=torch.uint8, device=dev)
             cnt = torch.zeros((nq, L.NQLEV, L.NPIV), dtype=torch.int32, device=dev)
             kw.update(knn=knn.data_ptr(), knn_cnt=cnt.data_ptr())
-        r = calls.query(lib(), self.h, lb=lb, ub=ub, ranked=ranked, detail=detail,
+        r = calls.query(lib(), self.h, lb=lb, ub=ub, ranked=ranked, detail=detail, matches=matches,
                         tolerate=(CC_ECAPACITY,) if allow_flagged else (), **kw)
         if want_knn:
             knn, cnt = knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy()
-        return _ret(r.res, knn, cnt, r.rank, r.detail)
+        return _ret(r.res, knn, cnt, r.rank, r.detail, r.match)
 
-    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False, mask=None):
+    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False, mask=None, matches=None):
         """Asynchronous form of query(): queues the batch and returns the result array, which is only valid after
         query_wait() (cc_db_query_submit / cc_db_query_wait).  qdesc may be overwritten by work queued afterwards on the
         current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait();
         with detail=True followed by the [nq, K] detail array (see query()).  qdesc may be self.stored(idx) or a Packed.
-        mask=ScanMask(...): as for query(); the pending list keeps the mask's table alive until query_wait()."""
+        mask=ScanMask(...): as for query(); the pending list keeps the mask's table alive until query_wait().
+        matches=inlier_px: followed by the [nq, K] match array (see query()), valid after query_wait() like the rest."""
         kw, _dev, _nq = self._query_kw(qdesc, epochs, mask)
-        r = calls.query(lib(), self.h, lb=lb, ub=ub, ranked=ranked, detail=detail, wait=False, keep=self._held(qdesc, mask), **kw)
-        return _ret(r.res, r.rank, r.detail)
+        r = calls.query(lib(), self.h, lb=lb, ub=ub, ranked=ranked, detail=detail, matches=matches, wait=False, keep=self._held(qdesc, mask), **kw)
+        return _ret(r.res, r.rank, r.detail, r.match)
 
     def query_wait(self):
         _chk(lib().cc_db_query_wait(self.h), "cc_db_query_wait")
@@ -947,17 +960,17 @@ class Database:
         _chk(lib().cc_db_add_packed(self.h, hot.data_ptr(), feat.data_ptr(), n, ts.ctypes.data, seeds.ctypes.data, stream),
              "cc_db_add_packed")
 
-    def check_hints(self, qdesc, hints, lb=None, ub=None, max_fine_opt=10, ranked=None, detail=False):
+    def check_hints(self, qdesc, hints, lb=None, ub=None, max_fine_opt=10, ranked=None, detail=False, matches=None):
         """CandidateManager driven by explicit hints (checkCandWithHint in the given order, tidyUpCandidates, fineOptimize).
         qdesc: torch uint8 CUDA [DESC_BYTES] of the query scan; hints: array of L.hint_dt (cand_gidx = DB index).
         Returns (cc_query_result_t record, per-hint L.hint_score_dt array); with ranked=K followed by (cands [1, K], counts [1]),
-        and with detail=True by the [1, K] detail array (see query())."""
+        and with detail=True by the [1, K] detail array, with matches=inlier_px by the [1, K] match array (see query())."""
         import torch
         qdesc = qdesc.reshape(-1)
         assert qdesc.is_cuda and qdesc.is_contiguous() and qdesc.numel() == DESC_BYTES
         r = calls.check_hints(lib(), self.h, qdesc.data_ptr(), hints, lb, ub, max_fine_opt, torch.cuda.current_stream(qdesc.device).cuda_stream,
-                              ranked, detail)
-        return _ret(r.res[0], r.scores, r.rank, r.detail)
+                              ranked, detail, matches)
+        return _ret(r.res[0], r.scores, r.rank, r.detail, r.match)
 
     def _verify(self, qdesc, cands, max_fine_opt, want_hints=False, **kw):
         """what verify() and verify_submit() share: the tensor checks, the stream, the device's hint lists, the call
@@ -975,7 +988,7 @@ class Database:
         return r, d_h, d_n
 
     def verify(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
-               want_hints=False, allow_flagged=False, ranked=None, detail=False):
+               want_hints=False, allow_flagged=False, ranked=None, detail=False, matches=None):
         """Score candidates the caller proposes, in one batch (cc_db_verify_batch).  qdesc: torch uint8 CUDA [n_desc, DESC_BYTES]
         -- or self.stored(idx) / Packed(hot, feat, idx): item i is record idx[i] (or qidx[i] of a source without idx), read from
         the packed records (cc_db_verify_submit_packed + the wait); an item may name a stored scan among its own candidates;
@@ -987,25 +1000,26 @@ class Database:
         ranked=K: followed by (cands [n, K] of L.ranked_cand_dt, counts [n]) -- every refined candidate of an item, best first
         (cc_db_verify_submit_ranked), instead of one item per (query, candidate) pair.  Like query(ranked=K) it is the submit
         followed by the wait, so a large batch is chunked by the streamed rule (whole chunks), not one chunk per lane.
-        detail=True (with ranked=K): followed by the [n, K] detail array as well (see query())."""
+        detail=True (with ranked=K): followed by the [n, K] detail array as well (see query()).
+        matches=inlier_px (with ranked=K): followed by the [n, K] match array as well (see query(); cc_db_verify_submit_matched)."""
         r, d_h, d_n = self._verify(qdesc, cands, max_fine_opt, want_hints, qidx=qidx, levels=levels, max_key_dist_sq=max_key_dist_sq, lb=lb, ub=ub,
-                                   ranked=ranked, detail=detail, tolerate=(CC_ECAPACITY,) if allow_flagged else ())
+                                   ranked=ranked, detail=detail, matches=matches, tolerate=(CC_ECAPACITY,) if allow_flagged else ())
         hints = None
         if want_hints:
             cnt = d_n.cpu().numpy()
             allh = d_h.cpu().numpy().view(L.hint_dt).reshape(-1, L.HINT_MAX)
             hints = [allh[i, :cnt[i]].copy() for i in range(len(r.res))]
-        return _ret(r.res, hints, r.rank, r.detail)
+        return _ret(r.res, hints, r.rank, r.detail, r.match)
 
     def verify_submit(self, qdesc, cands, qidx=None, levels=(1, 2, 3, 4), max_key_dist_sq=1000.0, lb=None, ub=None, max_fine_opt=None,
-                      ranked=None, detail=False):
+                      ranked=None, detail=False, matches=None):
         """Asynchronous form of verify(): queues the batch and returns the result array, which is only valid after query_wait()
         (cc_db_verify_submit; verify and query chunks share the lanes and are collected together).  ranked=K: returns
         (results, (cands [n, K], counts [n])), with detail=True followed by the [n, K] detail array.  qdesc may be self.stored(idx)
-        or a Packed, as for verify()."""
+        or a Packed, as for verify().  matches=inlier_px: followed by the [n, K] match array."""
         r = self._verify(qdesc, cands, max_fine_opt, qidx=qidx, levels=levels, max_key_dist_sq=max_key_dist_sq, lb=lb, ub=ub,
-                         ranked=ranked, detail=detail, wait=False, keep=self._held(qdesc))[0]
-        return _ret(r.res, r.rank, r.detail)
+                         ranked=ranked, detail=detail, matches=matches, wait=False, keep=self._held(qdesc))[0]
+        return _ret(r.res, r.rank, r.detail, r.match)
 
     def _pose(self, qdesc, q, gidx, tf, **kw):
         """what score_poses() and score_poses_submit() share: the tensor checks, the stream, the call"""

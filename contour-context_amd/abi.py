@@ -167,6 +167,16 @@ I cc_ingest_rig PPPIPIPPPP
 I cc_ingest_rig_host PPPIPIPPP
 I cc_scan_ingest_rig PPIPIPIP
 """,
+    "cont2_amd_matches.h": """
+I cc_match_pairs PPI
+I cc_db_query_submit_matched PPPPIPPPPPPPPPPP
+I cc_db_verify_submit_matched PPIPPPIPPPPPPPPPP
+I cc_db_check_hints_matched PPPIPPIPPPPPP
+I cc_db_query_scan_batch_submit_matched PPIPPPPPPP
+I cc_db_query_batch_host_matched PPIPPPPPPPP
+I cc_db_verify_batch_host_matched PPIPPIPPPPPPP
+I cc_db_check_hints_host_matched PPPIPPIPPPPP
+""",
 }
 ADDONS = {hdr: _table(spec) for hdr, spec in _ADDON_SPEC.items()}
 

@@ -13,6 +13,8 @@ entry point runs is behaviour (a synchronous *_batch cuts one chunk per lane, a 
   verify   descriptors: cc_db_verify_batch (wait) / cc_db_verify_submit; ranked: cc_db_verify_submit_ranked[_detail];
            a record source: cc_db_verify_submit_packed
   hints    cc_db_check_hints[_ranked[_detail]] (synchronous by itself)
+  matches  (include/cont2_amd_matches.h) matches=inlier_px beside ranked=K on the three flows above: the flow's one *_matched entry
+           point, which takes every other form's arguments (descriptors or a record source, a mask, the detail rows)
   pose     descriptors: cc_db_pose_batch (wait) / cc_db_pose_submit; a record source: cc_db_pose_submit_packed
 Beside the scoring flows: ingest_images / scan_ingest_image, the calls of include/cont2_amd_images.h (descriptors from max-height images),
 class_filter / range_filter / ingest_points_filtered / scan_ingest_points_filtered, those of include/cont2_amd_filter.h (records
@@ -205,18 +207,28 @@ def _rank(n, ranked, detail):
     return (cands, cnt), ro, det
 
 
+def _match(n, ranked, matches):
+    """matches=inlier_px -> (rows [n, ranked] of L.ranked_match_dt, cc_match_out_t), else (None, None)"""
+    if matches is None:
+        return None, None
+    if ranked is None:
+        raise ValueError("matches=inlier_px needs ranked=K: the match rows belong to the entries of the ranked list")
+    return L.match_buffers(n, ranked, matches)
+
+
 def _ranked_fn(stem, ro, det):
     """the descriptor form's entry point with a ranked list (and detail), and the arguments it takes after the stream"""
     return stem + "_ranked" + ("_detail" if det is not None else ""), (_a(ro),) + (() if det is None else (_a(det),))
 
 
 def query(lib, db, epochs, qdesc=None, src=None, idx=None, mask=None, lb=None, ub=None, knn=None, knn_cnt=None, stream=None,
-          ranked=None, detail=False, wait=True, tolerate=(), keep=None):
+          ranked=None, detail=False, matches=None, wait=True, tolerate=(), keep=None):
     """qdesc: the descriptors' address, or src: an L.PackedSrc with idx, its record selector (None: query i is record i).
-    mask: (bits address, n_rows, row_words, int32 rows [nq]).  -> Out(res, rank, detail)"""
+    mask: (bits address, n_rows, row_words, int32 rows [nq]).  matches: inlier_px (with ranked).  -> Out(res, rank, detail, match)"""
     epochs = np.ascontiguousarray(epochs, np.int32).reshape(-1)
     nq = len(epochs)
     rk, ro, det = _rank(nq, ranked, detail) if ranked is not None or detail else (None, None, None)
+    mt, mo = _match(nq, ranked, matches)
     if lb is None:
         lb, ub = L.default_thresholds()
     if idx is not None:
@@ -233,7 +245,9 @@ def query(lib, db, epochs, qdesc=None, src=None, idx=None, mask=None, lb=None, u
         mask = (rows, cm)
     res = np.zeros(nq, L.query_result_dt)
     mid = (nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub), res.ctypes.data, knn, knn_cnt, stream)
-    if cm is not None:
+    if mo is not None:
+        fn, args = "cc_db_query_submit_matched", (db, None if src is not None else qdesc, _a(src), _a(idx)) + mid + (_a(ro), _a(det), _a(cm), _a(mo))
+    elif cm is not None:
         fn, args = "cc_db_query_submit_masked", (db, qdesc, _a(src), _a(idx)) + mid + (_a(ro), _a(det), _a(cm))
     elif src is not None:
         fn, args = "cc_db_query_submit_packed", (db, _a(src), _a(idx)) + mid + (_a(ro), _a(det))
@@ -242,9 +256,9 @@ def query(lib, db, epochs, qdesc=None, src=None, idx=None, mask=None, lb=None, u
         args = (db, qdesc) + mid + tail
     else:
         fn, args = "cc_db_query_batch" if wait else "cc_db_query_submit", (db, qdesc) + mid
-    held = (src, idx, epochs, lb, ub, res, rk, ro, det, mask)
+    held = (src, idx, epochs, lb, ub, res, rk, ro, det, mask, mt, mo)
     _call(lib, db, fn, args, wait, tolerate, keep, held)
-    return Out(held, res=res, rank=rk, detail=det)
+    return Out(held, res=res, rank=rk, detail=det, match=mt)
 
 
 def cand_table(cands):
@@ -278,8 +292,9 @@ def level_mask(levels):
 
 
 def verify(lib, db, cands, qdesc=None, n_desc=0, src=None, idx=None, qidx=None, levels=(1, 2, 3, 4), max_fine_opt=10, max_key_dist_sq=1000.0,
-           lb=None, ub=None, hints=None, n_hints=None, stream=None, ranked=None, detail=False, wait=True, tolerate=(), keep=None):
-    """cands: see cand_table; item i is descriptor (or record) qidx[i] (None: i).  levels: see level_mask.  hints / n_hints: device addresses of the generated hint lists.  -> Out(res, rank, detail)"""
+           lb=None, ub=None, hints=None, n_hints=None, stream=None, ranked=None, detail=False, matches=None, wait=True, tolerate=(), keep=None):
+    """cands: see cand_table; item i is descriptor (or record) qidx[i] (None: i).  levels: see level_mask.  hints / n_hints: device addresses of the generated hint lists.
+    matches: inlier_px (with ranked).  -> Out(res, rank, detail, match)"""
     if lb is None:
         lb, ub = L.default_thresholds()
     if src is not None:
@@ -294,31 +309,38 @@ def verify(lib, db, cands, qdesc=None, n_desc=0, src=None, idx=None, qidx=None, 
             raise ValueError("qidx must name one descriptor per item")
     cfg = L.VerifyCfg(level_mask(levels), int(max_fine_opt), float(max_key_dist_sq), 0)
     rk, ro, det = _rank(n, ranked, detail)
+    mt, mo = _match(n, ranked, matches)
     res = np.zeros(n, L.query_result_dt)
     mid = (_a(qidx), _a(tab), n, _a(cfg), _a(lb), _a(ub), _a(res), hints, n_hints, stream)
-    if src is not None:
+    if mo is not None:
+        fn, args = "cc_db_verify_submit_matched", (db, None if src is not None else qdesc, n_desc, _a(src)) + mid + (_a(ro), _a(det), _a(mo))
+    elif src is not None:
         fn, args = "cc_db_verify_submit_packed", (db, _a(src)) + mid + (_a(ro), _a(det))
     elif ranked is not None:
         fn, tail = _ranked_fn("cc_db_verify_submit", ro, det)
         args = (db, qdesc, n_desc) + mid + tail
     else:
         fn, args = "cc_db_verify_batch" if wait else "cc_db_verify_submit", (db, qdesc, n_desc) + mid
-    held = (src, qidx, tab, cfg, lb, ub, res, rk, ro, det)
+    held = (src, qidx, tab, cfg, lb, ub, res, rk, ro, det, mt, mo)
     _call(lib, db, fn, args, wait, tolerate, keep, held)
-    return Out(held, res=res, rank=rk, detail=det)
+    return Out(held, res=res, rank=rk, detail=det, match=mt)
 
 
-def check_hints(lib, db, qdesc, hints, lb=None, ub=None, max_fine_opt=10, stream=None, ranked=None, detail=False):
-    """qdesc: the address of the query scan's descriptor; hints: array of L.hint_dt.  -> Out(res [1], scores, rank, detail)"""
+def check_hints(lib, db, qdesc, hints, lb=None, ub=None, max_fine_opt=10, stream=None, ranked=None, detail=False, matches=None):
+    """qdesc: the address of the query scan's descriptor; hints: array of L.hint_dt.  matches: inlier_px (with ranked).
+    -> Out(res [1], scores, rank, detail, match)"""
     rk, ro, det = _rank(1, ranked, detail)
+    mt, mo = _match(1, ranked, matches)
     if lb is None:
         lb, ub = L.default_thresholds()
     hints = np.ascontiguousarray(hints, L.hint_dt)
     res = np.zeros(1, L.query_result_dt)
     sc = np.zeros(len(hints), L.hint_score_dt)
     fn, tail = ("cc_db_check_hints", ()) if ranked is None else _ranked_fn("cc_db_check_hints", ro, det)
+    if mo is not None:
+        fn, tail = "cc_db_check_hints_matched", (_a(ro), _a(det), _a(mo))
     chk(lib, getattr(lib, fn)(db, qdesc, _a(hints), len(hints), _a(lb), _a(ub), int(max_fine_opt), _a(res), _a(sc), stream, *tail), fn)
-    return Out((), res=res, scores=sc, rank=rk, detail=det)
+    return Out((), res=res, scores=sc, rank=rk, detail=det, match=mt)
 
 
 def pose(lib, db, q, gidx, tf, qdesc=None, n_desc=0, src=None, idx=None, refine=True, min_corr=None, tries=None, curvature=False,

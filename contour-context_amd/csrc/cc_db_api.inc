@@ -156,6 +156,11 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   cc_ranked_detail_t *d_detail = nullptr;   // [QB * CC_RANK_MAX] cc_k_final_rd's rows, beside d_rank
   cc_ranked_detail_t *h_detail = nullptr;   // the same, pinned (small chunks: written by the kernel)
   cc_ranked_detail_t *detail_dst = nullptr; // where the chunk's detail rows go when it is collected (nullptr: not a detail chunk)
+  // matched chunks (the *_matched entry points, include/cont2_amd_matches.h), allocated with the first one
+  cc_match_rec *d_mrec = nullptr;           // [QB][CC_MAXCAND] cc_k_merge_m's selected proposal per problem, at the problem's place
+  cc_ranked_match_t *d_match = nullptr;     // [QB * CC_RANK_MAX] cc_k_match_emit's rows, beside d_rank
+  cc_ranked_match_t *h_match = nullptr;     // the same, pinned (small chunks: written by the kernel)
+  cc_ranked_match_t *match_dst = nullptr;   // where the chunk's match rows go when it is collected (nullptr: not a matched chunk)
   // pose chunks (cc_db_pose_submit), allocated with the first one.  In: item table | try poses | descriptor selector, filled by
   // the submit, one copy per chunk.  Out: result rows | try results | curvature rows, one copy back (small chunks: written by the kernels)
   char *d_pin = nullptr, *h_pin = nullptr;
@@ -339,6 +344,9 @@ static void db_free(cc_db *db) {
     hipFree(ln.d_hess);
     hipFree(ln.d_detail);
     if (ln.h_detail) hipHostFree(ln.h_detail);
+    hipFree(ln.d_mrec);
+    hipFree(ln.d_match);
+    if (ln.h_match) hipHostFree(ln.h_match);
     if (ln.done) hipEventDestroy(ln.done);
     if (ln.prep) hipEventDestroy(ln.prep);
     if (ln.fin) hipEventDestroy(ln.fin);
@@ -438,7 +446,28 @@ static int lane_alloc_detail(cc_qlane &ln) {
   LANE_BUF(ln.d_detail, bytes, false);
   return CC_OK;
 }
+// the buffers of a lane's matched chunks, allocated with the lane's first one: the selected proposals at the problem's place
+// (QB * CC_MAXCAND records of 72 B: 85 MB, a tenth of what the lane holds anyway) and the rows (2 x 1.5 MB)
+static int lane_alloc_match(cc_qlane &ln) {
+  const size_t bytes = sizeof(cc_ranked_match_t) * (size_t)cc_db::QB * CC_RANK_MAX;
+  LANE_BUF(ln.h_match, bytes, true);
+  LANE_BUF(ln.d_match, bytes, false);
+  LANE_BUF(ln.d_mrec, sizeof(cc_match_rec) * (size_t)cc_db::QB * CC_MAXCAND, false);
+  return CC_OK;
+}
 #undef LANE_BUF
+// The refusals of the *_matched entry points (match given), worded with the entry point's name; db may be NULL (the call's own
+// argument check names that).
+static int want_match(const char *fn, const cc_db *db, const cc_rank_out_t *rank, const cc_match_out_t *match) {
+  if (!rank) return set_err(CC_EINVAL, (std::string(fn) + ": match comes with rank (the rows belong to the entries of the ranked list)").c_str());
+  if (!match->h_match) return set_err(CC_EINVAL, (std::string(fn) + ": h_match must be given").c_str());
+  if (!(match->inlier_px >= 0.0) || std::isinf(match->inlier_px))
+    return set_err(CC_EINVAL, (std::string(fn) + ": inlier_px must be finite and >= 0").c_str());
+  if (db && db->dyn_thres)
+    return set_err(CC_EINVAL, (std::string(fn) + ": matches are not supported in dynamic-threshold mode (cc_db_set_dynamic_thres): no test oracle "
+                                                 "for merged constellations under rising bars exists").c_str());
+  return CC_OK;
+}
 // The refusals of the *_ranked / *_ranked_detail entry points, worded with the entry point's name (`fn`).  need_detail: the
 // call is a *_ranked_detail one.
 static int want_ranked(const char *fn, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail, bool need_detail) {
@@ -1186,13 +1215,15 @@ static void launch_refine(cc_db *db, cc_qlane &ln, float corr_bar) {
 static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_params &CP, const cc_score_t *lb, const cc_score_t *ub,
                                 int max_fine_opt, hipEvent_t *ev, int *d_scores, bool zc /*results and counters straight into the lane's pinned host buffers*/,
                                 int km, int max_ret = 0 /*> 0: a ranked chunk (cc_k_final_r writes the lists to the lane's rank buffer)*/,
-                                bool detail = false /*with max_ret > 0: cc_k_gmm_hess behind the refinement, cc_k_final_rd writes the detail rows as well*/) {
+                                bool detail = false /*with max_ret > 0: cc_k_gmm_hess behind the refinement, cc_k_final_rd writes the detail rows as well*/,
+                                const cc_match_out_t *match = nullptr /*with max_ret > 0: the matched merge instance, cc_k_match_emit behind cc_k_final_r*/) {
   hipStream_t ls = ln.stream;
   const bool lg = km != CC_KNN_MAX;
   // dynamic thresholds (the mode at submission): the stages leave their scores in the pass records, cc_k_check_dyn replays the
   // checks in order, cc_k_select<true> / cc_k_final<true> the post bars
   const bool dyn = db->dyn_thres != 0;
   if (dyn && !ln.d_tidy) return set_err(CC_EHIP, "launch_scoring_chain: the lane has no dynamic-threshold buffers");
+  if (match && (dyn || max_ret <= 0 || !ln.d_mrec)) return set_err(CC_EHIP, "launch_scoring_chain: a matched chain is a ranked one on static thresholds with the lane's match buffers");
   cc_pass_rec *const dpass = dyn ? ln.d_pass : nullptr;
   unsigned char *const dok = dyn ? ln.d_pass_ok : nullptr;
   const cc_hot_desc_t *qh = ln.d_qhot, *dh = db->d_hot;
@@ -1213,9 +1244,14 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
     hipLaunchKernelGGL(lg ? cc_k_check_dyn_l : cc_k_check_dyn, dim3(nb), dim3(64), 0, ls, nb, *lb, *ub, (const cc_pass_rec *)ln.d_pass, ln.d_pass_ok, ln.d_pass_cnt,
                        d_scores);
   if (ev) HIPCHK(hipEventRecord(ev[2], ls));
-  hipLaunchKernelGGL(lg ? cc_k_merge_l : cc_k_merge, dim3(nb), dim3(CC_MERGE_BLOCK), 0, ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
-                     (const unsigned char *)ln.d_pass_ok, (const int *)ln.d_pass_cnt, ln.d_cands, ln.d_qstate, ln.d_prob, ln.d_prob_list,
-                     ln.d_nprob, dyn ? ln.d_cpost : (cc_cand_post *)nullptr);
+  if (match)  // the matched instance replaces the plain one; a chain without `match` launches what it always launched
+    hipLaunchKernelGGL(lg ? cc_k_merge_lm : cc_k_merge_m, dim3(nb), dim3(CC_MERGE_BLOCK), 0, ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
+                       (const unsigned char *)ln.d_pass_ok, (const int *)ln.d_pass_cnt, ln.d_cands, ln.d_qstate, ln.d_prob, ln.d_prob_list,
+                       ln.d_nprob, ln.d_mrec);
+  else
+    hipLaunchKernelGGL(lg ? cc_k_merge_l : cc_k_merge, dim3(nb), dim3(CC_MERGE_BLOCK), 0, ls, nb, *lb, db->n_row, db->n_col, qh, dh, (const cc_pass_rec *)ln.d_pass,
+                       (const unsigned char *)ln.d_pass_ok, (const int *)ln.d_pass_cnt, ln.d_cands, ln.d_qstate, ln.d_prob, ln.d_prob_list,
+                       ln.d_nprob, dyn ? ln.d_cpost : (cc_cand_post *)nullptr);
   if (ev) HIPCHK(hipEventRecord(ev[3], ls));
   // initial correlation of every candidate; the candidates fineOptimize would refine; L-BFGS on those only
   launch_gmm_init(db, ln);
@@ -1247,6 +1283,11 @@ static int launch_scoring_chain(cc_db *db, cc_qlane &ln, int nb, const cc_check_
                        (const int *)ln.d_hit_cnt, qh, zc ? ln.h_results : ln.d_results, (const unsigned short *)db->d_perm_tab, (const int *)ln.d_nprob,
                        zc ? ln.h_nprob : (int *)nullptr, (const unsigned char *)ln.d_tidy);
   }
+  if (match)  // the rows of the list cc_k_final_r* just wrote (small chunks: read from and written to the pinned buffers)
+    hipLaunchKernelGGL(lg ? cc_k_match_emit_l : cc_k_match_emit, dim3(nb), dim3(64), 0, ls, nb, max_ret, max_fine_opt, match->inlier_px,
+                       (const cc_query_result_t *)(zc ? ln.h_results : ln.d_results), (const cc_ranked_cand_t *)(zc ? ln.h_rank : ln.d_rank),
+                       (const cc_cand_out *)ln.d_cands, (const cc_qstate *)ln.d_qstate, (const cc_match_rec *)ln.d_mrec, qh, dh,
+                       zc ? ln.h_match : ln.d_match);
   if (ev) HIPCHK(hipEventRecord(ev[5], ls));
   HIPCHK(hipGetLastError());
   return CC_OK;
@@ -1306,6 +1347,8 @@ static int lane_finish(cc_db *db, cc_qlane &ln) {
   if (ln.rank_dst.h_cands) rank_deliver(ln, ln.rank_dst, ln.b0, ln.nb, ln.rank_mfo);
   if (ln.detail_dst)
     memcpy(ln.detail_dst + (size_t)ln.b0 * ln.rank_dst.max_ret, ln.h_detail, sizeof(cc_ranked_detail_t) * (size_t)ln.nb * ln.rank_dst.max_ret);
+  if (ln.match_dst)
+    memcpy(ln.match_dst + (size_t)ln.b0 * ln.rank_dst.max_ret, ln.h_match, sizeof(cc_ranked_match_t) * (size_t)ln.nb * ln.rank_dst.max_ret);
   if (ln.profiled) add_stage_times(db, ln, 0x1Fu);
   return chunk_status(ln, ln.nb);
 }
@@ -1467,14 +1510,15 @@ static int submit_chunks(cc_db *db, int n, hipStream_t stream, const cc_chunk_pl
 }
 
 // query and verify chunks: the lane's on-demand buffers of the chain's modes ...
-static int lane_alloc_modes(cc_db *db, cc_qlane &ln, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail) {
+static int lane_alloc_modes(cc_db *db, cc_qlane &ln, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail, const cc_match_out_t *match = nullptr) {
   int rc = db->dyn_thres ? lane_alloc_dyn(ln) : CC_OK;
   if (rc == CC_OK && rank) rc = lane_alloc_rank(ln);
   if (rc == CC_OK && detail) rc = lane_alloc_detail(ln);
+  if (rc == CC_OK && match) rc = lane_alloc_match(ln);
   return rc;
 }
 // ... what launch_scoring_chain left on the device, to the lane's pinned buffers ...
-static int results_copy_back(const cc_chunk &c, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail) {
+static int results_copy_back(const cc_chunk &c, const cc_rank_out_t *rank, const cc_ranked_detail_t *detail, const cc_match_out_t *match = nullptr) {
   cc_qlane &ln = c.ln;
   hipStream_t ls = ln.stream;
   const int nb = c.nb;
@@ -1482,11 +1526,14 @@ static int results_copy_back(const cc_chunk &c, const cc_rank_out_t *rank, const
   HIPCHK(hipMemcpyAsync(ln.h_nprob, ln.d_nprob, sizeof(int) * 4, hipMemcpyDeviceToHost, ls));
   if (rank) HIPCHK(hipMemcpyAsync(ln.h_rank, ln.d_rank, sizeof(cc_ranked_cand_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
   if (detail) HIPCHK(hipMemcpyAsync(ln.h_detail, ln.d_detail, sizeof(cc_ranked_detail_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
+  if (match) HIPCHK(hipMemcpyAsync(ln.h_match, ln.d_match, sizeof(cc_ranked_match_t) * (size_t)nb * rank->max_ret, hipMemcpyDeviceToHost, ls));
   return CC_OK;
 }
 // ... and where lane_finish delivers them
-static void results_note(cc_qlane &ln, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *detail, int max_fine_opt) {
+static void results_note(cc_qlane &ln, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *detail, int max_fine_opt,
+                         const cc_match_out_t *match = nullptr) {
   ln.h_dst = h_res;
+  ln.match_dst = match ? match->h_match : nullptr;
   ln.rank_dst = rank ? *rank : cc_rank_out_t{nullptr, nullptr, 0, 0};
   ln.detail_dst = detail;
   ln.rank_mfo = max_fine_opt;
@@ -1516,7 +1563,8 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
     cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
                              const cc_rec_src *rec = nullptr /*the queries are packed records (then d_qdesc is nullptr) ...*/,
                              const int32_t *h_rec = nullptr /*... query i is record h_rec[i] of them, or nullptr: record i*/,
-                             const cc_scan_mask_t *mask = nullptr /*the scans that may answer (bits: device), or nullptr: all of them*/) {
+                             const cc_scan_mask_t *mask = nullptr /*the scans that may answer (bits: device), or nullptr: all of them*/,
+                             const cc_match_out_t *match = nullptr /*with rank: where the chunks' match rows go (validated by the entry point), or nullptr*/) {
   if (!db || (!d_qdesc && !rec) || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch");
   if (mask) {
@@ -1554,7 +1602,7 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
   plan.alloc = [&](cc_qlane &ln) -> int {
     int rc = rec ? lane_alloc_verify(ln) : CC_OK;  // (the record selector of a packed chunk goes where a verify chunk's does)
     if (rc == CC_OK && mask) rc = lane_alloc_mask(ln);
-    return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail);
+    return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail, match);
   };
   plan.stage = [&](const cc_chunk &c) {  // the queries' epoch records
     cc_query_meta *h_meta = c.ln.h_meta;
@@ -1638,14 +1686,14 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
     cc_qlane &ln = c.ln;
     hipStream_t ls = ln.stream;
     const int nb = c.nb, b0 = c.b0;
-    const int rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, c.ev, nullptr, c.zc, db->kmax, rank ? rank->max_ret : 0, detail != nullptr);
+    const int rc = launch_scoring_chain(db, ln, nb, CP, lb, ub, db->cfg.max_fine_opt, c.ev, nullptr, c.zc, db->kmax, rank ? rank->max_ret : 0, detail != nullptr, match);
     if (rc != CC_OK) return rc;
     if (d_knn) HIPCHK(hipMemcpyAsync(d_knn + (size_t)b0 * NS * db->kmax, ln.d_hits, sizeof(cc_knn_hit_t) * (size_t)nb * NS * db->kmax, hipMemcpyDeviceToDevice, ls));
     if (d_knn_cnt) HIPCHK(hipMemcpyAsync(d_knn_cnt + (size_t)b0 * NS, ln.d_hit_cnt, sizeof(int) * nb * NS, hipMemcpyDeviceToDevice, ls));
     return CC_OK;
   };
-  plan.copy_back = [&](const cc_chunk &c) -> int { return results_copy_back(c, rank, detail); };
-  plan.note = [&](const cc_chunk &c) { results_note(c.ln, h_res, rank, detail, db->cfg.max_fine_opt); };
+  plan.copy_back = [&](const cc_chunk &c) -> int { return results_copy_back(c, rank, detail, match); };
+  plan.note = [&](const cc_chunk &c) { results_note(c.ln, h_res, rank, detail, db->cfg.max_fine_opt, match); };
   return submit_chunks(db, nq, (hipStream_t)stream_, plan);
 }
 
@@ -1829,7 +1877,8 @@ int cc_db_add_scan_batch(cc_db *db, cc_scan *const *scans, int n, const double *
 
 static int query_scan_batch_submit_impl(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
                                         const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank,
-    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
+                                        const cc_match_out_t *match = nullptr) {
   if (!db || !scans || n < 1 || n > CC_SCAN_BATCH_MAX || !h_epoch || !lb || !ub || !h_res)
     return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit: bad argument (1..CC_SCAN_BATCH_MAX scans)");
   DB_POISON_CHK(db, "cc_db_query_scan_batch_submit");
@@ -1838,7 +1887,7 @@ static int query_scan_batch_submit_impl(cc_db *db, cc_scan *const *scans, int n,
   const cc_scan_desc_t *d = nullptr;
   const int rc = gather_handles(db, scans, n, 1, "cc_db_query_scan_batch_submit: null scan handle", &d);
   if (rc != CC_OK) return rc;
-  return query_submit_impl(db, d, n, h_epoch, lb, ub, h_res, nullptr, nullptr, db->ctx->s_loop, rank, detail);
+  return query_submit_impl(db, d, n, h_epoch, lb, ub, h_res, nullptr, nullptr, db->ctx->s_loop, rank, detail, nullptr, nullptr, nullptr, match);
 }
 int cc_db_query_scan_batch_submit(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
                                   const cc_score_t *ub, cc_query_result_t *h_res) {
@@ -1876,7 +1925,8 @@ int cc_db_query_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_score_t 
 static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                             const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_,
                             const cc_rank_out_t *rank,
-    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
+                            const cc_match_out_t *match = nullptr /*with rank: where the match rows go (validated by the entry point), or nullptr*/) {
   if (!db || !d_qdesc || n_hints < 0 || (n_hints > 0 && !h_hints) || !lb || !ub || !h_res || max_fine_opt < 1)
     return set_err(CC_EINVAL, "cc_db_check_hints: bad argument");
   DB_POISON_CHK(db, "cc_db_check_hints");
@@ -1907,7 +1957,7 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
   if (!db->d_hint_scores) HIPCHK(hipMalloc(&db->d_hint_scores, sizeof(int) * (size_t)CC_CHK_STRIDE * CC_NSCORE));
   cc_qlane &ln = db->lane[0];
   {
-    const int arc = lane_alloc_modes(db, ln, rank, detail);
+    const int arc = lane_alloc_modes(db, ln, rank, detail, match);
     if (arc != CC_OK) return arc;
   }
   HIPCHK(hipEventRecord(ln.done, stream));  // start after what the caller queued
@@ -1927,11 +1977,11 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
       if (h_hints[i].seq_tgt >= ql.n_cont[h_hints[i].level - 1])
         return set_err(CC_EINVAL, "cc_db_check_hints: hint names a contour of the query scan that does not exist");
   }
-  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr);  // any database: 64-stride
+  rc = launch_scoring_chain(db, ln, 1, CP, lb, ub, max_fine_opt, nullptr, db->d_hint_scores, false, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr, match);  // any database: 64-stride
   if (rc != CC_OK) return rc;
   std::vector<int> sc((size_t)CC_CHK_STRIDE * CC_NSCORE);
   std::vector<unsigned char> ok(CC_CHK_STRIDE);
-  rc = results_copy_back(cc_chunk{ln, 0, 1, false, nullptr}, rank, detail);
+  rc = results_copy_back(cc_chunk{ln, 0, 1, false, nullptr}, rank, detail, match);
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpyAsync(sc.data(), db->d_hint_scores, sizeof(int) * sc.size(), hipMemcpyDeviceToHost, ln.stream));
   HIPCHK(hipMemcpyAsync(ok.data(), ln.d_pass_ok, ok.size(), hipMemcpyDeviceToHost, ln.stream));
@@ -1940,6 +1990,7 @@ static int check_hints_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_h
   *h_res = ln.h_results[0];
   if (rank) rank_deliver(ln, *rank, 0, 1, max_fine_opt);
   if (detail) memcpy(detail, ln.h_detail, sizeof(cc_ranked_detail_t) * (size_t)rank->max_ret);
+  if (match) memcpy(match->h_match, ln.h_match, sizeof(cc_ranked_match_t) * (size_t)rank->max_ret);
   if (h_scores)
     for (int i = 0; i < n_hints; i++) {
       const int *p = &sc[(size_t)i * CC_NSCORE];
@@ -2028,13 +2079,14 @@ int cc_db_debug_cands(cc_db *db, cc_cand_dbg_t *h_out, int cap, int *n_out) {
 static int check_hints_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                  const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
                                  const cc_rank_out_t *rank,
-    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
+                                 const cc_match_out_t *match = nullptr) {
   if (!db || !h_qdesc) return set_err(CC_EINVAL, "cc_db_check_hints_host: bad argument");
   HIPCHK(hipSetDevice(db->device));
   int rc = stage_reserve(db, 1);
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t), hipMemcpyHostToDevice));
-  return check_hints_impl(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr, rank, detail);
+  return check_hints_impl(db, db->d_stage, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, nullptr, rank, detail, match);
 }
 int cc_db_check_hints_host(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                            const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores) {
@@ -2091,7 +2143,8 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
                               const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                               cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank,
     cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
-                              const cc_rec_src *rec = nullptr /*the queries are packed records: d_qdesc is nullptr, n_desc their number*/) {
+                              const cc_rec_src *rec = nullptr /*the queries are packed records: d_qdesc is nullptr, n_desc their number*/,
+                              const cc_match_out_t *match = nullptr /*with rank: where the chunks' match rows go (validated by the entry point), or nullptr*/) {
   {  // everything that can be refused is refused before anything is queued or collected
     const int vrc = verify_validate(db, rec ? (const void *)rec->hot : (const void *)d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rec != nullptr);
     if (vrc != CC_OK) return vrc;
@@ -2106,7 +2159,7 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
   cc_chunk_plan plan;
   plan.alloc = [&](cc_qlane &ln) -> int {
     const int rc = lane_alloc_verify(ln);
-    return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail);
+    return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail, match);
   };
   plan.stage = [&](const cc_chunk &c) {  // the chunk's table, packed: [nb] | [nb][CC_VERIFY_CANDS_MAX]
     int *h_sel = c.ln.h_vin, *h_cl = c.ln.h_vin + c.nb;
@@ -2128,10 +2181,10 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
     return CC_OK;
   };
   plan.body = [&](const cc_chunk &c) -> int {
-    return launch_scoring_chain(db, c.ln, c.nb, CP, lb, ub, cfg->max_fine_opt, c.ev, nullptr, c.zc, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr);
+    return launch_scoring_chain(db, c.ln, c.nb, CP, lb, ub, cfg->max_fine_opt, c.ev, nullptr, c.zc, CC_KNN_MAX, rank ? rank->max_ret : 0, detail != nullptr, match);
   };
-  plan.copy_back = [&](const cc_chunk &c) -> int { return results_copy_back(c, rank, detail); };
-  plan.note = [&](const cc_chunk &c) { results_note(c.ln, h_res, rank, detail, cfg->max_fine_opt); };
+  plan.copy_back = [&](const cc_chunk &c) -> int { return results_copy_back(c, rank, detail, match); };
+  plan.note = [&](const cc_chunk &c) { results_note(c.ln, h_res, rank, detail, cfg->max_fine_opt, match); };
   return submit_chunks(db, n, (hipStream_t)stream_, plan);
 }
 int cc_db_verify_submit(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
@@ -2167,7 +2220,8 @@ int cc_db_verify_batch(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, con
 static int verify_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                                   const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
                                   const cc_rank_out_t *rank,
-    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/) {
+    cc_ranked_detail_t *detail /*with rank: where the chunks' detail rows go, or nullptr*/,
+                                  const cc_match_out_t *match = nullptr) {
   {
     const int vrc = verify_validate(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res);
     if (vrc != CC_OK) return vrc;
@@ -2178,7 +2232,7 @@ static int verify_batch_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, int 
   if (rc != CC_OK) return rc;
   HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)n_desc, hipMemcpyHostToDevice));
   if (!rank) return cc_db_verify_batch(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr);
-  return run_sync(db, [&] { return verify_submit_impl(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail); });
+  return run_sync(db, [&] { return verify_submit_impl(db, db->d_stage, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, nullptr, nullptr, nullptr, rank, detail, nullptr, match); });
 }
 int cc_db_verify_batch_host(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
                             const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res) {
@@ -2390,12 +2444,13 @@ int cc_db_query_submit_masked(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc
 
 // ... with host descriptors and a host table: both are staged on the device (the table in a buffer of the handle's that grows
 // on demand; the call is synchronous, so the next one finds it free), then the submit above and the wait.
-int cc_db_query_batch_host_masked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
-                                  const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
-                                  const cc_scan_mask_t *mask) {
+// (fn: the entry point's name for the refusals of its modes; the messages of the body name the masked host form, whose body it is)
+static int query_batch_host_masked_impl(const char *fn, cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                        const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                                        const cc_scan_mask_t *mask, const cc_match_out_t *match) {
   if (!db || !h_qdesc || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch_host_masked: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch_host_masked");
-  int rc = packed_modes(__func__, rank, h_detail);
+  int rc = packed_modes(fn, rank, h_detail);
   if (rc != CC_OK) return rc;
   if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch_host_masked: thresholds must satisfy lb.strictSmaller(ub)");
   for (int i = 0; i < nq; i++)
@@ -2423,7 +2478,103 @@ int cc_db_query_batch_host_masked(cc_db *db, const cc_scan_desc_t *h_qdesc, int 
     dm = *mask;
     dm.bits = db->d_mask_stage;
   }
-  return run_sync(db, [&] { return query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank, h_detail, nullptr, nullptr, mask ? &dm : nullptr); });
+  return run_sync(db, [&] { return query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank, h_detail, nullptr, nullptr, mask ? &dm : nullptr, match); });
+}
+int cc_db_query_batch_host_masked(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                  const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                                  const cc_scan_mask_t *mask) {
+  return query_batch_host_masked_impl(__func__, db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank, h_detail, mask, nullptr);
+}
+
+// ---- the matched contour pairs behind each ranked entry (include/cont2_amd_matches.h; k_merge.h: the _m instances, k_match.h) ----
+// One entry point per flow with the flow's most general argument list, then `match`; match NULL is the existing call of the same
+// arguments.  The refusals of `match` come first (want_match), then the underlying call's.
+#define CC_WANT_MATCH()                                        \
+  if (match) {                                                 \
+    const int mrc_ = want_match(__func__, db, rank, match);    \
+    if (mrc_ != CC_OK) return mrc_;                            \
+  }
+int cc_db_query_submit_matched(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_packed_src_t *src, const int32_t *h_rec, int nq,
+                               const int32_t *h_epoch, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn,
+                               int32_t *d_knn_cnt, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                               const cc_scan_mask_t *mask, const cc_match_out_t *match) {
+  if (!match) return cc_db_query_submit_masked(db, d_qdesc, src, h_rec, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, mask);
+  CC_WANT_MATCH();
+  if ((d_qdesc != nullptr) == (src != nullptr)) return set_err(CC_EINVAL, "cc_db_query_submit_matched: exactly one of d_qdesc and src must be given");
+  int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  if (!src) return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, nullptr, nullptr, mask, match);
+  cc_rec_src rs;
+  vrc = packed_resolve(__func__, db, src, &rs);
+  if (vrc != CC_OK) return vrc;
+  return query_submit_impl(db, nullptr, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, &rs, h_rec, mask, match);
+}
+int cc_db_query_batch_host_matched(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                   const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                                   const cc_scan_mask_t *mask, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  return query_batch_host_masked_impl(__func__, db, h_qdesc, nq, h_epoch, lb, ub, h_res, rank, h_detail, mask, match);
+}
+int cc_db_query_scan_batch_submit_matched(cc_db *db, cc_scan *const *scans, int n, const int32_t *h_epoch, const cc_score_t *lb,
+                                          const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank,
+                                          cc_ranked_detail_t *h_detail, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  const int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  if (lb && ub && !thres_strict_smaller(lb, ub))  // (before the handles are gathered: a refused call queues nothing)
+    return set_err(CC_EINVAL, "cc_db_query_scan_batch_submit_matched: thresholds must satisfy lb.strictSmaller(ub)");
+  return query_scan_batch_submit_impl(db, scans, n, h_epoch, lb, ub, h_res, rank, h_detail, match);
+}
+int cc_db_verify_submit_matched(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc, const cc_packed_src_t *src, const int32_t *h_qidx,
+                                const int32_t *h_cands, int n, const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub,
+                                cc_query_result_t *h_res, cc_hint_t *d_hints, int32_t *d_n_hints, void *stream_, const cc_rank_out_t *rank,
+                                cc_ranked_detail_t *h_detail, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  if ((d_qdesc != nullptr) == (src != nullptr)) return set_err(CC_EINVAL, "cc_db_verify_submit_matched: exactly one of d_qdesc and src must be given");
+  int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  if (!src) return verify_submit_impl(db, d_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank, h_detail, nullptr, match);
+  cc_rec_src rs;
+  vrc = packed_resolve(__func__, db, src, &rs);
+  if (vrc != CC_OK) return vrc;
+  return verify_submit_impl(db, nullptr, rs.n_rec, h_qidx, h_cands, n, cfg, lb, ub, h_res, d_hints, d_n_hints, stream_, rank, h_detail, &rs, match);
+}
+int cc_db_verify_batch_host_matched(cc_db *db, const cc_scan_desc_t *h_qdesc, int n_desc, const int32_t *h_qidx, const int32_t *h_cands, int n,
+                                    const cc_verify_cfg_t *cfg, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res,
+                                    const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  const int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  return verify_batch_host_impl(db, h_qdesc, n_desc, h_qidx, h_cands, n, cfg, lb, ub, h_res, rank, h_detail, match);
+}
+int cc_db_check_hints_matched(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                              const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores, void *stream_,
+                              const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  const int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  return check_hints_impl(db, d_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, stream_, rank, h_detail, match);
+}
+int cc_db_check_hints_host_matched(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
+                                   const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
+                                   const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  const int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank, h_detail, match);
+}
+#undef CC_WANT_MATCH
+// host only: the pairs of a row in key order
+int cc_match_pairs(const cc_ranked_match_t *m, cc_match_pair_t *out, int cap) {
+  if (!m) return -1;
+  int n = 0;
+  for (int w = 0; w < 7; w++)
+    for (uint64_t b = m->pairs[w]; b; b &= b - 1) {
+      const int bit = w * 64 + __builtin_ctzll(b);
+      if (out && n < cap) out[n] = cc_match_pair_t{(int8_t)(bit / 100 + 1), (int8_t)((bit % 100) / 10), (int8_t)(bit % 10), 0};
+      n++;
+    }
+  return n;
 }
 
 // Parity / debug: which retrieval the query chunks submitted so far ran

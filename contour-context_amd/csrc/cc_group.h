@@ -343,3 +343,14 @@ __device__ __forceinline__ int cc_wave_scan_total(int incl) {
   return __shfl(incl, 63);
 #endif
 }
+// sum and maximum of a double over the wave's 64 lanes, result in every lane; ALL 64 lanes must be active at the call.
+// The sum: the row sums on DPP moves (cc_group_sum_d), then the four rows' totals in a fixed order -- the same association on
+// the device and on the CPU harness.  The maximum (order-free): six butterfly steps.
+__device__ __forceinline__ double cc_wave_sum_d(double v) {
+  v = cc_group_sum_d(v);
+  return (__shfl(v, 0) + __shfl(v, 16)) + (__shfl(v, 32) + __shfl(v, 48));
+}
+__device__ __forceinline__ double cc_wave_max_d(double v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  return v;
+}

@@ -27,6 +27,7 @@
 #include "../../include/cont2_amd_rig.h"
 #include "../../include/cont2_amd_paths.h"
 #include "../../include/cont2_amd_cands.h"
+#include "../../include/cont2_amd_matches.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
 #include "k_image.h"
@@ -38,6 +39,7 @@
 #include "k_merge.h"
 #include "k_gmm.h"
 #include "k_gmm_hess.h"
+#include "k_match.h"
 #include "k_verify.h"
 #include "k_pose.h"
 #include "k_prep_packed.h"

@@ -37,6 +37,13 @@ struct cc_cand_post {  // dynamic thresholds: what tidyUpCandidates' post bars t
   float area_perc;
   int pad;
 };
+struct cc_match_rec {  // matched chains: the selected proposal of a candidate that goes on to the correlation (cc_k_match_emit reads it)
+  unsigned long long bits[7];  // constell_ as cc_dprop keeps it
+  int vote_cnt, nprops;        // anch_props_[0].vote_cnt_ after the swap, anch_props_.size()
+  float area_perc;             // anch_props_[0].area_perc_
+  int pad;
+};
+static_assert(sizeof(cc_match_rec) == 72, "cc_match_rec: 72 bytes at the problem's place");
 struct cc_qstate {
   int n_cand;  // candidates_.size() before tidyUpCandidates
   int flags;
@@ -60,13 +67,16 @@ static_assert(CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE) <= 32767, "check slots and list 
 static_assert(CC_MERGE_BLOCK == 64, "the list building below uses wave ballots");
 
 // grid = nq, block = CC_MERGE_BLOCK
-template <int KM>
+// MATCH (the _m instances, chains that asked for matches): the selected proposal of every candidate that goes on to the
+// correlation is written to mrec at the problem's place as well; nothing else differs.
+template <int KM, bool MATCH = false>
 __device__ __forceinline__ void cc_merge_body(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *qdesc,
                                               const cc_hot_desc_t *db_desc, const cc_pass_rec *pass, const unsigned char *pass_ok,
                                               const int *pass_cnt, cc_cand_out *cands_all, cc_qstate *qstate,
                                               cc_gmm_problem *probs /*[nq][CC_MAXCAND]: problem of candidate k of query q*/,
                                               int *prob_list /*dense list of the problems that exist*/, int *n_prob,
-                                              cc_cand_post *post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
+                                              cc_cand_post *post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/,
+                                              cc_match_rec *mrec = nullptr /*MATCH only: [nq][CC_MAXCAND] at the problem's place*/) {
   __shared__ cc_merge_lds<CC_CHK_STRIDE_K(KM)> L;
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (q >= nq) return;
@@ -313,6 +323,15 @@ __device__ __forceinline__ void cc_merge_body(int nq, cc_score_t lb, int n_row, 
           cp.pad = 0;
           post[gi] = cp;
         }
+        if constexpr (MATCH) {
+          cc_match_rec mr;
+          for (int w = 0; w < 7; w++) mr.bits[w] = p0->bits[w];
+          mr.vote_cnt = p0->vote_cnt;
+          mr.nprops = c->nprops;
+          mr.area_perc = p0->area_perc;
+          mr.pad = 0;
+          mrec[gi] = mr;
+        }
       }
     }
     L.want[k] = gi >= 0 ? 1 : 0;
@@ -357,4 +376,20 @@ cc_k_merge_l(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *_
              cc_cand_post *__restrict__ post /*dynamic thresholds: [nq][CC_MAXCAND] at the problem's place, else nullptr*/) {
   cc_merge_body<CC_KNN_MAX_LARGE>(nq, lb, n_row, n_col, qdesc, db_desc, pass, pass_ok, pass_cnt, cands_all, qstate, probs, prob_list, n_prob, post);
 }
-
+// the matched instances: the same replay, and the selected proposal of every problem to mrec[problem]
+__global__ void __launch_bounds__(CC_MERGE_BLOCK)
+cc_k_merge_m(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__restrict__ qdesc,
+             const cc_hot_desc_t *__restrict__ db_desc, const cc_pass_rec *__restrict__ pass, const unsigned char *__restrict__ pass_ok,
+             const int *__restrict__ pass_cnt, cc_cand_out *__restrict__ cands_all, cc_qstate *__restrict__ qstate,
+             cc_gmm_problem *__restrict__ probs, int *__restrict__ prob_list, int *__restrict__ n_prob,
+             cc_match_rec *__restrict__ mrec /*[nq][CC_MAXCAND] at the problem's place*/) {
+  cc_merge_body<CC_KNN_MAX, true>(nq, lb, n_row, n_col, qdesc, db_desc, pass, pass_ok, pass_cnt, cands_all, qstate, probs, prob_list, n_prob, nullptr, mrec);
+}
+__global__ void __launch_bounds__(CC_MERGE_BLOCK)
+cc_k_merge_lm(int nq, cc_score_t lb, int n_row, int n_col, const cc_hot_desc_t *__restrict__ qdesc,
+              const cc_hot_desc_t *__restrict__ db_desc, const cc_pass_rec *__restrict__ pass, const unsigned char *__restrict__ pass_ok,
+              const int *__restrict__ pass_cnt, cc_cand_out *__restrict__ cands_all, cc_qstate *__restrict__ qstate,
+              cc_gmm_problem *__restrict__ probs, int *__restrict__ prob_list, int *__restrict__ n_prob,
+              cc_match_rec *__restrict__ mrec /*[nq][CC_CHK_STRIDE_K(CC_KNN_MAX_LARGE)] at the problem's place*/) {
+  cc_merge_body<CC_KNN_MAX_LARGE, true>(nq, lb, n_row, n_col, qdesc, db_desc, pass, pass_ok, pass_cnt, cands_all, qstate, probs, prob_list, n_prob, nullptr, mrec);
+}

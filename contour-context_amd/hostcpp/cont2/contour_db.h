@@ -7,6 +7,7 @@
 
 #include "../tools/bm_util.h"
 #include "contour_mng.h"
+#include "../../../include/cont2_amd_matches.h"
 
 // The reference's DYNAMIC_THRES=1 build (CMakeLists.txt:19-20; contour_db.h:439-466, 566-574) raises the lower bars of a
 // query's checks from candidate to candidate inside CandidateManager.  Built with that macro, every database of this mirror
@@ -72,11 +73,16 @@ class ContourDB {
     std::shared_ptr<std::vector<int32_t>> nblock;           // [batch]
     bool detail = false;                                    // setWantDetail when the scan was queued: the batch's detail rows
     std::shared_ptr<std::vector<cc_ranked_detail_t>> dblock; // [batch][max_ret], travels with rblock
+    double matches = -1.0;                                  // setWantMatches when the scan was queued (< 0: off): the batch's match rows
+    std::shared_ptr<std::vector<cc_ranked_match_t>> mblock; // [batch][max_ret], travels with rblock
     cc_query_result_t *result() const { return block->data() + idx; }
   };
   bool want_detail_ = false;  // setWantDetail: the answers go through the ranked calls' _detail forms (also with max_ret_ == 1)
   mutable std::vector<cc_ranked_detail_t> last_details_;  // lastDetails()
-  bool rankedPath() const { return max_ret_ > 1 || want_detail_; }
+  double want_matches_ = -1.0;  // setWantMatches: inlier_px, or < 0: off.  On: the answers go through the *_matched forms (also with max_ret_ == 1)
+  mutable std::vector<cc_ranked_match_t> last_matches_;  // lastMatches()
+  bool wantMatches() const { return want_matches_ >= 0.0; }
+  bool rankedPath() const { return max_ret_ > 1 || want_detail_ || wantMatches(); }
   int max_ret_ = 1;  // setMaxReturn: entries queryRangedKNN / verifyCandidates hand out (fineOptimize's ret_size, contour_db.h:630)
   static constexpr int SPEC_LOW = 2;  // fewer answers than this queued ahead of the driver: a step goes out with whatever has been published
   mutable std::deque<Spec> spec_;   // scans appended ahead of the driver, oldest first (spec_[j] sits at DB index n_official + j)
@@ -224,11 +230,18 @@ class ContourDB {
       std::shared_ptr<std::vector<cc_ranked_cand_t>> rblock;
       std::shared_ptr<std::vector<int32_t>> nblock;
       std::shared_ptr<std::vector<cc_ranked_detail_t>> dblock;
-      if (rankedPath()) {  // the answers carry their ranked lists (and, if wanted, the detail rows)
+      std::shared_ptr<std::vector<cc_ranked_match_t>> mblock;
+      if (rankedPath()) {  // the answers carry their ranked lists (and, if wanted, the detail and the match rows)
         rblock = std::make_shared<std::vector<cc_ranked_cand_t>>((size_t)n * max_ret_);
         nblock = std::make_shared<std::vector<int32_t>>((size_t)n);
         const cc_rank_out_t ro = {rblock->data(), nblock->data(), max_ret_, 0};
-        if (want_detail_) {
+        if (wantMatches()) {
+          if (want_detail_) dblock = std::make_shared<std::vector<cc_ranked_detail_t>>((size_t)n * max_ret_);
+          mblock = std::make_shared<std::vector<cc_ranked_match_t>>((size_t)n * max_ret_);
+          const cc_match_out_t mo = {mblock->data(), want_matches_};
+          if (cc_db_query_scan_batch_submit_matched(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data(), &ro, want_detail_ ? dblock->data() : nullptr, &mo) != CC_OK)
+            die_cc();
+        } else if (want_detail_) {
           dblock = std::make_shared<std::vector<cc_ranked_detail_t>>((size_t)n * max_ret_);
           if (cc_db_query_scan_batch_submit_ranked_detail(db_, scans, n, epoch, &last_lb_, &last_ub_, block->data(), &ro, dblock->data()) != CC_OK)
             die_cc();
@@ -255,6 +268,8 @@ class ContourDB {
         sp.nblock = nblock;
         sp.detail = want_detail_;
         sp.dblock = dblock;
+        sp.matches = want_matches_;
+        sp.mblock = mblock;
         spec_.push_back(std::move(sp));
       }
       pos += (size_t)n;
@@ -353,6 +368,14 @@ class ContourDB {
   void setWantDetail(bool on) { want_detail_ = on; }  // (answers queued with another setting are asked again, as for setMaxReturn)
   bool wantDetail() const { return want_detail_; }
   const std::vector<cc_ranked_detail_t> &lastDetails() const { return last_details_; }
+  // Mirror-only: collect, next to every candidate queryRangedKNN / queryStored / queryAllowed / verifyCandidates / verifyStored hands
+  // out, its cc_ranked_match_t (include/cont2_amd_matches.h): the matched contour pairs the pose was built from -- what the reference
+  // keeps in CandidateManager (anch_props_[0].constell_) and its drivers draw -- the proposal's votes and area, and the pairs'
+  // residuals at the returned pose with the number within inlier_px pixels.  lastMatches() after the call, one row per returned
+  // candidate, in their order; cc_match_pairs() lists a row's pairs.  A negative value (the default) switches it off: the calls the
+  // mirror always made.  (Answers queued with another setting are asked again, as for setMaxReturn.)
+  void setWantMatches(double inlier_px) { want_matches_ = inlier_px >= 0.0 ? inlier_px : -1.0; }
+  const std::vector<cc_ranked_match_t> &lastMatches() const { return last_matches_; }
 
   // contour_db.h:698-703
   void queryRangedKNN(const std::shared_ptr<const ContourManager> &q_ptr, const CandidateScoreEnsemble &thres_lb,
@@ -366,10 +389,13 @@ class ContourDB {
     cc_query_result_t r;
     cc_ranked_cand_t rl[CC_RANK_MAX];  // the ranked list (rankedPath())
     cc_ranked_detail_t dl[CC_RANK_MAX];  // ... and its detail rows (want_detail_)
+    cc_ranked_match_t ml[CC_RANK_MAX];   // ... and its match rows (wantMatches())
     int32_t rn = 0;
     const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
-    const bool rk = rankedPath();
+    const cc_match_out_t mo = {ml, want_matches_};
+    const bool rk = rankedPath(), wm = wantMatches();
     last_details_.clear();
+    last_matches_.clear();
     TicToc wall;
     if (need_rebuild_) rebuild();
     last_lb_ = lb;
@@ -377,7 +403,7 @@ class ContourDB {
     have_thres_ = true;
     cc_scan *qh = q_ptr->scanHandle();
     if (!spec_.empty() && qh && spec_.front().scan == qh && same(spec_.front().lb, lb) && same(spec_.front().ub, ub) &&
-        spec_.front().max_ret == max_ret_ && spec_.front().detail == want_detail_) {
+        spec_.front().max_ret == max_ret_ && spec_.front().detail == want_detail_ && spec_.front().matches == want_matches_) {
       // the answer was queued when the scan was published (at the epoch the database is officially in now); only ITS chain is
       // waited for, the queries queued behind it stay in flight
       collectOne(0);
@@ -387,6 +413,7 @@ class ContourDB {
         rn = (*sp.nblock)[sp.idx];
         std::copy(sp.rblock->begin() + (size_t)sp.idx * max_ret_, sp.rblock->begin() + (size_t)(sp.idx + 1) * max_ret_, rl);
         if (want_detail_) std::copy(sp.dblock->begin() + (size_t)sp.idx * max_ret_, sp.dblock->begin() + (size_t)(sp.idx + 1) * max_ret_, dl);
+        if (wm) std::copy(sp.mblock->begin() + (size_t)sp.idx * max_ret_, sp.mblock->begin() + (size_t)(sp.idx + 1) * max_ret_, ml);
       }
       n_spec_hit_++;
     } else {
@@ -394,7 +421,8 @@ class ContourDB {
       const int32_t epoch = (int32_t)all_bevs_.size();  // the scans appended ahead of the driver are hidden by the epoch
       int rc;
       if (qh && cc_scan_on_device(qh)) {
-        rc = want_detail_ ? cc_db_query_scan_batch_submit_ranked_detail(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro, dl)
+        rc = wm           ? cc_db_query_scan_batch_submit_matched(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro, want_detail_ ? dl : nullptr, &mo)
+             : want_detail_ ? cc_db_query_scan_batch_submit_ranked_detail(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro, dl)
              : rk         ? cc_db_query_scan_batch_submit_ranked(db_, &qh, 1, &epoch, &lb, &ub, &r, &ro)
                           : cc_db_query_scan_submit(db_, qh, epoch, &lb, &ub, &r);
         const int r2 = cc_db_query_wait(db_);
@@ -402,7 +430,8 @@ class ContourDB {
         if (rc == CC_OK) rc = r2;
       } else {  // a scan that was offloaded goes by its host copy
         collectSpec();
-        rc = want_detail_ ? cc_db_query_batch_host_ranked_detail(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro, dl)
+        rc = wm           ? cc_db_query_batch_host_matched(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro, want_detail_ ? dl : nullptr, nullptr, &mo)
+             : want_detail_ ? cc_db_query_batch_host_ranked_detail(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro, dl)
              : rk         ? cc_db_query_batch_host_ranked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro)
                           : cc_db_query_batch_host(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r);
       }
@@ -419,16 +448,17 @@ class ContourDB {
         stp.addSample("L2 opt", (ms[3] + ms[4]) * 1e-3);
       }
     }
-    handOut(rk, r, rl, rn, dl, cand_ptrs, cand_corr, cand_tf);
+    handOut(rk, r, rl, rn, dl, ml, cand_ptrs, cand_corr, cand_tf);
   }
-  // an answer as the reference's result vectors hold it: the ranked list (with its detail rows), or the one candidate of the plain
-  // call.  Returns the number of entries.
-  int handOut(bool ranked, const cc_query_result_t &r, const cc_ranked_cand_t *rl, int rn, const cc_ranked_detail_t *dl,
+  // an answer as the reference's result vectors hold it: the ranked list (with its detail and match rows), or the one candidate of
+  // the plain call.  Returns the number of entries.
+  int handOut(bool ranked, const cc_query_result_t &r, const cc_ranked_cand_t *rl, int rn, const cc_ranked_detail_t *dl, const cc_ranked_match_t *ml,
               std::vector<std::shared_ptr<const ContourManager>> &res_cand, std::vector<double> &res_corr,
               std::vector<Eigen::Isometry2d> &res_T) const {
     if (ranked) {
       for (int k = 0; k < rn; k++) pushRanked(all_bevs_, rl[k], res_cand, res_corr, res_T);
       if (want_detail_) last_details_.assign(dl, dl + rn);
+      if (wantMatches()) last_matches_.assign(ml, ml + rn);
       return rn;
     }
     if (r.n_res > 0) {
@@ -462,14 +492,18 @@ class ContourDB {
     const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
     const bool rk = rankedPath();
     last_details_.clear();
+    last_matches_.clear();
+    cc_ranked_match_t ml[CC_RANK_MAX];
+    const cc_match_out_t mo = {ml, want_matches_};
     const cc_packed_src_t own = {nullptr, nullptr, 0, 0};
     const int32_t rec = idx, ep = epoch;
-    int rc = cc_db_query_submit_packed(db_, &own, &rec, 1, &ep, &lb, &ub, &r, nullptr, nullptr, nullptr, rk ? &ro : nullptr, want_detail_ ? dl : nullptr);
+    int rc = wantMatches() ? cc_db_query_submit_matched(db_, nullptr, &own, &rec, 1, &ep, &lb, &ub, &r, nullptr, nullptr, nullptr, &ro, want_detail_ ? dl : nullptr, nullptr, &mo)
+                           : cc_db_query_submit_packed(db_, &own, &rec, 1, &ep, &lb, &ub, &r, nullptr, nullptr, nullptr, rk ? &ro : nullptr, want_detail_ ? dl : nullptr);
     const int r2 = cc_db_query_wait(db_);
     for (auto &sp : spec_) sp.collected = true;  // the wait collected every chain in flight
     if (rc == CC_OK) rc = r2;
     if (rc != CC_OK) die_cc();
-    handOut(rk, r, rl, rn, dl, cand_ptrs, cand_corr, cand_tf);
+    handOut(rk, r, rl, rn, dl, ml, cand_ptrs, cand_corr, cand_tf);
   }
   // Mirror-only: queryRangedKNN among the scans the caller allows -- scans of this database by their index in adding order
   // (another session's part of the map, the scans near a position prior, everything but a retired key frame) -- as if the other
@@ -499,10 +533,14 @@ class ContourDB {
     const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
     const bool rk = rankedPath();
     last_details_.clear();
-    const int rc = cc_db_query_batch_host_masked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, rk ? &ro : nullptr, want_detail_ ? dl : nullptr, &mask);
+    last_matches_.clear();
+    cc_ranked_match_t ml[CC_RANK_MAX];
+    const cc_match_out_t mo = {ml, want_matches_};
+    const int rc = wantMatches() ? cc_db_query_batch_host_matched(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro, want_detail_ ? dl : nullptr, &mask, &mo)
+                                 : cc_db_query_batch_host_masked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, rk ? &ro : nullptr, want_detail_ ? dl : nullptr, &mask);
     for (auto &sp : spec_) sp.collected = true;  // the synchronous call (its wait) collected every chain in flight
     if (rc != CC_OK) die_cc();
-    handOut(rk, r, rl, rn, dl, cand_ptrs, cand_corr, cand_tf);
+    handOut(rk, r, rl, rn, dl, ml, cand_ptrs, cand_corr, cand_tf);
   }
   // one entry of a ranked list as the reference's result vectors hold it
   template <class Scans>
@@ -570,22 +608,27 @@ class ContourDB {
     cc_ranked_detail_t dl[CC_RANK_MAX];
     const cc_rank_out_t ro = {rl, &rn, max_ret, 0};
     last_details_.clear();
-    const bool rk = max_ret > 1 || want_detail_;
+    last_matches_.clear();
+    cc_ranked_match_t ml[CC_RANK_MAX];
+    const cc_match_out_t mo = {ml, want_matches_};
+    const bool wm = wantMatches(), rk = max_ret > 1 || want_detail_ || wm;
     int rc;
     if (q) {
-      rc = want_detail_ ? cc_db_verify_batch_host_ranked_detail(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro, dl)
+      rc = wm           ? cc_db_verify_batch_host_matched(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro, want_detail_ ? dl : nullptr, &mo)
+           : want_detail_ ? cc_db_verify_batch_host_ranked_detail(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro, dl)
            : max_ret > 1 ? cc_db_verify_batch_host_ranked(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r, &ro)
                          : cc_db_verify_batch_host(db_, &q->desc(), 1, nullptr, cands, 1, &vc, &lb, &ub, &r);
     } else {
       const cc_packed_src_t own = {nullptr, nullptr, 0, 0};
       const int32_t rec = idx;
-      rc = cc_db_verify_submit_packed(db_, &own, &rec, cands, 1, &vc, &lb, &ub, &r, nullptr, nullptr, nullptr, rk ? &ro : nullptr, want_detail_ ? dl : nullptr);
+      rc = wm ? cc_db_verify_submit_matched(db_, nullptr, 0, &own, &rec, cands, 1, &vc, &lb, &ub, &r, nullptr, nullptr, nullptr, &ro, want_detail_ ? dl : nullptr, &mo)
+              : cc_db_verify_submit_packed(db_, &own, &rec, cands, 1, &vc, &lb, &ub, &r, nullptr, nullptr, nullptr, rk ? &ro : nullptr, want_detail_ ? dl : nullptr);
       const int r2 = cc_db_query_wait(db_);
       if (rc == CC_OK) rc = r2;
     }
     for (auto &sp : spec_) sp.collected = true;  // the synchronous call (the wait) collected every chain in flight
     if (rc != CC_OK) die_cc();
-    return handOut(rk, r, rl, rn, dl, res_cand, res_corr, res_T);
+    return handOut(rk, r, rl, rn, dl, ml, res_cand, res_corr, res_T);
   }
   // Mirror-only as a database call: ConstellCorrelation's public interface (correlation.h:175-238) on scans of this database,
   // in one device pass (cc_db_pose_batch_host).  Per query: the candidate by its index in adding order (as verifyCandidates
@@ -824,6 +867,8 @@ class CandidateManager {
   std::vector<cc_hint_t> hints_;                                // cand_gidx = index into my_cands_ until the call is made
   bool want_detail_ = false;                      // setWantDetail
   std::vector<cc_ranked_detail_t> last_details_;  // lastDetails()
+  double want_matches_ = -1.0;                    // setWantMatches (< 0: off)
+  std::vector<cc_ranked_match_t> last_matches_;   // lastMatches()
   std::vector<std::shared_ptr<const ContourManager>> my_cands_;  // this manager's candidate scans, first-appearance order
   std::map<int, int> id2local_;                                 // the reference keys candidates_ by getIntID() (contour_db.h:468-476)
   int flow_valve = 0;
@@ -912,6 +957,10 @@ class CandidateManager {
   // hint flow); lastDetails() after fineOptimize, one row per returned candidate.  Off (the default): the calls made before.
   void setWantDetail(bool on) { want_detail_ = on; }
   const std::vector<cc_ranked_detail_t> &lastDetails() const { return last_details_; }
+  // Mirror-only: ... and their match rows (ContourDB::setWantMatches' counterpart: the constellation this manager merged for each
+  // returned candidate -- anch_props_[0].constell_ -- with its residuals at the refined pose); negative: off, the default.
+  void setWantMatches(double inlier_px) { want_matches_ = inlier_px >= 0.0 ? inlier_px : -1.0; }
+  const std::vector<cc_ranked_match_t> &lastMatches() const { return last_matches_; }
 
   // contour_db.h:604-648: returns the number of results (0 or 1; with max_ret > 1 -- mirror-only, the reference's ret_size is
   // hard-wired to 1 -- up to min(max_ret, max_fine_opt) refined candidates, best first)
@@ -930,18 +979,25 @@ class CandidateManager {
     std::vector<cc_hint_t> hs(hints_);
     for (auto &h : hs) h.cand_gidx = st_->pos[my_cands_[h.cand_gidx].get()];
     last_details_.clear();
-    if (max_ret > 1 || want_detail_) {
+    last_matches_.clear();
+    const bool wm = want_matches_ >= 0.0;
+    if (max_ret > 1 || want_detail_ || wm) {
       cc_ranked_cand_t rl[CC_RANK_MAX];
       cc_ranked_detail_t dl[CC_RANK_MAX];
+      cc_ranked_match_t ml[CC_RANK_MAX];
       int32_t rn = 0;
       const cc_rank_out_t ro = {rl, &rn, max_ret, 0};
-      const int rc = want_detail_ ? cc_db_check_hints_host_ranked_detail(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt,
+      const cc_match_out_t mo = {ml, want_matches_};
+      const int rc = wm ? cc_db_check_hints_host_matched(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r, nullptr, &ro,
+                                                         want_detail_ ? dl : nullptr, &mo)
+                     : want_detail_ ? cc_db_check_hints_host_ranked_detail(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt,
                                                                          &r, nullptr, &ro, dl)
                                   : cc_db_check_hints_host_ranked(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r,
                                                                   nullptr, &ro);
       if (rc != CC_OK) die();
       for (int k = 0; k < rn; k++) ContourDB::pushRanked(st_->keep, rl[k], res_cand, res_corr, res_T);
       if (want_detail_) last_details_.assign(dl, dl + rn);
+      if (wm) last_matches_.assign(ml, ml + rn);
       return rn;
     }
     if (cc_db_check_hints_host(st_->db, &cm_tgt_->desc(), hs.data(), (int)hs.size(), &lb, &ub, max_fine_opt, &r, nullptr) != CC_OK)

@@ -2,7 +2,9 @@
 // the class mirror: two KITTI .bin scans -> two ContourManagers -> every plausible anchor pair of the two scans goes
 // through CandidateManager::checkCandWithHint -> tidyUpCandidates -> fineOptimize -> score + 3-DoF pose (BEV frame and
 // sensor frame).  Output: one line per hint `H level seq_src seq_tgt  ovlp_sum max_one in_ang_rng  indiv_sim orie_sim`,
-// then `R n_res correlation x y theta  sens_x sens_y sens_theta`.
+// then `R n_res correlation x y theta  sens_x sens_y sens_theta`, then the evidence of the winning candidate (what the reference keeps
+// as anch_props_[0].constell_ and draws): `M n_pairs vote_cnt n_props area_perc  res_rms res_max n_inlier` (residuals of the
+// matched contours' centres at the refined pose, in pixels; inliers within 2 px) and one `P level seq_src seq_tgt` per matched pair.
 //   g++ -O2 -std=c++17 pair_demo.cpp -I.. -I../../../include -L../.. -lcont2_amd -Wl,-rpath,$PWD/../.. -L/opt/rocm/lib -lamdhip64
 //   ./pair_demo old.bin new.bin [max_fine_opt [image_prefix]]
 // With image_prefix the SAVE_MID_FILE artefacts of the reference drivers are written too: <prefix>_pair.png
@@ -68,6 +70,7 @@ int main(int argc, char **argv) {
   const ContourSimThresConfig cont_sim;
 
   CandidateManager cand_mng(cm_new, lb, ub);
+  if (!CC_MIRROR_DYNAMIC_THRES) cand_mng.setWantMatches(2.0);  // (a DYNAMIC_THRES=1 build has no match rows: the library refuses them there)
   // as if the key search had returned every key pair that is not absurdly far apart (kitti_read_bin_test.cpp:229-262);
   // anchors come from the levels that carry distance bits (1..4)
   for (int ll = 1; ll <= CC_BCI_LAYERS; ll++) {
@@ -95,5 +98,11 @@ int main(int argc, char **argv) {
   const Eigen::Isometry2d T_sens = ConstellCorrelation::getEstSensTF(res_T[0], config);
   printf("R %d %.9g %.9g %.9g %.9g  %.9g %.9g %.9g\n", n, res_corr[0], res_T[0](0, 2), res_T[0](1, 2),
          std::atan2(res_T[0](1, 0), res_T[0](0, 0)), T_sens(0, 2), T_sens(1, 2), std::atan2(T_sens(1, 0), T_sens(0, 0)));
+  if (cand_mng.lastMatches().empty()) return 0;
+  const cc_ranked_match_t &m = cand_mng.lastMatches()[0];
+  printf("M %d %d %d %.9g  %.9g %.9g %d\n", m.n_pairs, m.vote_cnt, m.n_props, m.area_perc, m.res_rms, m.res_max, m.n_inlier);
+  cc_match_pair_t pairs[400];
+  const int np = cc_match_pairs(&m, pairs, 400);
+  for (int i = 0; i < np; i++) printf("P %d %d %d\n", pairs[i].level, pairs[i].seq_src, pairs[i].seq_tgt);
   return 0;
 }

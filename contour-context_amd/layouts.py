@@ -91,6 +91,34 @@ def hess_matrix(h6):
     return np.array([[h[0], h[1], h[2]], [h[1], h[3], h[4]], [h[2], h[4], h[5]]])
 
 
+# cc_ranked_match_t / cc_match_out_t (include/cont2_amd_matches.h): the matched contour pairs behind a ranked entry -- the selected
+# proposal's constellation as a 400-bit set (bit (level-1)*100 + seq_src*10 + seq_tgt) and its residuals at the entry's pose
+ranked_match_dt = np.dtype([("pairs", "<u8", (7,)), ("n_pairs", "<i4"), ("vote_cnt", "<i4"), ("n_props", "<i4"), ("area_perc", "<f4"),
+                            ("res_rms", "<f8"), ("res_max", "<f8"), ("n_inlier", "<i4"), ("flags", "<i4")], align=True)
+assert ranked_match_dt.itemsize == 96
+
+
+class MatchOut(C.Structure):  # cc_match_out_t
+    _fields_ = [("h_match", C.c_void_p), ("inlier_px", C.c_double)]
+
+
+assert C.sizeof(MatchOut) == 16
+
+
+def match_buffers(n, max_ret, inlier_px):
+    """([n, max_ret] of ranked_match_dt, MatchOut pointing at it) for a *_matched call of n queries"""
+    rows = np.zeros((n, max(int(max_ret), 0)), ranked_match_dt)
+    return rows, MatchOut(rows.ctypes.data, float(inlier_px))
+
+
+def match_pairs(row):
+    """the pairs of one ranked_match_dt record in key order -> int8 [n_pairs, 3] of (level, seq_src, seq_tgt); what cc_match_pairs
+    gives in C"""
+    words = np.asarray(row["pairs"], np.uint64).reshape(7)
+    bits = [w * 64 + b for w in range(7) for b in range(64) if (int(words[w]) >> b) & 1]
+    return np.array([(b // 100 + 1, (b % 100) // 10, b % 10) for b in bits], np.int8).reshape(-1, 3)
+
+
 # caller-given relative poses (cc_db_pose_*): cc_pose_item_t, cc_pose_result_t, cc_pose_curv_t, cc_pose_cfg_t
 POSE_TRY_MAX = 8      # CC_POSE_TRY_MAX
 PF_REFINED = 0x100    # CC_PF_REFINED
