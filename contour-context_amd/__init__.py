@@ -25,7 +25,7 @@ import sharding  # noqa: E402,F401
 
 LIB_PATH = os.path.join(_HERE, "libcont2_amd.so")
 _SRCS = ["cont2_amd.hip", "cc_dev.h", "cc_group.h", "cc_hostcfg.h", "cc_sort.h", "cc_stats.h", "cc_fmath.h", "k_rasterize.h", "k_image.h", "k_contours.h", "k_contours_list.h",
-         "k_knn.h", "k_mask.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_match.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
+         "k_knn.h", "k_knn_list.h", "k_mask.h", "k_check.h", "k_merge.h", "k_gmm.h", "k_gmm_hess.h", "k_match.h", "k_verify.h", "k_pose.h", "k_prep_packed.h", "cc_hostdb.h", "cc_db_api.inc", "cc_comm.inc"]
 
 # how every gfx950 code object of this project that includes csrc/ headers is compiled: the library below and the device
 # probe library of the test suite (tests/dev_probe.py), so that what the probes measure is the code the library runs
@@ -807,6 +807,45 @@ class ScanMask:
         return self.bits.data_ptr(), int(self.bits.shape[0]), int(self.bits.shape[1]), self.rows
 
 
+class ScanLists:
+    """The scans that may answer a query as index lists (the among= of Database.query / query_submit; include/cont2_amd_lists.h):
+    list r is idx[off[r] : off[r + 1]] -- strictly increasing database indices, at most L.LIST_SCANS_MAX of them -- and rows names
+    one list per query (-1: no restriction; many queries may share a list).  A listed query answers exactly like the masked
+    query whose row has the list's bits set, but its retrieval reads the listed scans' keys only: its cost follows the list, not
+    the map (about 1 us per listed scan per 1 024 queries; it meets the masked walk near 960 scans per list at 5 000 scans:
+    DESIGN.md 3.13).  Everything is host memory and is read before the call returns; nothing has to be kept alive."""
+
+    def __init__(self, idx, off, rows):
+        self.idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        self.off = np.ascontiguousarray(off, np.int32).reshape(-1)
+        self.rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+
+    @classmethod
+    def from_lists(cls, lists, rows=None):
+        """lists: a sequence of index sequences, taken as they are (nothing is sorted or de-duplicated: the library refuses a list
+        that is not strictly increasing).  rows: the list of every query (default: query i names list i)."""
+        ls = [np.asarray(l, np.int64).reshape(-1) for l in lists]
+        off = np.zeros(len(ls) + 1, np.int64)
+        np.cumsum([len(l) for l in ls], out=off[1:])
+        idx = np.concatenate(ls) if ls else np.zeros(0, np.int64)
+        return cls(idx, off, np.arange(len(ls), dtype=np.int32) if rows is None else rows)
+
+    @classmethod
+    def from_gates(cls, xy, gates, rows=None):
+        """The lists of a position prior, made on the host: xy [n_scans, 2] the scans' positions, gates [n_rows, 3] of (x, y,
+        radius), numpy arrays or tensors.  List r holds the set bits of Context.gate_mask's row r (the same f32 expression)."""
+        to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)  # noqa: E731
+        idx, off = L.gate_lists(to_np(xy), to_np(gates))
+        return cls(idx, off, np.arange(len(off) - 1, dtype=np.int32) if rows is None else rows)
+
+    def lists(self):
+        """the lists as numpy arrays"""
+        return [self.idx[self.off[r]:self.off[r + 1]] for r in range(len(self.off) - 1)]
+
+    def _c(self):
+        return self.idx, self.off, self.rows
+
+
 class Database:
     """cc_db: device-resident ContourDB (contour_db.h:673-845) + batched queryRangedKNN."""
 
@@ -878,14 +917,18 @@ class Database:
         self._pending.append((objs, keep))
         return keep
 
-    def _query_kw(self, qdesc, epochs, mask):
-        """what query() and query_submit() hand to calls.query for their query, epochs and mask -> (keywords, device, nq)"""
+    def _query_kw(self, qdesc, epochs, mask, among=None):
+        """what query() and query_submit() hand to calls.query for their query, epochs, mask and lists -> (keywords, device, nq)"""
         if mask is not None and not isinstance(mask, ScanMask):
             raise TypeError("mask must be a ScanMask")
+        if among is not None and not isinstance(among, ScanLists):
+            raise TypeError("among must be a ScanLists")
+        if mask is not None and among is not None:
+            raise ValueError("give the scans that may answer as mask= or as among=, not both")
         kw, dev, stream = self._source(qdesc)
         epochs = np.ascontiguousarray(epochs, np.int32).reshape(-1)
         assert "src" in kw or qdesc.shape[0] == len(epochs)
-        kw.update(epochs=epochs, stream=stream, mask=None if mask is None else mask._c())
+        kw.update(epochs=epochs, stream=stream, mask=None if mask is None else mask._c(), among=None if among is None else among._c())
         return kw, dev, len(epochs)
 
     def add_scans_prepare(self, desc):
@@ -897,7 +940,8 @@ class Database:
 
     _detail_args = staticmethod(calls.detail_buffer)  # (kept under this name for tests/test_emu_ranked_detail.py, which asks it for the refusal)
 
-    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False, mask=None, matches=None):
+    def query(self, qdesc, epochs, lb=None, ub=None, want_knn=False, allow_flagged=False, ranked=None, detail=False, mask=None, matches=None,
+              among=None):
         """qdesc: torch uint8 CUDA [nq, DESC_BYTES]; epochs int32 [nq] (DB state each query sees).
         In the place of qdesc: self.stored(idx) -- scans of this database by index -- or Packed(hot, feat, idx): the query comes
         from the packed records instead of from descriptors (cc_db_query_submit_packed + the wait), with the same answers.
@@ -917,9 +961,12 @@ class Database:
         contour pairs its pose was built from (the selected proposal's constellation as a 400-bit set: match_pairs(row) lists
         them), the proposal's votes and area, and the pairs' residuals at the entry's pose: rms, max and how many lie within
         inlier_px pixels (cc_db_query_submit_matched).  It combines with stored / Packed queries, mask= and detail=True; a
-        database in dynamic-threshold mode refuses it.  Without ranked it is a ValueError."""
+        database in dynamic-threshold mode refuses it.  Without ranked it is a ValueError.
+        among=ScanLists(...): only the scans of each query's LIST may answer (cc_db_query_submit_listed + the wait): the answers of
+        the mask whose rows hold the lists' bits, from a retrieval that reads the listed scans' keys only.  It combines with every
+        form above except mask= (giving both is a ValueError)."""
         import torch
-        kw, dev, nq = self._query_kw(qdesc, epochs, mask)
+        kw, dev, nq = self._query_kw(qdesc, epochs, mask, among)
         knn = cnt = None
         if want_knn:
             ks = self.knn_stride
@@ -932,14 +979,15 @@ class Database:
             knn, cnt = knn.cpu().numpy().view(L.knn_hit_dt).reshape(nq, L.NQLEV, L.NPIV, ks), cnt.cpu().numpy()
         return _ret(r.res, knn, cnt, r.rank, r.detail, r.match)
 
-    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False, mask=None, matches=None):
+    def query_submit(self, qdesc, epochs, lb=None, ub=None, ranked=None, detail=False, mask=None, matches=None, among=None):
         """Asynchronous form of query(): queues the batch and returns the result array, which is only valid after
         query_wait() (cc_db_query_submit / cc_db_query_wait).  qdesc may be overwritten by work queued afterwards on the
         current stream.  ranked=K: returns (results, (cands [nq, K], counts [nq])), all of them valid after query_wait();
         with detail=True followed by the [nq, K] detail array (see query()).  qdesc may be self.stored(idx) or a Packed.
         mask=ScanMask(...): as for query(); the pending list keeps the mask's table alive until query_wait().
-        matches=inlier_px: followed by the [nq, K] match array (see query()), valid after query_wait() like the rest."""
-        kw, _dev, _nq = self._query_kw(qdesc, epochs, mask)
+        matches=inlier_px: followed by the [nq, K] match array (see query()), valid after query_wait() like the rest.
+        among=ScanLists(...): as for query(); the lists are read before this returns."""
+        kw, _dev, _nq = self._query_kw(qdesc, epochs, mask, among)
         r = calls.query(lib(), self.h, lb=lb, ub=ub, ranked=ranked, detail=detail, matches=matches, wait=False, keep=self._held(qdesc, mask), **kw)
         return _ret(r.res, r.rank, r.detail, r.match)
 

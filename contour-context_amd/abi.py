@@ -177,6 +177,11 @@ I cc_db_query_batch_host_matched PPIPPPPPPPP
 I cc_db_verify_batch_host_matched PPIPPIPPPPPPP
 I cc_db_check_hints_host_matched PPPIPPIPPPPP
 """,
+    "cont2_amd_lists.h": """
+I cc_db_query_submit_listed PPPPIPPPPPPPPPPP
+I cc_db_query_batch_host_listed PPIPPPPPPPP
+I cc_db_debug_knn_chunks_listed PP
+""",
 }
 ADDONS = {hdr: _table(spec) for hdr, spec in _ADDON_SPEC.items()}
 

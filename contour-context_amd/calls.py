@@ -9,7 +9,8 @@ with some of its chunks queued, and the library goes on writing into their buffe
 hands in `keep`, a list it holds until its wait, and the flow appends its buffers to it before the entry point is called.  Which
 entry point runs is behaviour (a synchronous *_batch cuts one chunk per lane, a submit + wait whole chunks):
   query    descriptors: cc_db_query_batch (wait) / cc_db_query_submit; ranked: cc_db_query_submit_ranked[_detail];
-           a record source: cc_db_query_submit_packed; a mask, either kind of query: cc_db_query_submit_masked
+           a record source: cc_db_query_submit_packed; a mask, either kind of query: cc_db_query_submit_masked;
+           per-query lists of scans (include/cont2_amd_lists.h), with whatever else the call has: cc_db_query_submit_listed
   verify   descriptors: cc_db_verify_batch (wait) / cc_db_verify_submit; ranked: cc_db_verify_submit_ranked[_detail];
            a record source: cc_db_verify_submit_packed
   hints    cc_db_check_hints[_ranked[_detail]] (synchronous by itself)
@@ -222,9 +223,11 @@ def _ranked_fn(stem, ro, det):
 
 
 def query(lib, db, epochs, qdesc=None, src=None, idx=None, mask=None, lb=None, ub=None, knn=None, knn_cnt=None, stream=None,
-          ranked=None, detail=False, matches=None, wait=True, tolerate=(), keep=None):
+          ranked=None, detail=False, matches=None, wait=True, tolerate=(), keep=None, among=None):
     """qdesc: the descriptors' address, or src: an L.PackedSrc with idx, its record selector (None: query i is record i).
-    mask: (bits address, n_rows, row_words, int32 rows [nq]).  matches: inlier_px (with ranked).  -> Out(res, rank, detail, match)"""
+    mask: (bits address, n_rows, row_words, int32 rows [nq]).  among: (int32 idx, int32 off [n_lists + 1], int32 rows [nq]), host
+    arrays -- list r is idx[off[r] : off[r + 1]], query i names list rows[i] or -1; not together with mask.
+    matches: inlier_px (with ranked).  -> Out(res, rank, detail, match)"""
     epochs = np.ascontiguousarray(epochs, np.int32).reshape(-1)
     nq = len(epochs)
     rk, ro, det = _rank(nq, ranked, detail) if ranked is not None or detail else (None, None, None)
@@ -243,9 +246,22 @@ def query(lib, db, epochs, qdesc=None, src=None, idx=None, mask=None, lb=None, u
             raise ValueError("the mask names rows for %d queries, the call has %d" % (len(rows), nq))
         cm = L.ScanMaskC(bits, int(n_rows), int(row_words), rows.ctypes.data)
         mask = (rows, cm)
+    cl = None
+    if among is not None:
+        if mask is not None:
+            raise ValueError("give the scans that may answer as mask= or as among=, not both")
+        l_idx, l_off, l_rows = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in among)
+        if len(l_rows) != nq:
+            raise ValueError("the lists name rows for %d queries, the call has %d" % (len(l_rows), nq))
+        if len(l_off) < 1 or (len(l_off) > 1 and int(l_off[-1]) > len(l_idx)):
+            raise ValueError("off must hold n_lists + 1 offsets into idx (%d entries)" % len(l_idx))
+        cl = L.ScanListsC(l_idx.ctypes.data, l_off.ctypes.data, len(l_off) - 1, l_rows.ctypes.data)
+        among = (l_idx, l_off, l_rows, cl)
     res = np.zeros(nq, L.query_result_dt)
     mid = (nq, epochs.ctypes.data, C.addressof(lb), C.addressof(ub), res.ctypes.data, knn, knn_cnt, stream)
-    if mo is not None:
+    if cl is not None:
+        fn, args = "cc_db_query_submit_listed", (db, None if src is not None else qdesc, _a(src), _a(idx)) + mid + (_a(ro), _a(det), _a(cl), _a(mo))
+    elif mo is not None:
         fn, args = "cc_db_query_submit_matched", (db, None if src is not None else qdesc, _a(src), _a(idx)) + mid + (_a(ro), _a(det), _a(cm), _a(mo))
     elif cm is not None:
         fn, args = "cc_db_query_submit_masked", (db, qdesc, _a(src), _a(idx)) + mid + (_a(ro), _a(det), _a(cm))
@@ -256,7 +272,7 @@ def query(lib, db, epochs, qdesc=None, src=None, idx=None, mask=None, lb=None, u
         args = (db, qdesc) + mid + tail
     else:
         fn, args = "cc_db_query_batch" if wait else "cc_db_query_submit", (db, qdesc) + mid
-    held = (src, idx, epochs, lb, ub, res, rk, ro, det, mask, mt, mo)
+    held = (src, idx, epochs, lb, ub, res, rk, ro, det, mask, mt, mo, among)
     _call(lib, db, fn, args, wait, tolerate, keep, held)
     return Out(held, res=res, rank=rk, detail=det, match=mt)
 

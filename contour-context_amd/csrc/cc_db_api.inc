@@ -15,6 +15,7 @@ namespace {
 // Transfers of a few hundred bytes are not worth a copy command in a launch chain (a blit kernel + its dispatch gap, ~10 us
 // each on the per-scan loop): up to this many scans / queries the kernels read and write pinned host memory directly.
 #define CC_ZC_MAX 64
+#define CC_LIST_ZC_ENT 256  // ... and up to this many staged entries of a listed chunk (4 KB) the list retrieval reads where they lie
 #define CC_NVIEW 4     // buffers of a layer's sorted view: an append writes the next one, which the chunks submitted CC_NVIEW - 1 appends ago
                        // were the last to read -- with two (rounds 2-4) every append waited for the queries queued just before the previous one
 #define CC_NSTAGE 4    // pinned staging buffers of the small appends (the per-scan loop): an append does not wait for the one before it
@@ -146,6 +147,13 @@ struct cc_qlane {  // scratch of one in-flight chunk of <= QB queries
   // masked chunks (cc_db_query_submit_masked), allocated with the first one: the row of the mask each query names, or -1
   int *d_mrow = nullptr;              // [QB]
   int *h_mrow = nullptr;              // the same, pinned
+  // listed chunks (cc_db_query_submit_listed, include/cont2_amd_lists.h), allocated with the first one: per query its staged
+  // entries (first, count) or (-1, 0), and the entries -- as many as the largest listed chunk the lane has seen
+  cc_list_row *d_lrow = nullptr;      // [QB]
+  cc_list_row *h_lrow = nullptr;      // the same, pinned
+  cc_list_ent *d_lent = nullptr;      // [lent_cap]
+  cc_list_ent *h_lent = nullptr;      // the same, pinned
+  size_t lent_cap = 0;
   // ranked chunks (the *_ranked entry points), allocated with the first one: cc_k_final_r's lists, [nb][max_ret]
   cc_ranked_cand_t *d_rank = nullptr; // [QB * CC_RANK_MAX]
   cc_ranked_cand_t *h_rank = nullptr; // the same, pinned: copied out beside h_results (small chunks: written by the kernel)
@@ -265,6 +273,7 @@ struct cc_db {
   uint32_t *d_mask_stage = nullptr;   // staging for the table of cc_db_query_batch_host_masked, in words
   size_t mask_stage_cap = 0;
   long long knn_chunks[3] = {0, 0, 0};  // query chunks by retrieval so far: walk | tiled | masked walk (cc_db_debug_knn_chunks)
+  long long knn_chunks_listed[2] = {0, 0};  // ... that ran the list retrieval alone | behind the unrestricted one (cc_db_debug_knn_chunks_listed)
   cc_scan_desc_t *d_hstage[2] = {nullptr, nullptr};  // [CC_SCAN_BATCH_MAX] each: the descriptors of a batch of scan handles, gathered (append | query)
   int *d_hint_scores = nullptr;     // [CC_CHK_STRIDE][CC_NSCORE] per-check gate scores (cc_db_check_hints)
   bool prof = false;
@@ -335,6 +344,10 @@ static void db_free(cc_db *db) {
     if (ln.h_vin) hipHostFree(ln.h_vin);
     hipFree(ln.d_mrow);
     if (ln.h_mrow) hipHostFree(ln.h_mrow);
+    hipFree(ln.d_lrow);
+    if (ln.h_lrow) hipHostFree(ln.h_lrow);
+    hipFree(ln.d_lent);
+    if (ln.h_lent) hipHostFree(ln.h_lent);
     hipFree(ln.d_rank);
     if (ln.h_rank) hipHostFree(ln.h_rank);
     hipFree(ln.d_pin);
@@ -415,6 +428,28 @@ static int lane_alloc_mask(cc_qlane &ln) {
   const size_t bytes = sizeof(int) * (size_t)cc_db::QB;
   LANE_BUF(ln.h_mrow, bytes, true);
   LANE_BUF(ln.d_mrow, bytes, false);
+  return CC_OK;
+}
+// the tables of a lane's listed chunks: the row table (8 KB) with the lane's first one; the entries grow to the largest chunk
+// the lane has seen (`need` entries for the chunk at hand; 16 MB for a full chunk of full lists).  The lane is idle here
+// (submit_chunks has collected its previous chunk), so the old buffers may go.
+static int lane_alloc_lists(cc_qlane &ln, size_t need) {
+  LANE_BUF(ln.h_lrow, sizeof(cc_list_row) * (size_t)cc_db::QB, true);
+  LANE_BUF(ln.d_lrow, sizeof(cc_list_row) * (size_t)cc_db::QB, false);
+  if (need <= ln.lent_cap) return CC_OK;
+  // to the next power of two (at least 4 096 entries, 64 KB): chunks that slowly get larger do not pay a hipFree -- a
+  // device-wide synchronisation -- and a pinned allocation per step
+  size_t cap = 4096;
+  while (cap < need) cap <<= 1;
+  need = cap;
+  hipFree(ln.d_lent);
+  if (ln.h_lent) hipHostFree(ln.h_lent);
+  ln.d_lent = nullptr;
+  ln.h_lent = nullptr;
+  ln.lent_cap = 0;
+  LANE_BUF(ln.h_lent, sizeof(cc_list_ent) * need, true);
+  LANE_BUF(ln.d_lent, sizeof(cc_list_ent) * need, false);
+  ln.lent_cap = need;
   return CC_OK;
 }
 // the tables of a lane's pose chunks (2 x 228 KB in, 2 x 200 KB out), allocated with the lane's first one
@@ -553,6 +588,8 @@ int cc_db_create(cc_ctx *ctx, const cc_db_cfg_t *cfg, int capacity_scans, cc_db 
   for (int i = 0; i < cfg->n_q_levels; i++)
     if (cfg->q_levels[i] < 1 || cfg->q_levels[i] > CC_HOT_LEVELS) return set_err(CC_EINVAL, "cc_db_create: q_levels_ must be within 1..4");
   if (cfg->max_fine_opt < 1) return set_err(CC_EINVAL, "cc_db_create: max_fine_opt_ must be positive");
+  // a key id fits 28 bits: the staged entries of a listed query pack (first key id << 3 | key count) into 32 (k_knn_list.h)
+  if ((long long)capacity_scans * CC_NPIV > (1ll << 28)) return set_err(CC_EINVAL, "cc_db_create: capacity_scans * CC_NPIV keys per layer exceed 2^28 key ids");
   HIPCHK(hipSetDevice(ctx->device));
   cc_db *db = new cc_db();
   db->ctx = ctx;
@@ -1424,7 +1461,7 @@ struct cc_prep_src {  // what the prep stage makes a chunk's query records from
 // What a submit does of its own, in the order the driver calls it.  The steps from `upload` on return a CC_* code with the
 // message set (HIPCHK for their HIP calls).
 struct cc_chunk_plan {
-  std::function<int(cc_qlane &)> alloc;                          // the lane's on-demand buffers the chunk needs
+  std::function<int(cc_qlane &, int, int)> alloc;                // the lane's on-demand buffers the chunk (items [b0, b0 + nb)) needs
   std::function<void(const cc_chunk &)> stage;                   // fill the lane's pinned staging from the caller's arrays
   std::function<int(const cc_chunk &, cc_prep_src &)> upload;    // the copies in front of the prep kernels, and what those read
   std::function<int(const cc_chunk &)> head;                     // what stands in the place of the retrieval (stage ev[0] .. ev[1])
@@ -1487,7 +1524,7 @@ static int submit_chunks(cc_db *db, int n, hipStream_t stream, const cc_chunk_pl
     cc_qlane &ln = db->lane[db->next_lane];
     db->next_lane = (db->next_lane + 1) % db->n_lanes;
     int rc = lane_finish(db, ln);
-    if (rc == CC_OK) rc = plan.alloc(ln);  // before anything of the chunk is queued (a lane whose earlier allocation failed tries again)
+    if (rc == CC_OK) rc = plan.alloc(ln, b0, nb);  // before anything of the chunk is queued (a lane whose earlier allocation failed tries again)
     if (rc != CC_OK) return rc;
     cc_chunk c{ln, b0, nb, nb <= CC_ZC_MAX, nullptr};
     plan.stage(c);
@@ -1556,6 +1593,37 @@ static int mask_validate(const cc_db *db, const cc_scan_mask_t *mask, int nq, co
   return CC_OK;
 }
 
+// The refusals of a listed query (cc_db_query_submit_listed / cc_db_query_batch_host_listed, include/cont2_amd_lists.h), before
+// anything is queued.  Everything is host memory, so everything is checked.
+// fn: the entry point's name, for the messages.
+static int lists_validate(const char *fn, const cc_db *db, const cc_scan_lists_t *lists, int nq) {
+  auto bad = [&](const char *what) { return set_err(CC_EINVAL, (std::string(fn) + ": " + what).c_str()); };
+  if (!lists->h_off || (!lists->h_row && nq > 0)) return bad("the lists' h_off and h_row must be given");
+  if (lists->n_lists < 1) return bad("the lists need n_lists >= 1");
+  if (db->dyn_thres)
+    return bad("listed queries are not supported in dynamic-threshold mode (cc_db_set_dynamic_thres)");
+  if (lists->h_off[0] != 0) return bad("h_off must start at 0");
+  for (int r = 0; r < lists->n_lists; r++) {
+    const int lo = lists->h_off[r], hi = lists->h_off[r + 1];
+    if (hi < lo) return bad("h_off must be non-decreasing");
+    if (hi - lo > CC_LIST_SCANS_MAX)
+      return bad("a list is longer than CC_LIST_SCANS_MAX = 1024 scans (use the mask form, cc_db_query_submit_masked, for larger sets)");
+    if (hi > lo && !lists->h_idx) return bad("h_idx must be given");
+  }
+  for (int r = 0; r < lists->n_lists; r++) {  // (the offsets are in order: nothing beyond h_idx[h_off[n_lists]) is read)
+    const int lo = lists->h_off[r], hi = lists->h_off[r + 1];
+    for (int j = lo; j < hi; j++) {
+      const int g = lists->h_idx[j];
+      if (g < 0 || g >= db->n_scans) return bad("a list names a scan outside [0, cc_db_size)");
+      if (j > lo && g <= lists->h_idx[j - 1]) return bad("a list must be strictly increasing");
+    }
+  }
+  for (int i = 0; i < nq; i++)
+    if (lists->h_row[i] < -1 || lists->h_row[i] >= lists->n_lists)
+      return bad("h_row names a list outside [-1, n_lists)");
+  return CC_OK;
+}
+
 // rank: where the chunks' ranked lists go (the *_ranked entry points, validated there), or nullptr: the plain call
 static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
                              const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn, int32_t *d_knn_cnt, void *stream_,
@@ -1564,7 +1632,9 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
                              const cc_rec_src *rec = nullptr /*the queries are packed records (then d_qdesc is nullptr) ...*/,
                              const int32_t *h_rec = nullptr /*... query i is record h_rec[i] of them, or nullptr: record i*/,
                              const cc_scan_mask_t *mask = nullptr /*the scans that may answer (bits: device), or nullptr: all of them*/,
-                             const cc_match_out_t *match = nullptr /*with rank: where the chunks' match rows go (validated by the entry point), or nullptr*/) {
+                             const cc_match_out_t *match = nullptr /*with rank: where the chunks' match rows go (validated by the entry point), or nullptr*/,
+                             const cc_scan_lists_t *lists = nullptr /*per query a list of the scans that may answer (host; never with mask), or nullptr*/,
+                             bool lists_checked = false /*the entry point has run lists_validate under its own name*/) {
   if (!db || (!d_qdesc && !rec) || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch: bad argument");
   DB_POISON_CHK(db, "cc_db_query_batch");
   if (mask) {
@@ -1596,18 +1666,69 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
       const int r = h_rec ? h_rec[i] : i;
       if (r < 0 || r >= rec->n_rec) return set_err(CC_EINVAL, "cc_db_query_submit_packed: record index outside the source");
     }
+  if (lists && !lists_checked) {  // (after what the call without lists refuses)
+    const int vrc = lists_validate("cc_db_query_submit_listed", db, lists, nq);
+    if (vrc != CC_OK) return vrc;
+  }
   bool chunk_vis = false;  // some query of the chunk sees a bucket whose kd-tree does not index its whole range
   bool chunk_masked = false;  // some query of the chunk names a row of the mask
+  // listed calls: 0 no query of the chunk names a list, 1 some do (the list retrieval runs behind the unrestricted one), 2 all do
+  int chunk_listed = 0;
+  size_t chunk_lent = 0;      // the chunk's staged entries
+  bool lent_zc = false;       // ... are read from the pinned buffer where they lie (a small chunk with a few of them)
+  // the distinct lists of a chunk, in the order its queries first name them: each is staged once
+  std::vector<int> list_at(lists ? (size_t)lists->n_lists : 0, -1);  // where list r starts among the chunk's entries, or -1
+  std::vector<int> list_used;
+  int lists_b0 = -1, lists_nb = 0;  // the chunk the two describe (plan.alloc fills them, plan.stage finds them)
+  size_t lists_n = 0;
+  auto chunk_lists = [&](int b0, int nb) -> size_t {  // fills the two for items [b0, b0 + nb) -> the entries they take
+    if (b0 == lists_b0 && nb == lists_nb) return lists_n;
+    for (int r : list_used) list_at[r] = -1;
+    list_used.clear();
+    size_t n = 0;
+    for (int i = 0; i < nb; i++) {
+      const int r = lists->h_row[b0 + i];
+      if (r < 0 || list_at[r] >= 0) continue;
+      list_at[r] = (int)n;  // (<= QB * CC_LIST_SCANS_MAX = 2^20)
+      list_used.push_back(r);
+      n += (size_t)(lists->h_off[r + 1] - lists->h_off[r]);
+    }
+    lists_b0 = b0;
+    lists_nb = nb;
+    lists_n = n;
+    return n;
+  };
   cc_chunk_plan plan;
-  plan.alloc = [&](cc_qlane &ln) -> int {
+  plan.alloc = [&](cc_qlane &ln, int b0, int nb) -> int {
     int rc = rec ? lane_alloc_verify(ln) : CC_OK;  // (the record selector of a packed chunk goes where a verify chunk's does)
     if (rc == CC_OK && mask) rc = lane_alloc_mask(ln);
+    if (rc == CC_OK && lists) rc = lane_alloc_lists(ln, chunk_lists(b0, nb));
     return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail, match);
   };
   plan.stage = [&](const cc_chunk &c) {  // the queries' epoch records
     cc_query_meta *h_meta = c.ln.h_meta;
     chunk_vis = false;
     chunk_masked = false;
+    chunk_listed = 0;
+    if (lists) {  // per query where its list lies among the chunk's entries; per listed scan its key ids of the three layers
+      chunk_lent = chunk_lists(c.b0, c.nb);
+      int n_named = 0;
+      for (int i = 0; i < c.nb; i++) {
+        const int r = lists->h_row[c.b0 + i];
+        c.ln.h_lrow[i] = r < 0 ? make_int2(-1, 0) : make_int2(list_at[r], lists->h_off[r + 1] - lists->h_off[r]);
+        n_named += r >= 0;
+      }
+      for (int r : list_used) {
+        cc_list_ent *e = c.ln.h_lent + list_at[r];
+        for (int j = lists->h_off[r]; j < lists->h_off[r + 1]; j++, e++) {
+          const int g = lists->h_idx[j];
+          e->g = g;
+          for (int l = 0; l < CC_NQLEV; l++)  // scan g's keys of layer l: ids [nkeys_hist[g][l], nkeys_hist[g + 1][l]), in anchor order
+            e->w[l] = (db->nkeys_hist[g][l] << 3) | (db->nkeys_hist[g + 1][l] - db->nkeys_hist[g][l]);
+        }
+      }
+      chunk_listed = n_named == 0 ? 0 : n_named == c.nb ? 2 : 1;
+    }
     if (mask)
       for (int i = 0; i < c.nb; i++) {
         const int r = mask->h_row[c.b0 + i];
@@ -1636,6 +1757,11 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
     if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_qmeta, ln.h_meta, sizeof(cc_query_meta) * c.nb, hipMemcpyHostToDevice, ln.stream));
     // (small chunks: the masked walk reads its rows from the pinned buffer, as cc_k_prep_packed reads the selector below)
     if (chunk_masked && !c.zc) HIPCHK(hipMemcpyAsync(ln.d_mrow, ln.h_mrow, sizeof(int) * c.nb, hipMemcpyHostToDevice, ln.stream));
+    if (chunk_listed) {  // (small chunks: the list retrieval reads its rows from the pinned buffer as well, and a few entries with them)
+      if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_lrow, ln.h_lrow, sizeof(cc_list_row) * c.nb, hipMemcpyHostToDevice, ln.stream));
+      lent_zc = c.zc && chunk_lent <= CC_LIST_ZC_ENT;
+      if (!lent_zc && chunk_lent > 0) HIPCHK(hipMemcpyAsync(ln.d_lent, ln.h_lent, sizeof(cc_list_ent) * chunk_lent, hipMemcpyHostToDevice, ln.stream));
+    }
     if (rec) {  // (small chunks: cc_k_prep_packed reads the selector from the pinned buffer too)
       if (!c.zc) HIPCHK(hipMemcpyAsync(ln.d_vin, ln.h_vin, sizeof(int) * c.nb, hipMemcpyHostToDevice, ln.stream));
       src = cc_prep_src{nullptr, c.zc, c.zc ? ln.h_vin : ln.d_vin, rec};
@@ -1649,6 +1775,29 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
     hipStream_t ls = ln.stream;
     const int nb = c.nb;
     const cc_query_meta *qmeta_dev = ln.d_qmeta;
+    // The list retrieval (k_knn_list.h): alone when every query of the chunk names a list, else behind the chunk's unrestricted
+    // retrieval, whose hit tables it overwrites for the queries that do.  It reads the layers by key id (d_keys, d_kactive,
+    // d_kgidx, d_kseq), not the sorted view: everything there is append-only but the tails of d_kactive, where a later append
+    // only ever replaces "never" by an epoch later than any query in flight; the lanes' wait for add_done (submit_chunks) orders
+    // these reads behind the append that covers the chunk's largest epoch, as it orders the view's.
+    auto launch_list = [&]() -> int {
+      db->knn_chunks_listed[chunk_listed == 2 ? 0 : 1]++;
+      cc_knn_list_params LP;
+      for (int l = 0; l < CC_NQLEV; l++) {
+        LP.keys[l] = db->d_keys[l];
+        LP.act[l] = db->d_kactive[l];
+      }
+      const cc_list_row *qlist = c.zc ? ln.h_lrow : ln.d_lrow;
+      const cc_list_ent *ent = lent_zc ? ln.h_lent : ln.d_lent;
+      if (db->kmax != CC_KNN_MAX)
+        hipLaunchKernelGGL(chunk_vis ? cc_k_knn_list_l<true> : cc_k_knn_list_l<false>, dim3(nb * NS), dim3(64), 0, ls, KP, LP,
+                           (const cc_hot_desc_t *)ln.d_qhot, qmeta_dev, ln.d_hits, ln.d_hit_cnt, qlist, ent);
+      else
+        hipLaunchKernelGGL(chunk_vis ? cc_k_knn_list<true> : cc_k_knn_list<false>, dim3(nb * NS), dim3(64), 0, ls, KP, LP,
+                           (const cc_hot_desc_t *)ln.d_qhot, qmeta_dev, ln.d_hits, ln.d_hit_cnt, qlist, ent);
+      return CC_OK;
+    };
+    if (chunk_listed == 2) return launch_list();
     int max_keys = 0;
     for (int l = 0; l < nql; l++) max_keys = db->n_keys[l] > max_keys ? db->n_keys[l] : max_keys;
     // (a large-k database always walks: the tiled search has no large-k instance)
@@ -1680,7 +1829,7 @@ static int query_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int nq, c
       hipLaunchKernelGGL(chunk_vis ? cc_k_knn<true> : cc_k_knn<false>, dim3(nb * NS), dim3(64), 0, ls, KP, (const cc_hot_desc_t *)ln.d_qhot, qmeta_dev,
                          ln.d_hits, ln.d_hit_cnt);
     }
-    return CC_OK;
+    return chunk_listed ? launch_list() : CC_OK;
   };
   plan.body = [&](const cc_chunk &c) -> int {
     cc_qlane &ln = c.ln;
@@ -2157,7 +2306,7 @@ static int verify_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_de
   VP.max_key_dist_sq = cfg->max_key_dist_sq;
   // the chain is the 64-stride one on any database, as in the hint flow
   cc_chunk_plan plan;
-  plan.alloc = [&](cc_qlane &ln) -> int {
+  plan.alloc = [&](cc_qlane &ln, int, int) -> int {
     const int rc = lane_alloc_verify(ln);
     return rc != CC_OK ? rc : lane_alloc_modes(db, ln, rank, detail, match);
   };
@@ -2304,7 +2453,7 @@ static int pose_submit_impl(cc_db *db, const cc_scan_desc_t *d_qdesc, int n_desc
     return tables{it, tp, (int *)(tp + (size_t)nb * nt * 3), res, tr, (cc_pose_curv_t *)(tr + (size_t)nb * nt)};
   };
   cc_chunk_plan plan;
-  plan.alloc = [&](cc_qlane &ln) -> int { return lane_alloc_pose(ln); };
+  plan.alloc = [&](cc_qlane &ln, int, int) -> int { return lane_alloc_pose(ln); };
   plan.stage = [&](const cc_chunk &c) {
     const tables h = tables_at(c.ln.h_pin, c.ln.h_pout, c.nb);
     memcpy(h.it, h_items + c.b0, sizeof(cc_pose_item_t) * (size_t)c.nb);
@@ -2562,6 +2711,51 @@ int cc_db_check_hints_host_matched(cc_db *db, const cc_scan_desc_t *h_qdesc, con
   const int vrc = packed_modes(__func__, rank, h_detail);
   if (vrc != CC_OK) return vrc;
   return check_hints_host_impl(db, h_qdesc, h_hints, n_hints, lb, ub, max_fine_opt, h_res, h_scores, rank, h_detail, match);
+}
+
+// ---- listed queries: the retrieval among per-query lists of scans (include/cont2_amd_lists.h; k_knn_list.h) ----
+// The most general query submit with `lists` in the mask's place.  lists NULL is the call without it, launch for launch.
+int cc_db_query_submit_listed(cc_db *db, const cc_scan_desc_t *d_qdesc, const cc_packed_src_t *src, const int32_t *h_rec, int nq,
+                              const int32_t *h_epoch, const cc_score_t *lb, const cc_score_t *ub, cc_query_result_t *h_res, cc_knn_hit_t *d_knn,
+                              int32_t *d_knn_cnt, void *stream_, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                              const cc_scan_lists_t *lists, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  if ((d_qdesc != nullptr) == (src != nullptr)) return set_err(CC_EINVAL, "cc_db_query_submit_listed: exactly one of d_qdesc and src must be given");
+  int vrc = packed_modes(__func__, rank, h_detail);
+  if (vrc != CC_OK) return vrc;
+  if (!src) return query_submit_impl(db, d_qdesc, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, nullptr, nullptr, nullptr, match, lists);
+  cc_rec_src rs;
+  vrc = packed_resolve(__func__, db, src, &rs);
+  if (vrc != CC_OK) return vrc;
+  return query_submit_impl(db, nullptr, nq, h_epoch, lb, ub, h_res, d_knn, d_knn_cnt, stream_, rank, h_detail, &rs, h_rec, nullptr, match, lists);
+}
+// ... with host descriptors: staged on the device, then the submit above and the wait (the lists are host memory either way)
+int cc_db_query_batch_host_listed(cc_db *db, const cc_scan_desc_t *h_qdesc, int nq, const int32_t *h_epoch, const cc_score_t *lb,
+                                  const cc_score_t *ub, cc_query_result_t *h_res, const cc_rank_out_t *rank, cc_ranked_detail_t *h_detail,
+                                  const cc_scan_lists_t *lists, const cc_match_out_t *match) {
+  CC_WANT_MATCH();
+  if (!db || !h_qdesc || nq < 0 || !h_epoch || !lb || !ub || !h_res) return set_err(CC_EINVAL, "cc_db_query_batch_host_listed: bad argument");
+  DB_POISON_CHK(db, "cc_db_query_batch_host_listed");
+  int rc = packed_modes(__func__, rank, h_detail);
+  if (rc != CC_OK) return rc;
+  if (!thres_strict_smaller(lb, ub)) return set_err(CC_EINVAL, "cc_db_query_batch_host_listed: thresholds must satisfy lb.strictSmaller(ub)");
+  for (int i = 0; i < nq; i++)
+    if (h_epoch[i] < 0 || h_epoch[i] > db->n_scans) return set_err(CC_EINVAL, "cc_db_query_batch_host_listed: epoch out of range");
+  if (lists) {  // (before anything is staged: a refused call copies nothing)
+    rc = lists_validate(__func__, db, lists, nq);
+    if (rc != CC_OK) return rc;
+  }
+  if (nq == 0) return CC_OK;
+  HIPCHK(hipSetDevice(db->device));
+  rc = stage_reserve(db, nq);
+  if (rc != CC_OK) return rc;
+  HIPCHK(hipMemcpy(db->d_stage, h_qdesc, sizeof(cc_scan_desc_t) * (size_t)nq, hipMemcpyHostToDevice));
+  return run_sync(db, [&] { return query_submit_impl(db, db->d_stage, nq, h_epoch, lb, ub, h_res, nullptr, nullptr, nullptr, rank, h_detail, nullptr, nullptr, nullptr, match, lists, true); });
+}
+int cc_db_debug_knn_chunks_listed(const cc_db *db, int64_t out[2]) {
+  if (!db || !out) return set_err(CC_EINVAL, "cc_db_debug_knn_chunks_listed: bad argument");
+  for (int i = 0; i < 2; i++) out[i] = db->knn_chunks_listed[i];
+  return CC_OK;
 }
 #undef CC_WANT_MATCH
 // host only: the pairs of a row in key order

@@ -28,12 +28,14 @@
 #include "../../include/cont2_amd_paths.h"
 #include "../../include/cont2_amd_cands.h"
 #include "../../include/cont2_amd_matches.h"
+#include "../../include/cont2_amd_lists.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
 #include "k_image.h"
 #include "k_contours.h"
 #include "k_contours_list.h"
 #include "k_knn.h"
+#include "k_knn_list.h"
 #include "k_mask.h"
 #include "k_check.h"
 #include "k_merge.h"

@@ -8,6 +8,7 @@
 #include "../tools/bm_util.h"
 #include "contour_mng.h"
 #include "../../../include/cont2_amd_matches.h"
+#include "../../../include/cont2_amd_lists.h"
 
 // The reference's DYNAMIC_THRES=1 build (CMakeLists.txt:19-20; contour_db.h:439-466, 566-574) raises the lower bars of a
 // query's checks from candidate to candidate inside CandidateManager.  Built with that macro, every database of this mirror
@@ -538,6 +539,42 @@ class ContourDB {
     const cc_match_out_t mo = {ml, want_matches_};
     const int rc = wantMatches() ? cc_db_query_batch_host_matched(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, &ro, want_detail_ ? dl : nullptr, &mask, &mo)
                                  : cc_db_query_batch_host_masked(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, rk ? &ro : nullptr, want_detail_ ? dl : nullptr, &mask);
+    for (auto &sp : spec_) sp.collected = true;  // the synchronous call (its wait) collected every chain in flight
+    if (rc != CC_OK) die_cc();
+    handOut(rk, r, rl, rn, dl, ml, cand_ptrs, cand_corr, cand_tf);
+  }
+  // Mirror-only: queryAllowed for callers whose set is a short index list (the result of a radius search over the poses): the same
+  // answers, from the retrieval that enumerates the listed scans' keys instead of walking the layer under a bit row
+  // (cc_db_query_batch_host_listed, include/cont2_amd_lists.h).  allowed_indices: strictly increasing, at most CC_LIST_SCANS_MAX.
+  // Synchronous, at the official epoch; honours setMaxReturn / setWantDetail / setWantMatches like queryAllowed.
+  void queryAmong(const std::shared_ptr<const ContourManager> &q_ptr, const std::vector<int> &allowed_indices,
+                  const CandidateScoreEnsemble &thres_lb, const CandidateScoreEnsemble &thres_ub,
+                  std::vector<std::shared_ptr<const ContourManager>> &cand_ptrs, std::vector<double> &cand_corr,
+                  std::vector<Eigen::Isometry2d> &cand_tf) const {
+    cand_ptrs.clear();
+    cand_corr.clear();
+    cand_tf.clear();
+    const int n_db = (int)all_bevs_.size();
+    for (const int c : allowed_indices) CC_CHECK(c >= 0 && c < n_db);  // (scans appended ahead of the driver are not the caller's yet)
+    ensure(*q_ptr);
+    if (need_rebuild_) rebuild();
+    const cc_score_t lb = to_c(thres_lb), ub = to_c(thres_ub);
+    const std::vector<int32_t> idx(allowed_indices.begin(), allowed_indices.end());
+    const int32_t off[2] = {0, (int32_t)idx.size()};
+    const int32_t epoch = n_db, r0 = 0;
+    const cc_scan_lists_t lists = {idx.data(), off, 1, &r0};
+    cc_query_result_t r;
+    cc_ranked_cand_t rl[CC_RANK_MAX];
+    cc_ranked_detail_t dl[CC_RANK_MAX];
+    int32_t rn = 0;
+    const cc_rank_out_t ro = {rl, &rn, max_ret_, 0};
+    const bool rk = rankedPath();
+    last_details_.clear();
+    last_matches_.clear();
+    cc_ranked_match_t ml[CC_RANK_MAX];
+    const cc_match_out_t mo = {ml, want_matches_};
+    const int rc = cc_db_query_batch_host_listed(db_, &q_ptr->desc(), 1, &epoch, &lb, &ub, &r, rk ? &ro : nullptr, want_detail_ ? dl : nullptr, &lists,
+                                                 wantMatches() ? &mo : nullptr);
     for (auto &sp : spec_) sp.collected = true;  // the synchronous call (its wait) collected every chain in flight
     if (rc != CC_OK) die_cc();
     handOut(rk, r, rl, rn, dl, ml, cand_ptrs, cand_corr, cand_tf);

@@ -181,6 +181,35 @@ def pack_mask_rows(allowed, n_db=None, row_words=None):
     return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little").view("<u4").reshape(a.shape[0], rw))
 
 
+LIST_SCANS_MAX = 1024  # CC_LIST_SCANS_MAX (include/cont2_amd_lists.h)
+
+
+class ScanListsC(C.Structure):  # cc_scan_lists_t (the listed query forms): list r is h_idx[h_off[r] .. h_off[r + 1]), all host memory
+    _fields_ = [("h_idx", C.c_void_p), ("h_off", C.c_void_p), ("n_lists", C.c_int32), ("h_row", C.c_void_p)]
+
+
+assert C.sizeof(ScanListsC) == 32 and ScanListsC.h_off.offset == 8 and ScanListsC.n_lists.offset == 16 and ScanListsC.h_row.offset == 24
+
+
+def gate_lists(xy, gates):
+    """The scans within each gate's circle as index lists, on the host: cc_mask_gates' f32 expression as written --
+    dx = x_g - x_r, dy = y_g - y_r, dx * dx + dy * dy <= rad_r * rad_r and rad_r >= 0; a NaN anywhere sets nothing -- so list r
+    holds the set bits of Context.gate_mask's row r.  xy [n_scans, 2], gates [n_rows, 3] of (x, y, radius) -> (idx int32,
+    off int32 [n_rows + 1])."""
+    xy = np.asarray(xy, np.float32).reshape(-1, 2)
+    gates = np.asarray(gates, np.float32).reshape(-1, 3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dx = xy[None, :, 0] - gates[:, None, 0]
+        dy = xy[None, :, 1] - gates[:, None, 1]
+        lhs = (dx * dx).astype(np.float32) + (dy * dy).astype(np.float32)
+        rad = gates[:, None, 2]
+        inside = (lhs <= (rad * rad).astype(np.float32)) & (rad >= 0)
+    r, g = np.nonzero(inside)  # row-major: ascending scans within a row
+    off = np.zeros(len(gates) + 1, np.int32)
+    np.cumsum(np.bincount(r, minlength=len(gates)), out=off[1:])
+    return np.ascontiguousarray(g, np.int32), off
+
+
 pass_dbg_dt = np.dtype([("hint", "<i4"), ("n_pairs", "<i4"), ("tf", "<f8", (3,)), ("pairs", "<u8", (7,))], align=True)
 assert pass_dbg_dt.itemsize == 88
 # cc_cand_dbg_t (include/cont2_amd_cands.h): a candidate of the last hint call as the merge left it
