@@ -1110,6 +1110,19 @@ class Database:
         _chk(lib().cc_db_debug_cands(self.h, out.ctypes.data, cap, C.byref(n)), "cc_db_debug_cands")
         return out[:n.value]
 
+    def debug_key_view(self, layer):
+        """The sorted key view of query layer `layer` as the last append left it (cc_db_debug_key_view, include/cont2_amd_keyview.h):
+        (keys [11, n] -- ten rows of key entries and the |key|^2 row --, key ids [n], activation epochs [n]) in the view's order."""
+        n = C.c_int32()
+        z = np.zeros(L.KEY_DIM + 1, np.float32)
+        rc = lib().cc_db_debug_key_view(self.h, int(layer), 0, z.ctypes.data, z.ctypes.data, z.ctypes.data, C.byref(n))  # cap 0: the size
+        if rc != CC_ECAPACITY:
+            _chk(rc, "cc_db_debug_key_view")
+        cap = max(n.value, 1)
+        keys, sid, sact = np.zeros((L.KEY_DIM + 1, cap), np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        _chk(lib().cc_db_debug_key_view(self.h, int(layer), cap, keys.ctypes.data, sid.ctypes.data, sact.ctypes.data, C.byref(n)), "cc_db_debug_key_view")
+        return keys[:, :n.value], sid[:n.value], sact[:n.value]
+
     def set_lanes(self, n):
         """1 = query chunks one after the other, 2 (default) = two 256-query chunks in flight on internal streams."""
         _chk(lib().cc_db_set_lanes(self.h, int(n)), "cc_db_set_lanes")

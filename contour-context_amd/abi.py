@@ -182,6 +182,9 @@ I cc_db_query_submit_listed PPPPIPPPPPPPPPPP
 I cc_db_query_batch_host_listed PPIPPPPPPPP
 I cc_db_debug_knn_chunks_listed PP
 """,
+    "cont2_amd_keyview.h": """
+I cc_db_debug_key_view PIIPPPP
+""",
 }
 ADDONS = {hdr: _table(spec) for hdr, spec in _ADDON_SPEC.items()}
 

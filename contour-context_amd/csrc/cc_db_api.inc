@@ -2225,6 +2225,25 @@ int cc_db_debug_cands(cc_db *db, cc_cand_dbg_t *h_out, int cap, int *n_out) {
   return CC_OK;
 }
 
+// include/cont2_amd_keyview.h: the buffer of the layer's sorted view that the next chunk would read (scur), after the chunks in
+// flight and the last append's merge have finished; read-only
+int cc_db_debug_key_view(cc_db *db, int layer, int cap, float *keys, int32_t *sid, int32_t *sact, int32_t *n) {
+  if (!db || !keys || !sid || !sact || !n || cap < 0 || layer < 0 || layer >= db->cfg.n_q_levels)
+    return set_err(CC_EINVAL, "cc_db_debug_key_view: bad argument");
+  HIPCHK(hipSetDevice(db->device));
+  DB_DRAIN(db);
+  if (db->add_done) HIPCHK(hipEventSynchronize(db->add_done));
+  const int nk = db->n_keys[layer], cur = db->scur[layer];
+  *n = nk;
+  if (nk > cap) return set_err(CC_ECAPACITY, "cc_db_debug_key_view: the layer holds more keys than cap");
+  if (nk == 0) return CC_OK;
+  for (int d = 0; d <= CC_KEY_DIM; d++)
+    HIPCHK(hipMemcpy(keys + (size_t)d * (size_t)cap, db->d_skeys[layer][cur] + (size_t)d * (size_t)db->cap_k, sizeof(float) * (size_t)nk, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sid, db->d_sid[layer][cur], sizeof(int) * (size_t)nk, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sact, db->d_sact[layer][cur], sizeof(int) * (size_t)nk, hipMemcpyDeviceToHost));
+  return CC_OK;
+}
+
 static int check_hints_host_impl(cc_db *db, const cc_scan_desc_t *h_qdesc, const cc_hint_t *h_hints, int n_hints, const cc_score_t *lb,
                                  const cc_score_t *ub, int max_fine_opt, cc_query_result_t *h_res, cc_hint_score_t *h_scores,
                                  const cc_rank_out_t *rank,

@@ -29,6 +29,7 @@
 #include "../../include/cont2_amd_cands.h"
 #include "../../include/cont2_amd_matches.h"
 #include "../../include/cont2_amd_lists.h"
+#include "../../include/cont2_amd_keyview.h"
 #include "cc_hostcfg.h"
 #include "k_rasterize.h"
 #include "k_image.h"
